@@ -1,16 +1,24 @@
 #!/usr/bin/env python3
 """Benchmark of the DeepQ-Decoding hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode loop|act|learn|env] [--config c3] [--minibatch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode loop|act|learn|env] [--config c3] [--minibatch B] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: every lattice of the batch (4096 per GPU at the
 headline config c3: d=5 depolarising p=0.011 with faulty syndromes, depth 5) receives an action, the
 batched environment kernel steps them, the transition lands in the device replay ring, and (mode
 `loop`) one DQN minibatch update runs.  Rank 0 prints ONE JSON line (contract in the task statement):
-`value` = whole-job env steps/s with all inputs resident in HBM; `roofline` is for the dominant kernel (its duration: HIP
-events bound to a sample of its launches inside the timed region -- the dispatch packets' own timestamps, csrc/prof.hip);
-`cpu_baseline` times the CPU oracle (a port; the reference's Python cannot travel to the GPU box) on
-this host's cores for a bounded sample.
+`value` = whole-job env steps/s with all inputs resident in HBM, `ms_per_step` = milliseconds per timed step (exactly --steps of them).
+
+A plain run only sets up, warms up, times the K steps and prints the line (`roofline` null).  `--full` adds everything else:
+`roofline` for the dominant kernel (an untimed probe picks it; its duration: HIP events bound to a sample of its launches inside the
+timed region -- the dispatch packets' own timestamps, csrc/prof.hip), `reference_replay_ratio` (a second timed leg, loop mode, 1 GPU),
+`cpu_baseline` (the CPU oracle, a port of the reference's Python, on this host's cores for a bounded sample; --no-cpu-baseline
+drops it), `build` (library vs source digest), `params_checksum`, and with several ranks `replicas_identical`
+and `allreduce`.  The probe's untimed steps come before the timed region, so a --full run ends in another state than a plain one.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed on rank 0 -- the arrays a caller of the path
+receives -- as DIR/<name>.npy (float32), at most 64 MB in all: lattice-indexed arrays beyond that are cut to a fixed, seeded sample of
+lattices whose indices go to DIR/lattice_index.npy.  Inputs are seeded: the same arguments give the same inputs from run to run.
 
 Modes (SURVEY.md 8d "reported numbers"): `loop` (iv) full loop, the default and the headline; `env` (i) environment kernel
 + uniform-legal device policy; `act` (ii) Q forward + epsilon-greedy + environment step, no learning; `learn` (iii) the
@@ -227,7 +235,14 @@ def main():
                     help="minibatch updates per vector step (loop mode).  The reference trains 32 samples per environment step "
                          "(one 32-sample update per step, Single_Point_Training_Script.py:119-127): --updates-per-step 32 at the default "
                          "minibatch = lattices, or --minibatch 32 --updates-per-step <lattices>")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline of the dominant kernel, the replay-ratio leg, CPU baselines, "
+                         "build digest, parameter checksum, several-rank checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)
@@ -330,11 +345,12 @@ def main():
         os.environ["DQ_DIST_MODE"] = dist_tune["chosen"]
         for _ in range(5):
             runner.step(timed=False)
-    if hasattr(runner, "pick_dominant"):
+    if args.full and hasattr(runner, "pick_dominant"):
         runner.pick_dominant()          # untimed probe: which kernel family takes the most time per step
-    if os.environ.get("DQ_BENCH_NO_ARM") != "1":     # (diagnostic: the timed region without any event, no roofline object)
-        runner.arm(args.steps)          # ... launches of that family inside the timed region carry a HIP event pair (prof.hip; a sample of them, see prof_stride)
-    if (world > 1 or force_dist) and hasattr(runner, "core"):
+    # launches of that family inside the timed region carry a HIP event pair (prof.hip; a sample of them, see prof_stride); DQ_BENCH_NO_ARM=1 (diagnostic):
+    # the --full timed region without any event, no roofline object.  EnvOnly.arm also fixes the timed region's length, so it is called in every run
+    runner.arm(args.steps, prof=args.full and os.environ.get("DQ_BENCH_NO_ARM") != "1")
+    if args.full and (world > 1 or force_dist) and hasattr(runner, "core"):
         runner.core.ar_events = []      # HIP events around the exposed part of the gradient all-reduce, inside the timed loop
         runner.core.ar_stride = importlib.import_module("deepq-decoding_amd.bench_loop").prof_stride(args.steps)      # (a sample of the steps, as the kernel timing)
         runner.core.ar_pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps // runner.core.ar_stride + 8)]
@@ -348,6 +364,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(runner, args.dump_outputs)      # (before anything below steps the loop again)
 
     if os.environ.get("DQ_BENCH_FAMILIES") == "1" and hasattr(runner, "family_times") and rank == 0:
         extra = runner.report(args.steps, dt, world)       # (collects the timed region's events first)
@@ -358,7 +376,7 @@ def main():
         runner.report = lambda *a, _e=extra: _e
 
     replicas_identical, allreduce = None, None
-    if (world > 1 or force_dist) and hasattr(runner, "core"):
+    if args.full and (world > 1 or force_dist) and hasattr(runner, "core"):
         # outside the timed region: every rank must hold bit-identical parameters (same all-reduced gradient, same Adam step)
         chk = runner.core.params.view(torch.int32).to(torch.int64).sum().reshape(1)
         lo, hi = chk.clone(), chk.clone()
@@ -376,7 +394,7 @@ def main():
         runner.core.ar_events = None
 
     params_checksum = None
-    if hasattr(runner, "core"):                     # outside the timed region: what the run left in the parameters (path-equivalence checks)
+    if args.full and hasattr(runner, "core"):       # outside the timed region: what the run left in the parameters (path-equivalence checks)
         params_checksum = int(runner.core.params.view(torch.int32).to(torch.int64).sum().item())
     if world > 1 or force_dist:
         ctypes.CDLL(None).fflush(None)              # every rank's buffered library output leaves before rank 0's line does
@@ -401,10 +419,11 @@ def main():
                                     f"{n_local} lattices/GPU, mode={mode}", **runner.config()),
         }
         out.update(runner.report(args.steps, dt, world))
-        dg = importlib.import_module("deepq-decoding_amd._digest").csrc_digest()
-        lib_dg = importlib.import_module("deepq-decoding_amd._lib").lib().dq_build_digest().decode()
-        out["build"] = dict(library_digest=lib_dg[:16], sources_digest=dg[:16], library_built_from_these_sources=lib_dg == dg)      # (the .so is prebuilt: say which sources it is)
-        if world == 1 and mode == "loop" and args.updates_per_step == 1 and args.ratio_steps > 0 and hasattr(runner, "reference_ratio_leg"):
+        if args.full:
+            dg = importlib.import_module("deepq-decoding_amd._digest").csrc_digest()
+            lib_dg = importlib.import_module("deepq-decoding_amd._lib").lib().dq_build_digest().decode()
+            out["build"] = dict(library_digest=lib_dg[:16], sources_digest=dg[:16], library_built_from_these_sources=lib_dg == dg)      # (the .so is prebuilt: say which sources it is)
+        if args.full and world == 1 and mode == "loop" and args.updates_per_step == 1 and args.ratio_steps > 0 and hasattr(runner, "reference_ratio_leg"):
             # the driver's line carries the whole claim: the same loop at the reference's training intensity (k = 32 n / B updates per vector step)
             out["reference_replay_ratio"] = runner.reference_ratio_leg(steps=args.ratio_steps, warmup=max(2, args.ratio_steps // 10))
         if params_checksum is not None:
@@ -412,11 +431,12 @@ def main():
         if world > 1 or force_dist:
             out["rccl_ranks"] = rccl_ranks                            # (from ncclCommCount behind a checked pre-flight all-reduce, above)
             out["dist_backend"] = "rccl" if backend == "nccl" else backend
-            out["replicas_identical"] = replicas_identical
-            out["allreduce"] = allreduce
+            if args.full:
+                out["replicas_identical"] = replicas_identical
+                out["allreduce"] = allreduce
             out["dist_mode"] = dict(dist_tune, how="both forms timed before the timed region, the faster one ran") if dist_tune else \
                 dict(chosen=os.environ.get("DQ_DIST_MODE", "single"), how="DQ_DIST_MODE" if "DQ_DIST_MODE" in os.environ else "default")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             full = dict(cfg, n_envs=n_local)
             if mode == "env":
                 out["cpu_baseline"] = cpu_baseline_env(full)
@@ -436,6 +456,49 @@ def main():
         if hasattr(runner, "core"):
             runner.core.close_comm()            # the learner's own communicator first, on every rank, everything drained
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 60_000_000      # --dump-outputs: data bytes of all arrays together (below 64 MB with the .npy headers)
+LATTICE_OUTPUTS = ("q_values", "actions", "rewards", "done", "observations")     # first dimension = the rank's lattices
+
+
+def step_outputs(runner):
+    """name -> device tensor: what the last timed step handed back to a caller of the path.  Acting modes: the acting forward's Q-values, the
+    actions taken, rewards, done flags and the successor observations (uint8 image, decoded from the ring's patch words when the ring holds
+    them); learning modes: the parameters after the step's Adam update and (loss, mean Q) of its last update."""
+    if isinstance(runner, EnvOnly):
+        return runner.last_step_outputs()
+    import torch
+    core, out = runner.core, {}
+    if runner.mode in ("loop", "act"):
+        last = (core.cur - 1) % core.T
+        out.update(q_values=core.q_act, actions=core.action_ring[last], rewards=core.reward_ring[last], done=core.terminal_ring[last],
+                   observations=core.obs_ring[core.cur])
+    if runner.mode in ("loop", "learn"):
+        out.update(params=core.params, loss_mean_q=torch.tensor(core.read_metrics(), dtype=torch.float32))
+    return out
+
+
+def dump_outputs(runner, directory):
+    """--dump-outputs: step_outputs() as DIR/<name>.npy in float32 (every value here is exact in float32).  Beyond DUMP_LIMIT_BYTES the
+    lattice-indexed arrays keep a fixed, seeded sample of lattices (the same rows in each), listed in DIR/lattice_index.npy."""
+    import numpy as np
+    import torch
+    outs = step_outputs(runner)
+    os.makedirs(directory, exist_ok=True)
+    lattice = [k for k in outs if k in LATTICE_OUTPUTS]
+    n = int(outs[lattice[0]].shape[0]) if lattice else 0
+    fixed = sum(4 * v.numel() for k, v in outs.items() if k not in LATTICE_OUTPUTS)
+    per_lattice = sum(4 * outs[k].numel() for k in lattice) // max(1, n)
+    if lattice and fixed + per_lattice * n > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - fixed) // per_lattice)
+        rows = np.sort(np.random.RandomState(0).choice(n, size=keep, replace=False))
+        idx = torch.from_numpy(rows).to(outs[lattice[0]].device)
+        for k in lattice:
+            outs[k] = outs[k].index_select(0, idx)
+        outs["lattice_index"] = torch.from_numpy(rows.astype(np.float32))
+    for k, v in outs.items():
+        np.save(os.path.join(directory, k + ".npy"), v.detach().to("cpu", torch.float32).numpy())
 
 
 def allreduce_probe(torch, dist, core, backend, iters=20):
@@ -497,11 +560,18 @@ class EnvOnly:
         self.armed = False
         self.launch_steps = []
 
-    def arm(self, steps):
-        # a sample of the launches carries a HIP event pair (the dispatch's own timestamps, prof.hip)
+    def arm(self, steps, prof=True):
+        # the timed region launches exactly `steps` agent steps; with prof a sample of its launches carries a HIP event pair (the dispatch's own timestamps, prof.hip)
         self.pending, self.left = 0, steps
         self.launch_steps = []
-        self.armed = self.bl.prof_arm(self.L, "env_kernel", (steps + self.T - 1) // self.T, 1)
+        self.armed = bool(prof) and self.bl.prof_arm(self.L, "env_kernel", (steps + self.T - 1) // self.T, 1)
+
+    def last_step_outputs(self):
+        """What the last launched agent step wrote: its ring slot's actions / rewards / done and the successor observation in the slot behind it."""
+        last = (self.t - 1) % self.slots
+        nxt = (last + 1) % self.slots
+        obs = self.env.patch_to_obs(self.patch[nxt]) if self.obs_form == "patch" else self.obs[nxt]
+        return {"actions": self.action[last], "rewards": self.reward[last], "done": self.done[last], "observations": obs}
 
     def step(self, timed):
         """One vector step; every T-th call launches the next T (the timed region's last launch: what is left of it)."""

@@ -248,8 +248,8 @@ class FullLoop:
         _lib.check(self.L.dq_prof_arm(-1, 0))
         return out
 
-    def arm(self, steps):
-        if self.prof_family:
+    def arm(self, steps, prof=True):
+        if prof and self.prof_family:
             prof_arm(self.L, self.prof_family, steps, self.kernel_families()[self.prof_family][0])
 
     def units_per_step(self):

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,7 +24,7 @@ def _clean_env(**extra):
 def test_bench_self_launches_two_ranks_that_stay_identical(mode):
     # (overlap: on a gloo group -- no RCCL communicator of the learner's own -- the mode takes the split form through torch.distributed)
     # mode None (round 6): no DQ_DIST_MODE -- bench.py times both forms before the timed region, every rank picks the same one, the line says which and why
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3", "--no-cpu-baseline", "--dist-probe-steps", "6"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3", "--full", "--no-cpu-baseline", "--dist-probe-steps", "6"]
     env = _clean_env(DQ_DIST_BACKEND="gloo", **({"DQ_DIST_MODE": mode} if mode else {}))
     if mode is None:
         env.pop("DQ_DIST_MODE", None)
@@ -56,7 +57,7 @@ def test_one_rank_rccl_group_drives_the_several_gpu_branch():
     one rank the sum is the identity, so the parameters after the run must be the bits the one-GPU branch (Adam fused on the reduction) leaves."""
     def run(**extra):
         # (--dist-probe-steps 0: no timing of both exchange forms in front of the timed region -- its extra steps would move the parameters this test compares)
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "24", "--warmup", "4", "--no-cpu-baseline", "--dist-probe-steps", "0", "--ratio-steps", "0"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "24", "--warmup", "4", "--full", "--no-cpu-baseline", "--dist-probe-steps", "0", "--ratio-steps", "0"]
         r = subprocess.run(cmd, cwd=ROOT, env=_clean_env(**extra), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = r.stdout.strip().splitlines()
@@ -92,7 +93,7 @@ def test_bench_refuses_a_world_that_differs_from_gpus():
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["act", "learn", "env"])
 def test_bench_modes_print_one_contract_line(mode):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", mode, "--steps", "20", "--warmup", "3", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", mode, "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline"],
                        cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
@@ -220,10 +221,10 @@ def test_rccl_preflight_on_a_one_rank_group():
 
 @pytest.mark.gpu
 def test_default_bench_line_carries_the_whole_claim():
-    """a driver-shaped run (`python bench.py --steps 20 --warmup 5`, cpu baseline off here for time) prints ONE line whose `roofline` names the
+    """a driver-shaped run with everything measured (`python bench.py --full --steps 20 --warmup 5`, cpu baseline off here for time) prints ONE line whose `roofline` names the
     kernel SYMBOL that ran beside its family, carries the launch spread and a non-null PMC traffic (the committed pass matches the sources: the CPU suite's
     test_pmc_stamp_matches_sources), and whose `reference_replay_ratio` is a second timed leg at 32 trained samples per environment step."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--ratio-steps", "20"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--ratio-steps", "20"]
     r = subprocess.run(cmd, cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith('{"metric"')]
@@ -240,3 +241,30 @@ def test_default_bench_line_carries_the_whole_claim():
     ratio = out["reference_replay_ratio"]
     assert ratio["updates_per_vector_step"] == 32 and ratio["samples_trained_per_env_step"] == 32.0 and ratio["steps"] == 20
     assert ratio["value"] > 5e5 and abs(ratio["value"] - 4096 * 1e3 / ratio["ms_per_step"]) < 1.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["loop", "env"])
+def test_plain_bench_run_prints_only_the_headline_and_dumps_the_last_step(mode, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the contract line without the --full measurements; --dump-outputs writes
+    what the last timed step computed, in float32, and a second run with the same arguments writes the same arrays (seeded inputs).  70 steps:
+    the environment mode's last launch of the timed region is a partial one (64 steps per launch)."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", mode, "--steps", "70", "--warmup", "3", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = r.stdout.strip().splitlines()
+        assert len(lines) == 1 and lines[0].startswith('{"metric"'), r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 70 and out["warmup"] == 3 and out["ms_per_step"] > 0 and out["roofline"] is None
+        assert abs(out["value"] - 4096 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]          # value and ms_per_step describe the same region
+        assert not {"cpu_baseline", "reference_replay_ratio", "build", "params_checksum"} & set(out)
+        dumps.append({f.stem: np.load(f) for f in d.glob("*.npy")})
+    want = {"actions", "rewards", "done", "observations"} | ({"q_values", "params", "loss_mean_q"} if mode == "loop" else set())
+    assert set(dumps[0]) == want
+    for k, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.array_equal(a, dumps[1][k]), k
+    assert dumps[0]["observations"].shape == (4096, 7, 11, 11) and dumps[0]["actions"].shape == (4096,)
+    assert all(np.isfinite(a).all() for a in dumps[0].values())

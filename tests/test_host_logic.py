@@ -255,10 +255,10 @@ def test_keras_and_gym_standins_recognise_the_reference_architecture():
         sys.path.pop(0)
 
 
-REF_H5 = "/root/reference/trained_models/d5_dp/0.007/final_dqn_weights.h5f"
+# one shipped agent's weight file, stored as data (trained_models/d5_dp/0.007/final_dqn_weights.h5f of the reference, byte for byte)
+REF_H5 = os.path.join(ROOT, "tests", "golden", "final_dqn_weights_d5_dp_0.007.h5f")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_H5), reason="reference checkout not present (GPU box)")
 def test_hdf5_reader_on_shipped_keras_weights():
     """The pure-Python HDF5 reader returns the shipped agent's tensors in Keras order with the shapes SURVEY.md §8a-D1
     lists; the committed fixture tests/golden/keras_weights_d5_dp_0.007.npz is exactly this file's content."""
@@ -274,43 +274,6 @@ def test_hdf5_reader_on_shipped_keras_weights():
     assert names[0] == "/conv2d_1/conv2d_1/bias:0" and names[-1] == "/dense_3/dense_3_1/kernel:0"
     at = h.read_attributes(REF_H5)                                   # the attribute parser the writer's test relies on, on a real file
     assert at["/"]["layer_names"][:2] == [b"conv2d_1_input", b"conv2d_1"] and at["/dense_3"] == {"weight_names": [b"dense_3_1/kernel:0", b"dense_3_1/bias:0"]}
-
-
-@pytest.mark.skipif(not os.path.exists(REF_H5), reason="reference checkout not present (GPU box)")
-def test_weight_fixtures_regenerate_and_all_shipped_agents_load():
-    """tools/gen_weight_fixtures.py reproduces the committed fixtures array for array, and the pure-Python HDF5 reader loads every one
-    of the 14 shipped agents (trained_models/d5_x/*, d5_dp/*) with the tensor shapes of SURVEY.md 8a-D1."""
-    import glob
-    import sys
-    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
-    sys.path.insert(0, tools)
-    try:
-        import gen_weight_fixtures as gw
-    finally:
-        sys.path.pop(0)
-    for family, p in gw.AGENTS:
-        fx = load_golden(gw.fixture_name(family, p))
-        fresh = gw.build(family, p)
-        assert sorted(fx.files) == sorted(fresh)
-        for k in fresh:
-            assert np.array_equal(fx[k], fresh[k]), (family, p, k)
-    tails, fresh_tails = load_golden("training_history_tails"), gw.build_history_tails()
-    assert all(np.array_equal(tails[k], fresh_tails[k]) for k in fresh_tails) and sorted(tails.files) == sorted(fresh_tails)
-    for family, p in gw.HISTORIES:                         # the two from-scratch training records (training_history.json + their configs)
-        fx = load_golden(gw.history_fixture_name(family, p))
-        fresh = gw.build_history(family, p)
-        assert sorted(fx.files) == sorted(fresh)
-        for k in fresh:
-            assert np.array_equal(fx[k], fresh[k], equal_nan=fresh[k].dtype.kind == "f"), (family, p, k)
-    h = importlib.import_module("deepq-decoding_amd.hdf5_reader")
-    files = sorted(glob.glob("/root/reference/trained_models/*/*/final_dqn_weights.h5f"))
-    assert len(files) == 14
-    for f in files:
-        C, A = (6, 26) if "/d5_x/" in f else (7, 51)
-        w = h.read_keras_weights(f)
-        assert [x.shape for x in w] == [(3, 3, C, 64), (64,), (2, 2, 64, 32), (32,), (2, 2, 32, 32), (32,), (288, 512), (512,),
-                                        (512, A), (A,), (A, A + 1), (A + 1,)], f
-        assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in w)
 
 
 def test_grid_files_follow_the_reference_schema(tmp_path):
@@ -337,11 +300,11 @@ def test_grid_files_follow_the_reference_schema(tmp_path):
     assert (v36["learning_rate"], v36["exploration_fraction"], v36["final_eps"]) == (0.00001, 200000, 0.001)
     cfg, number = runner.load_configs(dirs[6])
     assert number == "7" and cfg["d"] == 5 and cfg["learning_rate"] == v1["learning_rate"] and set(cfg) == set(fixed) | set(v1)
-    if os.path.exists("/root/reference/trained_models/d5_dp/fixed_config.p"):        # the reference's own pickles carry the same keys
-        ref_fixed = pickle.load(open("/root/reference/trained_models/d5_dp/fixed_config.p", "rb"))
-        assert set(ref_fixed) == set(runner.FIXED_KEYS) and ref_fixed == fixed
-        ref_var = pickle.load(open("/root/reference/trained_models/d5_dp/0.011/variable_config_92.p", "rb"))
-        assert set(ref_var) == set(runner.VARIABLE_KEYS)
+    # the reference's own pickles (trained_models/d5_dp/fixed_config.p and 0.011/variable_config_92.p, stored as data) carry the same keys
+    ref_fixed = pickle.load(open(os.path.join(ROOT, "tests", "golden", "fixed_config_d5_dp.p"), "rb"))
+    assert set(ref_fixed) == set(runner.FIXED_KEYS) and ref_fixed == fixed
+    ref_var = pickle.load(open(os.path.join(ROOT, "tests", "golden", "variable_config_d5_dp_0.011_92.p"), "rb"))
+    assert set(ref_var) == set(runner.VARIABLE_KEYS)
     # Controller bookkeeping
     assert runner.collect_results(os.path.join(fam, "0.001"))["3"] == "not started"
     assert runner.select_best({"1": 900.0, "2": 1200.0, "3": "still running", "4": 1500.0}, 1000, 1) == {"4": 1500.0}
@@ -571,3 +534,45 @@ def test_reference_records_pin_the_early_stopping_rule():
         # before min_nb_steps the count runs past the patience without effect
         assert agent.stopping_flags(False, False, 0.0, r["max_tsb_before_min"], mn - 1, r["success_threshold"], pat, mn) == (False, False)
     assert stopped == 9 and max(r["max_tsb_before_min"] for r in rows) > 9000
+
+
+def test_bench_dump_outputs_sample_a_large_step_under_64_mb(tmp_path):
+    """bench.py --dump-outputs (host side, a stand-in loop runner on CPU tensors): the last step's arrays as float32 .npy files; a small step
+    whole; a step beyond the size limit keeps one fixed, seeded sample of lattices -- the same rows in every lattice-indexed array, listed in
+    lattice_index.npy -- and the parameters and (loss, mean Q) whole, under 64 MB in all."""
+    import types
+    import torch
+    import bench
+
+    def runner(n, T=2, cur=1):
+        g = torch.Generator().manual_seed(n)
+        core = types.SimpleNamespace(
+            cur=cur, T=T, q_act=torch.randn(n, 51, generator=g), action_ring=torch.randint(0, 51, (T, n), dtype=torch.int32, generator=g),
+            reward_ring=torch.rand(T, n, generator=g), terminal_ring=torch.randint(0, 2, (T, n), dtype=torch.uint8, generator=g),
+            obs_ring=torch.randint(0, 2, (T, n, 7, 11, 11), dtype=torch.uint8, generator=g), params=torch.randn(193000, generator=g),
+            read_metrics=lambda: (0.25, -1.5))
+        return types.SimpleNamespace(mode="loop", core=core)
+
+    def load(d):
+        return {f.stem: np.load(f) for f in d.glob("*.npy")}
+
+    small = runner(100)
+    bench.dump_outputs(small, str(tmp_path / "small"))
+    got = load(tmp_path / "small")
+    assert set(got) == {"q_values", "actions", "rewards", "done", "observations", "params", "loss_mean_q"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    c = small.core
+    assert np.array_equal(got["actions"], c.action_ring[0].numpy()) and np.array_equal(got["observations"], c.obs_ring[1].numpy())
+    assert np.array_equal(got["q_values"], c.q_act.numpy()) and got["loss_mean_q"].tolist() == [0.25, -1.5]
+
+    big = runner(40000)
+    for name in ("big", "again"):
+        bench.dump_outputs(big, str(tmp_path / name))
+    got, again = load(tmp_path / "big"), load(tmp_path / "again")
+    assert sum(f.stat().st_size for f in (tmp_path / "big").glob("*.npy")) < 64 * 10 ** 6
+    rows = got["lattice_index"].astype(np.int64)
+    assert np.array_equal(got["lattice_index"], again["lattice_index"]) and 0 < len(rows) < 40000 and np.all(np.diff(rows) > 0)
+    c = big.core
+    assert np.array_equal(got["actions"], c.action_ring[0].numpy()[rows]) and np.array_equal(got["done"], c.terminal_ring[0].numpy()[rows])
+    assert np.array_equal(got["observations"], c.obs_ring[1].numpy()[rows]) and np.array_equal(got["q_values"], c.q_act.numpy()[rows])
+    assert np.array_equal(got["params"], c.params.numpy())

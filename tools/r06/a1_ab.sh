@@ -1,10 +1,10 @@
 mkdir -p gpurun_out/r06c; o=gpurun_out/r06c
 python -m pytest tests/test_compact_gpu.py tests/test_qnet_gpu.py -m gpu -x -q > $o/tests_conv.log 2>&1; tail -3 $o/tests_conv.log
 line() { grep '^{"metric"' | tail -1; }
-python bench.py --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_recompute.json
-DQ_CONV_BWD_A1=saved python bench.py --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_saved.json
-python bench.py --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_recompute2.json
-DQ_CONV_BWD_A1=saved python bench.py --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_saved2.json
+python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_recompute.json
+DQ_CONV_BWD_A1=saved python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_saved.json
+python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_recompute2.json
+DQ_CONV_BWD_A1=saved python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_saved2.json
 for v in recompute saved; do
   rm -rf $o/prof
   (cd /tmp && export TMPDIR=/tmp && DQ_CONV_BWD_A1=$v rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$o/prof" -- python "$GRAFT_REPO_ROOT/bench.py" --steps 500 --warmup 50 --no-cpu-baseline --ratio-steps 0 > "$GRAFT_REPO_ROOT/$o/prof_$v.log" 2>&1)

@@ -1,4 +1,4 @@
-run() { echo "== $*"; python bench.py "$@" --no-cpu-baseline 2>&1 | tail -1 | python -c "
+run() { echo "== $*"; python bench.py --full "$@" --no-cpu-baseline 2>&1 | tail -1 | python -c "
 import json,sys
 l=sys.stdin.readline()
 try:

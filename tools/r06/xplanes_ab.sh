@@ -2,8 +2,8 @@ mkdir -p gpurun_out/r06j; o=gpurun_out/r06j
 python -m pytest tests/test_compact_gpu.py tests/test_qnet_gpu.py tests/test_agent_gpu.py -m gpu -x -q > $o/tests.log 2>&1; tail -3 $o/tests.log | cut -c1-250
 line() { grep '^{"metric"' | tail -1; }
 for i in 1 2; do
-python bench.py --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_planes$i.json
-DQ_X_PLANES=0 python bench.py --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_f32_$i.json
+python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_planes$i.json
+DQ_X_PLANES=0 python bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline 2>/dev/null | line > $o/bench_f32_$i.json
 done
 for v in 1 0; do
   rm -rf $o/prof

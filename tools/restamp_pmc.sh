@@ -9,4 +9,4 @@ tools/pmc_traffic.sh env c3 > gpurun_out/restamp/env.log 2>&1
 cp gpurun_out/pmc_traffic_*.json gpurun_out/restamp/; cp gpurun_out/pmc_traffic_*.json profiles/
 rm -rf gpurun_out/pmc_FETCH_SIZE gpurun_out/pmc_WRITE_SIZE
 tail -4 gpurun_out/restamp/c3.log
-python bench.py --steps 20 --warmup 5 2>/dev/null | grep '^{"metric"' | tail -1 | tee gpurun_out/restamp/bench_driver_shape.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('driver-shaped run:', d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['frac'], 'traffic', d['roofline']['traffic'])"
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | grep '^{"metric"' | tail -1 | tee /dev/stderr | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('driver-shaped --full run:', d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['frac'], 'traffic', d['roofline']['traffic'])"
