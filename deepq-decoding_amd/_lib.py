@@ -66,7 +66,8 @@ class TdJob(ctypes.Structure):
                 ("index_dev", ctypes.c_void_p), ("gamma", ctypes.c_double), ("grad_scale", ctypes.c_double), ("batch", ctypes.c_int32),
                 ("n_actions", ctypes.c_int32), ("y_dev", ctypes.c_void_p), ("dq_dev", ctypes.c_void_p), ("metrics_dev", ctypes.c_void_p),
                 ("done_dev", ctypes.c_void_p), ("was_reset_dev", ctypes.c_void_p), ("lifetime_dev", ctypes.c_void_p),
-                ("step_reward_dev", ctypes.c_void_p), ("n", ctypes.c_int32), ("stats_dev", ctypes.c_void_p), ("auto_scale", ctypes.c_int32)]
+                ("step_reward_dev", ctypes.c_void_p), ("n", ctypes.c_int32), ("stats_dev", ctypes.c_void_p), ("auto_scale", ctypes.c_int32),
+                ("delta_clip", ctypes.c_double)]
 
 
 class EnvStepJob(ctypes.Structure):
@@ -161,6 +162,8 @@ SIGNATURES = {
     "dq_replay_sample_multi": (_i, [_vp, _i, _i, _i, _i, _i, _seedp, _u64, _i, _u32, _vp, _vp]),
     "dq_td_target": (_i, [_vp, _vp, _vp, _vp, _vp, _dbl, _i, _i, _vp, _vp]),
     "dq_td_loss_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _dbl, _vp, _vp, _vp]),
+    "dq_td_loss_grad_clip": (_i, [_vp, _vp, _vp, _vp, _i, _i, _dbl, _dbl, _vp, _vp, _vp]),
+    "dq_td_step": (_i, [ctypes.POINTER(TdJob), _vp]),
     "dq_episode_stats": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "dq_test_bookkeeping": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "dq_td_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _i, _i, _dbl, _vp, _vp, _vp, _vp]),

@@ -36,7 +36,7 @@ import torch
 
 from .core import DQNCore, MIN_FILLED
 from .env import Surface_Code_Environment_Multi_Decoding_Cycles, VectorEnv
-from .qnet import QNetwork
+from .qnet import QNetwork, check_delta_clip
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -319,8 +319,7 @@ class DQNAgent:
             raise ValueError(f'Model output "{model.output_shape}" has invalid shape. DQN expects a model that has one dimension for each action, in this case {nb_actions}.')
         if dueling_type != 'avg':
             raise NotImplementedError("only dueling_type='avg' (the keras-rl default the reference uses) is implemented")
-        if not np.isinf(delta_clip):
-            raise NotImplementedError("delta_clip != inf is not used by the reference and not implemented")
+        self.delta_clip = check_delta_clip(delta_clip)     # inf: the squared TD error (the reference); finite > 0: keras-rl's Huber loss
         if target_model_update < 1:
             raise NotImplementedError("soft target updates (target_model_update < 1) are not used by the reference")
         if memory_interval != 1:
@@ -367,7 +366,7 @@ class DQNAgent:
         return dict(nb_actions=self.nb_actions, gamma=self.gamma, batch_size=self.batch_size, nb_steps_warmup=self.nb_steps_warmup,
                     train_interval=self.train_interval, target_model_update=self.target_model_update,
                     enable_double_dqn=self.enable_double_dqn, enable_dueling_network=self.enable_dueling_network, dueling_type='avg',
-                    updates_per_vector_step=self.updates_per_vector_step)
+                    delta_clip=self.delta_clip, updates_per_vector_step=self.updates_per_vector_step)
 
     # -- binding to an environment ------------------------------------------------------------------------------
     def _bind(self, env):
@@ -391,7 +390,7 @@ class DQNAgent:
         self._core = DQNCore(venv, self._net, batch_size=self.batch_size, memory_limit=self.memory.limit, gamma=self.gamma,
                              lr=opt.lr, beta_1=opt.beta_1, beta_2=opt.beta_2, epsilon=opt.epsilon,
                              target_model_update=self.target_model_update, enable_double_dqn=self.enable_double_dqn,
-                             seed=self.seed if self.seed is not None else venv.seed, rank=rank, world_size=world)
+                             seed=self.seed if self.seed is not None else venv.seed, rank=rank, world_size=world, delta_clip=self.delta_clip)
         self._env = venv
         if old is not None:
             self._net.set_weights(self._core.params, old)

@@ -17,6 +17,7 @@ over unchanged.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib, dist as _dist, qnet as _q
@@ -69,8 +70,11 @@ class ObsRingView:
 class DQNCore:
     def __init__(self, env, net, batch_size=32, memory_limit=50000, gamma=0.99, lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
                  target_model_update=10000, enable_double_dqn=True, seed=None, rank=0, world_size=1, process_group=None,
-                 params=None, compact=None):
+                 params=None, compact=None, delta_clip=np.inf):
+        """delta_clip: keras-rl's DQNAgent(delta_clip) -- inf (the reference's setting) trains on the squared TD error, a finite value > 0 on the
+        Huber loss at that delta (include/deepq_hip.h dq_td_job.delta_clip), on every update path."""
         self.env, self.net = env, net
+        self.delta_clip = _q.check_delta_clip(delta_clip)
         self.N, self.A = env.n_envs, env.num_actions
         assert net.n_actions == self.A and tuple(net.input_shape) == tuple(env.obs_shape)
         self.device = env.device
@@ -433,7 +437,8 @@ class DQNCore:
         q_sel = self.q1_online if self.enable_double_dqn else self.q1_target
         return dict(q_online_s1=q_sel, q_target_s1=self.q1_target, q_s0=self.q0, reward=self.reward_ring, terminal=self.terminal_ring,
                     action=self.action_ring, gamma=self.gamma, grad_scale=_dist.grad_scale(self.batch_size, self.world_size),
-                    index=self.index, y=self.y, dq=self.dq, metrics=self.metrics, step_stats=step_stats, auto_scale=self.auto_scale)
+                    index=self.index, y=self.y, dq=self.dq, metrics=self.metrics, step_stats=step_stats, auto_scale=self.auto_scale,
+                    delta_clip=self.delta_clip)
 
     def local_gradient(self, index=None):
         """This rank's contribution to the NEXT update's gradient, without the all-reduce and without the optimizer step: minibatch
@@ -642,8 +647,10 @@ class DQNCore:
             # from the first update (nothing is ever discarded).
             n_lost = self.net.range_discarded()
             self.discarded_updates += n_lost
-            # (the FORWARD's guard -- a parameter or activation outside the f16 pieces' range: a diverged run -- is always fatal: no gradient scale helps)
-            if e.status != -6 or "[forward]" in str(e) or self.auto_scale or os.environ.get("DQ_TD_AUTOSCALE") is not None:
+            # (the FORWARD's guard -- a parameter or activation outside the f16 pieces' range: a diverged run -- is always fatal: no gradient scale helps;
+            # so is any trip with a finite delta_clip: its scale already carries every finite TD error, what is left is a NaN one or a diverged network)
+            if e.status != -6 or "[forward]" in str(e) or self.auto_scale or os.environ.get("DQ_TD_AUTOSCALE") is not None \
+                    or not np.isinf(self.delta_clip):
                 raise
             self.auto_scale = True
             self.range_switches = getattr(self, "range_switches", 0) + 1

@@ -86,6 +86,15 @@ static inline u32 dq_rate_threshold16(double p) {
     return ((double)f < t) ? f + 1 : f;
 }
 
+// keras-rl's delta_clip as the TD kernels take it: float, +inf = no clipping (dq_huber_grad below).  keras-rl asserts delta > 0: zero, a negative
+// value, NaN and a double that rounds to float zero are DQ_ERR_INVALID -- except 0 where zero_means_inf (dq_td_job.delta_clip: a zero-initialised job).
+static inline dq_status dq_td_delta(double delta_clip, int zero_means_inf, float* out) {
+    if (zero_means_inf && delta_clip == 0.0) delta_clip = INFINITY;
+    DQ_REQUIRE(delta_clip > 0.0 && (float)delta_clip > 0.f, DQ_ERR_INVALID, "delta_clip must be > 0 (got %g)", delta_clip);
+    *out = (float)delta_clip;
+    return DQ_OK;
+}
+
 // ---- device helpers -----------------------------------------------------------------------------
 #ifdef __HIPCC__
 
@@ -172,6 +181,15 @@ __device__ __forceinline__ void dq_wave_argmax(float& best, int& best_a) {
     for (int r = 16; r < 64; r += 16)
         dq_argmax_take(v, a, __builtin_bit_cast(float, __builtin_amdgcn_readlane(ib, r)), __builtin_amdgcn_readlane(best_a, r));
     best = v; best_a = a;
+}
+
+// keras-rl's Huber loss (huber_loss / clipped_masked_error) of a TD error x at delta > 0, fp32: h(x) = 0.5 x^2 where |x| <= delta, delta (|x| - 0.5 delta)
+// beyond; its gradient c(x) = x clamped to [-delta, delta].  delta = +inf is keras-rl's delta_clip = inf: the compare is never true, so h and c are
+// 0.5 x^2 and x with the bits of the plain expressions (the linear branch, inf - inf, is never taken).  The clamp is a COMPARE, not fminf / fmaxf: a NaN
+// TD error stays NaN (as in TensorFlow) for the fused backward's range guard to see; an infinite one becomes +-delta (also as in TensorFlow).
+__device__ __forceinline__ float dq_huber_grad(float x, float delta) { return fabsf(x) > delta ? copysignf(delta, x) : x; }
+__device__ __forceinline__ float dq_huber_loss(float x, float delta) {
+    return fabsf(x) > delta ? delta * (fabsf(x) - 0.5f * delta) : 0.5f * x * x;
 }
 
 // index of the k-th (0-based) set bit of a 128-bit mask; -1 if fewer bits are set

@@ -54,13 +54,14 @@ __global__ void td_target_kernel(const float* __restrict__ q_online, const float
     }
 }
 
-// dq[b, a] = grad_scale * (Q[b,a_b] - y_b) at a = a_b, else 0;  metrics[0] = mean_b 0.5 (Q[b,a_b]-y_b)^2,
-// metrics[1] = mean_b max_a Q[b,a].  One wave per sample; per-block partials land in metrics[2 + 2*block ...] and a
-// second single-block pass adds them in a fixed order (deterministic).
+// dq[b, a] = grad_scale * c(Q[b,a_b] - y_b) at a = a_b, else 0;  metrics[0] = mean_b h(Q[b,a_b]-y_b),
+// metrics[1] = mean_b max_a Q[b,a].  c / h: keras-rl's Huber loss at delta (common.h dq_huber_grad / dq_huber_loss; delta = +inf: x and
+// 0.5 x^2).  One wave per sample; per-block partials land in metrics[2 + 2*block ...] and a second single-block pass adds them in a
+// fixed order (deterministic).
 #define TD_MAX_BLOCKS 1024
 __global__ __launch_bounds__(256) void td_loss_grad_kernel(const float* __restrict__ q, const int32_t* __restrict__ action,
                                                            const int32_t* __restrict__ index, const float* __restrict__ y, int B,
-                                                           int A, float grad_scale, float* __restrict__ dq, float* __restrict__ metrics) {
+                                                           int A, float grad_scale, float delta, float* __restrict__ dq, float* __restrict__ metrics) {
     __shared__ float s_loss[4], s_q[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float loss = 0.f, mq = 0.f;
@@ -68,15 +69,15 @@ __global__ __launch_bounds__(256) void td_loss_grad_kernel(const float* __restri
         const float* row = q + (size_t)b * A;
         float* drow = dq + (size_t)b * A;
         const int a_b = action[index ? index[b] : b];
+        const float diff = row[a_b] - y[b], dc = dq_huber_grad(diff, delta);
         float mx = -INFINITY;
         for (int a = lane; a < A; a += 64) {
             const float v = row[a];
             mx = fmaxf(mx, v);
-            drow[a] = a == a_b ? (v - y[b]) * grad_scale : 0.f;
+            drow[a] = a == a_b ? dc * grad_scale : 0.f;
         }
         for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
-        const float diff = row[a_b] - y[b];
-        loss += 0.5f * diff * diff;
+        loss += dq_huber_loss(diff, delta);
         mq += mx;
     }
     if (lane == 0) { s_loss[wave] = loss; s_q[wave] = mq; }
@@ -90,13 +91,13 @@ __global__ __launch_bounds__(256) void td_loss_grad_kernel(const float* __restri
 struct TdStats { const u8* done; const u8* was_reset; const u32* lifetime; const float* reward; int n; unsigned long long* stats; };
 
 // The whole TD step of one update in one launch (one wave per sample): double-DQN target from Q_online(s1) / Q_target(s1), then the
-// masked squared-error loss and its gradient on Q(s0).  Same arithmetic and the same per-block metric partials as
+// masked Huber loss (delta = +inf: squared error) and its gradient on Q(s0).  Same arithmetic and the same per-block metric partials as
 // td_target_kernel + td_loss_grad_kernel; y is also written (nullable) for tests / logging.
 __global__ __launch_bounds__(256) void td_update_kernel(const float* __restrict__ q_online, const float* __restrict__ q_target,
                                                         const float* __restrict__ q, const float* __restrict__ reward,
                                                         const u8* __restrict__ terminal, const int32_t* __restrict__ action,
                                                         const int32_t* __restrict__ index, float gamma, int B, int A, float grad_scale,
-                                                        float* __restrict__ y_out, float* __restrict__ dq, float* __restrict__ metrics,
+                                                        float delta, float* __restrict__ y_out, float* __restrict__ dq, float* __restrict__ metrics,
                                                         int td_blocks, TdStats st) {
     if ((int)blockIdx.x >= td_blocks) {                             // the episode bookkeeping of the step just taken rides along
         dq_episode_stats_lane(st.done, st.was_reset, st.lifetime, st.reward, st.n, ((int)blockIdx.x - td_blocks) * blockDim.x + threadIdx.x,
@@ -125,15 +126,15 @@ __global__ __launch_bounds__(256) void td_update_kernel(const float* __restrict_
         const float* row = q + (size_t)b * A;
         float* drow = dq + (size_t)b * A;
         const int a_b = action[r];
+        const float diff = row[a_b] - yb, dc = dq_huber_grad(diff, delta);
         float mx = -INFINITY;
         for (int a = lane; a < A; a += 64) {
             const float v = row[a];
             mx = fmaxf(mx, v);
-            drow[a] = a == a_b ? (v - yb) * grad_scale : 0.f;
+            drow[a] = a == a_b ? dc * grad_scale : 0.f;
         }
         for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
-        const float diff = row[a_b] - yb;
-        loss += 0.5f * diff * diff;
+        loss += dq_huber_loss(diff, delta);
         mq += mx;
     }
     if (lane == 0) { s_loss[wave] = loss; s_q[wave] = mq; }
@@ -268,8 +269,8 @@ dq_status dq_post_step(const uint8_t* terminal_ring_dev, int n_envs, int n_slots
 
 static dq_status launch_td_update(const float* q_online_s1_dev, const float* q_target_s1_dev, const float* q_s0_dev, const float* reward_dev,
                                   const uint8_t* terminal_dev, const int32_t* action_dev, const int32_t* index_dev, double gamma, int batch,
-                                  int n_actions, double grad_scale, float* y_dev, float* dq_dev, float* metrics_dev, const TdStats& ts,
-                                  void* stream) {
+                                  int n_actions, double grad_scale, float delta, float* y_dev, float* dq_dev, float* metrics_dev,
+                                  const TdStats& ts, void* stream) {
     DQ_REQUIRE(q_online_s1_dev && q_target_s1_dev && q_s0_dev && reward_dev && terminal_dev && action_dev && dq_dev, DQ_ERR_INVALID,
                "dq_td_update: null argument");
     DQ_REQUIRE(batch >= 1 && n_actions >= 1, DQ_ERR_INVALID, "dq_td_update: bad sizes");
@@ -278,7 +279,7 @@ static dq_status launch_td_update(const float* q_online_s1_dev, const float* q_t
     dq_prof_begin(DQ_K_TD, (hipStream_t)stream);
     td_update_kernel<<<blocks + stat_blocks, 256, 0, (hipStream_t)stream>>>(q_online_s1_dev, q_target_s1_dev, q_s0_dev, reward_dev, terminal_dev,
                                                                             action_dev, index_dev, (float)gamma, batch, n_actions,
-                                                                            (float)grad_scale, y_dev, dq_dev, metrics_dev, blocks, ts);
+                                                                            (float)grad_scale, delta, y_dev, dq_dev, metrics_dev, blocks, ts);
     dq_prof_end(DQ_K_TD, (hipStream_t)stream);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
@@ -290,7 +291,7 @@ dq_status dq_td_update(const float* q_online_s1_dev, const float* q_target_s1_de
     TdStats ts;
     memset(&ts, 0, sizeof(ts));
     return launch_td_update(q_online_s1_dev, q_target_s1_dev, q_s0_dev, reward_dev, terminal_dev, action_dev, index_dev, gamma, batch, n_actions,
-                            grad_scale, y_dev, dq_dev, metrics_dev, ts, stream);
+                            grad_scale, INFINITY, y_dev, dq_dev, metrics_dev, ts, stream);
 }
 
 dq_status dq_td_update_stats(const float* q_online_s1_dev, const float* q_target_s1_dev, const float* q_s0_dev, const float* reward_dev,
@@ -301,7 +302,22 @@ dq_status dq_td_update_stats(const float* q_online_s1_dev, const float* q_target
     DQ_REQUIRE(done_dev && lifetime_dev && step_reward_dev && stats_dev && n >= 1, DQ_ERR_INVALID, "dq_td_update_stats: bad statistics argument");
     TdStats ts = {done_dev, was_reset_dev, lifetime_dev, step_reward_dev, n, reinterpret_cast<unsigned long long*>(stats_dev)};
     return launch_td_update(q_online_s1_dev, q_target_s1_dev, q_s0_dev, reward_dev, terminal_dev, action_dev, index_dev, gamma, batch, n_actions,
-                            grad_scale, y_dev, dq_dev, metrics_dev, ts, stream);
+                            grad_scale, INFINITY, y_dev, dq_dev, metrics_dev, ts, stream);
+}
+
+dq_status dq_td_step(const dq_td_job* td, void* stream) {
+    DQ_REQUIRE(td, DQ_ERR_INVALID, "dq_td_step: null job");
+    float delta = INFINITY;
+    const dq_status rc = dq_td_delta(td->delta_clip, 1, &delta);
+    if (rc != DQ_OK) return rc;
+    TdStats ts;
+    memset(&ts, 0, sizeof(ts));
+    if (td->n > 0) {
+        DQ_REQUIRE(td->done_dev && td->lifetime_dev && td->step_reward_dev && td->stats_dev, DQ_ERR_INVALID, "dq_td_step: bad statistics argument");
+        ts = TdStats{td->done_dev, td->was_reset_dev, td->lifetime_dev, td->step_reward_dev, td->n, reinterpret_cast<unsigned long long*>(td->stats_dev)};
+    }
+    return launch_td_update(td->q_online_s1_dev, td->q_target_s1_dev, td->q_s0_dev, td->reward_dev, td->terminal_dev, td->action_dev, td->index_dev,
+                            td->gamma, td->batch, td->n_actions, td->grad_scale, delta, td->y_dev, td->dq_dev, td->metrics_dev, ts, stream);
 }
 
 dq_status dq_td_metrics(float* metrics_dev, int batch, void* stream) {
@@ -368,16 +384,29 @@ dq_status dq_td_target(const float* q_online_s1_dev, const float* q_target_s1_de
     return DQ_OK;
 }
 
-dq_status dq_td_loss_grad(const float* q_s0_dev, const int32_t* action_dev, const int32_t* index_dev, const float* y_dev, int batch,
-                          int n_actions, double grad_scale, float* dq_dev, float* metrics_dev, void* stream) {
+static dq_status launch_td_loss_grad(const float* q_s0_dev, const int32_t* action_dev, const int32_t* index_dev, const float* y_dev, int batch,
+                                     int n_actions, double grad_scale, float delta, float* dq_dev, float* metrics_dev, void* stream) {
     DQ_REQUIRE(q_s0_dev && action_dev && y_dev && dq_dev, DQ_ERR_INVALID, "dq_td_loss_grad: null argument");
     DQ_REQUIRE(batch >= 1 && n_actions >= 1, DQ_ERR_INVALID, "dq_td_loss_grad: bad sizes");
     const int blocks = (batch + 3) / 4 < TD_MAX_BLOCKS ? (batch + 3) / 4 : TD_MAX_BLOCKS;
-    td_loss_grad_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(q_s0_dev, action_dev, index_dev, y_dev, batch, n_actions, (float)grad_scale,
+    td_loss_grad_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(q_s0_dev, action_dev, index_dev, y_dev, batch, n_actions, (float)grad_scale, delta,
                                                                  dq_dev, metrics_dev);
     if (metrics_dev) td_metrics_kernel<<<1, 256, 0, (hipStream_t)stream>>>(metrics_dev, blocks, batch);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
+}
+
+dq_status dq_td_loss_grad(const float* q_s0_dev, const int32_t* action_dev, const int32_t* index_dev, const float* y_dev, int batch,
+                          int n_actions, double grad_scale, float* dq_dev, float* metrics_dev, void* stream) {
+    return launch_td_loss_grad(q_s0_dev, action_dev, index_dev, y_dev, batch, n_actions, grad_scale, INFINITY, dq_dev, metrics_dev, stream);
+}
+
+dq_status dq_td_loss_grad_clip(const float* q_s0_dev, const int32_t* action_dev, const int32_t* index_dev, const float* y_dev, int batch,
+                               int n_actions, double grad_scale, double delta_clip, float* dq_dev, float* metrics_dev, void* stream) {
+    float delta = INFINITY;
+    const dq_status rc = dq_td_delta(delta_clip, 0, &delta);
+    if (rc != DQ_OK) return rc;
+    return launch_td_loss_grad(q_s0_dev, action_dev, index_dev, y_dev, batch, n_actions, grad_scale, delta, dq_dev, metrics_dev, stream);
 }
 
 dq_status dq_adam_step(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev, size_t n, double lr, double beta_1,

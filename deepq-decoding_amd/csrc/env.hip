@@ -301,7 +301,7 @@ void dq_set_error(const char* fmt, ...) {
 
 extern "C" {
 
-int dq_version(void) { return 1; }
+int dq_version(void) { return 2; }
 const char* dq_last_error(void) { return g_err; }
 long dq_struct_size(int id) {
     switch (id) {

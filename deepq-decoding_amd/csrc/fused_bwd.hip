@@ -351,7 +351,7 @@ __global__ __launch_bounds__(DENSE_THREADS, 2) void dense_bwd_chain_kernel(Dense
     // ---- the TD step's three Q rows of this wave's two samples do not hang on the replay rows: requested first of all (round 3, second pass:
     //      they used to go out behind the first barrier, a round trip of their own) ----
     float loss = 0.f, mq = 0.f;
-    float yb[RPW] = {0.f, 0.f}, qv[RPW][2] = {{0.f, 0.f}, {0.f, 0.f}};
+    float dc[RPW] = {0.f, 0.f}, qv[RPW][2] = {{0.f, 0.f}, {0.f, 0.f}};     // dc: the sample's clipped TD error c(Q(s0)[a_b] - y), computed once
     int a_b[RPW] = {-1, -1};
     float q1[RPW][2] = {{0.f, 0.f}, {0.f, 0.f}}, q1t[RPW][2] = {{0.f, 0.f}, {0.f, 0.f}}, rw[RPW] = {0.f, 0.f};
     int term[RPW] = {0, 0};
@@ -467,8 +467,8 @@ __global__ __launch_bounds__(DENSE_THREADS, 2) void dense_bwd_chain_kernel(Dense
             w3r[u][1] = lane + 64 < a.w3q_rows ? row[lane + 64] : 0.f;
         }
     }
-    // ---- (TD step: y = r + gamma (1 - terminal) Q_target(s1)[argmax Q_online(s1)], dq = (Q(s0)[a] - y) * scale at the action taken,
-    //      dqn.hip td_update_kernel's arithmetic, one wave per sample) then the dueling backward:
+    // ---- (TD step: y = r + gamma (1 - terminal) Q_target(s1)[argmax Q_online(s1)], dq = c(Q(s0)[a] - y) * scale at the action taken (c: the
+    //      Huber loss's clamp at td.delta, common.h dq_huber_grad), dqn.hip td_update_kernel's arithmetic, one wave per sample) then the dueling backward:
     //      g3[b,0] = sum_a dq[b,a];  g3[b,1+a] = dq[b,a] - (1/A) sum_a' dq[b,a'] ---------------------------------------------
     if constexpr (TD) {
         // No load stage of its own any more (round 3: the Q rows are requested at the top of the kernel, the replay rows behind the preloads and
@@ -496,23 +496,25 @@ __global__ __launch_bounds__(DENSE_THREADS, 2) void dense_bwd_chain_kernel(Dense
             const int row = wave + DENSE_WAVES * u;
             if (row >= ns) continue;
             const int b = b0 + row;
-            yb[u] = rw[u] + (term[u] ? 0.f : a.td.gamma * qt[u]);
-            if (lane == 0 && a.td.y_out) a.td.y_out[b] = yb[u];
+            const float yb = rw[u] + (term[u] ? 0.f : a.td.gamma * qt[u]);
+            if (lane == 0 && a.td.y_out) a.td.y_out[b] = yb;
             float mx = -INFINITY;
 #pragma unroll
             for (int h = 0; h < 2; ++h) if (lane + 64 * h < A) mx = fmaxf(mx, qv[u][h]);
             mx = dq_wave_max(mx);
             // Q(s0)[a_b] lives in lane a_b & 63, half a_b >> 6 (a_b: one replay row's action, the same in every lane)
             const int ab = __builtin_amdgcn_readfirstlane(a_b[u]);
-            const float diff = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ab < 64 ? qv[u][0] : qv[u][1]), ab & 63)) - yb[u];
-            loss += 0.5f * diff * diff;
+            const float diff = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ab < 64 ? qv[u][0] : qv[u][1]), ab & 63)) - yb;
+            dc[u] = dq_huber_grad(diff, a.td.delta);                // (wave-uniform; every use below reads it instead of Q(s0)[a_b] - y)
+            loss += dq_huber_loss(diff, a.td.delta);
             mq += mx;
-            if (!(fabsf(diff * a.td.grad_scale * GS) < 32768.f) && lane == 0) atomicMax(a.skip_word, a.skip_tag);      // (never taken in a healthy run)
+            // (never taken in a healthy run; with a finite delta the host's scale keeps |dc| x grad_scale x GS <= 64: only a NaN TD error trips it)
+            if (!(fabsf(dc[u] * a.td.grad_scale * GS) < 32768.f) && lane == 0) atomicMax(a.skip_word, a.skip_tag);
             if (a.td.dq_out)
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int c = lane + 64 * h;
-                    if (c < A) a.td.dq_out[(size_t)b * A + c] = c == a_b[u] ? (qv[u][h] - yb[u]) * a.td.grad_scale : 0.f;
+                    if (c < A) a.td.dq_out[(size_t)b * A + c] = c == a_b[u] ? dc[u] * a.td.grad_scale : 0.f;
                 }
         }
     }
@@ -524,14 +526,13 @@ __global__ __launch_bounds__(DENSE_THREADS, 2) void dense_bwd_chain_kernel(Dense
         const float* dr = a.dq + (size_t)b * A;
         auto dval = [&](int h) {                                    // dq[b][lane + 64 h]
             const int c = lane + 64 * h;
-            return TD ? (c == a_b[u] ? (qv[u][h] - yb[u]) * a.td.grad_scale * GS : 0.f) : dr[c] * GS;
+            return TD ? (c == a_b[u] ? dc[u] * a.td.grad_scale * GS : 0.f) : dr[c] * GS;
         };
         if (N3 > 0) {
             float s = 0.f;
             if constexpr (TD) {                                         // one non-zero per row: its sum is that value (the butterfly's bits: x + 0 ... + 0)
                 const int ab = __builtin_amdgcn_readfirstlane(a_b[u]);
-                const float qa = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ab < 64 ? qv[u][0] : qv[u][1]), ab & 63));
-                s = (unsigned)ab < (unsigned)A ? (qa - yb[u]) * a.td.grad_scale * GS : 0.f;
+                s = (unsigned)ab < (unsigned)A ? dc[u] * a.td.grad_scale * GS : 0.f;
             } else {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) if (lane + 64 * h < A) s += dval(h);      // (a run-time trip count would index qv dynamically: scratch memory)
@@ -1850,7 +1851,15 @@ dq_status fused_backward(dq_qnet* Q, const float* params_dev, const float* dq_de
     if (phases & 1) {
     // ---- gradient scale (see grad_scale_kernel): host-known with the TD step fused in, else from max |dq| on the device ----------
     const float known = td ? td->grad_scale : Q->grad_scale_hint;  // the loss scale dq carries, when the host knows it
-    if (td && td->auto_scale) {                                     // measured on the device from this minibatch's TD errors (td_scale_kernel)
+    if (td && td->delta < INFINITY) {                               // Huber loss: |dq| <= delta x grad_scale is known before any kernel runs
+        // S = min(S_known, S_delta): S_known x grad_scale in [4, 8) as below, S_delta x grad_scale x delta in [32, 64) -- td_scale_kernel's rule with the
+        // minibatch's maximum replaced by its bound.  No finite TD error can trip the early range guard (|S dq| <= 64 < 2^15) and nothing is measured
+        // (auto_scale is moot); delta <= 8 gives S_known itself, i.e. the bits of the unclipped path wherever no sample is clipped.
+        int e = 0, ed = 0;
+        (void)frexp((double)known, &e);
+        (void)frexp((double)known * (double)td->delta, &ed);
+        Q->bwd_scale = (float)fmin(ldexp(1.0, 3 - e), ldexp(1.0, max(-100, min(100, 6 - ed))));
+    } else if (td && td->auto_scale) {                              // measured on the device from this minibatch's TD errors (td_scale_kernel)
         Q->bwd_scale = 0.f;                                         // = read gs_slot
         TdScaleArgs ta;
         ta.td = *td; ta.B = B; ta.A = Q->cfg.n_actions; ta.out = gs_slot; ta.work = reinterpret_cast<unsigned*>(gs_slot) + 4;

@@ -373,6 +373,7 @@ struct TdFused {
     int st_n;
     unsigned long long* st_stats;
     int auto_scale;                     // dq_td_job.auto_scale: the gradient scale from this minibatch's max |TD error| (fused_bwd.hip td_scale_kernel)
+    float delta;                        // dq_td_job.delta_clip as a float, +inf = none (common.h dq_td_delta): the Huber loss's delta; finite: bounds the gradient
 };
 // rider != NULL (needs td): the lattices' environment step (env_dev.h parameters, filled by env_fill_act_step) runs as extra
 // workgroups of the dense backward's first launch

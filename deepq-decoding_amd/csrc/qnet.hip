@@ -721,6 +721,7 @@ static TdFused td_fused_from(const dq_td_job* tdj) {
     td.st_done = tdj->done_dev; td.st_was_reset = tdj->was_reset_dev; td.st_lifetime = tdj->lifetime_dev;
     td.st_reward = tdj->step_reward_dev; td.st_n = tdj->n; td.st_stats = reinterpret_cast<unsigned long long*>(tdj->stats_dev);
     td.auto_scale = tdj->auto_scale ? 1 : 0;
+    (void)dq_td_delta(tdj->delta_clip, 1, &td.delta);               // (validated by check_td_job)
     return td;
 }
 
@@ -732,17 +733,13 @@ static dq_status check_td_job(const dq_qnet* Q, const dq_td_job* tdj) {
                Q->cfg.n_actions);
     DQ_REQUIRE(tdj->n == 0 || (tdj->done_dev && tdj->lifetime_dev && tdj->step_reward_dev && tdj->stats_dev && tdj->n > 0), DQ_ERR_INVALID,
                "dq_qnet_td_backward: bad statistics argument");
-    return DQ_OK;
+    float delta;
+    return dq_td_delta(tdj->delta_clip, 1, &delta);
 }
 
 static dq_status separate_td(const dq_td_job* tdj, void* stream) {
     DQ_REQUIRE(tdj->dq_dev, DQ_ERR_INVALID, "dq_qnet_td_backward: the per-layer path needs dq_dev");
-    return tdj->n > 0
-        ? dq_td_update_stats(tdj->q_online_s1_dev, tdj->q_target_s1_dev, tdj->q_s0_dev, tdj->reward_dev, tdj->terminal_dev, tdj->action_dev,
-                             tdj->index_dev, tdj->gamma, tdj->batch, tdj->n_actions, tdj->grad_scale, tdj->y_dev, tdj->dq_dev, tdj->metrics_dev,
-                             tdj->done_dev, tdj->was_reset_dev, tdj->lifetime_dev, tdj->step_reward_dev, tdj->n, tdj->stats_dev, stream)
-        : dq_td_update(tdj->q_online_s1_dev, tdj->q_target_s1_dev, tdj->q_s0_dev, tdj->reward_dev, tdj->terminal_dev, tdj->action_dev,
-                       tdj->index_dev, tdj->gamma, tdj->batch, tdj->n_actions, tdj->grad_scale, tdj->y_dev, tdj->dq_dev, tdj->metrics_dev, stream);
+    return dq_td_step(tdj, stream);                                 // dq_td_update(_stats) with the job's delta_clip
 }
 
 static dq_status backward_adam(dq_qnet* Q, float* params_dev, const float* dq_dev, const dq_td_job* tdj, float* grads_dev, float* m_dev,

@@ -243,6 +243,21 @@ def _backward_adam(self, params, dq, grads, m, v, t, lr, beta_1=0.9, beta_2=0.99
 QNetwork.backward_adam = _backward_adam
 
 
+def check_delta_clip(delta_clip):
+    """keras-rl's delta_clip as a float: +inf (the default) = the squared error, a finite value > 0 = the Huber loss at that delta.  keras-rl asserts
+    delta > 0: zero, negative, NaN and values that round to float32 zero are a ValueError."""
+    d = float(delta_clip)
+    if not (d > 0.0 and np.float32(d) > 0.0):
+        raise ValueError(f"delta_clip must be > 0 (keras-rl's huber_loss asserts clip_value > 0), got {delta_clip!r}")
+    return d
+
+
+def _c_delta(delta_clip):
+    """dq_td_job.delta_clip: 0 for +inf (what a zero-initialised job means), else the value."""
+    d = check_delta_clip(delta_clip)
+    return 0.0 if np.isinf(d) else d
+
+
 def _td_job(td):
     B, A = td["q_s0"].shape
     j = _lib.TdJob()
@@ -251,6 +266,7 @@ def _td_job(td):
     j.gamma, j.grad_scale, j.batch, j.n_actions = float(td["gamma"]), float(td.get("grad_scale") or 1.0 / B), B, A
     j.y_dev, j.dq_dev, j.metrics_dev = ptr(td.get("y")), ptr(td.get("dq")), ptr(td.get("metrics"))
     j.auto_scale = int(bool(td.get("auto_scale", False)))
+    j.delta_clip = _c_delta(td["delta_clip"] if td.get("delta_clip") is not None else np.inf)
     st = td.get("step_stats")
     if st is not None:
         done, was_reset, lifetime, step_reward, n, stats = st
@@ -262,7 +278,8 @@ def _td_job(td):
 def _td_backward_adam(self, params, td, grads, m, v, t, lr, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
     """td_update() (+ episode bookkeeping) + backward() + adam_step() with the TD step computed by the backward's first kernel and the
     optimizer step applied by its last one.  td: dict with q_online_s1, q_target_s1, q_s0, reward, terminal, action, index, gamma,
-    grad_scale and optional y, dq, metrics, step_stats = (done, was_reset, lifetime, reward, n, stats)."""
+    grad_scale and optional y, dq, metrics, step_stats = (done, was_reset, lifetime, reward, n, stats), auto_scale, delta_clip (keras-rl's
+    Huber delta; default inf: the squared error)."""
     j = _td_job(td)
     check(self.L.dq_qnet_td_backward_adam(self._h, ptr(params), ctypes.byref(j), ptr(grads), ptr(m), ptr(v), float(lr), float(beta_1),
                                           float(beta_2), float(epsilon), int(t), self._stream()))
@@ -338,25 +355,39 @@ def td_target(q_online_s1, q_target_s1, reward, terminal, gamma, index=None, out
     return out
 
 
-def td_loss_grad(q_s0, action, y, grad_scale=None, index=None, dq=None, metrics=None):
+def td_loss_grad(q_s0, action, y, grad_scale=None, index=None, dq=None, metrics=None, delta_clip=np.inf):
+    """dq and (loss, mean_q) of keras-rl's clipped_masked_error: the squared error (delta_clip = inf, dq_td_loss_grad) or the Huber loss at a finite
+    delta_clip (dq_td_loss_grad_clip)."""
     B, A = q_s0.shape
+    delta_clip = check_delta_clip(delta_clip)
     if dq is None:
         dq = torch.empty_like(q_s0)
     if metrics is None:
         metrics = torch.empty(TD_METRICS_FLOATS, dtype=torch.float32, device=q_s0.device)
-    check(_lib.lib().dq_td_loss_grad(ptr(q_s0), ptr(action), ptr(index), ptr(y), B, A, 1.0 / B if grad_scale is None else float(grad_scale),
-                                     ptr(dq), ptr(metrics), _lib.current_stream(q_s0.device)))
+    gs = 1.0 / B if grad_scale is None else float(grad_scale)
+    if np.isinf(delta_clip):
+        check(_lib.lib().dq_td_loss_grad(ptr(q_s0), ptr(action), ptr(index), ptr(y), B, A, gs, ptr(dq), ptr(metrics), _lib.current_stream(q_s0.device)))
+    else:
+        check(_lib.lib().dq_td_loss_grad_clip(ptr(q_s0), ptr(action), ptr(index), ptr(y), B, A, gs, delta_clip, ptr(dq), ptr(metrics),
+                                              _lib.current_stream(q_s0.device)))
     return dq, metrics
 
 
 def td_update(q_online_s1, q_target_s1, q_s0, reward, terminal, action, gamma, grad_scale=None, index=None, y=None, dq=None, metrics=None,
-              step_stats=None):
+              step_stats=None, delta_clip=np.inf):
     """td_target + td_loss_grad in one launch (dq_td_update); metrics[0..1] are valid only after td_metrics().
     step_stats = (done, was_reset, lifetime, reward, n, stats): the episode bookkeeping of the step just taken rides along
-    (dq_td_update_stats)."""
+    (dq_td_update_stats).  A finite delta_clip: keras-rl's Huber loss at that delta (dq_td_step)."""
     B, A = q_s0.shape
+    delta_clip = check_delta_clip(delta_clip)
     if dq is None:
         dq = torch.empty_like(q_s0)
+    if not np.isinf(delta_clip):
+        j = _td_job(dict(q_online_s1=q_online_s1, q_target_s1=q_target_s1, q_s0=q_s0, reward=reward, terminal=terminal, action=action,
+                         index=index, gamma=gamma, grad_scale=1.0 / B if grad_scale is None else float(grad_scale), y=y, dq=dq, metrics=metrics,
+                         step_stats=step_stats, delta_clip=delta_clip))
+        check(_lib.lib().dq_td_step(ctypes.byref(j), _lib.current_stream(q_s0.device)))
+        return dq
     if step_stats is not None:
         done, was_reset, lifetime, step_reward, n, stats = step_stats
         check(_lib.lib().dq_td_update_stats(ptr(q_online_s1), ptr(q_target_s1), ptr(q_s0), ptr(reward), ptr(terminal), ptr(action), ptr(index),

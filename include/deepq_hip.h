@@ -442,7 +442,8 @@ dq_status dq_qnet_mark_conv_backward(dq_qnet* net, void* hip_event);
  * parameter and moments untouched.  This call synchronises `stream`, returns DQ_ERR_RANGE if the flag was raised since the last call
  * and clears it; DQ_OK otherwise (always on the per-layer f32 path).  The agent loop calls it at its host synchronisation points.  With
  * S x grad_scale in [4, 8) the guard trips for |TD error| of a few thousand (the reference's recorded losses, trained_models/ * / * /
- * training_history.json, stay below 160, i.e. |TD error| ~ 20).  No reference counterpart. */
+ * training_history.json, stay below 160, i.e. |TD error| ~ 20); with a finite dq_td_job.delta_clip the host picks S from the bound
+ * |dq| <= delta_clip x grad_scale and no finite TD error trips it (a NaN one still does).  No reference counterpart. */
 /* (round 6) The fused FORWARD is guarded too: its activations travel as f16 pieces as well, and one of 65504 or more would turn into inf, the products it enters
  * into NaN and the next ReLU into 0 -- finite, wrong Q-values.  Every layer's epilogue compares what it splits with the range, the packing launch checks every
  * parameter (finite, < 65504), the dense chain checks the Q-values it stores; any of them raises the same device-side flag and this call returns DQ_ERR_RANGE with
@@ -450,8 +451,8 @@ dq_status dq_qnet_mark_conv_backward(dq_qnet* net, void* hip_event);
 dq_status dq_qnet_range_check(dq_qnet* net, void* stream);
 /* How many optimizer steps the guard's early half discarded WHOLE since the last call (the TD step saw a sample beyond the host-known scale's range: the
  * final reduction wrote NaN into every gradient element and moved no parameter -- with several ranks the all-reduce carries the NaNs to all of them and
- * dq_qnet_adam_step counts on each); synchronises `stream`, clears the count.  What the reference (delta_clip = inf, fp32) would have applied and this
- * path did not: the agent loop logs it.  No reference counterpart. */
+ * dq_qnet_adam_step counts on each); synchronises `stream`, clears the count.  What the reference (fp32) would have applied and this path did not
+ * (with a finite delta_clip only an update whose TD errors include a NaN): the agent loop logs it.  No reference counterpart. */
 dq_status dq_qnet_range_discarded(dq_qnet* net, unsigned* count, void* stream);
 
 /* The same backward in two phases, for overlapping the gradient all-reduce with compute on several GPUs (no reference
@@ -484,7 +485,7 @@ dq_status dq_test_bookkeeping(const uint8_t* done_dev, const uint8_t* was_reset_
 dq_status dq_qnet_adam_step(dq_qnet* net, float* params_dev, const float* grads_dev, float* m_dev, float* v_dev, double lr, double beta_1,
                             double beta_2, double epsilon, uint64_t t, void* stream);
 
-/* The learner half of one DQNAgent.backward in the fewest launches: dq_td_update (+ dq_episode_stats when n > 0) computed in the
+/* The learner half of one DQNAgent.backward in the fewest launches: dq_td_step (+ dq_episode_stats when n > 0) computed in the
  * dense backward's first kernel, then dq_qnet_backward, then dq_adam_step on the final reduction.  Same y / dq / gradient / parameter
  * bits as the separate calls; the loss / mean_q partials are summed in a different order (dq_td_metrics reads them the same way).
  * y_dev, dq_dev (needed only by the per-layer path), metrics_dev nullable.
@@ -510,10 +511,16 @@ typedef struct dq_td_job {
     const float* step_reward_dev;
     int n;
     uint64_t* stats_dev;
-    int auto_scale;                 /* fused backward only.  0: its gradients are carried at the power-of-two scale that follows from grad_scale (TD errors up to
-                                     * a few thousand; beyond: dq_qnet_range_check).  1: the scale is MEASURED -- max |TD error x grad_scale| of this minibatch, by one
-                                     * small launch in front of the backward -- so that any finite TD error fp32 can hold is carried, as in the reference's
-                                     * TensorFlow arithmetic (keras-rl delta_clip = inf, Single_Point_Training_Script.py:119-127) */
+    int auto_scale;                 /* fused backward with delta_clip = inf only.  0: its gradients are carried at the power-of-two scale that follows from
+                                     * grad_scale (TD errors up to a few thousand; beyond: dq_qnet_range_check).  1: the scale is MEASURED -- max |TD error x
+                                     * grad_scale| of this minibatch, by one small launch in front of the backward -- so that any finite TD error fp32 can hold is
+                                     * carried, as in the reference's TensorFlow arithmetic (Single_Point_Training_Script.py:119-127).  Ignored with a finite
+                                     * delta_clip: the bound on |dq| gives the scale */
+    double delta_clip;              /* keras-rl DQNAgent(delta_clip): the Huber loss's delta (dq_td_loss_grad_clip's semantics).  0 (a zero-initialised job) or
+                                     * +inf: none, the squared error -- the reference's setting, bit for bit as before this field existed; > 0: Huber, and the
+                                     * fused backward's gradient scale S is the largest power of two that keeps both S x grad_scale < 8 and S x grad_scale x
+                                     * delta_clip < 64 (no finite TD error can trip the range guard; delta_clip <= 8 keeps the unclipped S).  Negative or NaN:
+                                     * DQ_ERR_INVALID.  Read as a float. */
 } dq_td_job;
 dq_status dq_qnet_td_backward_adam(dq_qnet* net, float* params_dev, const dq_td_job* td, float* grads_dev, float* m_dev, float* v_dev,
                                    double lr, double beta_1, double beta_2, double epsilon, uint64_t t, void* stream);
@@ -596,6 +603,15 @@ dq_status dq_td_target(const float* q_online_s1_dev, const float* q_target_s1_de
 #define DQ_TD_METRICS_FLOATS 2050
 dq_status dq_td_loss_grad(const float* q_s0_dev, const int32_t* action_dev, const int32_t* index_dev, const float* y_dev,
                           int batch, int n_actions, double grad_scale, float* dq_dev, float* metrics_dev, void* stream);
+/* The same with keras-rl's finite delta_clip (huber_loss / clipped_masked_error of keras-rl 0.4.2), fp32, delta = (float)delta_clip,
+ * x_b = Q[b,a_b] - y_b:
+ *   loss        mean_b h(x_b),  h(x) = 0.5 x^2 if |x| <= delta, else delta (|x| - 0.5 delta)
+ *   dq_dev      grad_scale * c(x_b) at a_b, 0 elsewhere,  c(x) = |x| > delta ? copysign(delta, x) : x
+ * The clamp is that compare: a NaN TD error stays NaN (as in TensorFlow; the fused backward's range guard sees it), an infinite one
+ * gives +-delta.  delta_clip = +inf is dq_td_loss_grad, bit for bit; delta_clip <= 0 or NaN: DQ_ERR_INVALID (keras-rl asserts > 0). */
+dq_status dq_td_loss_grad_clip(const float* q_s0_dev, const int32_t* action_dev, const int32_t* index_dev, const float* y_dev,
+                               int batch, int n_actions, double grad_scale, double delta_clip, float* dq_dev, float* metrics_dev,
+                               void* stream);
 
 /* dq_td_target + dq_td_loss_grad in one launch (same arithmetic, same per-block metric partials), WITHOUT the final metric
  * reduction: call dq_td_metrics(metrics_dev, batch) before reading metrics_dev[0..1] (the training loop only reads them at its
@@ -609,6 +625,10 @@ dq_status dq_td_update_stats(const float* q_online_s1_dev, const float* q_target
                              int n_actions, double grad_scale, float* y_dev, float* dq_dev, float* metrics_dev, const uint8_t* done_dev,
                              const uint8_t* was_reset_dev, const uint32_t* lifetime_dev, const float* step_reward_dev, int n,
                              uint64_t* stats_dev, void* stream);
+/* dq_td_update (td->n == 0) or dq_td_update_stats (td->n > 0) driven by a dq_td_job, with its delta_clip (dq_td_loss_grad_clip's
+ * semantics; 0 / +inf: the squared error, the bits of those calls).  auto_scale is not read.  The per-layer path of the
+ * dq_qnet_td_backward_* calls runs this. */
+dq_status dq_td_step(const dq_td_job* td, void* stream);
 dq_status dq_td_metrics(float* metrics_dev, int batch, void* stream);
 
 /* dq_replay_sample (for the next update) + dq_episode_stats (of the step just taken) in one launch. */
