@@ -84,6 +84,17 @@ class EnvRing(ctypes.Structure):
                 ("patch_ring_dev", ctypes.c_void_p), ("patch_stride_words", ctypes.c_int32), ("n_slots", ctypes.c_int32), ("slot0", ctypes.c_int32)]
 
 
+class DecodeCfg(ctypes.Structure):
+    """dq_decode_cfg (include/deepq_hip.h)."""
+    _fields_ = [("d", ctypes.c_int32), ("volume_depth", ctypes.c_int32), ("error_model", ctypes.c_int32), ("use_Y", ctypes.c_int32),
+                ("masked_greedy", ctypes.c_int32), ("max_actions", ctypes.c_int32), ("action_planes", ctypes.c_int32), ("obs_form", ctypes.c_int32)]
+
+
+DECODE_ACTIVE, DECODE_IDENTITY, DECODE_REPEAT, DECODE_STOPPED = 0, 1, 2, 3
+DECODE_PLANES_ENV, DECODE_PLANES_README = 0, 1
+DECODE_OBS_UINT8, DECODE_OBS_PATCH = 0, 1
+
+
 _vp, _i, _u32, _u64, _dbl = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
 _sz = ctypes.c_size_t
 _seedp = ctypes.POINTER(ctypes.c_uint32)
@@ -171,6 +182,9 @@ SIGNATURES = {
     "dq_td_metrics": (_i, [_vp, _i, _vp]),
     "dq_post_step": (_i, [_vp, _i, _i, _i, _i, _i, _seedp, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "dq_adam_step": (_i, [_vp, _vp, _vp, _vp, _sz, _dbl, _dbl, _dbl, _dbl, _u64, _vp]),
+    "dq_decode_create": (_i, [ctypes.POINTER(DecodeCfg), _i, ctypes.POINTER(_vp)]),
+    "dq_decode_destroy": (None, [_vp]),
+    "dq_decode_run": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), _vp]),
     "dq_prof_kernel_count": (_i, []),
     "dq_prof_kernel_name": (ctypes.c_char_p, [_i]),
     "dq_prof_kernel_symbol": (ctypes.c_char_p, [_i]),

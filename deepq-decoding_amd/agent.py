@@ -430,6 +430,40 @@ class DQNAgent:
             return int(max(legal, key=lambda a: (q[a], -a)))
         return int(np.argmax(q))
 
+    # -- batched decoding of measured volumes (README.md:786-829, notebook 3b; decoder.py) --------------------------------------
+    def decode(self, faulty_syndromes, env=None, masked_greedy=None, max_actions=None, action_planes="environment", obs_form=None,
+               chunk=None, to_host=True):
+        """Decodes faulty syndrome volumes (uint8-like 0/1 [N, volume_depth, d+1, d+1], or one volume) with the online weights on the
+        device: per volume the greedy actions up to the first identity or repeat (DESIGN.md "Batched decoding").  Returns a
+        decoder.DecodeResult (corrections, n_corrections, frame, status).  env: the lattice (binds the agent to it); default the bound
+        environment.  masked_greedy: default the test policy's.  obs_form: "patch" / "uint8" (default: patch words where the network
+        accepts them).  chunk: volumes per device launch sequence (default decoder.DEFAULT_CHUNK)."""
+        from . import decoder as D
+        lattice_env = env if env is not None else self._env
+        if lattice_env is None:
+            raise RuntimeError("decode() needs the lattice: pass env= or bind the agent to an environment first (fit()/test())")
+        d, model, use_Y, depth = D.lattice_of(lattice_env)
+        shape = tuple(getattr(faulty_syndromes, "shape", np.shape(faulty_syndromes)))
+        D.check_decode_args(d, model, use_Y, depth, shape, action_planes, max_actions, obs_form)
+        D.check_binary(faulty_syndromes)
+        if env is not None:
+            self._bind(env)
+        if masked_greedy is None:
+            masked_greedy = self.test_policy.current(False)[1]
+        chunk = D.DEFAULT_CHUNK if chunk is None else int(chunk)
+        key = (d, model, use_Y, depth, bool(masked_greedy), max_actions, action_planes, obs_form, chunk, str(self._core.device))
+        if getattr(self, "_decoder_key", None) != key:
+            old = getattr(self, "_decoder", None)
+            self._decoder = None
+            if old is not None:
+                old.close()
+            self._decoder = D.BatchDecoder(self.model.input_shape, self.model.c_layers, self.model.ff_layers, self.nb_actions, d, model, use_Y,
+                                           depth, dueling=self.enable_dueling_network, masked_greedy=bool(masked_greedy),
+                                           max_actions=max_actions, action_planes=action_planes, obs_form=obs_form, chunk=chunk,
+                                           device=self._core.device)
+            self._decoder_key = key
+        return self._decoder.decode(self._core.params, faulty_syndromes, to_host=to_host)
+
     def compute_q_values(self, observation):
         obs = torch.as_tensor(np.asarray(observation), dtype=torch.uint8, device=self._core.device).reshape((1,) + tuple(self.model.input_shape)).contiguous()
         return self._net.forward(self._core.params, obs, batch=1)[0].cpu().numpy()

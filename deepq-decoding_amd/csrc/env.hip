@@ -301,7 +301,7 @@ void dq_set_error(const char* fmt, ...) {
 
 extern "C" {
 
-int dq_version(void) { return 2; }
+int dq_version(void) { return 3; }
 const char* dq_last_error(void) { return g_err; }
 long dq_struct_size(int id) {
     switch (id) {
@@ -313,6 +313,7 @@ long dq_struct_size(int id) {
         case 5: return (long)sizeof(dq_td_job);
         case 6: return (long)sizeof(dq_env_step_job);
         case 7: return (long)sizeof(dq_env_ring);
+        case 8: return (long)sizeof(dq_decode_cfg);
         default: return -1;
     }
 }

@@ -68,7 +68,7 @@ int dq_version(void);
 const char* dq_build_digest(void);
 const char* dq_last_error(void);
 /* sizeof() of the public structs as THIS library was compiled: 0 dq_env_cfg, 1 dq_env_info, 2 dq_sample_job, 3 dq_qnet_cfg, 4 dq_qnet_job, 5 dq_td_job,
- * 6 dq_env_step_job; -1 for any other id.  A binding (the ctypes structures of _lib.py) checks its own layouts against it: a struct of the wrong size handed
+ * 6 dq_env_step_job, 7 dq_env_ring, 8 dq_decode_cfg; -1 for any other id.  A binding (the ctypes structures of _lib.py) checks its own layouts against it: a struct of the wrong size handed
  * across the boundary is silent memory corruption (tests/test_abi.py).  No reference counterpart. */
 long dq_struct_size(int id);
 /* Number of visible HIP devices (0 if none / runtime unavailable).  Never fails. */
@@ -649,6 +649,55 @@ dq_status dq_episode_stats(const uint8_t* done_dev, const uint8_t* was_reset_dev
  * form -- such elements skipped and flagged -- is dq_qnet_adam_step and the optimizer step riding on the fused backward.) */
 dq_status dq_adam_step(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev, size_t n, double lr,
                        double beta_1, double beta_2, double epsilon, uint64_t t, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched decoding: replaces the reference's "Using a Trained Decoder in Production" loop (README.md:786-829, notebook 3 section 3b),
+ * which calls dqn.forward(input_state) once per action of one volume.  Here n volumes are decoded together on the device.
+ *
+ * Input: syndromes_dev uint8 [n][volume_depth][d+1][d+1] (4-byte aligned), the faulty syndrome slices of each volume on the reference's
+ * (d+1) x (d+1) grid, cells 0 or 1 (the binding rejects other values; the kernels read any nonzero cell as 1).  Cells are copied into the
+ * observation exactly as padding_syndrome does (Environments.py:273-299), dead corners included.
+ * Per volume, starting with empty action planes and legal set = reset_legal_moves of the summed volume (Environments.py:238-258):
+ *   1. observation = the padded slices + the action planes;  2. Q = the network's forward with params_dev;
+ *   3. a = first maximum of Q (policy_kernel's rule with eps = 0), over the legal set when cfg.masked_greedy != 0;
+ *   4. stop if a is the identity (status DQ_DECODE_IDENTITY) or already completed (DQ_DECODE_REPEAT: Environments.py:131 treats a repeat as
+ *      the identity); the stopping action is not recorded;
+ *   5. otherwise record a, mark completed_actions[a], add the neighbours x layers of a newly acted-on qubit to the legal set
+ *      (Environments.py:186-196), set the action-plane cell; after cfg.max_actions recorded actions stop (DQ_DECODE_STOPPED).
+ * That is the sequence of actions a greedy agent takes in the environment on that volume up to its first identity.
+ * Action planes: DQ_DECODE_PLANES_ENV marks qubit q of layer l for action l d^2 + q (Environments.py:199-201).  DQ_DECODE_PLANES_README
+ * (X model only: one action layer) reproduces README.md:807 statement for statement: `padding_actions(corrections)` with the LIST of action
+ * indices, i.e. qubit i is marked iff corrections[i] != 0.
+ * Outputs: corrections_dev int32 [n][max_actions] in the order chosen, padded with -1; n_corr_dev int32 [n]; frame_dev uint8 [n][d][d] the
+ * net Pauli frame of the recorded corrections as hidden_state codes 0..3 (XOR of index_to_move over them, env.hip's layer -> Pauli map);
+ * status_dev uint8 [n].
+ * The network: cfg.obs_form DQ_DECODE_OBS_PATCH reads patch words (dq_env_patch_output's layout; needs dq_qnet_set_patch_input(net,
+ * volume_depth, stride)), DQ_DECODE_OBS_UINT8 padded uint8 images.  packed_dev: dq_qnet_pack(params_dev) output for this network (NULL:
+ * every iteration packs).  n <= min(max_volumes, the network's max_batch).  Lattices: d <= 7 and num_actions <= 128 (DQ_ERR_UNSUPPORTED).
+ * Per iteration: one dq_qnet_forward_multi over the volumes still decoding (index gather over the active list), one selection launch and
+ * one stable compaction launch; the host then reads the 4-byte active count to size the next launches.  That read is the loop's one host
+ * wait, so dq_decode_run SYNCHRONISES `stream` once per iteration (at most max_actions iterations; *iterations receives the number) and is
+ * not hipGraph-capturable.  At the end it runs dq_qnet_range_check(net): a forward that met a non-finite value returns DQ_ERR_RANGE
+ * ("dq_qnet_range_check[forward]") and its outputs are not to be used.  No reference counterpart beyond the loop above. */
+typedef struct dq_decode dq_decode;
+enum { DQ_DECODE_ACTIVE = 0, DQ_DECODE_IDENTITY = 1, DQ_DECODE_REPEAT = 2, DQ_DECODE_STOPPED = 3 };
+enum { DQ_DECODE_PLANES_ENV = 0, DQ_DECODE_PLANES_README = 1 };
+enum { DQ_DECODE_OBS_UINT8 = 0, DQ_DECODE_OBS_PATCH = 1 };
+typedef struct {
+    int32_t d;              /* 3, 5 or 7 */
+    int32_t volume_depth;   /* 1..16 */
+    int32_t error_model;    /* DQ_MODEL_* */
+    int32_t use_Y;
+    int32_t masked_greedy;  /* 0: plain argmax (notebook 3b's dqn.forward), 1: argmax over the legal set (test()'s GreedyQPolicy(masked_greedy=True)) */
+    int32_t max_actions;    /* 1 .. num_actions - 1 */
+    int32_t action_planes;  /* DQ_DECODE_PLANES_ENV / DQ_DECODE_PLANES_README */
+    int32_t obs_form;       /* DQ_DECODE_OBS_UINT8 / DQ_DECODE_OBS_PATCH */
+} dq_decode_cfg;
+/* Owns the per-volume state, observation rows, Q rows and active lists for up to max_volumes volumes. */
+dq_status dq_decode_create(const dq_decode_cfg* cfg, int max_volumes, dq_decode** out);
+void dq_decode_destroy(dq_decode* dec);
+dq_status dq_decode_run(dq_decode* dec, dq_qnet* net, const float* params_dev, const void* packed_dev, const uint8_t* syndromes_dev, int n,
+                        int32_t* corrections_dev, int32_t* n_corr_dev, uint8_t* frame_dev, uint8_t* status_dev, int* iterations, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Live kernel timing (measurement only; no reference counterpart).  dq_prof_arm(id, n) times up to n
