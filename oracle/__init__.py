@@ -10,7 +10,8 @@ back to this code.
 Pinning status
 --------------
 * Environment half (``lattice.py``, ``env_oracle.py``, ``env_oracle.c``,
-  ``referee.py``, ``philox.py``): PINNED.  Checked against golden vectors made
+  ``env_oracle_wide.c``, ``referee.py``, ``matching_referee.py``,
+  ``philox.py``): PINNED.  Checked against golden vectors made
   by importing the reference's own ``Environments.py`` /
   ``Function_Library.py`` in the build container under an injected RNG stream
   (``tools/gen_golden.py`` -> ``tests/golden/*.npz``) and against the one
