@@ -109,6 +109,7 @@ SIGNATURES = {
     "dq_env_destroy": (None, [_vp]),
     "dq_env_get_info": (_i, [_vp, ctypes.POINTER(EnvInfo)]),
     "dq_env_set_rates": (_i, [_vp, _dbl, _dbl]),
+    "dq_env_set_rates_per_lattice": (_i, [_vp, _vp, _vp, _i, _vp]),
     "dq_env_build_referee": (_i, [_vp, _vp]),
     "dq_env_build_referee_ml": (_i, [_vp, _dbl, _vp]),
     "dq_env_set_referee": (_i, [_vp, _vp, _vp]),
@@ -134,6 +135,7 @@ SIGNATURES = {
     "dq_envb_destroy": (None, [_vp]),
     "dq_envb_get_info": (_i, [_vp, ctypes.POINTER(EnvInfo), ctypes.POINTER(_i)]),
     "dq_envb_set_rates": (_i, [_vp, _dbl, _dbl]),
+    "dq_envb_set_rates_per_lattice": (_i, [_vp, _vp, _vp, _i, _vp]),
     "dq_envb_reset": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_envb_step": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_envb_act_step": (_i, [_vp, _vp, _dbl, _i, _seedp, _u64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

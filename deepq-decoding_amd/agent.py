@@ -670,10 +670,74 @@ class DQNAgent:
         finally:
             core.end_eval()
 
+    def test_error_rates(self, env, error_rates, nb_episodes=1, p_meas=None, verbose=1, interval=100):
+        """The evaluation sweep of TRAIN:164-222 -- `nb_episodes` greedy episodes at each rate of `error_rates` -- as ONE batched
+        evaluation: the bound VectorEnv's N lattices are split into K = len(error_rates) contiguous blocks of m = N // K; block k runs at
+        error_rates[k] (p_meas: None = the same rates, a scalar, or one rate per entry) and shares its nb_episodes over its m lattices by
+        test()'s ceil-share rule; lattices beyond K m run but record nothing.  The wall time is that of the slowest rate instead of the
+        sum over the rates.  Returns {rate: History} with test()'s keys, each in test()'s order (vector step, then lattice), and the
+        same entries as test() on a VectorEnv holding that block's lattices alone (env_id_base = the block's first global id, same seed
+        and history).  The environment's previous rates are restored on the way out."""
+        venv = env._v if isinstance(env, Surface_Code_Environment_Multi_Decoding_Cycles) else env
+        rates = [float(r) for r in error_rates]
+        K, N = len(rates), int(venv.n_envs)
+        if K < 1:
+            raise ValueError("test_error_rates: no error rates")
+        if K > N:
+            raise ValueError(f"test_error_rates: {K} error rates need at least {K} lattices, the environment has {N}")
+        if len(set(rates)) != K:
+            raise ValueError("test_error_rates: the error rates must be distinct (they key the result)")
+        if p_meas is None:
+            meas = rates
+        elif np.ndim(p_meas) == 0:
+            meas = [float(p_meas)] * K
+        else:
+            meas = [float(r) for r in p_meas]
+            if len(meas) != K:
+                raise ValueError(f"test_error_rates: {len(meas)} measurement rates for {K} error rates")
+        for r in rates + meas:
+            if not (0.0 <= r <= 1.0):
+                raise ValueError(f"test_error_rates: rate {r!r} is not in [0, 1]")
+        venv = self._bind(env)
+        m = N // K
+        ph, pm = np.empty(N), np.empty(N)
+        ph[:K * m] = np.repeat(rates, m); pm[:K * m] = np.repeat(meas, m)
+        ph[K * m:], pm[K * m:] = rates[-1], meas[-1]                 # (idle lattices: any valid rate)
+        quota = np.zeros(N, dtype=np.int64)
+        share = np.full(m, nb_episodes // m, dtype=np.int64)
+        share[:nb_episodes % m] += 1
+        quota[:K * m] = np.tile(share, K)
+        core = self._core
+        self.training = False
+        if verbose >= 1:
+            print(f"Testing for {nb_episodes} episodes at each of {K} error rates ({m} lattices each) ...")
+        eps, masked = self.test_policy.current(False)
+        previous = venv._rate_forms()
+        venv.set_rates(ph, pm)
+        core.begin_eval()
+        try:
+            rec = self._test_records(core, venv, N, quota, eps, masked)
+        finally:
+            core.end_eval()
+            venv.set_rates(*previous)
+        out = {}
+        for k, r in enumerate(rates):
+            sel = rec[(rec[:, 1] >= k * m) & (rec[:, 1] < (k + 1) * m)]
+            out[r] = self._history_from_records(sel, verbose >= 2, interval)
+            if verbose >= 1 and len(sel):
+                print(f"p = {r}: {len(sel)} episodes, average lifetime {out[r].history['episode_lifetimes_rolling_avg'][-1]:.3f}")
+        return out
+
     def _test_loop(self, core, venv, N, quota, eps, masked, history, verbose, interval, sync_interval=None):
         """Device-resident: the episode records are appended on the device (dq_test_bookkeeping, one small launch per vector step); the host
         looks at the record counter every `sync_interval` steps only, so a batched evaluation costs what its kernels cost (rounds 1-2 did
         four device-to-host copies and a Python loop over the finished lattices per vector step)."""
+        rec = self._test_records(core, venv, N, quota, eps, masked, sync_interval)
+        return self._history_from_records(rec, verbose >= 2, interval, history)
+
+    def _test_records(self, core, venv, N, quota, eps, masked, sync_interval=None):
+        """_test_loop's device part: the episode records (vector step, lattice, reward bits, length, lifetime), sorted by vector step, then
+        lattice: the serial loop's order."""
         from ._lib import check, ptr
         dev = core.device
         total = int(quota.sum())
@@ -697,15 +761,20 @@ class DQNAgent:
                 break
         rec = records.cpu().numpy()[:total]
         rec = rec[np.lexsort((rec[:, 1], rec[:, 0]))]                     # by vector step, then lattice: the serial loop's order
-        lifetimes, run = [], 0.0
+        core.read_stats()
+        return rec
+
+    @staticmethod
+    def _history_from_records(rec, show, interval, history=None):
+        history = History() if history is None else history
+        run = 0.0
         for episode, (t, i, rbits, length, life) in enumerate(rec, 1):
             run += int(life)
             logs = {"episode_reward": float(np.int32(rbits).view(np.float32)), "nb_steps": int(length), "episode_lifetime": int(life),
                     "episode_lifetimes_rolling_avg": run / episode}
             history.append(logs)
-            if verbose >= 2 and (episode - 1) % max(1, interval) == 0:
+            if show and (episode - 1) % max(1, interval) == 0:
                 print(f"-----------------\nEpisode: {episode}\nThis Episode Length: {logs['nb_steps']}\n"
                       f"This Episode Reward: {logs['episode_reward']}\nThis Episode Lifetime: {logs['episode_lifetime']}\n\n"
                       f"Episode Lifetimes Avg: {logs['episode_lifetimes_rolling_avg']:.3f}\n")
-        core.read_stats()
         return history

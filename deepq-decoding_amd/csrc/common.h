@@ -77,6 +77,43 @@ static inline u64 dq_rate_threshold(double p) {
     u64 f = (u64)t;
     return ((double)f < t) ? f + 1 : f;
 }
+// Per-lattice error rates (dq_env_set_rates_per_lattice / dq_envb_set_rates_per_lattice): lattice i's thresholds at [2 i] (physical) and [2 i + 1]
+// (measurement) of a device table owned by the handle, 2 n + 2 words (the last pair pads the two-lattices-per-wave load of env_dev.h env_block2).
+// The upload is ONE copy ordered on the caller's stream, out of a pinned staging buffer of the handle: the caller's arrays are read before the call
+// returns; the device table is allocated once and written only by that copy, i.e. behind every earlier launch of the stream and ahead of every later
+// one; the staging buffer is refilled only once the previous copy out of it has completed (its event).  POD: zeroed with the handle.
+struct DqRateTable {
+    u64* dev;
+    u64* host;
+    hipEvent_t copied;
+    bool pending;
+};
+static inline dq_status dq_rate_table_upload(DqRateTable& R, int n, const double* p_phys, const double* p_meas, hipStream_t st) {
+    DQ_REQUIRE(p_phys && p_meas, DQ_ERR_INVALID, "per-lattice rates: null array");
+    for (int i = 0; i < n; ++i)                                      // (NaN fails both compares; an infinity fails one)
+        DQ_REQUIRE(p_phys[i] >= 0.0 && p_phys[i] <= 1.0 && p_meas[i] >= 0.0 && p_meas[i] <= 1.0, DQ_ERR_INVALID,
+                   "per-lattice rates: lattice %d has p_phys=%g, p_meas=%g; rates must be finite and in [0, 1]", i, p_phys[i], p_meas[i]);
+    const size_t bytes = (2 * (size_t)n + 2) * sizeof(u64);
+    if (!R.dev) {
+        DQ_HIP(hipMalloc(&R.dev, bytes));
+        DQ_HIP(hipHostMalloc(&R.host, bytes, hipHostMallocDefault));
+        DQ_HIP(hipEventCreateWithFlags(&R.copied, hipEventDisableTiming));
+    }
+    if (R.pending) { DQ_HIP(hipEventSynchronize(R.copied)); R.pending = false; }
+    for (int i = 0; i < n; ++i) { R.host[2 * i] = dq_rate_threshold(p_phys[i]); R.host[2 * i + 1] = dq_rate_threshold(p_meas[i]); }
+    R.host[2 * n] = R.host[2 * n - 2]; R.host[2 * n + 1] = R.host[2 * n - 1];
+    DQ_HIP(hipMemcpyAsync(R.dev, R.host, bytes, hipMemcpyHostToDevice, st));
+    DQ_HIP(hipEventRecord(R.copied, st));
+    R.pending = true;
+    return DQ_OK;
+}
+static inline void dq_rate_table_free(DqRateTable& R) {
+    if (R.pending) (void)hipEventSynchronize(R.copied);
+    if (R.copied) (void)hipEventDestroy(R.copied);
+    if (R.host) (void)hipHostFree(R.host);
+    if (R.dev) (void)hipFree(R.dev);
+    R = DqRateTable{};
+}
 // the same for a 16-bit draw (dropout: eight decisions per Philox call):  H / 2^16 < p  <=>  H < ceil(p * 2^16)
 static inline u32 dq_rate_threshold16(double p) {
     double t = p * 65536.0;

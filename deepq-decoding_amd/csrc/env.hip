@@ -39,6 +39,8 @@ struct dq_env {
     int P;                 // cells per observation plane
     u64 T_phys, T_meas;
     bool rates_set;
+    bool per_lattice;              // dq_env_set_rates_per_lattice is in force (the launches read rate_tab.dev); dq_env_set_rates clears it
+    DqRateTable rate_tab;
     EnvTables h_tab;
     EnvTables* d_tab;
     u64* d_state;
@@ -147,10 +149,12 @@ __global__ __launch_bounds__(256) void env_kernel(EnvParams p) {
     else env_block<ENVS_PER_BLOCK>(p, (int)blockIdx.x, smem);
 }
 
-// p.steps agent steps of the lattices in one launch (env_dev.h env_block2<EPB, true>; dq_env_act_steps): d <= 5 (two lattices per wave)
+// p.steps agent steps of the lattices in one launch (env_dev.h env_block2<EPB, true>; dq_env_act_steps): d <= 5 (two lattices per wave).
+// PER_LATTICE: the thresholds from p.T_lat (dq_env_set_rates_per_lattice); false: the kernel arguments, the code of the uniform form as it was
+template <bool PER_LATTICE>
 __global__ __launch_bounds__(256) void env_multi_kernel(EnvParams p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
-    env_block2<2 * ENVS_PER_BLOCK, true>(p, (int)blockIdx.x, smem);
+    env_block2<2 * ENVS_PER_BLOCK, true, PER_LATTICE ? ENV_RATES_LATTICE : ENV_RATES_UNIFORM>(p, (int)blockIdx.x, smem);
 }
 
 // ---- state export / import (tests, checkpointing) ------------------------------------------------
@@ -301,7 +305,7 @@ void dq_set_error(const char* fmt, ...) {
 
 extern "C" {
 
-int dq_version(void) { return 3; }
+int dq_version(void) { return 4; }
 const char* dq_last_error(void) { return g_err; }
 long dq_struct_size(int id) {
     switch (id) {
@@ -369,6 +373,7 @@ void dq_env_destroy(dq_env* E) {
     if (E->d_lut_z) (void)hipFree(E->d_lut_z);
     if (E->d_dec) (void)hipFree(E->d_dec);
     if (E->d_mlp_cells) (void)hipFree(E->d_mlp_cells);
+    dq_rate_table_free(E->rate_tab);
     delete E;
 }
 
@@ -384,6 +389,17 @@ dq_status dq_env_set_rates(dq_env* E, double p_phys, double p_meas) {
     E->T_phys = dq_rate_threshold(p_phys);
     E->T_meas = dq_rate_threshold(p_meas);
     E->rates_set = true;
+    E->per_lattice = false;
+    return DQ_OK;
+}
+
+dq_status dq_env_set_rates_per_lattice(dq_env* E, const double* p_phys, const double* p_meas, int n, void* stream) {
+    DQ_REQUIRE(E, DQ_ERR_INVALID, "dq_env_set_rates_per_lattice: null handle");
+    DQ_REQUIRE(n == E->cfg.n_envs, DQ_ERR_INVALID, "dq_env_set_rates_per_lattice: n=%d, the handle has %d lattices", n, E->cfg.n_envs);
+    const dq_status rc = dq_rate_table_upload(E->rate_tab, n, p_phys, p_meas, (hipStream_t)stream);
+    if (rc != DQ_OK) return rc;
+    E->rates_set = true;
+    E->per_lattice = true;
     return DQ_OK;
 }
 
@@ -616,6 +632,7 @@ static dq_status fill_common(dq_env* E, EnvParams& p, int epb, bool rider = fals
     p.obs_size = E->info.obs_c * E->P;
     p.env_id_base = E->cfg.env_id_base; p.seed0 = E->cfg.seed[0]; p.seed1 = E->cfg.seed[1];
     p.T_phys = E->T_phys; p.T_meas = E->T_meas;
+    p.T_lat = E->per_lattice ? E->rate_tab.dev : nullptr;    // (every launch -- stand-alone or riding, qnet.hip / fused_bwd.hip -- is filled here)
     // two to a wave where the lattice fits half a wave (d <= 5): where the step rides on the dense backward it halves the rounds of environment
     // workgroups (-3.7 us per vector step); the stand-alone launch measured 17.4 us one per wave against 17.8 us two per wave in round 3's first pass
     // (round 3, second pass: two to a wave in the stand-alone launch too -- with the step's loads in one batch and the planes composed from registers it
@@ -764,8 +781,11 @@ dq_status dq_env_act_steps(dq_env* E, int n_steps, const uint32_t seed[2], uint6
         DQ_REQUIRE(p.pair, DQ_ERR_STATE, "dq_env_act_steps: DQ_ENV_PAIR=1 restricts the two-per-wave form to riders");
         p.patch = ring->patch_ring_dev; p.patch_stride = ring->patch_stride_words;
         p.steps = n_steps; p.ring_slots = ring->n_slots; p.ring_slot0 = ring->slot0;
-        dq_launch(DQ_K_ENV, "env_multi_kernel", env_multi_kernel, dim3(p.env_blocks), dim3(64 * ENVS_PER_BLOCK),
-                  env_block_lds(2 * ENVS_PER_BLOCK, ENVS_PER_BLOCK, p.obs_size, p.lut_words), (hipStream_t)stream, p);
+        const size_t lds = env_block_lds(2 * ENVS_PER_BLOCK, ENVS_PER_BLOCK, p.obs_size, p.lut_words);
+        if (p.T_lat)
+            dq_launch(DQ_K_ENV, "env_multi_kernel", env_multi_kernel<true>, dim3(p.env_blocks), dim3(64 * ENVS_PER_BLOCK), lds, (hipStream_t)stream, p);
+        else
+            dq_launch(DQ_K_ENV, "env_multi_kernel", env_multi_kernel<false>, dim3(p.env_blocks), dim3(64 * ENVS_PER_BLOCK), lds, (hipStream_t)stream, p);
         DQ_LAUNCH_CHECK();
         return DQ_OK;
     }

@@ -37,6 +37,7 @@ struct BigParams {
     int n_envs, d2, n_stab, depth, layers, n_actions, identity, model, use_Y, sw, P, W, LW, obs_size;
     u32 env_id_base, seed0, seed1;
     u64 T_phys, T_meas;
+    const u64* T_lat;                   // != NULL: per-lattice rates, [2 i] = T_phys, [2 i + 1] = T_meas of lattice i (dq_envb_set_rates_per_lattice)
     int mode, auto_reset;               // mode 0: reset, 1: step
     const u8* which;
     const int32_t* action;
@@ -210,6 +211,13 @@ __global__ __launch_bounds__(64 * BIG_EPB) void env_big_kernel(BigParams p) {
         }
     }
     if (need_volume) {                                               // ENV:157-172 == ENV:216-231
+        // the lattice's rates (wave-uniform: scalar loads).  Loaded here, where they are used, rather than next to the record: live across the
+        // matching referee they cost 4 VGPRs and an occupancy step at W = 1 and W = 3
+        u64 T_phys = p.T_phys, T_meas = p.T_meas;
+        if (p.T_lat != nullptr) {
+            const int iu = __builtin_amdgcn_readfirstlane(i);
+            T_phys = p.T_lat[2 * (size_t)iu]; T_meas = p.T_lat[2 * (size_t)iu + 1];
+        }
         u64 summed[W];
         u64 any;
         do {
@@ -222,12 +230,12 @@ __global__ __launch_bounds__(64 * BIG_EPB) void env_big_kernel(BigParams p) {
                     const int site = lane + 64 * w;
                     u32 wd[4];
                     philox4x32_10((u32)round, (u32)(round >> 32), p.env_id_base + (u32)i, (u32)site, p.seed0, p.seed1, wd);
-                    const bool hit = site < p.d2 && (u64)wd[0] < p.T_phys;  // FL:99 / FL:119
+                    const bool hit = site < p.d2 && (u64)wd[0] < T_phys;    // FL:99 / FL:119
                     const int typ = p.model == DQ_MODEL_X ? 1 : 1 + (int)__umulhi(wd[1], 3u);   // FL:100
-                    const bool zhit = site < p.d2 && (u64)wd[1] < p.T_phys; // IIDXZ (FL:134-160): the second uniform is an independent Z flip
+                    const bool zhit = site < p.d2 && (u64)wd[1] < T_phys;   // IIDXZ (FL:134-160): the second uniform is an independent Z flip
                     ex[w] = __ballot(p.model == DQ_MODEL_IIDXZ ? hit : hit && typ != 3);
                     ez[w] = __ballot(p.model == DQ_MODEL_IIDXZ ? zhit : hit && typ != 1);
-                    fl[w] = __ballot(site < p.n_stab && (u64)wd[2] < p.T_meas);   // FL:191-221
+                    fl[w] = __ballot(site < p.n_stab && (u64)wd[2] < T_meas);     // FL:191-221
                 }
                 ++round;
 #pragma unroll
@@ -383,6 +391,8 @@ struct dq_envb {
     int W, LW, sw, ew, P;
     u64 T_phys, T_meas;
     bool rates_set;
+    bool per_lattice;                   // dq_envb_set_rates_per_lattice is in force; dq_envb_set_rates clears it
+    DqRateTable rate_tab;
     u8* d_blob;                         // all tables in one allocation
     BigTables tab;
     dq_match* match;
@@ -404,6 +414,7 @@ void dq_envb_destroy(dq_envb* E) {
     if (E->d_blob) (void)hipFree(E->d_blob);
     if (E->d_state) (void)hipFree(E->d_state);
     if (E->match) dq_match_destroy(E->match);
+    dq_rate_table_free(E->rate_tab);
     delete E;
 }
 
@@ -418,7 +429,7 @@ dq_status dq_envb_create(const dq_env_cfg* cfg, dq_envb** out) {
     DQ_REQUIRE(cfg->n_envs >= 1, DQ_ERR_INVALID, "n_envs must be positive");
     dq_envb* E = new (std::nothrow) dq_envb();
     DQ_REQUIRE(E, DQ_ERR_NOMEM, "out of host memory");
-    E->cfg = *cfg; E->d_blob = nullptr; E->d_state = nullptr; E->match = nullptr; E->rates_set = false;
+    E->cfg = *cfg; E->d_blob = nullptr; E->d_state = nullptr; E->match = nullptr; E->rates_set = false; E->per_lattice = false;
     const int d = cfg->d, d2 = d * d, n = 2 * d + 1;
     const int layers = cfg->error_model == DQ_MODEL_X ? 1 : (cfg->use_Y ? 3 : 2);             // ENV:55-65
     E->info.n_action_layers = layers;
@@ -508,6 +519,17 @@ dq_status dq_envb_set_rates(dq_envb* E, double p_phys, double p_meas) {
     E->T_phys = dq_rate_threshold(p_phys);
     E->T_meas = dq_rate_threshold(p_meas);
     E->rates_set = true;
+    E->per_lattice = false;
+    return DQ_OK;
+}
+
+dq_status dq_envb_set_rates_per_lattice(dq_envb* E, const double* p_phys, const double* p_meas, int n, void* stream) {
+    DQ_REQUIRE(E, DQ_ERR_INVALID, "dq_envb_set_rates_per_lattice: null handle");
+    DQ_REQUIRE(n == E->cfg.n_envs, DQ_ERR_INVALID, "dq_envb_set_rates_per_lattice: n=%d, the handle has %d lattices", n, E->cfg.n_envs);
+    const dq_status rc = dq_rate_table_upload(E->rate_tab, n, p_phys, p_meas, (hipStream_t)stream);
+    if (rc != DQ_OK) return rc;
+    E->rates_set = true;
+    E->per_lattice = true;
     return DQ_OK;
 }
 
@@ -527,6 +549,7 @@ static dq_status big_fill(dq_envb* E, BigParams& p) {
     p.obs_size = E->info.obs_c * E->P;
     p.env_id_base = E->cfg.env_id_base; p.seed0 = E->cfg.seed[0]; p.seed1 = E->cfg.seed[1];
     p.T_phys = E->T_phys; p.T_meas = E->T_meas;
+    p.T_lat = E->per_lattice ? E->rate_tab.dev : nullptr;
     return DQ_OK;
 }
 

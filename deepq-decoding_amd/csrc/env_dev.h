@@ -33,6 +33,8 @@ struct EnvParams {
     int n_envs, d2, n_stab, depth, layers, n_actions, identity, model, use_Y, sw, P, C, obs_size;
     u32 env_id_base, seed0, seed1;
     u64 T_phys, T_meas;
+    const u64* T_lat;              // != NULL: per-lattice rates, [2 i] = T_phys, [2 i + 1] = T_meas of lattice i (dq_env_set_rates_per_lattice;
+                                   // 2 n_envs + 2 words: the last pair pads the two-per-wave load); NULL: T_phys / T_meas for every lattice
     int mode, auto_reset;          // mode 0: reset, 1: step
     const u8* which;
     const int32_t* action;
@@ -195,6 +197,11 @@ static __device__ __forceinline__ void env_block(const EnvParams& p, const int b
     volatile u64* vol = s_vol + wave * DQ_MAX_DEPTH;   // written by lane 0, read by other lanes of the same wave
     u64* rec = p.state + (size_t)(active ? i : 0) * p.sw;
     const u64 word = lane < p.sw ? rec[lane] : 0;
+    u64 T_phys = p.T_phys, T_meas = p.T_meas;                               // the lattice's rates (wave-uniform: scalar loads)
+    if (p.T_lat != nullptr && active) {
+        const int iu = __builtin_amdgcn_readfirstlane(i);
+        T_phys = p.T_lat[2 * (size_t)iu]; T_meas = p.T_lat[2 * (size_t)iu + 1];
+    }
     float qpre[ENV_QPRE];
     const bool have_q = p.policy && p.q != nullptr;
 #pragma unroll
@@ -306,13 +313,13 @@ static __device__ __forceinline__ void env_block(const EnvParams& p, const int b
                 for (int j = 0; j < p.depth; ++j) {
                     u32 w[4];
                     philox4x32_10((u32)round, (u32)(round >> 32), p.env_id_base + (u32)i, (u32)lane, p.seed0, p.seed1, w);
-                    const bool hit = lane < p.d2 && (u64)w[0] < p.T_phys;   // FL:99 / FL:119
+                    const bool hit = lane < p.d2 && (u64)w[0] < T_phys;     // FL:99 / FL:119
                     const int typ = p.model == DQ_MODEL_X ? 1 : 1 + (int)__umulhi(w[1], 3u);   // FL:100
                     // IIDXZ (FL:134-160): the qubit's second uniform decides an independent Z flip instead of the Pauli type
-                    const bool zhit = lane < p.d2 && (u64)w[1] < p.T_phys;
+                    const bool zhit = lane < p.d2 && (u64)w[1] < T_phys;
                     const u64 ex = __ballot(p.model == DQ_MODEL_IIDXZ ? hit : hit && typ != 3);
                     const u64 ez = __ballot(p.model == DQ_MODEL_IIDXZ ? zhit : hit && typ != 1);
-                    const u64 flips = __ballot(lane < p.n_stab && (u64)w[2] < p.T_meas);      // FL:191-221
+                    const u64 flips = __ballot(lane < p.n_stab && (u64)w[2] < T_meas);        // FL:191-221
                     ++round;
                     xmask ^= ex;                                            // ENV:164, FL:226-241
                     zmask ^= ez;
@@ -439,7 +446,11 @@ static __device__ __forceinline__ u64 half_bcast64(u64 v, int src) {
 // step / auto-reset, transition into the replay ring --, the lattice's state carried in registers from step to step, the outputs of step s going to ring slot
 // (ring_slot0 + s) mod ring_slots (action, reward, done) and the successor observation to the slot behind it: an acting loop of T steps costs one launch
 // latency instead of T.  Same words, same bits as T launches (policy counter pt + s).
-template <int EPB, bool MULTI = false>
+// RATES: where the thresholds come from -- ENV_RATES_RUNTIME: p.T_lat decides (a kernel argument: a uniform branch); ENV_RATES_UNIFORM: the
+// kernel arguments T_phys / T_meas only (env_multi_kernel's uniform instantiation: the code of the form without per-lattice rates -- the
+// multi-step launch is bound by vector-ALU issue and measured 1.4 % slower with the runtime choice); ENV_RATES_LATTICE: p.T_lat only.
+enum { ENV_RATES_RUNTIME = 0, ENV_RATES_UNIFORM = 1, ENV_RATES_LATTICE = 2 };
+template <int EPB, bool MULTI = false, int RATES = ENV_RATES_RUNTIME>
 static __device__ __forceinline__ void env_block2(const EnvParams& p, const int block, u8* __restrict__ smem) {
     constexpr int THREADS = 32 * EPB;
     u64* s_vol = reinterpret_cast<u64*>(smem);                              // [EPB][16]
@@ -476,6 +487,20 @@ static __device__ __forceinline__ void env_block2(const EnvParams& p, const int 
     volatile u64* vol = s_vol + slot * DQ_MAX_DEPTH;   // written by lane 0 of the half, read by its other lanes
     u64* rec = p.state + (size_t)(active ? i : 0) * p.sw;
     const u64 word = hl < p.sw ? rec[hl] : 0;
+    // the rates of the wave's two lattices (2 w, 2 w + 1 of the block): one scalar load of four words (the table's padding pair covers a missing
+    // second lattice), kept in SGPRs; each half compares against its own pair (rate_lt).  Uniform rates: the kernel argument, as before
+    u64 Tp0 = p.T_phys, Tm0 = p.T_meas, Tp1 = p.T_phys, Tm1 = p.T_meas;
+    if (RATES == ENV_RATES_LATTICE || (RATES == ENV_RATES_RUNTIME && p.T_lat != nullptr)) {      // (kernel argument: uniform)
+        const int i0 = __builtin_amdgcn_readfirstlane(block * EPB + 2 * (tid >> 6));
+        if (i0 < p.n_envs) {
+            const u64* t = p.T_lat + 2 * (size_t)i0;
+            Tp0 = t[0]; Tm0 = t[1]; Tp1 = t[2]; Tm1 = t[3];
+        }
+    }
+    auto rate_lt = [&](u32 w, u64 t0, u64 t1) -> bool {
+        if constexpr (RATES == ENV_RATES_UNIFORM) return (u64)w < t0;
+        else return half ? (u64)w < t1 : (u64)w < t0;
+    };
     float qpre[ENV_QPRE];
     const bool have_q = p.policy && p.q != nullptr;
 #pragma unroll
@@ -604,12 +629,12 @@ static __device__ __forceinline__ void env_block2(const EnvParams& p, const int 
                 for (int j = 0; j < p.depth; ++j) {
                     u32 w[4];
                     philox4x32_10((u32)round, (u32)(round >> 32), p.env_id_base + (u32)i, (u32)hl, p.seed0, p.seed1, w);
-                    const bool hit = hl < p.d2 && (u64)w[0] < p.T_phys;     // FL:99 / FL:119
+                    const bool hit = hl < p.d2 && rate_lt(w[0], Tp0, Tp1);  // FL:99 / FL:119
                     const int typ = p.model == DQ_MODEL_X ? 1 : 1 + (int)__umulhi(w[1], 3u);   // FL:100
-                    const bool zhit = hl < p.d2 && (u64)w[1] < p.T_phys;    // IIDXZ (FL:134-160)
+                    const bool zhit = hl < p.d2 && rate_lt(w[1], Tp0, Tp1); // IIDXZ (FL:134-160)
                     const u64 ex = hb(p.model == DQ_MODEL_IIDXZ ? hit : hit && typ != 3);
                     const u64 ez = hb(p.model == DQ_MODEL_IIDXZ ? zhit : hit && typ != 1);
-                    const u64 flips = hb(hl < p.n_stab && (u64)w[2] < p.T_meas);          // FL:191-221
+                    const u64 flips = hb(hl < p.n_stab && rate_lt(w[2], Tm0, Tm1));       // FL:191-221
                     ++round;
                     xmask ^= ex;                                            // ENV:164, FL:226-241
                     zmask ^= ez;

@@ -117,6 +117,39 @@ def _obs_to_patch(obs, d, depth, layers, stride):
     return out.to(torch.int32)
 
 
+def validate_rates(value, n_envs, name="rate"):
+    """One argument of VectorEnv.set_rates: a real scalar -> float; a 1-D sequence / array / tensor of n_envs reals -> a read-only C-contiguous
+    float64 array.  Every rate must be finite and in [0, 1].  Raises ValueError (TypeError never) before anything reaches the library."""
+    if isinstance(value, torch.Tensor):
+        value = value.detach().cpu().numpy()
+    if isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"{name}: a boolean is not an error rate")
+    if isinstance(value, (int, float, np.integer, np.floating)):
+        v = float(value)
+        if not (0.0 <= v <= 1.0):
+            raise ValueError(f"{name}={value!r}: rates must be finite and in [0, 1]")
+        return v
+    try:
+        a = np.asarray(value)
+    except ValueError as e:                                       # ragged nesting (numpy >= 1.24 refuses it)
+        raise ValueError(f"{name}: not a 1-D sequence of rates ({e})") from None
+    if a.dtype == object or a.dtype.kind not in "iuf":
+        raise ValueError(f"{name}: rates must be real numbers (got dtype {a.dtype})")
+    if a.ndim == 0:
+        return validate_rates(a.item(), n_envs, name)
+    if a.ndim != 1:
+        raise ValueError(f"{name}: a scalar or a 1-D sequence of {n_envs} rates, got shape {a.shape}")
+    if a.shape[0] != n_envs:
+        raise ValueError(f"{name}: {a.shape[0]} rates for {n_envs} lattices")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if not (np.all(a >= 0.0) and np.all(a <= 1.0)):               # (NaN fails both)
+        bad = int(np.flatnonzero(~((a >= 0.0) & (a <= 1.0)))[0])
+        raise ValueError(f"{name}[{bad}]={a[bad]!r}: rates must be finite and in [0, 1]")
+    a = a.copy()
+    a.setflags(write=False)
+    return a
+
+
 class VectorEnv:
     """Batched environment: lattice i has global id ``env_id_base + i`` (its RNG stream)."""
 
@@ -157,6 +190,7 @@ class VectorEnv:
         self.action_space = _Space(n=self.num_actions)
         self._p_phys, self._p_meas = float(p_phys), float(p_meas)
         check(getattr(self.L, self._pfx + "set_rates")(self._h, self._p_phys, self._p_meas))
+        self._rates_arr = None          # set_rates with a sequence: the (p_phys, p_meas) arrays of the lattices; None: the scalar pair
         dev, n = self.device, self.n_envs
         self.obs = torch.zeros((n,) + self.obs_shape, dtype=torch.uint8, device=dev)
         self.reward = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -200,23 +234,61 @@ class VectorEnv:
             pass
 
     # -- rates are plain mutable attributes in the reference (Single_Point_Training_Script.py:200-201) ---
+    def set_rates(self, p_phys, p_meas=None):
+        """Error rates of the lattices.  Each argument is a scalar (every lattice) or a 1-D sequence of n_envs rates (lattice i runs at
+        entry i); p_meas=None: the same as p_phys.  A lattice keeps its own noise stream, so at rate p it draws exactly what a
+        uniform-rate environment at p draws for the same global id and seed.  Two scalars take the scalar entry point (the uniform
+        path, as before); anything else uploads per-lattice thresholds, ordered on the current stream.  The referee stays the one
+        installed: like the reference's fixed static_decoder it does not follow the rates (an "ml" table built for one rate is not
+        rebuilt per lattice).  Validation (validate_rates) happens before any library call."""
+        ph = validate_rates(p_phys, self.n_envs, "p_phys")
+        pm = ph if p_meas is None else validate_rates(p_meas, self.n_envs, "p_meas")
+        if isinstance(ph, float) and isinstance(pm, float):
+            check(getattr(self.L, self._pfx + "set_rates")(self._h, ph, pm))
+            self._p_phys, self._p_meas, self._rates_arr = ph, pm, None
+            return
+        full = lambda v: np.full(self.n_envs, v, dtype=np.float64) if isinstance(v, float) else v
+        a, b = full(ph), full(pm)
+        with torch.cuda.device(self.device):
+            check(getattr(self.L, self._pfx + "set_rates_per_lattice")(self._h, a.ctypes.data, b.ctypes.data, self.n_envs, self._stream()))
+        for v in (a, b):
+            v.setflags(write=False)
+        self._rates_arr = (a, b)
+
+    @staticmethod
+    def _rate_view(arr):
+        return float(arr[0]) if np.all(arr == arr[0]) else arr
+
+    @property
+    def rates(self):
+        """(p_phys, p_meas): two read-only float64 arrays of n_envs rates, whatever form set them."""
+        if self._rates_arr is not None:
+            return self._rates_arr
+        out = tuple(np.full(self.n_envs, v, dtype=np.float64) for v in (self._p_phys, self._p_meas))
+        for v in out:
+            v.setflags(write=False)
+        return out
+
+    def _rate_forms(self):
+        """What set_rates needs to restore the current rates."""
+        return (self._p_phys, self._p_meas) if self._rates_arr is None else self._rates_arr
+
     @property
     def p_phys(self):
-        return self._p_phys
+        """A float while every lattice has the same rate, else the read-only per-lattice array."""
+        return self._p_phys if self._rates_arr is None else self._rate_view(self._rates_arr[0])
 
     @p_phys.setter
     def p_phys(self, v):
-        self._p_phys = float(v)
-        check(getattr(self.L, self._pfx + "set_rates")(self._h, self._p_phys, self._p_meas))
+        self.set_rates(v, self._rate_forms()[1])
 
     @property
     def p_meas(self):
-        return self._p_meas
+        return self._p_meas if self._rates_arr is None else self._rate_view(self._rates_arr[1])
 
     @p_meas.setter
     def p_meas(self, v):
-        self._p_meas = float(v)
-        check(getattr(self.L, self._pfx + "set_rates")(self._h, self._p_phys, self._p_meas))
+        self.set_rates(self._rate_forms()[0], v)
 
     def build_ml_referee(self, q_flip):
         """Installs the maximum-likelihood referee for independent X- / Z-component flips with probability q_flip per qubit."""

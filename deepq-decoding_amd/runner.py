@@ -66,9 +66,24 @@ def load_configs(config_dir, fixed_config_path=None):
     return all_configs, number
 
 
+def sweep_prefix(error_rates, final_averages):
+    """TRAIN:214-222's stop rule over a sweep that has already run every rate: how many leading rates the sequential sweep keeps -- up to
+    and including the first whose final average lifetime is below 1 / p (all of them if none is)."""
+    for count, (p, avg) in enumerate(zip(error_rates, final_averages)):
+        if avg < 1.0 / p:
+            return count + 1
+    return len(error_rates)
+
+
 def train_single_point(config_dir, fixed_config_path=None, n_envs=1, verbose=2, device=None, seed=None, test_rates=None,
-                       batch_size=None, sync_interval=None):
-    """One grid point, TRAIN:92-222 (CONT when config_dir holds memory.p + initial_dqn_weights.h5f).  Returns all_results."""
+                       batch_size=None, sync_interval=None, sweep="sequential", sweep_lattices=None):
+    """One grid point, TRAIN:92-222 (CONT when config_dir holds memory.p + initial_dqn_weights.h5f).  Returns all_results.
+
+    sweep: "sequential" -- the reference's evaluation, one test() per error rate on the training environment; "batched" -- every rate
+    at once (DQNAgent.test_error_rates) on a fresh VectorEnv of K m lattices, K = number of rates, m = sweep_lattices or else
+    testing_length, then the same stop rule applied to the finished sweep: the same all_results keys and results.p."""
+    if sweep not in ("sequential", "batched"):
+        raise ValueError(f"sweep must be 'sequential' or 'batched', not {sweep!r}")
     dq = importlib.import_module(__package__)
     import torch
     cfg, number = load_configs(config_dir, fixed_config_path)
@@ -126,6 +141,18 @@ def train_single_point(config_dir, fixed_config_path=None, n_envs=1, verbose=2, 
     trained_at = cfg["p_phys"]
     error_rates = [j * 0.001 for j in range(1, 21)] if test_rates is None else list(test_rates)
     all_results = {}
+    if sweep == "batched":
+        m = int(sweep_lattices or cfg["testing_length"])
+        sweep_env = dq.VectorEnv(n_envs=len(error_rates) * m, **({} if seed is None else dict(seed=seed)), **kw)
+        histories = tester.test_error_rates(sweep_env, error_rates, nb_episodes=cfg["testing_length"], verbose=verbose, interval=10)
+        finals = [histories[float(p)].history["episode_lifetimes_rolling_avg"][-1] for p in error_rates]
+        for err_rate, final_result in list(zip(error_rates, finals))[:sweep_prefix(error_rates, finals)]:
+            all_results[str(err_rate)[:5]] = final_result
+            if abs(trained_at - err_rate) < 1e-6:
+                with open(os.path.join(config_dir, "results.p"), "wb") as f:
+                    pickle.dump(histories[float(err_rate)].history["episode_lifetimes_rolling_avg"], f)
+        sweep_env.close()
+        error_rates = []                                    # (the sequential loop below has nothing left to do)
     for count, err_rate in enumerate(error_rates):
         env.p_phys = err_rate
         env.p_meas = err_rate

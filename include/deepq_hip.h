@@ -106,6 +106,14 @@ dq_status dq_env_get_info(const dq_env* env, dq_env_info* out);
 /* env.p_phys / env.p_meas are plain attributes the drivers mutate between test sweeps
  * (Single_Point_Training_Script.py:200-201); converted to integer thresholds on the host. */
 dq_status dq_env_set_rates(dq_env* env, double p_phys, double p_meas);
+/* Per-lattice rates: lattice i (local index) runs at p_phys[i], p_meas[i] -- every threshold compare of its steps and of its resets'
+ * initialize_state rejection loop (Environments.py:157-172) -- and keeps its own Philox stream, so a lattice's trajectory equals that of a
+ * uniform-rate handle at its rates (same seed, env_id_base = its global id).  p_phys / p_meas: HOST arrays of n == n_envs doubles, each
+ * finite and in [0, 1] (else DQ_ERR_INVALID, nothing changed); the thresholds are those of dq_env_set_rates.  The handle owns the device
+ * table (freed by dq_env_destroy).  The upload is ordered on `stream`: launches on it after the call see the new rates, launches before it
+ * finish reading the old ones first; the caller may free its arrays on return.  Satisfies dq_env_set_rates' precondition; a later
+ * dq_env_set_rates returns the handle to one pair of rates for all lattices.  The referee is not touched (it is the one installed). */
+dq_status dq_env_set_rates_per_lattice(dq_env* env, const double* p_phys, const double* p_meas, int n, void* stream);
 
 /* Referee ("static_decoder", Environments.py:53,144,150).  The reference's Keras referee blobs are
  * not in the checkout; the library builds the deterministic minimum-weight look-up referee defined
@@ -283,6 +291,8 @@ dq_status dq_envb_create(const dq_env_cfg* cfg, dq_envb** out);
 void dq_envb_destroy(dq_envb* env);
 dq_status dq_envb_get_info(const dq_envb* env, dq_env_info* out, int* legal_words);
 dq_status dq_envb_set_rates(dq_envb* env, double p_phys, double p_meas);
+/* dq_env_set_rates_per_lattice for the wide handle (same semantics) */
+dq_status dq_envb_set_rates_per_lattice(dq_envb* env, const double* p_phys, const double* p_meas, int n, void* stream);
 dq_status dq_envb_reset(dq_envb* env, const uint8_t* which_dev, uint8_t* obs_dev, uint64_t* legal_dev, uint32_t* lifetime_dev, void* stream);
 dq_status dq_envb_step(dq_envb* env, const int32_t* action_dev, int auto_reset, uint8_t* obs_dev, float* reward_dev, uint8_t* done_dev,
                        uint64_t* legal_dev, uint32_t* lifetime_dev, uint8_t* was_reset_dev, uint8_t* inexact_dev, void* stream);
