@@ -93,6 +93,9 @@ class DecodeCfg(ctypes.Structure):
 DECODE_ACTIVE, DECODE_IDENTITY, DECODE_REPEAT, DECODE_STOPPED = 0, 1, 2, 3
 DECODE_PLANES_ENV, DECODE_PLANES_README = 0, 1
 DECODE_OBS_UINT8, DECODE_OBS_PATCH = 0, 1
+# dq_decode_verdict's byte and dq_decode_count's counters (include/deepq_hip.h DQ_VERDICT_* / DQ_EVAL_*)
+VERDICT_IN_CODESPACE, VERDICT_CLASS_SHIFT, VERDICT_SUCCESS, VERDICT_ALIVE, VERDICT_DECODED_SHIFT = 1, 1, 8, 16, 5
+EVAL_COUNTER_NAMES = ("volumes", "trivial", "in_codespace", "success", "alive", "identity", "repeat", "stopped", "corrections")
 
 
 _vp, _i, _u32, _u64, _dbl = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
@@ -187,6 +190,11 @@ SIGNATURES = {
     "dq_decode_create": (_i, [ctypes.POINTER(DecodeCfg), _i, ctypes.POINTER(_vp)]),
     "dq_decode_destroy": (None, [_vp]),
     "dq_decode_run": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), _vp]),
+    "dq_decode_eval_create": (_i, [ctypes.POINTER(DecodeCfg), _i, ctypes.POINTER(_vp)]),
+    "dq_decode_eval_destroy": (None, [_vp]),
+    "dq_decode_sample": (_i, [_vp, _vp, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dq_decode_verdict": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "dq_decode_count": (_i, [_vp, _vp, _vp, _vp, _i, ctypes.c_int64, _i, _i, _vp, _vp]),
     "dq_prof_kernel_count": (_i, []),
     "dq_prof_kernel_name": (ctypes.c_char_p, [_i]),
     "dq_prof_kernel_symbol": (ctypes.c_char_p, [_i]),

@@ -305,7 +305,7 @@ void dq_set_error(const char* fmt, ...) {
 
 extern "C" {
 
-int dq_version(void) { return 4; }
+int dq_version(void) { return 5; }
 const char* dq_last_error(void) { return g_err; }
 long dq_struct_size(int id) {
     switch (id) {
@@ -572,13 +572,15 @@ dq_status dq_env_set_referee_mlp(dq_env* E, int n_layers, const int32_t* dims, c
 }
 
 // the pre-pass of a step whose referee is the Dense stack: classes of the lattices' post-action syndromes into E->d_dec
-static dq_status launch_referee_mlp(dq_env* E, const int32_t* action_dev, int auto_reset, hipStream_t st) {
+// (state / sw / n / dec given: the same pass over a caller's records instead of the handle's lattices -- env_referee_mlp_classes below)
+static dq_status launch_referee_mlp(dq_env* E, const int32_t* action_dev, int auto_reset, hipStream_t st, const u64* state = nullptr, int sw = 0, int n = 0,
+                                    u8* dec = nullptr) {
     RefMlpParams r;
     memset(&r, 0, sizeof(r));
-    r.state = E->d_state; r.sw = E->sw; r.n_envs = E->cfg.n_envs; r.d2 = E->cfg.d * E->cfg.d; r.n_stab = E->info.n_stab;
+    r.state = state ? state : E->d_state; r.sw = state ? sw : E->sw; r.n_envs = state ? n : E->cfg.n_envs; r.d2 = E->cfg.d * E->cfg.d; r.n_stab = E->info.n_stab;
     r.n_actions = E->info.num_actions; r.identity = E->info.identity_index; r.model = E->cfg.error_model; r.use_Y = E->cfg.use_Y;
     r.auto_reset = auto_reset; r.tab = E->d_tab; r.action = action_dev; r.cells = E->d_mlp_cells; r.layers = E->mlp_layers; r.w = E->mlp_w;
-    r.dec = E->d_dec;
+    r.dec = state ? dec : E->d_dec;
     int mw = 1;
     for (int l = 0; l <= E->mlp_layers; ++l) { r.dims[l] = E->mlp_dims[l]; if (l > 0 && E->mlp_dims[l] > mw) mw = E->mlp_dims[l]; }
     r.max_width = (mw + 3) & ~3;
@@ -858,4 +860,23 @@ dq_status env_fill_act_step(dq_env* E, const float* q_dev, double eps, int maske
     p->stats = reinterpret_cast<unsigned long long*>(stats_dev);
     *lds = env_block_lds(p->pair ? 2 * waves : waves, waves, p->obs_size, p->lut_words);
     return DQ_OK;
+}
+
+// ---- the installed referee, for csrc/decode_eval.hip (the verdict on decoded volumes reads the tables where they are) ----------------------------
+dq_status env_referee_view(const dq_env* E, bool need_referee, EnvRefereeView* v) {
+    DQ_REQUIRE(E && v, DQ_ERR_INVALID, "env_referee_view: null argument");
+    DQ_REQUIRE(!need_referee || E->lut_x, DQ_ERR_STATE, "no referee installed on the environment (dq_env_build_referee / dq_env_set_referee*)");
+    memset(v, 0, sizeof(*v));
+    v->tab = E->d_tab; v->d = E->cfg.d; v->n_stab = E->info.n_stab; v->depth = E->cfg.volume_depth; v->model = E->cfg.error_model; v->use_Y = E->cfg.use_Y;
+    v->mlp = E->mlp_layers > 0;                                     // the step's precedence (env_dev.h env_block): Dense stack, joint table, component tables
+    if (!v->mlp) { v->lut_joint = E->lut_joint; v->lut_x = E->lut_x; v->lut_z = E->lut_z; }
+    return DQ_OK;
+}
+
+// Classes of the Dense-stack referee for n records of `sw` words each, words 0 / 1 = the X / Z planes (the pre-pass reads word 8 too: the caller pads),
+// action_dev[i] outside the action range = no move.
+dq_status env_referee_mlp_classes(dq_env* E, const u64* records_dev, int sw, int n, const int32_t* action_dev, u8* dec_dev, hipStream_t st) {
+    DQ_REQUIRE(E && records_dev && action_dev && dec_dev && n >= 1 && sw >= 2, DQ_ERR_INVALID, "env_referee_mlp_classes: bad argument");
+    DQ_REQUIRE(E->mlp_layers, DQ_ERR_STATE, "env_referee_mlp_classes: no Dense-stack referee installed");
+    return launch_referee_mlp(E, action_dev, 0, st, records_dev, sw, n, dec_dev);
 }

@@ -779,3 +779,14 @@ dq_status env_fill_act_step(dq_env* E, const float* q_dev, double eps, int maske
                             int32_t* action_dev, int auto_reset, uint8_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint64_t* legal_dev,
                             uint32_t* lifetime_dev, uint8_t* was_reset_dev, const dq_sample_job* sj, uint64_t* stats_dev, EnvParams* p,
                             size_t* lds, int threads = 512);      // threads per block of the carrying launch: 512 (env_block<8> / env_block2<16>) or 256 (<4> / <8>)
+
+// env.hip, for decode_eval.hip: the lattice and the referee a handle has installed (the tables stay where they are; `mlp`: the Dense stack decides and
+// env_referee_mlp_classes evaluates it), and the Dense stack's classes of n caller records (words 0 / 1 of each `sw`-word record: X / Z planes).
+struct EnvRefereeView {
+    const EnvTables* tab;
+    const u32 *lut_x, *lut_z, *lut_joint;
+    int d, n_stab, depth, model, use_Y;
+    bool mlp;
+};
+dq_status env_referee_view(const dq_env* E, bool need_referee, EnvRefereeView* v);
+dq_status env_referee_mlp_classes(dq_env* E, const u64* records_dev, int sw, int n, const int32_t* action_dev, u8* dec_dev, hipStream_t st);

@@ -18,6 +18,7 @@ to its first identity (or repeated action, which the environment treats as the i
 corrections[i] != 0 ([21] marks qubit 0).  Both readings are kept as they are.
 """
 import ctypes
+import math
 
 import numpy as np
 
@@ -88,6 +89,316 @@ def check_binary(x):
         raise ValueError("faulty syndrome cells must be 0 or 1")
 
 
+# ---- scoring a decode: sample -> decode -> verdict -> counts (include/deepq_hip.h dq_decode_sample / _verdict / _count) ----
+Z95 = 1.959963984540054                                           # the 97.5 % point of the standard normal distribution
+COUNTER_NAMES = ("volumes", "trivial", "in_codespace", "success", "alive", "identity", "repeat", "stopped", "corrections")
+VERDICT_IN_CODESPACE, VERDICT_CLASS_SHIFT, VERDICT_SUCCESS, VERDICT_ALIVE, VERDICT_DECODED_SHIFT = 1, 1, 8, 16, 5
+
+
+def wilson_interval(k, n, z=Z95):
+    """Wilson score interval (lo, hi) for k events in n trials, closed form:
+    centre = (p + z^2 / 2n) / (1 + z^2 / n), half = z sqrt(p (1 - p) / n + z^2 / 4n^2) / (1 + z^2 / n), p = k / n."""
+    k, n = int(k), int(n)
+    if n <= 0 or not 0 <= k <= n:
+        raise ValueError(f"wilson_interval: {k} events in {n} trials")
+    p, z2 = k / n, z * z
+    den = 1.0 + z2 / n
+    centre = (p + z2 / (2.0 * n)) / den
+    half = z * math.sqrt(p * (1.0 - p) / n + z2 / (4.0 * n * n)) / den
+    return max(0.0, centre - half), min(1.0, centre + half)
+
+
+def check_rates(value, n_volumes, name):
+    """A scalar rate -> float; a 1-D sequence of n_volumes rates -> a C-contiguous float64 array.  Finite and in [0, 1], else ValueError."""
+    if hasattr(value, "detach"):
+        value = value.detach().cpu().numpy()
+    if isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"{name}: a boolean is not an error rate")
+    try:
+        a = np.asarray(value)
+    except ValueError as e:
+        raise ValueError(f"{name}: not a scalar or a 1-D sequence of rates ({e})") from None
+    if a.dtype == object or a.dtype.kind not in "iuf":
+        raise ValueError(f"{name}: rates must be real numbers (got dtype {a.dtype})")
+    if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n_volumes):
+        raise ValueError(f"{name}: a scalar or a 1-D sequence of {n_volumes} rates (one per volume), got shape {a.shape}")
+    scalar = a.ndim == 0
+    a = np.array(a, dtype=np.float64, ndmin=1)                     # (a contiguous copy)
+    if not np.all((a >= 0.0) & (a <= 1.0)):                        # (NaN fails both)
+        raise ValueError(f"{name}: rates must be finite and in [0, 1]")
+    return float(a[0]) if scalar else a
+
+
+def check_eval_lattice(lattice, env):
+    """lattice: (d, error_model, use_Y, volume_depth) of the decoder, or None (the environment's own).  Validates the environment as the supplier of
+    the lattice and the referee without touching the library; returns its (d, error_model, use_Y, volume_depth)."""
+    if env is None:
+        raise ValueError("an environment is needed: it supplies the lattice and the referee")
+    got = lattice_of(env)
+    d, model, use_Y, depth = got
+    check_decode_args(d, model, use_Y, depth, (depth, d + 1, d + 1))                 # odd d, d <= 7, <= 128 actions, known error model
+    if getattr(getattr(env, "_v", env), "wide", False):
+        raise NotImplementedError("scoring covers the narrow environment's referees: the wide environment (backend='wide' / the matching referee) is not supported")
+    if lattice is not None:
+        want = (int(lattice[0]), str(lattice[1]), bool(lattice[2]), int(lattice[3]))
+        same = got[0] == want[0] and got[1] == want[1] and got[3] == want[3] and (got[1] == "X" or got[2] == want[2])
+        if not same:
+            raise ValueError(f"the environment's lattice (d, error model, use_Y, volume_depth) = {got} is not the decoder's {want}")
+    return got
+
+
+def check_eval_args(lattice, env, n_volumes, p_phys=None, p_meas=None, seed=None, env_id_base=0, block=None):
+    """Validates an evaluate / sample request without touching the library.  Returns (n_volumes, p_phys, p_meas, seed, env_id_base, block): rates as
+    floats or per-volume float64 arrays (default: the environment's, p_meas=None with a given p_phys: the same as p_phys), block = volumes per
+    block of counters (default: all in one)."""
+    check_eval_lattice(lattice, env)
+    v = getattr(env, "_v", env)
+    if isinstance(n_volumes, (bool, np.bool_)) or not isinstance(n_volumes, (int, np.integer)) or n_volumes < 1:
+        raise ValueError(f"n_volumes must be a positive integer, not {n_volumes!r}")
+    n_volumes = int(n_volumes)
+    if n_volumes >= 1 << 31:
+        raise ValueError("n_volumes must be below 2^31")
+    if p_phys is None:
+        if p_meas is not None:
+            raise ValueError("p_meas without p_phys: give both, p_phys alone (p_meas = p_phys), or neither (the environment's rates)")
+        p_phys, p_meas = v.p_phys, v.p_meas
+    elif p_meas is None:
+        p_meas = p_phys
+    p_phys, p_meas = check_rates(p_phys, n_volumes, "p_phys"), check_rates(p_meas, n_volumes, "p_meas")
+    if isinstance(p_phys, float) != isinstance(p_meas, float):      # one array: the scalar becomes one too
+        full = lambda x: np.full(n_volumes, x, dtype=np.float64) if isinstance(x, float) else x
+        p_phys, p_meas = full(p_phys), full(p_meas)
+    if seed is None:
+        seed = v.seed
+    try:
+        ok = len(seed) == 2 and all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) and 0 <= x < 1 << 32 for x in seed)
+        seed = (int(seed[0]), int(seed[1])) if ok else seed
+    except (TypeError, IndexError):
+        ok = False
+    if not ok:
+        raise ValueError(f"seed must be a pair of 32-bit words, not {seed!r}")
+    if isinstance(env_id_base, (bool, np.bool_)) or not isinstance(env_id_base, (int, np.integer)) or not 0 <= env_id_base < 1 << 32:
+        raise ValueError(f"env_id_base must be an integer in 0 .. 2^32 - 1, not {env_id_base!r}")
+    if block is None:
+        block = n_volumes
+    if isinstance(block, (bool, np.bool_)) or not isinstance(block, (int, np.integer)) or block < 1:
+        raise ValueError(f"block must be a positive integer, not {block!r}")
+    return n_volumes, p_phys, p_meas, seed, int(env_id_base), int(block)
+
+
+def check_codes(x, d, name, allow_none=False):
+    """hidden_state codes [N, d, d] (or [N, d*d]), every cell in 0..3; numpy or torch on any device.  Returns N."""
+    if x is None:
+        if allow_none:
+            return None
+        raise ValueError(f"{name} is required")
+    shape = tuple(int(k) for k in x.shape)
+    if not (len(shape) in (2, 3) and shape[0] >= 1 and int(np.prod(shape[1:])) == d * d and (len(shape) == 2 or shape[1:] == (d, d))):
+        raise ValueError(f"{name} must have shape [N, {d}, {d}], got {shape}")
+    if hasattr(x, "is_cuda") or type(x).__module__.startswith("torch"):
+        bad = bool(((x < 0) | (x > 3)).any().item())
+    else:
+        a = np.asarray(x)
+        if a.dtype.kind not in "biuf":
+            raise ValueError(f"{name} must be numeric, got dtype {a.dtype}")
+        bad = bool(((a != 0) & (a != 1) & (a != 2) & (a != 3)).any())
+    if bad:
+        raise ValueError(f"{name} cells must be Pauli codes 0..3")
+    return shape[0]
+
+
+class EvalResult:
+    """Counters of scored volumes (COUNTER_NAMES) and what follows from them.  success: the residual error is a stabilizer (in the code space, trivial
+    homology class: the step's reward 1); alive: success, or the referee still names the residual's class (the step's done == False).
+    failure_rate = 1 - success / volumes is the logical failure probability of decoding one volume; death_rate = 1 - alive / volumes.  With
+    return_volumes the per-volume device tensors ride along: volumes, hidden, trivial, decode (a DecodeResult of device tensors), verdict
+    (bytes: VERDICT_*).  no_decoder: the same counters for frame = 0 where they were asked for."""
+
+    def __init__(self, counters, p_phys=None, p_meas=None):
+        self.counters = {k: int(x) for k, x in zip(COUNTER_NAMES, counters)}
+        self.p_phys, self.p_meas = p_phys, p_meas
+        self.volumes = self.hidden = self.trivial = self.decode = self.verdict = None
+        self.no_decoder = None
+
+    def __getattr__(self, name):
+        if name.startswith("n_") and name[2:] in COUNTER_NAMES:
+            return self.counters[name[2:]]
+        raise AttributeError(name)
+
+    @property
+    def failure_rate(self):
+        return 1.0 - self.counters["success"] / self.counters["volumes"]
+
+    @property
+    def death_rate(self):
+        return 1.0 - self.counters["alive"] / self.counters["volumes"]
+
+    @property
+    def failure_interval(self):
+        """Wilson 95 % interval of failure_rate."""
+        return wilson_interval(self.counters["volumes"] - self.counters["success"], self.counters["volumes"])
+
+    @property
+    def death_interval(self):
+        return wilson_interval(self.counters["volumes"] - self.counters["alive"], self.counters["volumes"])
+
+    @property
+    def trivial_share(self):
+        return self.counters["trivial"] / self.counters["volumes"]
+
+    @property
+    def mean_corrections(self):
+        return self.counters["corrections"] / self.counters["volumes"]
+
+    @property
+    def status_histogram(self):
+        return {name: self.counters[name] for name in ("identity", "repeat", "stopped")}
+
+    def summary(self):
+        """A JSON-ready dict of the counters and the derived figures."""
+        out = dict(self.counters)
+        out.update(failure_rate=self.failure_rate, failure_interval=list(self.failure_interval), death_rate=self.death_rate,
+                   death_interval=list(self.death_interval), trivial_share=self.trivial_share, mean_corrections=self.mean_corrections)
+        if self.no_decoder is not None:
+            out["no_decoder"] = self.no_decoder.summary()
+        return out
+
+    def __repr__(self):
+        lo, hi = self.failure_interval
+        return f"EvalResult(volumes={self.counters['volumes']}, failure_rate={self.failure_rate:.6g} [{lo:.6g}, {hi:.6g}], death_rate={self.death_rate:.6g})"
+
+
+def counters_from_arrays(verdict, trivial=None, status=None, n_corrections=None):
+    """dq_decode_count's sums on the host, from per-volume arrays (the checker of the device counters)."""
+    v = np.asarray(verdict).astype(np.int64)
+    zero = np.zeros_like(v)
+    st = zero if status is None else np.asarray(status).astype(np.int64)
+    return [int(v.size), int(np.asarray(zero if trivial is None else trivial).astype(bool).sum()), int(((v & VERDICT_IN_CODESPACE) != 0).sum()),
+            int(((v & VERDICT_SUCCESS) != 0).sum()), int(((v & VERDICT_ALIVE) != 0).sum()), int((st == STATUS_IDENTITY).sum()),
+            int((st == STATUS_REPEAT).sum()), int((st == STATUS_STOPPED).sum()),
+            int(0 if n_corrections is None else np.asarray(n_corrections).astype(np.int64).sum())]
+
+
+def _narrow_env(env):
+    """The VectorEnv behind `env` (the drop-in class keeps one): the holder of the dq_env handle the kernels read the lattice and the referee from."""
+    v = getattr(env, "_v", env)
+    if getattr(v, "_h", None) is None or not hasattr(v, "device"):
+        raise TypeError("env must be a VectorEnv (or the drop-in environment class): its handle supplies the lattice tables and the referee")
+    return v
+
+
+class Evaluator:
+    """Owns a dq_decode_eval handle for chunks of at most `chunk` volumes of one lattice: the sampler, the verdict and the counters."""
+
+    def __init__(self, d, error_model, use_Y, volume_depth, chunk=DEFAULT_CHUNK, device=None):
+        import torch
+        from . import _lib
+        check_decode_args(d, error_model, use_Y, volume_depth, (volume_depth, d + 1, d + 1))
+        self.d, self.error_model, self.use_Y, self.volume_depth, self.chunk = int(d), error_model, bool(use_Y), int(volume_depth), int(chunk)
+        if self.chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        self.L = _lib.lib()
+        _lib.require_gpu()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        cfg = _lib.DecodeCfg(d=self.d, volume_depth=self.volume_depth, error_model=MODELS[error_model], use_Y=int(self.use_Y), masked_greedy=0,
+                             max_actions=1, action_planes=0, obs_form=0)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.dq_decode_eval_create(ctypes.byref(cfg), self.chunk, ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.dq_decode_eval_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def sample_into(self, venv, m, lattice_id, seed, p_phys, p_meas, volumes, hidden, trivial):
+        """m <= chunk volumes of lattices lattice_id .. lattice_id + m - 1 (mod 2^32) into the given device tensors."""
+        from . import _lib
+        arr = (ctypes.c_uint32 * 2)(*seed)
+        each = not isinstance(p_phys, float)
+        _lib.check(self.L.dq_decode_sample(self._h, venv._h, m, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
+                                           p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, _lib.ptr(volumes),
+                                           _lib.ptr(hidden), _lib.ptr(trivial), self._stream()))
+
+    def verdict_into(self, venv, hidden, frame, m, out):
+        from . import _lib
+        _lib.check(self.L.dq_decode_verdict(self._h, venv._h, _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), self._stream()))
+
+    def count_into(self, verdict, trivial, status, n_corr, m, first, block, counters):
+        from . import _lib
+        _lib.check(self.L.dq_decode_count(_lib.ptr(verdict), _lib.ptr(trivial), _lib.ptr(status), _lib.ptr(n_corr), m, first, block,
+                                          counters.shape[0], _lib.ptr(counters), self._stream()))
+
+
+def sample_volumes(env, n_volumes, p_phys=None, p_meas=None, seed=None, env_id_base=0, chunk=DEFAULT_CHUNK, to_host=False):
+    """n_volumes independent memory experiments from a clean lattice, drawn on the device: volume i is volume_depth rounds of (error, faulty
+    syndrome measurement) of lattice env_id_base + i under the environment's random-number convention, all-zero volumes included (the
+    environment's reset redraws those; this is the unbiased sample a failure rate needs).  env: the lattice (a VectorEnv or the drop-in class);
+    rates: scalars or one per volume, default the environment's; seed: default the environment's.  Returns (volumes uint8 [N, depth, d+1, d+1]
+    -- decode's input --, hidden uint8 [N, d, d] the accumulated error as hidden_state codes, trivial uint8 [N]: 1 where the volume is all zero),
+    device tensors unless to_host."""
+    import torch
+    n, ph, pm, seed, base, _ = check_eval_args(None, env, n_volumes, p_phys, p_meas, seed, env_id_base)
+    venv = _narrow_env(env)
+    d, model, use_Y, depth = lattice_of(venv)
+    dev = venv.device
+    ev = Evaluator(d, model, use_Y, depth, chunk=min(int(chunk), n), device=dev)
+    try:
+        vol = torch.empty((n, depth, d + 1, d + 1), dtype=torch.uint8, device=dev)
+        hid = torch.empty((n, d, d), dtype=torch.uint8, device=dev)
+        triv = torch.empty(n, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            for s in range(0, n, ev.chunk):
+                m = min(ev.chunk, n - s)
+                each = not isinstance(ph, float)
+                ev.sample_into(venv, m, base + s, seed, ph[s:s + m] if each else ph, pm[s:s + m] if each else pm, vol[s:s + m], hid[s:s + m],
+                               triv[s:s + m])
+            torch.cuda.current_stream(dev).synchronize()
+    finally:
+        ev.close()
+    out = (vol, hid, triv)
+    return tuple(x.cpu().numpy() for x in out) if to_host else out
+
+
+def verdict(hidden, frame, env, chunk=DEFAULT_CHUNK, to_host=False):
+    """What the environment's step decides on the residual error hidden XOR frame of each volume (hidden, frame: Pauli codes 0..3 [N, d, d], numpy
+    or torch; frame=None: no correction, the "no decoder" baseline), with the referee installed on `env`.  Returns (bytes uint8 [N] -- VERDICT_*:
+    in code space, class of the residual, success, alive, the referee's class --, EvalResult of their counts)."""
+    import torch
+    d, model, use_Y, depth = check_eval_lattice(None, env)
+    n = check_codes(hidden, d, "hidden")
+    if frame is not None and check_codes(frame, d, "frame") != n:
+        raise ValueError(f"hidden has {n} volumes, frame {int(frame.shape[0])}")
+    venv = _narrow_env(env)
+    dev = venv.device
+    on = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))).to(device=dev, dtype=torch.uint8).reshape(n, d, d).contiguous()
+    hid, frm = on(hidden), None if frame is None else on(frame)
+    ev = Evaluator(d, model, use_Y, depth, chunk=min(int(chunk), n), device=dev)
+    try:
+        out = torch.empty(n, dtype=torch.uint8, device=dev)
+        counters = torch.zeros((1, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            for s in range(0, n, ev.chunk):
+                m = min(ev.chunk, n - s)
+                ev.verdict_into(venv, hid[s:s + m], None if frm is None else frm[s:s + m], m, out[s:s + m])
+                ev.count_into(out[s:s + m], None, None, None, m, s, n, counters)
+            res = EvalResult(counters.cpu().numpy()[0])
+    finally:
+        ev.close()
+    return (out.cpu().numpy() if to_host else out), res
+
+
 class DecodeResult:
     """Per-volume results, in input order.  corrections int32 [N, max_actions] (padded with -1), n_corrections int32 [N], frame uint8
     [N, d, d] (net Pauli frame of the corrections as hidden_state codes 0..3), status uint8 [N] (STATUS_*).  One volume in: the leading
@@ -144,6 +455,9 @@ class BatchDecoder:
         self._h = h
 
     def close(self):
+        if getattr(self, "_eval", None) is not None:
+            self._eval.close()
+            self._eval = None
         if getattr(self, "_h", None):
             self.L.dq_decode_destroy(self._h)
             self._h = None
@@ -193,3 +507,93 @@ class BatchDecoder:
         if single:
             out = [x[0] for x in out]
         return DecodeResult(*out, iterations=iters)
+
+    # -- scoring: sample -> decode -> verdict -> counts on the device --------------------------------------------------
+    def _decode_into(self, params, packed, syn, m, corr, ncorr, frame, status):
+        """One dq_decode_run over m <= chunk volumes already on the device; returns the iterations."""
+        import torch
+        from . import _lib
+        it = ctypes.c_int(0)
+        _lib.check(self.L.dq_decode_run(self._h, self.net._h, _lib.ptr(params), _lib.ptr(packed), _lib.ptr(syn), m, _lib.ptr(corr), _lib.ptr(ncorr),
+                                        _lib.ptr(frame), _lib.ptr(status), ctypes.byref(it), torch.cuda.current_stream(self.device).cuda_stream))
+        return int(it.value)
+
+    def evaluate(self, params, env, n_volumes, p_phys=None, p_meas=None, seed=None, env_id_base=0, return_volumes=False, block=None,
+                 no_decoder=False, timings=None):
+        """Draws n_volumes volumes (sample_volumes' rule: lattice env_id_base + i, all-zero volumes kept), decodes them with `params`, asks the
+        referee installed on `env` for the verdict on hidden XOR frame and sums the flags, all on the device, at most `chunk` volumes resident;
+        the host reads the counters once.  Rates: scalars or one per volume; default the environment's.  block: volumes per contiguous block of
+        counters (one error rate per block): returns a list of EvalResult, one per block; default one EvalResult for all.  no_decoder: also count
+        the verdict for frame = 0 (EvalResult.no_decoder).  return_volumes: the per-volume device tensors ride on the (first) result.  timings:
+        a dict that receives the wall seconds of the phases (sample / decode / verdict), each closed by a synchronisation.  The results do not
+        depend on the chunk size."""
+        import time
+        import torch
+        mine = (self.d, self.error_model, self.use_Y, self.volume_depth)
+        n, ph, pm, seed, base, blk = check_eval_args(mine, env, n_volumes, p_phys, p_meas, seed, env_id_base, block)
+        venv = _narrow_env(env)
+        dev = self.device
+        index = lambda x: torch.cuda.current_device() if torch.device(x).index is None else torch.device(x).index
+        if index(venv.device) != index(dev):
+            raise ValueError(f"the environment lives on {venv.device}, the decoder on {dev}")
+        if getattr(self, "_eval", None) is None:
+            self._eval = Evaluator(*mine, chunk=self.chunk, device=dev)
+        ev = self._eval
+        d, depth, each = self.d, self.volume_depth, not isinstance(ph, float)
+        rows = n if return_volumes else min(self.chunk, n)
+        vol = torch.empty((rows, depth, d + 1, d + 1), dtype=torch.uint8, device=dev)
+        hid = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+        triv = torch.empty(rows, dtype=torch.uint8, device=dev)
+        corr = torch.empty((rows, self.max_actions), dtype=torch.int32, device=dev)
+        ncorr = torch.empty(rows, dtype=torch.int32, device=dev)
+        frame = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+        status = torch.empty(rows, dtype=torch.uint8, device=dev)
+        verd = torch.empty(rows, dtype=torch.uint8, device=dev)
+        verd0 = torch.empty(min(self.chunk, n), dtype=torch.uint8, device=dev) if no_decoder else None
+        n_blocks = -(-n // blk)
+        counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
+        counters0 = torch.zeros_like(counters) if no_decoder else None
+        iters = []
+
+        def phase(name, t0):
+            if timings is None:
+                return t0
+            torch.cuda.current_stream(dev).synchronize()
+            t1 = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + (t1 - t0)
+            return t1
+
+        with torch.cuda.device(dev):
+            packed = self.net.pack(params)
+            for s in range(0, n, self.chunk):
+                m = min(self.chunk, n - s)
+                o = s if return_volumes else 0
+                sl = slice(o, o + m)
+                t = phase("setup", time.perf_counter()) if timings is not None else 0.0
+                a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
+                if each and (a == a[0]).all() and (b == b[0]).all():   # one rate pair in this chunk: the scalar form (the same thresholds, no table upload)
+                    a, b = float(a[0]), float(b[0])
+                ev.sample_into(venv, m, base + s, seed, a, b, vol[sl], hid[sl], triv[sl])
+                t = phase("sample", t)
+                iters.append(self._decode_into(params, packed, vol[sl], m, corr[sl], ncorr[sl], frame[sl], status[sl]))
+                t = phase("decode", t)
+                ev.verdict_into(venv, hid[sl], frame[sl], m, verd[sl])
+                ev.count_into(verd[sl], triv[sl], status[sl], ncorr[sl], m, s, blk, counters)
+                if no_decoder:
+                    ev.verdict_into(venv, hid[sl], None, m, verd0[:m])
+                    ev.count_into(verd0[:m], triv[sl], None, None, m, s, blk, counters0)
+                t = phase("verdict", t)
+            host = counters.cpu().numpy()
+            host0 = counters0.cpu().numpy() if no_decoder else None
+        results = []
+        for b in range(n_blocks):
+            lo = b * blk
+            r = EvalResult(host[b], ph[lo] if each else ph, pm[lo] if each else pm)
+            if no_decoder:
+                r.no_decoder = EvalResult(host0[b], r.p_phys, r.p_meas)
+            results.append(r)
+        if return_volumes:
+            r = results[0]
+            r.volumes, r.hidden, r.trivial, r.verdict = vol, hid, triv, verd
+            r.decode = DecodeResult(corr, ncorr, frame, status, iterations=iters)
+        return results[0] if block is None else results

@@ -710,6 +710,51 @@ dq_status dq_decode_run(dq_decode* dec, dq_qnet* net, const float* params_dev, c
                         int32_t* corrections_dev, int32_t* n_corr_dev, uint8_t* frame_dev, uint8_t* status_dev, int* iterations, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Scoring batched decoding: sample -> dq_decode_run -> verdict -> counts, all on the device (csrc/decode_eval.hip).  The figure it serves is the
+ * logical failure probability of decoding ONE volume of volume_depth faulty rounds; the reference only reports mean episode lifetimes.
+ *
+ * dq_decode_sample: n independent memory experiments from a clean lattice.  Volume i runs volume_depth rounds, each one generate_error
+ * (Function_Library.py:67-122 / 134-160) followed by one generate_faulty_syndrome (Function_Library.py:176-223) -- the round of
+ * Environments.py:160-170 -- WITHOUT the redraw of all-zero volumes (Environments.py:171).  Random numbers: the environment's Philox convention,
+ * key = seed, lattice id = env_id_base + i (mod 2^32), round counter 0 .. volume_depth - 1, lane = site.  Volume i is therefore the first
+ * volume_depth rounds of lattice env_id_base + i, and where those are not all zero it is what dq_env_reset produces for that lattice.
+ * Rates: p_phys_each / p_meas_each NULL: the scalar pair for every volume; else HOST arrays of n rates, volume i runs at entry i (thresholds as
+ * dq_env_set_rates_per_lattice computes them; read before the call returns, uploaded by one copy ordered on `stream`).
+ * `env` supplies the lattice (its tables are read in place; its own lattices, rates and seed are not touched) and must be the lattice the handle
+ * was created for.  Outputs: volumes_dev uint8 [n][volume_depth][d+1][d+1] (dq_decode_run's input, 4-byte aligned), hidden_dev uint8 [n][d][d]
+ * the accumulated error as hidden_state codes 0..3, trivial_dev uint8 [n]: 1 where the whole volume is zero.
+ *
+ * dq_decode_verdict: per volume the residual error = hidden XOR frame (Pauli components XOR: obtain_new_error_configuration,
+ * Function_Library.py:226-241; frame_dev NULL = no correction), then what step() decides on that hidden state (Environments.py:139-151):
+ * true = perfect syndrome of the residual, correct = its homology class, decoded = the class the referee INSTALLED ON `env` assigns to true --
+ * every referee kind of the handle is honoured with the step's precedence (Dense stack, joint table, component tables), read in place.
+ * verdict_dev uint8 [n]: DQ_VERDICT_IN_CODESPACE (true == 0) | correct << DQ_VERDICT_CLASS_SHIFT | DQ_VERDICT_SUCCESS (correct == 0 and
+ * true == 0: the step's reward 1) | DQ_VERDICT_ALIVE (success or decoded == correct: the step's done == False) | decoded << DQ_VERDICT_DECODED_SHIFT.
+ * dq_decode_run does not record its stopping action, but the environment APPLIES a repeated action before it tests for the repeat
+ * (Environments.py:135-136 against :131): the verdict is what the environment returned on the stopping step for volumes of status
+ * DQ_DECODE_IDENTITY only.
+ *
+ * dq_decode_count: adds the flags of n volumes to DQ_EVAL_COUNTERS uint64 counters per contiguous block of `block` volumes: volume i counts into
+ * counters_dev[((first + i) / block) * DQ_EVAL_COUNTERS + DQ_EVAL_*] (`first`: the global index of volume 0, so that a chunked caller keeps one
+ * table; n_blocks: rows of the table).  trivial_dev / status_dev / n_corr_dev may be NULL (their counters stay).  The caller zeroes the table.
+ * No reference counterpart. */
+typedef struct dq_decode_eval dq_decode_eval;
+enum { DQ_VERDICT_IN_CODESPACE = 1, DQ_VERDICT_CLASS_SHIFT = 1, DQ_VERDICT_SUCCESS = 8, DQ_VERDICT_ALIVE = 16, DQ_VERDICT_DECODED_SHIFT = 5 };
+enum { DQ_EVAL_VOLUMES = 0, DQ_EVAL_TRIVIAL, DQ_EVAL_IN_CODESPACE, DQ_EVAL_SUCCESS, DQ_EVAL_ALIVE, DQ_EVAL_IDENTITY, DQ_EVAL_REPEAT, DQ_EVAL_STOPPED,
+       DQ_EVAL_CORRECTIONS, DQ_EVAL_COUNTERS };
+/* Owns the per-volume threshold table and the Dense-stack referee's scratch for up to max_volumes volumes; of cfg the lattice (d, volume_depth,
+ * error_model, use_Y) is read: the same limits as dq_decode_create (DQ_ERR_UNSUPPORTED beyond d = 7 / 128 actions). */
+dq_status dq_decode_eval_create(const dq_decode_cfg* cfg, int max_volumes, dq_decode_eval** out);
+void dq_decode_eval_destroy(dq_decode_eval* ev);
+dq_status dq_decode_sample(dq_decode_eval* ev, const dq_env* env, int n, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
+                           const double* p_phys_each, const double* p_meas_each, uint8_t* volumes_dev, uint8_t* hidden_dev, uint8_t* trivial_dev,
+                           void* stream);
+dq_status dq_decode_verdict(dq_decode_eval* ev, dq_env* env, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev,
+                            void* stream);
+dq_status dq_decode_count(const uint8_t* verdict_dev, const uint8_t* trivial_dev, const uint8_t* status_dev, const int32_t* n_corr_dev, int n,
+                          int64_t first, int block, int n_blocks, uint64_t* counters_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Live kernel timing (measurement only; no reference counterpart).  dq_prof_arm(id, n) times up to n
  * launches of kernel family `id` (0 <= id < dq_prof_kernel_count(), names from dq_prof_kernel_name) with HIP
  * events on the stream they are launched on -- the fused chains and the environment step carry the event pair
