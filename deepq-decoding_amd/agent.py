@@ -112,7 +112,7 @@ class Adam:
 # memory and policies
 # ----------------------------------------------------------------------------------------------------------
 class SequentialMemory:
-    """Capacity holder; the storage is the device replay ring of DQNCore (see core.py)."""
+    """Capacity holder; the storage is the device replay ring of DQNCore (core.ring, a replay.ReplayRing)."""
 
     def __init__(self, limit, window_length=1, ignore_episode_boundaries=False):
         if window_length != 1:
@@ -124,7 +124,7 @@ class SequentialMemory:
     @property
     def nb_entries(self):
         if self._core is not None:
-            return min(self._core.filled, self._core.T) * self._core.N
+            return self._core.ring.nb_entries
         if self._saved is not None:                 # unpickled, not bound to an agent yet
             T, N = self._saved["obs_shape"][:2]
             return min(int(self._saved["filled"]), T) * N
@@ -135,40 +135,14 @@ class SequentialMemory:
 
     # pickling (TRAIN:156-157 pickles dqn.memory; the Continue script reloads it)
     def __getstate__(self):
-        st = dict(limit=self.limit, window_length=1, _saved=None)
-        c = self._core
-        if c is not None:
-            st["_saved"] = dict(obs_shape=tuple(c.obs_ring.shape), action=c.action_ring.cpu().numpy(), reward=c.reward_ring.cpu().numpy(),
-                                terminal=c.terminal_ring.cpu().numpy(), cur=c.cur, filled=c.filled)
-            if getattr(c, "compact", False):     # the ring holds patch words (core.py): pickled as they are, d * d words per observation
-                st["_saved"]["patch"] = c.patch_ring.cpu().numpy()
-            else:
-                st["_saved"]["obs"] = np.packbits(c.obs_ring.cpu().numpy(), axis=None)
-        elif self._saved is not None:
-            st["_saved"] = self._saved
-        return st
+        saved = self._core.ring.state() if self._core is not None else self._saved      # the ring's own dict (ReplayRing.state)
+        return dict(limit=self.limit, window_length=1, _saved=saved)
 
     def __setstate__(self, st):
         self.limit, self.window_length, self._saved, self._core = st["limit"], 1, st.get("_saved"), None
 
     def _restore_into(self, core):
-        s = self._saved
-        if s is None or tuple(s["obs_shape"]) != tuple(core.obs_ring.shape):
-            return False
-        if "patch" in s:                            # pickled from a compact ring
-            patch = torch.from_numpy(s["patch"]).to(core.device)
-            if getattr(core, "compact", False) and tuple(patch.shape) == tuple(core.patch_ring.shape):
-                core.patch_ring.copy_(patch)
-            else:
-                core.obs_ring.copy_(core.env.patch_to_obs(patch))
-        else:
-            n = int(np.prod(s["obs_shape"]))
-            core.obs_ring.copy_(torch.from_numpy(np.unpackbits(s["obs"], count=n).reshape(s["obs_shape"])))
-        core.action_ring.copy_(torch.from_numpy(s["action"]))
-        core.reward_ring.copy_(torch.from_numpy(s["reward"]))
-        core.terminal_ring.copy_(torch.from_numpy(s["terminal"]))
-        core.cur, core.filled = int(s["cur"]), int(s["filled"])
-        return True
+        return core.ring.load_state(self._saved)
 
 
 class Policy:
@@ -404,12 +378,7 @@ class DQNAgent:
             if c.target_pk is not None and prev.target_pk is not None:
                 c.target_pk.copy_(prev.target_pk)
             c.updates, c.vector_steps = prev.updates, prev.vector_steps
-            if tuple(prev.obs_ring.shape) == tuple(c.obs_ring.shape):
-                for a, b in ((c.obs_ring, prev.obs_ring), (c.action_ring, prev.action_ring), (c.reward_ring, prev.reward_ring),
-                             (c.terminal_ring, prev.terminal_ring)):
-                    a.copy_(b)
-                c.cur, c.filled = prev.cur, prev.filled
-            elif prev.filled > 1:
+            if not c.ring.copy_from(prev.ring) and prev.filled > 1:
                 warnings.warn("the replay memory of the previous environment does not fit the new one (other lattice count or "
                               "observation shape) and was dropped")
         self.memory._core = self._core
@@ -803,7 +772,7 @@ class DQNAgent:
         while total > 0:
             slot = core.cur
             core.act_and_step(eps, masked_greedy=masked, record_stats=False)
-            check(L.dq_test_bookkeeping(ptr(core.terminal_ring[slot]), ptr(venv.was_reset), ptr(core.reward_ring[slot]), ptr(venv.lifetime), N, step,
+            check(L.dq_test_bookkeeping(ptr(core.ring.terminal[slot]), ptr(venv.was_reset), ptr(core.ring.reward[slot]), ptr(venv.lifetime), N, step,
                                         ptr(quota_d), ptr(ep_reward), ptr(ep_len), ptr(records), total, ptr(counter), core._stream()))
             step += 1
             if step % sync_interval == 0 and int(counter.item()) >= total:

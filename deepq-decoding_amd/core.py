@@ -6,14 +6,14 @@ This is the vectorised form of the loop keras-rl runs one lattice / one minibatc
 performs exactly that sequence per step; with N lattices every launch handles all of them and nothing is
 copied to the host inside a step.
 
-Replay ring (SequentialMemory(limit, window_length=1), :109): time-major device tensors
-    obs      uint8 [T, N, C, H, W]     action int32 [T, N]     reward float [T, N]     terminal uint8 [T, N]
-row (t, i) = what lattice i saw / did / received at vector step t; its successor observation is row (t+1, i).
-The environment kernel writes the new observation straight into slot t+1, so there is no append copy; a
-lattice that terminated spends its next step being reset (keras-rl's extra forward/backward on the terminal
-observation), which is what makes keras-rl's "skip entries whose predecessor was terminal" sampling rule carry
-over unchanged.
+The transitions live in `DQNCore.ring`, a replay.ReplayRing (time-major device tensors; its fields, slot arithmetic, pickled
+form and the scratch ring of an evaluation are that class's business).  The environment kernel writes the new observation
+straight into slot t+1, so there is no append copy; a lattice that terminated spends its next step being reset (keras-rl's
+extra forward/backward on the terminal observation), which is what makes keras-rl's "skip entries whose predecessor was
+terminal" sampling rule carry over unchanged.  An update is one procedure (`_learn`) whatever the number of GPUs: TD job,
+form of the gradient exchange (`_exchange_form`), backward, exchange, optimizer step, repack.
 """
+import contextlib
 import ctypes
 import os
 
@@ -22,49 +22,41 @@ import torch
 
 from . import _lib, dist as _dist, qnet as _q
 from ._lib import check, ptr
+from .replay import ObsRingView, ReplayRing      # (ObsRingView: re-exported)
 
 
 MIN_FILLED = 4      # ring slots an update needs: keras-rl asserts nb_entries >= window_length + 2 (csrc/common.h dq_replay_row)
 
 
-class ObsRingView:
-    """`DQNCore.obs_ring` where the ring holds PATCH WORDS (DQNCore.compact): the padded uint8 observations [T, N, C, H, W] the
-    reference's memory would hold (SequentialMemory stores the env's board_state, TRAIN:109), decoded on demand from
-    `DQNCore.patch_ring` (env.patch_to_obs: the image is a fixed function of the words).  Indexing returns decoded tensors; copy_()
-    encodes.  Tests, pickling and diagnostics only -- nothing in the loop touches it."""
+class _TargetAhead:
+    """State of DQ_TARGET_AHEAD=1 (off by default): the extra updates' TARGET forwards on a second stream.  The target network does not change
+    inside a vector step and the extra updates' rows are drawn by one launch in front of them, so Q_target(s1) of update i needs nothing
+    update i - 1 produces: a second network handle evaluates it on `stream`, released by a mark inside update i - 1's backward
+    (dq_qnet_mark_conv_backward) and handed to update i's TD launch by an event.  Bit-identical results (tests/test_agent_gpu.py) and SLOWER on
+    one MI355X, 138.5 against 123.9 us per update: the two event hand-offs cost more than the 10 us they move (NOTEBOOK.md Round 5 section 3)."""
 
-    def __init__(self, core):
-        self._c = core
+    def __init__(self, net, device):
+        self.net, self.stream = net, torch.cuda.Stream(device=device)      # (a network handle of its own: its own per-job scratch)
+        self.e_rows = torch.cuda.Event()             # behind the launch that drew the updates' rows
+        self.ready, self.marks = [], []              # per update: "Q_target(s1) ready" event, mark inside the backward
+        self.q1 = None                               # Q_target(s1) rows [k - 1][B][A]
 
-    @property
-    def shape(self):
-        p = self._c.patch_ring
-        return torch.Size(tuple(p.shape[:2]) + tuple(self._c.env.obs_shape))
 
-    dtype = torch.uint8
+class _SideStream:
+    """A second stream and the events that order it against the step's own.  DQ_ENV_STREAM=1 (e_fwd, e_env): the environment launch of a fused
+    step does not feed the same step's backward (keras-rl's sampling range), so it CAN run beside the backward chain -- 0.299 ms per step against
+    0.279 on one stream, the two hand-offs cost more than the 15 us launch they hide: off by default.  DQ_DIST_MODE=overlap (e_dense, e_ar): the
+    dense range's all-reduce (DQNCore._exchange)."""
 
-    @property
-    def device(self):
-        return self._c.patch_ring.device
+    def __init__(self, device, *events):
+        self.stream, self.inflight = torch.cuda.Stream(device=device), False
+        for name in events:
+            setattr(self, name, torch.cuda.Event())
 
-    def __getitem__(self, idx):
-        return self._c.env.patch_to_obs(self._c.patch_ring[idx])
 
-    def clone(self):
-        return self._c.env.patch_to_obs(self._c.patch_ring)
-
-    def cpu(self):
-        return self.clone().cpu()
-
-    def copy_(self, src):
-        if isinstance(src, ObsRingView):
-            self._c.patch_ring.copy_(src._c.patch_ring)
-        else:
-            self._c.patch_ring.copy_(self._c.env.obs_to_patch(torch.as_tensor(src).to(self.device)))
-        return self
-
-    def __eq__(self, other):
-        return self.clone() == (other.clone() if isinstance(other, ObsRingView) else other)
+def _ring_field(name):
+    """DQNCore.<attribute> = self.ring.<name>, for callers outside this module (the loop itself reads self.ring)."""
+    return property(lambda self: getattr(self.ring, name), lambda self, value: setattr(self.ring, name, value))
 
 
 class DQNCore:
@@ -87,47 +79,32 @@ class DQNCore:
         self.rank, self.world_size, self.pg = rank, world_size, process_group
         self.last_index = None       # rows of the most recent update (self.index, or a row of _index_multi)
         self._index_multi = None     # [k - 1][B] rows of the extra updates of a vector step (_extra_updates)
-        # The extra updates' TARGET forwards on a second stream (round 5; DQ_TARGET_AHEAD=1, off by default): the target network does not change inside a
-        # vector step and all the extra updates' rows are drawn by one launch in front of them (dq_replay_sample_multi), so Q_target(s1) of update i
-        # needs nothing update i - 1 produces.  A second network handle (its own per-job scratch) evaluates it on a side stream, released by a mark
-        # inside update i - 1's backward (dq_qnet_mark_conv_backward) and handed to update i's TD launch by an event; the updates' own launch pair then
-        # carries two forwards instead of three.  Bit-identical results (tests/test_agent_gpu.py) -- and SLOWER on one MI355X: 32 updates of 4096 per
-        # vector step run 123.9 us per update on one stream and 138.5 us this way (135.8 us with the side stream running free): the main stream's
-        # kernels do shrink to 113.5 us, but the two event hand-offs per update cost more than the 10 us they move (NOTEBOOK.md Round 5 section 3;
-        # the same result as DQ_ENV_STREAM in round 1 and DQ_DIST_MODE=overlap in round 4).
         self.target_ahead = os.environ.get("DQ_TARGET_AHEAD", "0") == "1"
-        self._side = None            # (QNetwork, stream, row event, [events], Q_target(s1) rows [k - 1][B][A])
+        self._side = None            # DQ_TARGET_AHEAD's state (_TargetAhead), created at its first use
         self.pair_targets = os.environ.get("DQ_PAIR_TARGETS", "1") != "0"      # extra updates in pairs (_extra_updates); 0: three forwards per launch pair
         self._q1_pair = None
         self._rccl, self._rccl2, self._rccl_tried = None, None, False       # the learner's own RCCL communicator (dist.make_rccl), created at the first several-GPU update
         self.L = _lib.lib()
         dev = self.device
         # ring
-        self.T = max(MIN_FILLED, int(memory_limit) // self.N + 1)
-        C, H, W = env.obs_shape
+        self._wide = bool(getattr(env, "wide", False))       # lattices beyond d = 7 (csrc/env_big.hip)
+        C = env.obs_shape[0]
         # Compact observations (include/deepq_hip.h dq_env_patch_output, dq_qnet_set_patch_input): the ring holds d * d patch words per
         # transition (128 bytes at d = 5 instead of the 847-byte padded image; 2^20 transitions: 134 MB instead of 0.9 GB), the environment
         # writes them, the first convolution reads them.  Where the fused chains and the one-word-per-plane environment cover the
         # configuration; DQ_COMPACT_OBS=0 (or compact=False) keeps the uint8 ring.
         if compact is None:
             compact = os.environ.get("DQ_COMPACT_OBS", "1") != "0"
-        self.compact = bool(compact and not getattr(env, "wide", False) and getattr(env, "patch_supported", False) and net.fused_supported
-                            and net.fused_enabled and C == env.volume_depth + env.n_action_layers and net.c_layers[0][1:] == [3, 2])
-        if self.compact:
+        compact = bool(compact and not self._wide and getattr(env, "patch_supported", False) and net.fused_supported
+                       and net.fused_enabled and C == env.volume_depth + env.n_action_layers and net.c_layers[0][1:] == [3, 2])
+        if compact:
             try:
                 net.set_patch_input(env.volume_depth, env.patch_stride)        # (before the first pack(): the packed buffer carries the compact kernel)
             except _lib.DeepQError:
-                self.compact = False
-        if self.compact:
-            self.patch_ring = torch.zeros((self.T, self.N, env.patch_stride), dtype=torch.int32, device=dev)
-            self._obs_ring = None
-        else:
-            self.patch_ring = None
-            self._obs_ring = torch.zeros((self.T, self.N, C, H, W), dtype=torch.uint8, device=dev)
-        self.action_ring = torch.zeros((self.T, self.N), dtype=torch.int32, device=dev)
-        self.reward_ring = torch.zeros((self.T, self.N), dtype=torch.float32, device=dev)
-        self.terminal_ring = torch.zeros((self.T, self.N), dtype=torch.uint8, device=dev)
-        self.cur, self.filled = 0, 0
+                compact = False
+        self.ring = ReplayRing(max(MIN_FILLED, int(memory_limit) // self.N + 1), self.N, env.obs_shape, env.patch_to_obs, env.obs_to_patch,
+                               env.patch_stride if compact else None, dev)
+        self._train_ring = None      # (the training ring, started) while an evaluation runs on a scratch ring (begin_eval)
         # parameters
         self.params = net.init_params(self.seed) if params is None else params
         _dist.broadcast_(self.params, src=0, group=self.pg)
@@ -142,7 +119,7 @@ class DQNCore:
         self.q_act = torch.zeros((self.N, self.A), dtype=torch.float32, device=dev)
         B = self.batch_size
         self.index = torch.zeros(B, dtype=torch.int32, device=dev)         # rows of the update in progress
-        self._index_next = torch.zeros(B, dtype=torch.int32, device=dev)   # rows drawn ahead by an environment launch (_presampled)
+        self._index_next = torch.zeros(B, dtype=torch.int32, device=dev)   # rows drawn ahead by an environment launch (ring.presampled)
         self.q1_online = torch.zeros((B, self.A), dtype=torch.float32, device=dev)
         self.q1_target = torch.zeros((B, self.A), dtype=torch.float32, device=dev)
         self.q0 = torch.zeros((B, self.A), dtype=torch.float32, device=dev)
@@ -151,16 +128,12 @@ class DQNCore:
         self.metrics = torch.zeros(_q.TD_METRICS_FLOATS, dtype=torch.float32, device=dev)
         self.stats = torch.zeros(4, dtype=torch.int64, device=dev)
         self._stats_pending = None   # episode bookkeeping not yet launched (slot,)
-        self._presampled = None      # (update number, head slot, filled slots) the minibatch in self.index was drawn for
         self.defer_stats = True      # act_and_step leaves the bookkeeping launch to the next update() (dq_post_step) / act / read_stats
         self._metrics_stale = False
         self.vector_steps = 0        # policy / environment counter
         self.updates = 0             # optimizer steps taken
         self.started = False
-        # The environment launch of a fused step does not feed the same step's backward (keras-rl's sampling range), so it CAN run on its
-        # own stream beside the backward chain (DQ_ENV_STREAM=1).  Measured on one MI355X: 0.299 ms per step against 0.279 on one stream
-        # -- the two cross-stream event hand-offs cost more than the 15 us launch they hide -- so it is off by default.
-        self._env_stream = torch.cuda.Stream(device=dev) if os.environ.get("DQ_ENV_STREAM", "0") == "1" else None
+        self._env_side = _SideStream(dev, "e_fwd", "e_env") if os.environ.get("DQ_ENV_STREAM", "0") == "1" else None
         # step_and_update on one GPU: the environment launch rides on the dense backward's first kernel (DQ_RIDE_ENV=0: separate launches)
         self.ride_env = os.environ.get("DQ_RIDE_ENV", "1") != "0"
         # DQ_TD_AUTOSCALE=1 (or auto_scale = True): the fused backward's gradient scale MEASURED from every minibatch's TD errors (dq_td_job.auto_scale: one
@@ -173,42 +146,28 @@ class DQNCore:
         self._range_ok_at = 0        # self.updates at the last synchronisation that found the range flag clear
         self.local_stats = [0, 0, 0, 0]
         self.inexact_total = 0
-        self._inexact_acc = torch.zeros((), dtype=torch.int64, device=dev) if getattr(env, "wide", False) else None
+        self._inexact_acc = torch.zeros((), dtype=torch.int64, device=dev) if self._wide else None
         self.ar_events = None        # bench.py: a list here collects HIP-event pairs around the exposed part of the gradient all-reduce
         self.ar_pool = []            # ... taken from this pool of pre-created pairs (creating two timing events per step costs host time inside the timed region)
         self.ar_stride, self._ar_seen = 1, 0     # ... in every ar_stride-th step only (two marker packets in the stream cost the step ~4 us)
-        self._e_fwd, self._e_env = torch.cuda.Event(), torch.cuda.Event()
-        self._ar_stream = None       # DQ_DIST_MODE=overlap: the second stream of the dense range's all-reduce (created at its first use)
-        self._env_inflight = False
+        self._overlap = None         # DQ_DIST_MODE=overlap: the dense range's all-reduce stream (_SideStream, created at its first use)
 
     # ------------------------------------------------------------------------------------------------------
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    @property
-    def obs_ring(self):
-        """uint8 [T, N, C, H, W]: the tensor itself, or -- compact -- a view that decodes the patch words on demand (ObsRingView)."""
-        return ObsRingView(self) if self.compact else self._obs_ring
-
-    @obs_ring.setter
-    def obs_ring(self, value):
-        if self.compact:
-            raise AttributeError("compact ring: assign patch_ring")
-        self._obs_ring = value
-
-    def _obs_slot(self, slot):
-        """(obs pointer, ring slot to arm as patch output) of an environment launch that writes ring slot `slot`."""
-        if self.compact:
-            self.env.arm_patch_output(self.patch_ring[slot])
-            return None
-        return ptr(self._obs_ring[slot])
+    # the ring's fields under the names bench.py, agent.py, the tests and tools/ use (obs_ring: uint8 [T, N, C, H, W], the tensor or -- compact
+    # ring -- an ObsRingView; patch_ring: the compact ring's words, else None)
+    T, cur, filled, compact = _ring_field("T"), _ring_field("cur"), _ring_field("filled"), _ring_field("compact")
+    action_ring, reward_ring, terminal_ring = _ring_field("action"), _ring_field("reward"), _ring_field("terminal")
+    obs_ring, patch_ring = _ring_field("obs"), _ring_field("patch")
 
     def _obs_job(self, **kw):
         """A forward job on the ring (rows through kw['index']) or on one slot of it (kw['slot'])."""
         slot = kw.pop("slot", None)
-        ring = self.patch_ring if self.compact else self._obs_ring
-        kw["obs"] = ring if slot is None else ring[slot]
-        if self.compact:
+        store = self.ring.store
+        kw["obs"] = store if slot is None else store[slot]
+        if self.ring.compact:
             kw["patch"] = True
         return kw
 
@@ -217,14 +176,14 @@ class DQNCore:
         yet).  If the ring already holds transitions (a second fit(), or a memory restored from a pickle), the entry
         before it is marked terminal so that no TD target bootstraps across the discontinuity."""
         self._join_env()
-        if self.filled >= 2:
-            prev = self.cur - 1 if self.cur > 0 else self.T - 1
-            self.terminal_ring[prev].fill_(1)
-        if self.compact:
-            self.env.reset(out_patch=self.patch_ring[self.cur], write_obs=False)
+        r = self.ring
+        if r.filled >= 2:
+            r.terminal[r.next_slot(-1)].fill_(1)
+        if r.compact:
+            self.env.reset(out_patch=r.store[r.cur], write_obs=False)
         else:
-            self.env.reset(out_obs=self._obs_ring[self.cur])
-        self.filled = max(self.filled, 1)
+            self.env.reset(out_obs=r.store[r.cur])
+        r.filled = max(r.filled, 1)
         self.started = True
 
     def act_and_step(self, eps, masked_greedy=False, use_q=True, record_stats=True, presample=False):
@@ -232,83 +191,99 @@ class DQNCore:
         step with auto-reset; the transition is recorded in the ring by construction.  presample=True when update() follows this
         step: its replay sampling then rides on the environment launch (the rule never reads the slot this step writes)."""
         self._flush_stats()          # bookkeeping of the previous step, if no update() took it along (env buffers are about to be reused)
-        env, cur = self.env, self.cur
-        nxt = cur + 1 if cur + 1 < self.T else 0
+        r = self.ring
+        cur = r.cur
         q = None
         if use_q:
             q = self.net.forward_multi([self._obs_job(params=self.params, slot=cur, batch=self.N, out=self.q_act, packed=self.params_pk)])[0]
         # action selection + environment step in one launch (dq_env_act_step == dq_policy_select then dq_env_step)
-        seed = (ctypes.c_uint32 * 2)(*env.seed)
-        args = (env._h, ptr(q), float(eps), int(masked_greedy), seed, int(self.vector_steps), ptr(self.action_ring[cur]), 1,
-                self._obs_slot(nxt), ptr(self.reward_ring[cur]), ptr(self.terminal_ring[cur]), ptr(env.legal),
-                ptr(env.lifetime), ptr(env.was_reset))
-        filled = min(self.T, self.filled + 1)
-        if presample and filled >= MIN_FILLED:
-            self._launch_env(args, self._sample_job(self.updates + 1, nxt, filled))
-        else:
-            self._launch_env(args, None)
+        sj = None
+        if presample and r.filled_after() >= MIN_FILLED:
+            sj = self._sample_job(self.updates + 1, r.next_slot(), r.filled_after())
+        self._launch_env(self._env_step(q, eps, masked_greedy, sj))
         # episode bookkeeping of this step: rides on the next update's TD launch (dq_td_update_stats) when an update follows, else
         # launched on its own
         self._stats_pending = (cur,) if record_stats else None
         if record_stats and not self.defer_stats:
             self._flush_stats()
-        self.cur = nxt
-        self.filled = filled
+        r.advance()
         self.vector_steps += 1
 
     def _sample_job(self, t, head, filled):
         """dq_sample_job for update number t, to be run on a ring with `head` / `filled`, into the look-ahead buffer (the update in
         progress may still be reading self.index)."""
         sj = _lib.SampleJob()
-        sj.terminal_ring_dev, sj.n_slots, sj.head_slot, sj.filled_slots, sj.batch = ptr(self.terminal_ring), self.T, head, filled, self.batch_size
+        sj.terminal_ring_dev, sj.n_slots, sj.head_slot, sj.filled_slots, sj.batch = ptr(self.ring.terminal), self.ring.T, head, filled, self.batch_size
         sj.seed[0], sj.seed[1] = int(self.seed[0]) & 0xFFFFFFFF, int(self.seed[1]) & 0xFFFFFFFF
         sj.t, sj.sample_base, sj.index_dev = t, _dist.shard(self.rank, self.N, self.batch_size)[1], ptr(self._index_next)
-        self._presampled = (t, head, filled)
+        self.ring.presampled = (t, head, filled)
         return sj
 
-    def _launch_env(self, args, sj):
-        if getattr(self.env, "wide", False):
-            # lattices beyond d = 7 (csrc/env_big.hip): selection + step in one launch; no replay sampling rides on it -- the update draws
-            # its own minibatch (_take_minibatch notices that no look-ahead draw was made)
-            self._presampled = None
-            check(self.L.dq_envb_act_step(*args, ptr(self.env.inexact), self._stream()))
-            self._inexact_acc += self.env.inexact.sum()              # (read and reported at the next read_stats())
-            return
+    def _env_step(self, q, eps, masked_greedy, sample=None, stats=None):
+        """THE description of the environment launch of the vector step about to be taken (ring slot `cur` -> its successor): the record
+        qnet._env_step_job reads for a launch that rides on the backward, and what _launch_env spells out as dq_env[b]_act_step[_sample]'s
+        arguments.  patch: the ring slot to arm as patch output in front of the launch (compact ring; obs is then None)."""
+        r, env = self.ring, self.env
+        cur, nxt = r.cur, r.next_slot()
+        return dict(q=q, eps=eps, masked_greedy=masked_greedy, seed=env.seed, t=self.vector_steps, action=r.action[cur], auto_reset=1,
+                    obs=None if r.compact else r.store[nxt], patch=r.store[nxt] if r.compact else None, reward=r.reward[cur], done=r.terminal[cur],
+                    legal=env.legal, lifetime=env.lifetime, was_reset=env.was_reset, sample=sample, stats=stats)
+
+    def _launch_env(self, step):
+        """The environment launch `step` (_env_step) on its own; an exception in front of it leaves no armed ring slot."""
+        env, sj = self.env, step["sample"]
         try:
-            if sj is not None:
+            if step["patch"] is not None:
+                env.arm_patch_output(step["patch"])
+            args = (env._h, ptr(step["q"]), float(step["eps"]), int(step["masked_greedy"]), (ctypes.c_uint32 * 2)(*step["seed"]), int(step["t"]),
+                    ptr(step["action"]), step["auto_reset"], ptr(step["obs"]), ptr(step["reward"]), ptr(step["done"]), ptr(step["legal"]),
+                    ptr(step["lifetime"]), ptr(step["was_reset"]))
+            if self._wide:
+                # selection + step in one launch; no replay sampling rides on it -- the update draws its own minibatch (_take_minibatch
+                # notices that no look-ahead draw was made)
+                self.ring.presampled = None
+                check(self.L.dq_envb_act_step(*args, ptr(env.inexact), self._stream()))
+                self._inexact_acc += env.inexact.sum()               # (read and reported at the next read_stats())
+            elif sj is not None:
                 check(self.L.dq_env_act_step_sample(*args, ctypes.byref(sj), self._stream()))
             else:
                 check(self.L.dq_env_act_step(*args, self._stream()))
         except BaseException:
-            self.env.disarm_patch_output()                           # (_obs_slot armed a ring slot for this launch)
+            env.disarm_patch_output()
             raise
 
     def _join_env(self):
         """Orders the current stream behind an environment launch still running on the side stream."""
-        if self._env_inflight:
-            torch.cuda.current_stream(self.device).wait_event(self._e_env)
-            self._env_inflight = False
+        side = self._env_side
+        if side is not None and side.inflight:
+            torch.cuda.current_stream(self.device).wait_event(side.e_env)
+            side.inflight = False
+
+    def _episode_stats(self, slot):
+        """The episode bookkeeping launch of the vector step recorded in ring slot `slot`, on the current stream."""
+        env, r = self.env, self.ring
+        check(self.L.dq_episode_stats(ptr(r.terminal[slot]), ptr(env.was_reset), ptr(env.lifetime), ptr(r.reward[slot]), self.N, ptr(self.stats),
+                                      self._stream()))
 
     def _flush_stats(self):
         self._join_env()
         if self._stats_pending is not None:
-            (slot,), env = self._stats_pending, self.env
-            check(self.L.dq_episode_stats(ptr(self.terminal_ring[slot]), ptr(env.was_reset), ptr(env.lifetime), ptr(self.reward_ring[slot]),
-                                          self.N, ptr(self.stats), self._stream()))
+            self._episode_stats(self._stats_pending[0])
             self._stats_pending = None
 
     def update(self, rows=None, target_ready=None, target_next=None):
         """One minibatch update (keras-rl DQNAgent.backward's training branch).  rows: its minibatch, already drawn (_extra_updates);
         target_ready: (Q_target(s1) of those rows, None or the event behind the forward that writes it): no target job in this update's launch pair;
         target_next: (rows of the NEXT update, buffer): its Q_target(s1) rides on this update's launch pair as a fourth job."""
-        assert self.filled >= MIN_FILLED, "fewer than three complete transitions in the replay ring"
+        r = self.ring
+        assert r.filled >= MIN_FILLED, "fewer than three complete transitions in the replay ring"
         self._join_env()
-        B, N, T = self.batch_size, self.N, self.T
+        B, N, T = self.batch_size, self.N, r.T
         self.updates += 1
         t = self.updates
         _, sample_base = _dist.shard(self.rank, N, B)
         if rows is None:
-            self._take_minibatch(t, self.cur, self.filled, sample_base)
+            self._take_minibatch(t, r.cur, r.filled, sample_base)
             self.last_index = self.index
             self.net.forward_multi(self._update_jobs(t, sample_base))
             self._learn(t)
@@ -343,7 +318,8 @@ class DQNCore:
         if self._index_multi is None or self._index_multi.shape[0] < k - 1:
             self._index_multi = torch.empty((k - 1, B), dtype=torch.int32, device=self.device)
         _, sample_base = _dist.shard(self.rank, self.N, B)
-        _q.replay_sample_multi(self.terminal_ring, self.N, self.T, self.cur, self.filled, B, self.seed, self.updates + 1, k - 1,
+        r = self.ring
+        _q.replay_sample_multi(r.terminal, self.N, r.T, r.cur, r.filled, B, self.seed, self.updates + 1, k - 1,
                                sample_base=sample_base, out=self._index_multi)
         if not (self.target_ahead and self.net.fused_supported and self.net.fused_enabled):
             # The target network does not change inside a vector step and the rows of all these updates are known, so Q_target(s1) of update i + 1 needs
@@ -372,57 +348,55 @@ class DQNCore:
         for i in range(k - 1):
             last = i + 1 == k - 1
             if not last:
-                self.net.mark_conv_backward(side[5][i])
+                self.net.mark_conv_backward(side.marks[i])
             try:
-                self.update(rows=self._index_multi[i], target_ready=(side[4][i], side[3][i]))
+                self.update(rows=self._index_multi[i], target_ready=(side.q1[i], side.ready[i]))
             finally:
                 self.net.mark_conv_backward(None)
             if not last:
-                self._side_forward(i + 1, side[5][i])
+                self._side_forward(i + 1, side.marks[i])
 
     def _side_setup(self, n):
         B, net = self.batch_size, self.net
         if self._side is None:
             net2 = _q.QNetwork(net.input_shape, net.c_layers, net.ff_layers, net.n_actions, dueling=net.dueling, max_batch=net.max_batch, device=self.device)
-            if self.compact:
+            if self.ring.compact:
                 net2.set_patch_input(self.env.volume_depth, self.env.patch_stride)
-            # [network handle with its own per-job scratch, stream, event behind the rows' draw, per-update "Q_target ready" events, Q_target(s1) rows,
-            #  per-update marks inside the backward]
-            self._side = [net2, torch.cuda.Stream(device=self.device), torch.cuda.Event(), [], None, []]
+            self._side = _TargetAhead(net2, self.device)
         side = self._side
-        if side[4] is None or side[4].shape[0] < n:
-            side[4] = torch.empty((n, B, self.A), dtype=torch.float32, device=self.device)
-        while len(side[3]) < n:
-            side[3].append(torch.cuda.Event())
-            side[5].append(torch.cuda.Event())
-        side[2].record(torch.cuda.current_stream(self.device))      # behind the launch that drew the rows (and behind every reader of last step's Q_target rows)
+        if side.q1 is None or side.q1.shape[0] < n:
+            side.q1 = torch.empty((n, B, self.A), dtype=torch.float32, device=self.device)
+        while len(side.ready) < n:
+            side.ready.append(torch.cuda.Event())
+            side.marks.append(torch.cuda.Event())
+        side.e_rows.record(torch.cuda.current_stream(self.device))  # behind the launch that drew the rows (and behind every reader of last step's Q_target rows)
         return side
 
     def _side_forward(self, i, after):
         """Q_target(s1) of extra update i (rows self._index_multi[i]) on the side stream, behind `after` (an event of the main stream) or, the first one,
         behind the rows' draw."""
-        net2, stream, e_rows, ready, q1, _ = self._side
-        with torch.cuda.stream(stream):
-            stream.wait_event(e_rows if after is None else after)
-            net2.forward_multi([self._obs_job(params=self.target, batch=self.batch_size, index=self._index_multi[i], index_off=self.N,
-                                              index_mod=self.T * self.N, out=q1[i], packed=self.target_pk)])
-            ready[i].record(stream)
+        side = self._side
+        with torch.cuda.stream(side.stream):
+            side.stream.wait_event(side.e_rows if after is None else after)
+            side.net.forward_multi([self._obs_job(params=self.target, batch=self.batch_size, index=self._index_multi[i], index_off=self.N,
+                                                  index_mod=self.ring.T * self.N, out=side.q1[i], packed=self.target_pk)])
+            side.ready[i].record(side.stream)
 
     def _take_minibatch(self, t, head, filled, sample_base):
         """self.index <- rows of update t on a ring with `head` / `filled`: the look-ahead draw if an environment launch made exactly
         that one, else a launch of its own."""
-        if self._presampled == (t, head, filled):
+        r = self.ring
+        if r.presampled == (t, head, filled):
             self.index, self._index_next = self._index_next, self.index
         else:
-            _q.replay_sample(self.terminal_ring, self.N, self.T, head, filled, self.batch_size, self.seed, t, sample_base=sample_base,
-                             out=self.index)
-        self._presampled = None
+            _q.replay_sample(r.terminal, self.N, r.T, head, filled, self.batch_size, self.seed, t, sample_base=sample_base, out=self.index)
+        r.presampled = None
 
     def _update_jobs(self, t, sample_base, with_target=True):
         # Q_online(s1) picks the action, Q_target(s1) values it (double DQN; without it Q_target does both); the training forward
         # on s0 is independent of both, so the three share one pair of launches
         B, N = self.batch_size, self.N
-        rows = self.T * N
+        rows = self.ring.T * N
         jobs = []
         if with_target:
             jobs.append(self._obs_job(params=self.target, batch=B, index=self.index, index_off=N, index_mod=rows, out=self.q1_target, packed=self.target_pk))
@@ -435,8 +409,9 @@ class DQNCore:
 
     def _td_job(self, step_stats=None):
         q_sel = self.q1_online if self.enable_double_dqn else self.q1_target
-        return dict(q_online_s1=q_sel, q_target_s1=self.q1_target, q_s0=self.q0, reward=self.reward_ring, terminal=self.terminal_ring,
-                    action=self.action_ring, gamma=self.gamma, grad_scale=_dist.grad_scale(self.batch_size, self.world_size),
+        r = self.ring
+        return dict(q_online_s1=q_sel, q_target_s1=self.q1_target, q_s0=self.q0, reward=r.reward, terminal=r.terminal,
+                    action=r.action, gamma=self.gamma, grad_scale=_dist.grad_scale(self.batch_size, self.world_size),
                     index=self.index, y=self.y, dq=self.dq, metrics=self.metrics, step_stats=step_stats, auto_scale=self.auto_scale,
                     delta_clip=self.delta_clip)
 
@@ -445,117 +420,117 @@ class DQNCore:
         draw (or the given ring rows), the three forwards, TD step, backward; scaled by 1 / (batch_size * world_size), so that the SUM
         over the ranks is the gradient of the global-minibatch mean loss.  Leaves counters and parameters untouched (tests, diagnostics:
         tests/test_agent_gpu.py compares the sum of eight shard gradients with the gradient of one eight-times-larger lattice batch)."""
-        assert self.filled >= MIN_FILLED
+        r = self.ring
+        assert r.filled >= MIN_FILLED
         self._join_env()
         t = self.updates + 1
         _, sample_base = _dist.shard(self.rank, self.N, self.batch_size)
         if index is None:
-            _q.replay_sample(self.terminal_ring, self.N, self.T, self.cur, self.filled, self.batch_size, self.seed, t, sample_base=sample_base,
-                             out=self.index)
+            _q.replay_sample(r.terminal, self.N, r.T, r.cur, r.filled, self.batch_size, self.seed, t, sample_base=sample_base, out=self.index)
         else:
             self.index.copy_(index)
-        self._presampled = None
+        r.presampled = None
         self.net.forward_multi(self._update_jobs(t, sample_base))
         self.net.td_backward_phase0(self.params, self._td_job(), self.grads)
         self.net.backward_phase(self.params, self.dq, self.grads, 1)
         self._metrics_stale = True
         return self.grads
 
+    def _exchange_form(self):
+        """How this update's gradient is exchanged: None on one GPU, else "single" | "overlap" | "split" (DQ_DIST_MODE, default single).  Read at
+        every call (bench.py times the forms against each other in one process).  overlap needs the learner's own RCCL communicator: a group
+        without one (gloo, DQ_DIST_NATIVE=0) takes split instead."""
+        if not _dist.dist_path(self.world_size):
+            return None
+        mode = os.environ.get("DQ_DIST_MODE", "single")
+        if mode == "overlap":
+            self.ensure_comm()
+            return "overlap" if self._rccl is not None else "split"
+        return "single" if mode == "single" else "split"
+
+    def _backward(self, td, t, ride, whole, m=None, v=None):
+        """The backward behind the forwards, TD step in its first launch.  whole: every layer in one sequence (td_backward_adam[_env]; with m, v
+        Adam on its last launch, with None, None the gradient only); else phase 0 -- dueling + dense layers --, backward_phase(.., 1) follows.
+        ride: the vector step's environment launch (_env_step) carried by the dense backward's first kernel."""
+        net = self.net
+        if ride is None:
+            f_whole, f_phase0, tail = net.td_backward_adam, net.td_backward_phase0, ()
+        else:
+            f_whole, f_phase0, tail = net.td_backward_adam_env, net.td_backward_phase0_env, (self.env._h, ride)
+        if whole:
+            f_whole(self.params, td, self.grads, m, v, t, self.lr, self.beta_1, self.beta_2, self.epsilon, *tail)
+        else:
+            f_phase0(self.params, td, self.grads, *tail)
+
+    @contextlib.contextmanager
+    def _exposed(self):
+        """Around the part of the gradient exchange the step WAITS for: bench.py's HIP-event pair (ar_events), in every ar_stride-th update."""
+        probe = self.ar_events is not None and self._ar_seen % self.ar_stride == 0
+        self._ar_seen += 1
+        if probe:
+            e0, e1 = self.ar_pool.pop() if self.ar_pool else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            e0.record()
+        yield
+        if probe:
+            e1.record()
+            self.ar_events.append((e0, e1))
+
+    def _exchange(self, form):
+        """Sums self.grads over the ranks behind _backward (whole for "single", phase 0 for the other two, which run phase 1 beside the dense
+        range's all-reduce)."""
+        net, nconv = self.net, self.net.n_conv_params
+        if form == "single":
+            # ONE all-reduce of the whole flat gradient, on THIS stream through the learner's own RCCL communicator (dist.RcclComm; through
+            # torch.distributed for gloo groups): the cheapest form up to 4 ranks (DESIGN.md section 7 compares the three)
+            with self._exposed():
+                self.ensure_comm()
+                if self._rccl is not None:
+                    self._rccl.allreduce_sum_(self.grads)
+                else:
+                    _dist.allreduce_sum_(self.grads, group=self.pg)
+        elif form == "overlap":
+            # the dense range (0.7 of the 0.77 MB at c3) on a SECOND stream through the learner's own RCCL communicator while the convolutional
+            # backward (32 us) runs on the step's stream -- one event each way --; the convolutional range (66 KB) follows in-stream.  The same
+            # collectives in the same order on every rank
+            main = torch.cuda.current_stream(self.device)
+            o = self._overlap = self._overlap or _SideStream(self.device, "e_dense", "e_ar")
+            o.e_dense.record(main)
+            with torch.cuda.stream(o.stream):
+                o.stream.wait_event(o.e_dense)
+                (self._rccl2 or self._rccl).allreduce_sum_(self.grads[nconv:])     # (the side stream's OWN communicator: two collectives of one communicator
+                o.e_ar.record(o.stream)                                            #  in flight on two streams rest on RCCL's implicit serialisation; ADVICE r4)
+            net.backward_phase(self.params, self.dq, self.grads, 1)
+            with self._exposed():
+                self._rccl.allreduce_sum_(self.grads[:nconv])
+                main.wait_event(o.e_ar)
+        else:
+            # split: the same through torch.distributed, the dense range on the communicator's stream; the step waits for the convolutional
+            # range's all-reduce (critical path) + whatever is left of the dense range's
+            work = _dist.allreduce_sum_async(self.grads[nconv:], group=self.pg)
+            net.backward_phase(self.params, self.dq, self.grads, 1)
+            with self._exposed():
+                _dist.allreduce_sum_(self.grads[:nconv], group=self.pg)
+                if work is not None:
+                    work.wait()
+
     def _learn(self, t, ride=None):
-        """TD step, backward, optimizer step, repack -- everything of an update behind its forwards.  ride: the vector step's
-        environment launch (qnet._env_step_job dict) to be carried by the dense backward's first kernel."""
-        B, N, net = self.batch_size, self.N, self.net
+        """TD step, backward, gradient exchange, optimizer step, repack -- everything of an update behind its forwards.  ride: the vector
+        step's environment launch (_env_step) to be carried by the dense backward's first kernel."""
         step_stats = None
         if self._stats_pending is not None:          # the pending episode bookkeeping rides on the TD launch
             assert ride is None
-            (slot,), env = self._stats_pending, self.env
-            step_stats = (self.terminal_ring[slot], env.was_reset, env.lifetime, self.reward_ring[slot], N, self.stats)
+            (slot,), env, r = self._stats_pending, self.env, self.ring
+            step_stats = (r.terminal[slot], env.was_reset, env.lifetime, r.reward[slot], self.N, self.stats)
             self._stats_pending = None
         td = self._td_job(step_stats)
         self._metrics_stale = True
-        if _dist.dist_path(self.world_size) and os.environ.get("DQ_DIST_MODE", "single") == "single":
-            # ONE all-reduce of the whole flat gradient behind the backward, on THIS stream through the learner's own RCCL communicator
-            # (dist.RcclComm; through torch.distributed for gloo groups): the communicator-stream hand-offs of the split form below cost
-            # more on a one-rank measurement than the 0.7 MB they hide (DESIGN.md section 7)
-            if ride is not None:                          # the whole backward, gradient only (m = v = None): no optimizer step on the reduction
-                net.td_backward_adam_env(self.params, td, self.grads, None, None, t, self.lr, self.beta_1, self.beta_2, self.epsilon, self.env._h, ride)
-            else:
-                net.td_backward_adam(self.params, td, self.grads, None, None, t, self.lr, self.beta_1, self.beta_2, self.epsilon)
-            probe = self.ar_events is not None and self._ar_seen % self.ar_stride == 0
-            self._ar_seen += 1
-            if probe:
-                e0, e1 = self.ar_pool.pop() if self.ar_pool else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                e0.record()
-            self.ensure_comm()
-            if self._rccl is not None:
-                self._rccl.allreduce_sum_(self.grads)
-            else:
-                _dist.allreduce_sum_(self.grads, group=self.pg)
-            if probe:
-                e1.record()
-                self.ar_events.append((e0, e1))
-            net.adam_step(self.params, self.grads, self.m, self.v, t, self.lr, self.beta_1, self.beta_2, self.epsilon)     # (skips AND flags non-finite elements: every rank alike)
-        elif _dist.dist_path(self.world_size) and os.environ.get("DQ_DIST_MODE") == "overlap" and self._comm_ready():
-            # DQ_DIST_MODE=overlap: the dense layers' gradient (0.7 of the 0.77 MB at c3) is all-reduced on a SECOND stream through the learner's own
-            # RCCL communicator while the convolutional backward (32 us) runs on the step's stream -- one event each way, no torch.distributed
-            # hand-off --; the convolutional range (66 KB) follows in-stream, then the guarded Adam.  The same communicator serves both streams: the
-            # two collectives are issued in the same order on every rank.  What it costs beside the default: the backward in two phases (two final
-            # reductions instead of one) and the two events; what it hides: the wire time of the dense range.
-            nconv = net.n_conv_params
-            if ride is not None:
-                net.td_backward_phase0_env(self.params, td, self.grads, self.env._h, ride)
-            else:
-                net.td_backward_phase0(self.params, td, self.grads)
-            main = torch.cuda.current_stream(self.device)
-            if self._ar_stream is None:
-                self._ar_stream = torch.cuda.Stream(device=self.device)
-                self._e_dense, self._e_ar = torch.cuda.Event(), torch.cuda.Event()
-            self._e_dense.record(main)
-            with torch.cuda.stream(self._ar_stream):
-                self._ar_stream.wait_event(self._e_dense)
-                (self._rccl2 or self._rccl).allreduce_sum_(self.grads[nconv:])      # (the side stream's OWN communicator: two collectives of one communicator
-                self._e_ar.record(self._ar_stream)                                 #  in flight on two streams rest on RCCL's implicit serialisation; ADVICE r4)
-            net.backward_phase(self.params, self.dq, self.grads, 1)
-            probe = self.ar_events is not None and self._ar_seen % self.ar_stride == 0
-            self._ar_seen += 1
-            if probe:
-                e0, e1 = self.ar_pool.pop() if self.ar_pool else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                e0.record()
-            self._rccl.allreduce_sum_(self.grads[:nconv])
-            main.wait_event(self._e_ar)
-            if probe:
-                e1.record()
-                self.ar_events.append((e0, e1))
-            net.adam_step(self.params, self.grads, self.m, self.v, t, self.lr, self.beta_1, self.beta_2, self.epsilon)
-        elif _dist.dist_path(self.world_size):
-            # the dense layers' gradient (most of the bytes) is all-reduced while the convolutional backward runs (DQ_DIST_MODE=split; =overlap on
-            # a process group without a RCCL communicator of our own: gloo)
-            nconv = net.n_conv_params
-            if ride is not None:
-                net.td_backward_phase0_env(self.params, td, self.grads, self.env._h, ride)
-            else:
-                net.td_backward_phase0(self.params, td, self.grads)       # TD step + dueling + dense layers
-            work = _dist.allreduce_sum_async(self.grads[nconv:], group=self.pg)
-            net.backward_phase(self.params, self.dq, self.grads, 1)
-            # what the step WAITS for: the convolutional range's all-reduce (critical path) + whatever is left of the dense range's
-            probe = self.ar_events is not None and self._ar_seen % self.ar_stride == 0
-            self._ar_seen += 1
-            if probe:
-                e0, e1 = self.ar_pool.pop() if self.ar_pool else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                e0.record()
-            _dist.allreduce_sum_(self.grads[:nconv], group=self.pg)
-            if work is not None:
-                work.wait()
-            if probe:
-                e1.record()
-                self.ar_events.append((e0, e1))
-            net.adam_step(self.params, self.grads, self.m, self.v, t, self.lr, self.beta_1, self.beta_2, self.epsilon)     # (skips AND flags non-finite elements: every rank alike)
-        elif ride is not None:
-            net.td_backward_adam_env(self.params, td, self.grads, self.m, self.v, t, self.lr, self.beta_1, self.beta_2, self.epsilon,
-                                     self.env._h, ride)
-        else:
-            # TD step in the backward's first launch, Adam on its last
-            net.td_backward_adam(self.params, td, self.grads, self.m, self.v, t, self.lr, self.beta_1, self.beta_2, self.epsilon)
+        form = self._exchange_form()
+        if form is None:                             # one GPU: Adam on the backward's last launch
+            self._backward(td, t, ride, True, self.m, self.v)
+        else:                                        # no optimizer step on the reduction: the guarded Adam behind the exchange
+            self._backward(td, t, ride, form == "single")
+            self._exchange(form)
+            self.net.adam_step(self.params, self.grads, self.m, self.v, t, self.lr, self.beta_1, self.beta_2, self.epsilon)     # (skips AND flags non-finite elements: every rank alike)
         self.repack()
 
     def step_and_update(self, eps, masked_greedy=False, record_stats=True, presample_next=True, extra_updates=0):
@@ -569,66 +544,56 @@ class DQNCore:
         With presample_next the environment launch also draws the NEXT step's minibatch (if that step does not update, update()
         notices the stale draw and redraws)."""
         self._flush_stats()
-        env, cur, B, N, T = self.env, self.cur, self.batch_size, self.N, self.T
-        nxt = cur + 1 if cur + 1 < T else 0
-        filled = min(T, self.filled + 1)
+        env, r, N = self.env, self.ring, self.N
+        cur, nxt, filled = r.cur, r.next_slot(), r.filled_after()
         assert filled >= MIN_FILLED, "fewer than three complete transitions in the replay ring"
         t = self.updates + 1
-        _, sample_base = _dist.shard(self.rank, N, B)
+        _, sample_base = _dist.shard(self.rank, N, self.batch_size)
         self._take_minibatch(t, nxt, filled, sample_base)        # (drawn from the ring as it WILL be after this step)
         self.last_index = self.index
         jobs = self._update_jobs(t, sample_base)
         jobs.append(self._obs_job(params=self.params, slot=cur, batch=N, out=self.q_act, packed=self.params_pk))
         self.net.forward_multi(jobs)
-        seed = (ctypes.c_uint32 * 2)(*env.seed)
         sj = None
         if extra_updates > 0:                    # the next update runs on THIS step's ring: the environment launch draws its minibatch
             sj = self._sample_job(t + 1, nxt, filled)
         elif presample_next:
-            nxt2 = nxt + 1 if nxt + 1 < T else 0
-            sj = self._sample_job(t + 1, nxt2, min(T, filled + 1))
-        if self.ride_env and self._env_stream is None and self.net.fused_supported and self.net.fused_enabled and not getattr(env, "wide", False) \
-                and not getattr(env, "mlp_referee", False):
-            # one launch fewer per step: the environment step (+ look-ahead sampling + this step's episode bookkeeping) rides on the
-            # dense backward's first kernel (dq_qnet_td_backward_adam_env / _phase0_env): neither needs the other's results
-            if self.compact:
-                env.arm_patch_output(self.patch_ring[nxt])           # (consumed by the riding step's launch)
-            step = dict(q=self.q_act, eps=eps, masked_greedy=masked_greedy, seed=env.seed, t=self.vector_steps, action=self.action_ring[cur],
-                        auto_reset=1, obs=None if self.compact else self._obs_ring[nxt], reward=self.reward_ring[cur], done=self.terminal_ring[cur],
-                        legal=env.legal, lifetime=env.lifetime, was_reset=env.was_reset, sample=sj, stats=self.stats if record_stats else None)
+            sj = self._sample_job(t + 1, r.next_slot(2), r.filled_after(2))
+        side = self._env_side
+        ride = self.ride_env and side is None and self.net.fused_supported and self.net.fused_enabled and not self._wide \
+            and not getattr(env, "mlp_referee", False)
+        # riding: one launch fewer per step -- the environment step (+ look-ahead sampling + this step's episode bookkeeping) rides on the
+        # dense backward's first kernel (dq_qnet_td_backward_adam_env / _phase0_env): neither needs the other's results
+        step = self._env_step(self.q_act, eps, masked_greedy, sj, self.stats if ride and record_stats else None)
+        if ride:
             self._stats_pending = None
-            self.cur, self.filled = nxt, filled
-            self.vector_steps += 1
-            self.updates = t
-            try:
-                self._learn(t, ride=step)
-            except BaseException:
-                env.disarm_patch_output()                           # (an error in front of the riding launch: no armed ring slot outlives the call)
-                raise
-            self._extra_updates(extra_updates)
-            return
-        args = (env._h, ptr(self.q_act), float(eps), int(masked_greedy), seed, int(self.vector_steps), ptr(self.action_ring[cur]), 1,
-                self._obs_slot(nxt), ptr(self.reward_ring[cur]), ptr(self.terminal_ring[cur]), ptr(env.legal),
-                ptr(env.lifetime), ptr(env.was_reset))
-        if self._env_stream is not None:
+        elif side is not None:
             main = torch.cuda.current_stream(self.device)
-            self._e_fwd.record(main)
-            with torch.cuda.stream(self._env_stream):
-                self._env_stream.wait_event(self._e_fwd)     # needs the acting forward's Q-values (and everything before it)
-                self._launch_env(args, sj)
+            side.e_fwd.record(main)
+            with torch.cuda.stream(side.stream):
+                side.stream.wait_event(side.e_fwd)           # needs the acting forward's Q-values (and everything before it)
+                self._launch_env(step)
                 if record_stats:                             # the bookkeeping needs this step's results: it stays with the environment
-                    check(self.L.dq_episode_stats(ptr(self.terminal_ring[cur]), ptr(env.was_reset), ptr(env.lifetime), ptr(self.reward_ring[cur]),
-                                                  N, ptr(self.stats), self._stream()))
-                self._e_env.record(self._env_stream)
-            self._env_inflight = True
+                    self._episode_stats(cur)
+                side.e_env.record(side.stream)
+            side.inflight = True
             self._stats_pending = None
         else:
-            self._launch_env(args, sj)
+            self._launch_env(step)
             self._stats_pending = (cur,) if record_stats else None
-        self.cur, self.filled = nxt, filled
+        r.advance()
         self.vector_steps += 1
         self.updates = t
-        self._learn(t)
+        if not ride:
+            self._learn(t)
+        else:
+            try:
+                if step["patch"] is not None:
+                    env.arm_patch_output(step["patch"])      # (consumed by the riding step's launch)
+                self._learn(t, ride=step)
+            except BaseException:
+                env.disarm_patch_output()                    # (an error in front of the riding launch: no armed ring slot outlives the call)
+                raise
         self._extra_updates(extra_updates)
 
     def read_metrics(self):
@@ -682,10 +647,6 @@ class DQNCore:
         # DQ_DIST_MODE=overlap: a second communicator for the dense range's all-reduce on the side stream (the same collective call on every rank)
         if self._rccl is not None and self._rccl2 is None and (with_overlap or os.environ.get("DQ_DIST_MODE") == "overlap"):
             self._rccl2 = _dist.make_rccl(self.rank, self.world_size, self.device, self.pg)
-
-    def _comm_ready(self):
-        self.ensure_comm()
-        return self._rccl is not None
 
     def close_comm(self, abort=False):
         """Destroys the learner's own RCCL communicator (dist.RcclComm) -- every rank, behind a synchronisation, BEFORE the process group
@@ -759,34 +720,18 @@ class DQNCore:
     def begin_eval(self):
         """keras-rl stores nothing in test mode (memory.append(training=False) is a no-op): greedy evaluation steps run on a scratch
         three-slot ring, so that fit -> test -> fit (or pickling the memory after test()) never trains on evaluation transitions."""
-        assert getattr(self, "_train_ring", None) is None
+        assert self._train_ring is None
         self._flush_stats()
         self._join_env()
         self.env.disarm_patch_output()                               # (nothing armed for the training ring survives the switch of rings)
-        self._train_ring = (self.patch_ring if self.compact else self._obs_ring, self.action_ring, self.reward_ring, self.terminal_ring, self.T,
-                            self.cur, self.filled, self._presampled, self.started)
-        T = 3
-        dev = self.device
-        if self.compact:
-            self.patch_ring = torch.zeros((T,) + tuple(self.patch_ring.shape[1:]), dtype=torch.int32, device=dev)
-        else:
-            self._obs_ring = torch.zeros((T,) + tuple(self._obs_ring.shape[1:]), dtype=torch.uint8, device=dev)
-        self.action_ring = torch.zeros((T, self.N), dtype=torch.int32, device=dev)
-        self.reward_ring = torch.zeros((T, self.N), dtype=torch.float32, device=dev)
-        self.terminal_ring = torch.zeros((T, self.N), dtype=torch.uint8, device=dev)
-        self.T, self.cur, self.filled, self._presampled = T, 0, 0, None
+        self._train_ring = (self.ring, self.started)
+        self.ring = self.ring.scratch()
 
     def end_eval(self):
         self._flush_stats()
         self._join_env()
         self.env.disarm_patch_output()
-        (ring, self.action_ring, self.reward_ring, self.terminal_ring, self.T, self.cur, self.filled, self._presampled,
-         self.started) = self._train_ring
-        if self.compact:
-            self.patch_ring = ring
-        else:
-            self._obs_ring = ring
-        self._train_ring = None
+        (self.ring, self.started), self._train_ring = self._train_ring, None
         # the lattices were reset and stepped by the evaluation: the ring's newest observation no longer describes them, so the next
         # fit() (which calls reset_env(): previous entry marked terminal, fresh observation into slot `cur`) must not skip its reset
         self.started = False
