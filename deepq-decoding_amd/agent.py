@@ -440,17 +440,21 @@ class DQNAgent:
         return self._decoder
 
     def decode_benchmark(self, env, n_volumes, rates=None, p_meas=None, masked_greedy=None, max_actions=None, obs_form=None, chunk=None, seed=None,
-                         env_id_base=0, return_volumes=False, no_decoder=False, timings=None):
+                         env_id_base=0, return_volumes=False, no_decoder=False, timings=None, baseline=None):
         """Scores decode() on the device: draws n_volumes independent volumes of volume_depth faulty rounds from a clean
         lattice (all-zero volumes included), decodes them with the online weights, and asks the referee installed on `env` whether each
         residual error is a stabilizer.  Returns a decoder.EvalResult: counters, failure_rate (the logical failure probability of decoding one
         volume) and death_rate with Wilson 95 % intervals, the share of trivial volumes, mean corrections, the status histogram.  env supplies
         the lattice, the referee and the default rates / seed.  rates=[...]: n_volumes at EACH physical rate (p_meas: None = the same rates, a
         scalar, or one per rate) in one batched evaluation; returns {rate: EvalResult}, rate k's volumes being lattices env_id_base + k n_volumes
-        + i: the result of its own call with that env_id_base.  no_decoder: EvalResult.no_decoder counts the verdict for frame = 0."""
+        + i: the result of its own call with that env_id_base.  no_decoder: EvalResult.no_decoder counts the verdict for frame = 0.
+        baseline="matching": returns (the result above, decoder.score_matching's result for the same volumes) -- the space-time minimum-weight
+        matching decoder of DESIGN.md section 13 beside the agent."""
         from . import decoder as D
         if env is None:
             raise ValueError("decode_benchmark() needs the environment: it supplies the lattice and the referee")
+        if baseline not in (None, "matching"):
+            raise ValueError(f"decode_benchmark: baseline must be None or 'matching', not {baseline!r}")
         d, model, use_Y, depth = D.check_eval_lattice(None, env)
         D.check_decode_args(d, model, use_Y, depth, (depth, d + 1, d + 1), "environment", max_actions, obs_form)
         layers = D.action_layers(model, use_Y)
@@ -463,24 +467,18 @@ class DQNAgent:
             total, ph, pm, blk, keys = n_volumes, None, None, None, None
             D.check_eval_args((d, model, use_Y, depth), env, n_volumes, None, None, seed, env_id_base)
         else:
-            keys = [float(r) for r in rates]
-            K = len(keys)
-            if K < 1:
-                raise ValueError("decode_benchmark: no error rates")
-            if len(set(keys)) != K:
-                raise ValueError("decode_benchmark: the error rates must be distinct (they key the result)")
-            meas = keys if p_meas is None else ([float(p_meas)] * K if np.ndim(p_meas) == 0 else [float(r) for r in p_meas])
-            if len(meas) != K:
-                raise ValueError(f"decode_benchmark: {len(meas)} measurement rates for {K} error rates")
-            D.check_eval_args((d, model, use_Y, depth), env, n_volumes, keys[0], meas[0], seed, env_id_base)
-            total, blk = int(n_volumes) * K, int(n_volumes)
-            ph, pm = np.repeat(np.asarray(keys, dtype=np.float64), blk), np.repeat(np.asarray(meas, dtype=np.float64), blk)
-            D.check_eval_args((d, model, use_Y, depth), env, total, ph, pm, seed, env_id_base, blk)
+            total, ph, pm, blk, keys = D.expand_rates((d, model, use_Y, depth), env, n_volumes, rates, p_meas, seed, env_id_base, "decode_benchmark")
         self._bind(env)
         dec = self._decoder_for(d, model, use_Y, depth, masked_greedy, max_actions, "environment", obs_form, chunk)
         out = dec.evaluate(self._core.params, env, total, ph, pm, seed=seed, env_id_base=env_id_base, return_volumes=return_volumes, block=blk,
                            no_decoder=no_decoder, timings=timings)
-        return out if keys is None else dict(zip(keys, out))
+        out = out if keys is None else dict(zip(keys, out))
+        if baseline is None:
+            return out
+        # (p_meas without rates was refused above; the decoder's own scoring handle serves the baseline, so its matching tables are built once)
+        match = D.score_matching(env, n_volumes, rates=rates, p_meas=p_meas if rates is not None else None, seed=seed, env_id_base=env_id_base,
+                                 evaluator=dec._eval)
+        return out, match
 
     def compute_q_values(self, observation):
         obs = torch.as_tensor(np.asarray(observation), dtype=torch.uint8, device=self._core.device).reshape((1,) + tuple(self.model.input_shape)).contiguous()

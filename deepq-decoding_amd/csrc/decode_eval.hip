@@ -181,15 +181,7 @@ __global__ __launch_bounds__(EVAL_COUNT_THREADS) void eval_count_kernel(EvalCoun
 
 }  // namespace
 
-struct dq_decode_eval {
-    int d, depth, model, use_Y, max_volumes;
-    DqRateTable rates;          // per-volume thresholds of a sample call (2 max_volumes + 2 words)
-    // the Dense-stack referee's pass (allocated at its first use): the residuals' planes as two-word records (padded: the pass reads word 8 of a
-    // record), "no move" actions, the classes
-    u64* xz;
-    int32_t* no_action;
-    u8* dec;
-};
+#include "decode_eval.h"
 
 static dq_status eval_same_lattice(const dq_decode_eval* V, const EnvRefereeView& R, bool depth_too, const char* who) {
     DQ_REQUIRE(R.d == V->d && R.model == V->model && (R.model == DQ_MODEL_X || (R.use_Y != 0) == (V->use_Y != 0)) && (!depth_too || R.depth == V->depth),
@@ -232,6 +224,7 @@ void dq_decode_eval_destroy(dq_decode_eval* V) {
     if (V->xz) (void)hipFree(V->xz);
     if (V->no_action) (void)hipFree(V->no_action);
     if (V->dec) (void)hipFree(V->dec);
+    match_st_free(V->match_st);
     delete V;
 }
 

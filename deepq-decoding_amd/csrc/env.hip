@@ -305,7 +305,7 @@ void dq_set_error(const char* fmt, ...) {
 
 extern "C" {
 
-int dq_version(void) { return 5; }
+int dq_version(void) { return 6; }
 const char* dq_last_error(void) { return g_err; }
 long dq_struct_size(int id) {
     switch (id) {

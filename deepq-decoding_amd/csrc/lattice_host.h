@@ -101,3 +101,43 @@ static inline void lattice_match_tables(const LatticeHost& L, int comp, std::vec
     }
     *w10 = best;
 }
+
+// One shortest path per entry of lattice_match_tables, as the set of its data qubits (bit q = qubit x * d + y; d^2 <= 64): path [n][n][2] for
+// dist, pathB [n][2] for distB -- the same breadth-first search over (node, class) with the parent of every state kept.  A path that passes a qubit twice
+// drops it (XOR): the set still has the path's end points and class.  Entries without a path (dist 255) stay 0.  For csrc/match_st.hip.
+static inline void lattice_match_paths(const LatticeHost& L, int comp, std::vector<u64>* path, std::vector<u64>* pathB) {
+    const int d = L.d, n = (int)L.typed[comp].size(), typ = comp == 0 ? 3 : 1;
+    struct Edge { int to, lg, q; };
+    std::vector<std::vector<Edge>> adj(n);
+    for (int x = 0; x < d; ++x) for (int y = 0; y < d; ++y) {
+        int ends[4], ne = 0;
+        for (int s : L.qubit_stabs[x * d + y]) if (L.stab_type[s] == typ) ends[ne++] = L.ref_bit[s];
+        const int lg = comp == 0 ? (y == 0) : (x == 0);
+        if (ne == 2) { adj[ends[0]].push_back({ends[1], lg, x * d + y}); adj[ends[1]].push_back({ends[0], lg, x * d + y}); }
+        else if (ne == 1) adj[ends[0]].push_back({-1, lg, x * d + y});
+    }
+    path->assign((size_t)n * n * 2, 0);
+    pathB->assign((size_t)n * 2, 0);
+    std::vector<int> seen(2 * n), hitB(2), frontier, next;
+    std::vector<u64> mask(2 * n);
+    for (int u = 0; u < n; ++u) {
+        std::fill(seen.begin(), seen.end(), -1);
+        seen[2 * u] = 0; mask[2 * u] = 0;
+        hitB[0] = hitB[1] = 0;
+        frontier.assign(1, 2 * u);
+        while (!frontier.empty()) {
+            next.clear();
+            for (int xc : frontier) {
+                const int x = xc >> 1, c = xc & 1;
+                for (const Edge& e : adj[x]) {
+                    const int c2 = c ^ e.lg;
+                    const u64 m = mask[xc] ^ (1ull << e.q);
+                    if (e.to < 0) { if (!hitB[c2]) { hitB[c2] = 1; (*pathB)[2 * u + c2] = m; } }
+                    else if (seen[2 * e.to + c2] < 0) { seen[2 * e.to + c2] = 1; mask[2 * e.to + c2] = m; next.push_back(2 * e.to + c2); }
+                }
+            }
+            frontier.swap(next);
+        }
+        for (int yc = 0; yc < 2 * n; ++yc) if (seen[yc] >= 0) (*path)[(size_t)u * n * 2 + yc] = mask[yc];
+    }
+}

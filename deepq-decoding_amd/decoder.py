@@ -212,11 +212,13 @@ class EvalResult:
     homology class: the step's reward 1); alive: success, or the referee still names the residual's class (the step's done == False).
     failure_rate = 1 - success / volumes is the logical failure probability of decoding one volume; death_rate = 1 - alive / volumes.  With
     return_volumes the per-volume device tensors ride along: volumes, hidden, trivial, decode (a DecodeResult of device tensors), verdict
-    (bytes: VERDICT_*).  no_decoder: the same counters for frame = 0 where they were asked for."""
+    (bytes: VERDICT_*).  no_decoder: the same counters for frame = 0 where they were asked for.  inexact: volumes on which the matching baseline
+    (score_matching) took its nearest-boundary fallback; 0 for every other decoder."""
 
-    def __init__(self, counters, p_phys=None, p_meas=None):
+    def __init__(self, counters, p_phys=None, p_meas=None, inexact=0):
         self.counters = {k: int(x) for k, x in zip(COUNTER_NAMES, counters)}
         self.p_phys, self.p_meas = p_phys, p_meas
+        self.inexact = int(inexact)
         self.volumes = self.hidden = self.trivial = self.decode = self.verdict = None
         self.no_decoder = None
 
@@ -259,6 +261,8 @@ class EvalResult:
         out = dict(self.counters)
         out.update(failure_rate=self.failure_rate, failure_interval=list(self.failure_interval), death_rate=self.death_rate,
                    death_interval=list(self.death_interval), trivial_share=self.trivial_share, mean_corrections=self.mean_corrections)
+        if self.inexact:
+            out["inexact"] = self.inexact
         if self.no_decoder is not None:
             out["no_decoder"] = self.no_decoder.summary()
         return out
@@ -331,6 +335,12 @@ class Evaluator:
                                            p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, _lib.ptr(volumes),
                                            _lib.ptr(hidden), _lib.ptr(trivial), self._stream()))
 
+    def match_into(self, volumes, m, frame, weight=None, n_defects=None, inexact=None):
+        """The matching baseline (dq_decode_match) on m <= chunk volumes already on the device."""
+        from . import _lib
+        _lib.check(self.L.dq_decode_match(self._h, _lib.ptr(volumes), m, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(inexact),
+                                          self._stream()))
+
     def verdict_into(self, venv, hidden, frame, m, out):
         from . import _lib
         _lib.check(self.L.dq_decode_verdict(self._h, venv._h, _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), self._stream()))
@@ -339,6 +349,72 @@ class Evaluator:
         from . import _lib
         _lib.check(self.L.dq_decode_count(_lib.ptr(verdict), _lib.ptr(trivial), _lib.ptr(status), _lib.ptr(n_corr), m, first, block,
                                           counters.shape[0], _lib.ptr(counters), self._stream()))
+
+
+def score_chunks(ev, venv, dev, n, chunk, ph, pm, seed, base, blk, decode, decode_phase, keep=False, no_decoder=False, timings=None):
+    """The loop behind BatchDecoder.evaluate and score_matching: per chunk of at most `chunk` volumes sample -> decode -> verdict -> counts on the
+    device, so that two decoders scored with the same (n, rates, seed, base) see the same volumes whatever their chunk sizes.  decode(vol, m, o)
+    decodes the m volumes `vol` (rows o .. o + m of the caller's per-volume buffers) and returns (frame, status, n_corr, extra) device tensors,
+    `extra` an optional uint8 flag per volume summed per block; its wall time is reported as timings[decode_phase].  keep: the per-volume
+    tensors of all n volumes stay (else one chunk is resident).  Returns (counters, counters of frame = 0 or None, extra sums, tensors) with the
+    counters int64 [n_blocks, 9] on the host and tensors = dict(volumes, hidden, trivial, verdict)."""
+    import time
+    import torch
+    d, depth, each = ev.d, ev.volume_depth, not isinstance(ph, float)
+    rows = n if keep else min(chunk, n)
+    vol = torch.empty((rows, depth, d + 1, d + 1), dtype=torch.uint8, device=dev)
+    hid = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+    triv = torch.empty(rows, dtype=torch.uint8, device=dev)
+    verd = torch.empty(rows, dtype=torch.uint8, device=dev)
+    verd0 = torch.empty(min(chunk, n), dtype=torch.uint8, device=dev) if no_decoder else None
+    n_blocks = -(-n // blk)
+    counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
+    counters0 = torch.zeros_like(counters) if no_decoder else None
+    extras = torch.zeros(n_blocks, dtype=torch.int64, device=dev)
+
+    def phase(name, t0):
+        if timings is None:
+            return t0
+        torch.cuda.current_stream(dev).synchronize()
+        t1 = time.perf_counter()
+        timings[name] = timings.get(name, 0.0) + (t1 - t0)
+        return t1
+
+    for s in range(0, n, chunk):
+        m = min(chunk, n - s)
+        o = s if keep else 0
+        sl = slice(o, o + m)
+        t = phase("setup", time.perf_counter()) if timings is not None else 0.0
+        a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
+        if each and (a == a[0]).all() and (b == b[0]).all():   # one rate pair in this chunk: the scalar form (the same thresholds, no table upload)
+            a, b = float(a[0]), float(b[0])
+        ev.sample_into(venv, m, base + s, seed, a, b, vol[sl], hid[sl], triv[sl])
+        t = phase("sample", t)
+        frame, status, ncorr, extra = decode(vol[sl], m, o)
+        t = phase(decode_phase, t)
+        ev.verdict_into(venv, hid[sl], frame, m, verd[sl])
+        ev.count_into(verd[sl], triv[sl], status, ncorr, m, s, blk, counters)
+        if extra is not None:
+            extras.index_add_(0, torch.div(torch.arange(s, s + m, device=dev), blk, rounding_mode="floor"), extra.to(torch.int64))
+        if no_decoder:
+            ev.verdict_into(venv, hid[sl], None, m, verd0[:m])
+            ev.count_into(verd0[:m], triv[sl], None, None, m, s, blk, counters0)
+        t = phase("verdict", t)
+    return (counters.cpu().numpy(), counters0.cpu().numpy() if no_decoder else None, extras.cpu().numpy(),
+            dict(volumes=vol, hidden=hid, trivial=triv, verdict=verd))
+
+
+def block_results(host, host0, extras, n_blocks, blk, ph, pm):
+    """One EvalResult per block of counters (score_chunks' output)."""
+    each = not isinstance(ph, float)
+    results = []
+    for k in range(n_blocks):
+        lo = k * blk
+        r = EvalResult(host[k], ph[lo] if each else ph, pm[lo] if each else pm, inexact=extras[k])
+        if host0 is not None:
+            r.no_decoder = EvalResult(host0[k], r.p_phys, r.p_meas)
+        results.append(r)
+    return results
 
 
 def sample_volumes(env, n_volumes, p_phys=None, p_meas=None, seed=None, env_id_base=0, chunk=DEFAULT_CHUNK, to_host=False):
@@ -397,6 +473,132 @@ def verdict(hidden, frame, env, chunk=DEFAULT_CHUNK, to_host=False):
     finally:
         ev.close()
     return (out.cpu().numpy() if to_host else out), res
+
+
+# ---- the space-time matching baseline (include/deepq_hip.h dq_decode_match; csrc/match_st.hip) ----------------------------
+class MatchResult:
+    """Per-volume results of matching_decode, in input order: frame uint8 [N, d, d] (the matching's net correction as hidden_state codes 0..3, what
+    verdict() takes), weight int32 [N, 2] (the matching's weight per Pauli component: 0 = X errors / type-3 plaquettes, 1 = Z errors / type-1),
+    n_defects int32 [N, 2], inexact uint8 [N] (1: a cluster beyond 14 defects or defects beyond the first 32 took the nearest-boundary fallback)."""
+
+    def __init__(self, frame, weight, n_defects, inexact):
+        self.frame, self.weight, self.n_defects, self.inexact = frame, weight, n_defects, inexact
+
+    def __repr__(self):
+        return f"MatchResult(volumes={int(self.frame.shape[0])})"
+
+
+def check_match_args(env, volumes, chunk=DEFAULT_CHUNK):
+    """Validates a matching_decode request without touching the library.  Returns (d, error_model, use_Y, volume_depth, n_volumes)."""
+    d, model, use_Y, depth = check_eval_lattice(None, env)
+    if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
+    if not hasattr(volumes, "shape") or not hasattr(volumes, "dtype"):
+        raise ValueError("volumes must be a numpy array or a torch tensor")
+    if str(volumes.dtype).replace("torch.", "") != "uint8":
+        raise ValueError(f"volumes must be uint8 (sample_volumes' format), got dtype {volumes.dtype}")
+    shape = tuple(int(x) for x in volumes.shape)
+    if len(shape) != 4 or shape[0] < 1 or shape[1:] != (depth, d + 1, d + 1):
+        raise ValueError(f"volumes must have shape [N, {depth}, {d + 1}, {d + 1}], got {shape}")
+    check_binary(volumes)
+    return d, model, use_Y, depth, shape[0]
+
+
+def matching_decode(volumes, env, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None):
+    """Minimum-weight matching on the space-time volume, unit weights, both Pauli components independently.  volumes: uint8
+    [N, volume_depth, d+1, d+1] with 0/1 cells (sample_volumes' output, decode's input), numpy or torch; env supplies the lattice (d <= 7, the narrow
+    environment).  Returns a MatchResult of device tensors (numpy arrays with to_host).  The result of a volume does not depend on the batch
+    around it or on `chunk`.  evaluator: an Evaluator of this lattice to run on (its chunk is used and it stays open, so that repeated calls build
+    the matching tables once); default: one for this call."""
+    import torch
+    d, model, use_Y, depth, n = check_match_args(env, volumes, chunk)
+    venv = _narrow_env(env)
+    dev = venv.device
+    vol = (volumes if isinstance(volumes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(volumes))).to(device=dev).contiguous()
+    if evaluator is not None and (evaluator.d, evaluator.error_model, evaluator.use_Y, evaluator.volume_depth) != (d, model, use_Y, depth):
+        raise ValueError(f"the evaluator's lattice is not the environment's {(d, model, use_Y, depth)}")
+    ev = Evaluator(d, model, use_Y, depth, chunk=min(int(chunk), n), device=dev) if evaluator is None else evaluator
+    try:
+        frame = torch.empty((n, d, d), dtype=torch.uint8, device=dev)
+        weight = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        ndef = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        inexact = torch.empty(n, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            for s in range(0, n, ev.chunk):
+                m = min(ev.chunk, n - s)
+                ev.match_into(vol[s:s + m], m, frame[s:s + m], weight[s:s + m], ndef[s:s + m], inexact[s:s + m])
+            torch.cuda.current_stream(dev).synchronize()
+    finally:
+        if evaluator is None:
+            ev.close()
+    out = (frame, weight, ndef, inexact)
+    return MatchResult(*(tuple(x.cpu().numpy() for x in out) if to_host else out))
+
+
+def expand_rates(lattice, env, n_volumes, rates, p_meas, seed, env_id_base, who):
+    """rates=[...] of decode_benchmark / score_matching: n_volumes at EACH physical rate in one evaluation of K n_volumes volumes in blocks of
+    n_volumes.  Validates without touching the library; returns (total, p_phys, p_meas, block, keys)."""
+    keys = [float(r) for r in rates]
+    K = len(keys)
+    if K < 1:
+        raise ValueError(f"{who}: no error rates")
+    if len(set(keys)) != K:
+        raise ValueError(f"{who}: the error rates must be distinct (they key the result)")
+    meas = keys if p_meas is None else ([float(p_meas)] * K if np.ndim(p_meas) == 0 else [float(r) for r in p_meas])
+    if len(meas) != K:
+        raise ValueError(f"{who}: {len(meas)} measurement rates for {K} error rates")
+    check_eval_args(lattice, env, n_volumes, keys[0], meas[0], seed, env_id_base)
+    total, blk = int(n_volumes) * K, int(n_volumes)
+    ph, pm = np.repeat(np.asarray(keys, dtype=np.float64), blk), np.repeat(np.asarray(meas, dtype=np.float64), blk)
+    check_eval_args(lattice, env, total, ph, pm, seed, env_id_base, blk)
+    return total, ph, pm, blk, keys
+
+
+def score_matching(env, n_volumes, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, chunk=DEFAULT_CHUNK, no_decoder=False, timings=None,
+                   evaluator=None):
+    """The matching baseline scored like DQNAgent.decode_benchmark scores the agent, on the SAME volumes for the same env, n_volumes, rates, seed and
+    env_id_base (both run score_chunks): sample -> dq_decode_match -> verdict -> counts on the device.  Returns an EvalResult ({rate: EvalResult}
+    with rates=[...]; p_meas then as in decode_benchmark; without rates p_phys / p_meas are scalars, default the environment's).  Counters: every
+    volume counts as status identity, corrections = the frame's non-zero cells; EvalResult.inexact = volumes that took the fallback.  no_decoder:
+    EvalResult.no_decoder counts the verdict for frame = 0.  timings: a dict that receives the wall seconds of the phases (sample / match /
+    verdict).  evaluator: an Evaluator of this lattice to run on (its chunk is used, it stays open: its matching tables are built once);
+    default: one of `chunk` volumes for this call."""
+    import torch
+    lat = check_eval_lattice(None, env)
+    if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
+    if rates is None:
+        keys = None
+        n, ph, pm, seed, base, blk = check_eval_args(lat, env, n_volumes, p_phys, p_meas, seed, env_id_base)
+    else:
+        if p_phys is not None:
+            raise ValueError("score_matching: rates=[...] are the physical rates; p_phys goes without them")
+        total, ph, pm, block, keys = expand_rates(lat, env, n_volumes, rates, p_meas, seed, env_id_base, "score_matching")
+        n, ph, pm, seed, base, blk = check_eval_args(lat, env, total, ph, pm, seed, env_id_base, block)
+    if evaluator is not None and (evaluator.d, evaluator.error_model, evaluator.use_Y, evaluator.volume_depth) != lat:
+        raise ValueError(f"the evaluator's lattice is not the environment's {lat}")
+    venv = _narrow_env(env)
+    d, model, use_Y, depth = lat
+    dev = venv.device
+    ev = Evaluator(d, model, use_Y, depth, chunk=min(int(chunk), n), device=dev) if evaluator is None else evaluator
+    try:
+        rows = min(ev.chunk, n)
+        frame = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+        inexact = torch.empty(rows, dtype=torch.uint8, device=dev)
+        status = torch.full((rows,), STATUS_IDENTITY, dtype=torch.uint8, device=dev)
+
+        def decode(vol, m, o):
+            ev.match_into(vol, m, frame[:m], None, None, inexact[:m])
+            return frame[:m], status[:m], (frame[:m] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), inexact[:m]
+
+        with torch.cuda.device(dev):
+            host, host0, extras, _ = score_chunks(ev, venv, dev, n, ev.chunk, ph, pm, seed, base, blk, decode, "match", no_decoder=no_decoder,
+                                                  timings=timings)
+    finally:
+        if evaluator is None:
+            ev.close()
+    results = block_results(host, host0, extras, -(-n // blk), blk, ph, pm)
+    return results[0] if keys is None else dict(zip(keys, results))
 
 
 class DecodeResult:
@@ -527,7 +729,6 @@ class BatchDecoder:
         the verdict for frame = 0 (EvalResult.no_decoder).  return_volumes: the per-volume device tensors ride on the (first) result.  timings:
         a dict that receives the wall seconds of the phases (sample / decode / verdict), each closed by a synchronisation.  The results do not
         depend on the chunk size."""
-        import time
         import torch
         mine = (self.d, self.error_model, self.use_Y, self.volume_depth)
         n, ph, pm, seed, base, blk = check_eval_args(mine, env, n_volumes, p_phys, p_meas, seed, env_id_base, block)
@@ -538,62 +739,26 @@ class BatchDecoder:
             raise ValueError(f"the environment lives on {venv.device}, the decoder on {dev}")
         if getattr(self, "_eval", None) is None:
             self._eval = Evaluator(*mine, chunk=self.chunk, device=dev)
-        ev = self._eval
-        d, depth, each = self.d, self.volume_depth, not isinstance(ph, float)
+        d = self.d
         rows = n if return_volumes else min(self.chunk, n)
-        vol = torch.empty((rows, depth, d + 1, d + 1), dtype=torch.uint8, device=dev)
-        hid = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
-        triv = torch.empty(rows, dtype=torch.uint8, device=dev)
         corr = torch.empty((rows, self.max_actions), dtype=torch.int32, device=dev)
         ncorr = torch.empty(rows, dtype=torch.int32, device=dev)
         frame = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
         status = torch.empty(rows, dtype=torch.uint8, device=dev)
-        verd = torch.empty(rows, dtype=torch.uint8, device=dev)
-        verd0 = torch.empty(min(self.chunk, n), dtype=torch.uint8, device=dev) if no_decoder else None
-        n_blocks = -(-n // blk)
-        counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
-        counters0 = torch.zeros_like(counters) if no_decoder else None
         iters = []
-
-        def phase(name, t0):
-            if timings is None:
-                return t0
-            torch.cuda.current_stream(dev).synchronize()
-            t1 = time.perf_counter()
-            timings[name] = timings.get(name, 0.0) + (t1 - t0)
-            return t1
-
         with torch.cuda.device(dev):
             packed = self.net.pack(params)
-            for s in range(0, n, self.chunk):
-                m = min(self.chunk, n - s)
-                o = s if return_volumes else 0
+
+            def decode(vol, m, o):
                 sl = slice(o, o + m)
-                t = phase("setup", time.perf_counter()) if timings is not None else 0.0
-                a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
-                if each and (a == a[0]).all() and (b == b[0]).all():   # one rate pair in this chunk: the scalar form (the same thresholds, no table upload)
-                    a, b = float(a[0]), float(b[0])
-                ev.sample_into(venv, m, base + s, seed, a, b, vol[sl], hid[sl], triv[sl])
-                t = phase("sample", t)
-                iters.append(self._decode_into(params, packed, vol[sl], m, corr[sl], ncorr[sl], frame[sl], status[sl]))
-                t = phase("decode", t)
-                ev.verdict_into(venv, hid[sl], frame[sl], m, verd[sl])
-                ev.count_into(verd[sl], triv[sl], status[sl], ncorr[sl], m, s, blk, counters)
-                if no_decoder:
-                    ev.verdict_into(venv, hid[sl], None, m, verd0[:m])
-                    ev.count_into(verd0[:m], triv[sl], None, None, m, s, blk, counters0)
-                t = phase("verdict", t)
-            host = counters.cpu().numpy()
-            host0 = counters0.cpu().numpy() if no_decoder else None
-        results = []
-        for b in range(n_blocks):
-            lo = b * blk
-            r = EvalResult(host[b], ph[lo] if each else ph, pm[lo] if each else pm)
-            if no_decoder:
-                r.no_decoder = EvalResult(host0[b], r.p_phys, r.p_meas)
-            results.append(r)
+                iters.append(self._decode_into(params, packed, vol, m, corr[sl], ncorr[sl], frame[sl], status[sl]))
+                return frame[sl], status[sl], ncorr[sl], None
+
+            host, host0, extras, kept = score_chunks(self._eval, venv, dev, n, self.chunk, ph, pm, seed, base, blk, decode, "decode",
+                                                     keep=return_volumes, no_decoder=no_decoder, timings=timings)
+        results = block_results(host, host0, extras, -(-n // blk), blk, ph, pm)
         if return_volumes:
             r = results[0]
-            r.volumes, r.hidden, r.trivial, r.verdict = vol, hid, triv, verd
+            r.volumes, r.hidden, r.trivial, r.verdict = kept["volumes"], kept["hidden"], kept["trivial"], kept["verdict"]
             r.decode = DecodeResult(corr, ncorr, frame, status, iterations=iters)
         return results[0] if block is None else results

@@ -753,6 +753,18 @@ dq_status dq_decode_verdict(dq_decode_eval* ev, dq_env* env, const uint8_t* hidd
                             void* stream);
 dq_status dq_decode_count(const uint8_t* verdict_dev, const uint8_t* trivial_dev, const uint8_t* status_dev, const int32_t* n_corr_dev, int n,
                           int64_t first, int block, int n_blocks, uint64_t* counters_dev, void* stream);
+/* dq_decode_match: the space-time minimum-weight matching baseline (csrc/match_st.hip) on n <= max_volumes volumes in
+ * dq_decode_run's input layout.  Per Pauli component (0: type-3 plaquettes / X errors, 1: type-1 / Z errors) the defects are S_t xor S_{t-1}
+ * (S_-1 = 0); unit-weight edges: a data error joins its plaquettes of the round (or the spatial boundary), a measurement error joins (s, t) and
+ * (s, t + 1), in the last round (s, depth - 1) and the open future boundary.  One matching of minimum total weight over both logical classes is
+ * returned: frame_dev uint8 [n][d][d] the XOR of its paths' spatial projections as hidden_state codes (what dq_decode_verdict takes),
+ * weight_dev int32 [n][2] its weight per component, n_defects_dev int32 [n][2], inexact_dev uint8 [n]: 1 where a cluster of more than 14 defects
+ * or defects beyond the first 32 of a component took the nearest-boundary fallback.  weight_dev / n_defects_dev / inexact_dev may be NULL.
+ * Deterministic per volume: no dependence on the batch.  The tables are built at the handle's first call, which therefore MODIFIES the handle: like
+ * every call on a dq_decode_eval this one is not thread-safe (one thread at a time per handle, and the first calls of a process serialised).  No reference counterpart (README.md:278
+ * names MWPM as the benchmark). */
+dq_status dq_decode_match(dq_decode_eval* ev, const uint8_t* volumes_dev, int n, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev,
+                          uint8_t* inexact_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Live kernel timing (measurement only; no reference counterpart).  dq_prof_arm(id, n) times up to n

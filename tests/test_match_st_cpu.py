@@ -1,0 +1,125 @@
+"""The space-time matching baseline, host side: the two checkers of tests/match_st_ref.py against each other (the subset DP's
+open and history minima equal the breadth-first search over fault histories), argument validation before any library call, the ABI.
+
+The first three tests cross-check the REFERENCES (the certificate the device tests rest on), not the code under test: they pass without the
+feature.  The validation, EvalResult and ABI tests below, and every test of tests/test_match_st_gpu.py, fail without it."""
+import types
+
+import numpy as np
+import pytest
+
+import match_st_ref as M
+
+
+def _rows(bits, depth, n):
+    return np.array([[(bits >> (t * n + u)) & 1 for u in range(n)] for t in range(depth)], dtype=np.int64)
+
+
+@pytest.mark.parametrize("comp", [0, 1])
+@pytest.mark.parametrize("depth", [1, 2])
+def test_dp_equals_the_search_over_fault_histories_for_every_defect_pattern(comp, depth):
+    """d = 3: every defect pattern; the open minimum, and the history minimum for every (m_last, class)."""
+    C, T = M.Component(3, comp), M.BfsTable(3, comp, depth)
+    n = C.n
+    assert n == 4
+    for D in range(1 << (n * depth)):
+        rows = _rows(D, depth, n)
+        assert M.dp_open(C, rows, depth) == T.open[D], (D, "open")
+        for m in range(1 << n):
+            for c in (0, 1):
+                mv = [(m >> u) & 1 for u in range(n)]
+                assert M.dp_history(C, rows, mv, c, depth) == T.history(D, m, c), (D, m, c)
+
+
+@pytest.mark.parametrize("comp", [0, 1])
+def test_dp_equals_the_search_on_sampled_patterns_at_depth_3(comp):
+    depth = 3
+    C, T = M.Component(3, comp), M.BfsTable(3, comp, depth)
+    n = C.n
+    rng = np.random.default_rng(20240 + comp)
+    for D, m, c in zip(rng.integers(0, 1 << (n * depth), 2000), rng.integers(0, 1 << n, 2000), rng.integers(0, 2, 2000)):
+        rows = _rows(int(D), depth, n)
+        assert M.dp_open(C, rows, depth) == T.open[D], (D, "open")
+        assert M.dp_history(C, rows, [(int(m) >> u) & 1 for u in range(n)], int(c), depth) == T.history(int(D), int(m), int(c)), (D, m, c)
+
+
+def test_search_table_hand_values():
+    """One data error: weight 1; a last-round defect alone: weight 1 through the future boundary; a same-site pair in consecutive rounds: weight 1."""
+    for comp in (0, 1):
+        T = M.BfsTable(3, comp, 2)
+        n = T.n
+        assert T.open[0] == 0
+        for u in range(n):
+            assert T.open[1 << (n + u)] == 1                                # (u, last round)
+            assert T.history(1 << (n + u), 1 << u, 0) == 1                  # ... explained by its measurement error
+            assert T.open[(1 << u) | (1 << (n + u))] == 1                   # (u, 0) and (u, 1): one measurement error
+        assert T.history(0, 0, 1) == 3                                      # the lightest logical operator
+
+
+# ---- validation before any library call ---------------------------------------------------------------------------------------------
+def _no_library(dq, monkeypatch):
+    _lib = __import__("importlib").import_module("deepq-decoding_amd._lib")
+
+    def no_library(*a, **k):
+        raise AssertionError("a library call was made before the arguments were validated")
+    monkeypatch.setattr(_lib, "lib", no_library)
+    monkeypatch.setattr(_lib, "require_gpu", no_library)
+
+
+def _env(**kw):
+    base = dict(d=5, error_model="DP", use_Y=False, volume_depth=5, p_phys=0.01, p_meas=0.01, seed=(1, 2), wide=False, n_envs=4)
+    base.update(kw)
+    return types.SimpleNamespace(**base)
+
+
+def test_matching_arguments_are_validated_before_any_library_call(dq, monkeypatch):
+    _no_library(dq, monkeypatch)
+    D = dq.decoder
+    ok = np.zeros((3, 5, 6, 6), np.uint8)
+    for vol, env, kw, exc in [(np.zeros((3, 5, 6, 5), np.uint8), _env(), {}, ValueError), (np.zeros((3, 4, 6, 6), np.uint8), _env(), {}, ValueError),
+                              (np.zeros((5, 6, 6), np.uint8), _env(), {}, ValueError), (np.zeros((0, 5, 6, 6), np.uint8), _env(), {}, ValueError),
+                              (ok.astype(np.int64), _env(), {}, ValueError), (ok.astype(np.float32), _env(), {}, ValueError),
+                              (np.full((3, 5, 6, 6), 2, np.uint8), _env(), {}, ValueError), ([[0]], _env(), {}, ValueError),
+                              (ok, None, {}, ValueError), (ok, _env(), dict(chunk=0), ValueError), (ok, _env(), dict(chunk=2.5), ValueError),
+                              (np.zeros((3, 5, 10, 10), np.uint8), _env(d=9), {}, NotImplementedError), (ok, _env(wide=True), {}, NotImplementedError),
+                              (ok, _env(), {}, TypeError)]:                # the last: valid arguments, but no environment handle behind them
+        with pytest.raises(exc):
+            D.matching_decode(vol, env, **kw)
+    for env, kw, exc in [(_env(), dict(n_volumes=0), ValueError), (_env(), dict(n_volumes=2.5), ValueError), (_env(), dict(n_volumes=8, rates=[]), ValueError),
+                         (_env(), dict(n_volumes=8, rates=[0.01, 0.01]), ValueError), (_env(), dict(n_volumes=8, rates=[1.5]), ValueError),
+                         (_env(), dict(n_volumes=8, rates=[0.01, 0.02], p_meas=[0.01]), ValueError), (_env(), dict(n_volumes=8, rates=[0.01], p_phys=0.01), ValueError),
+                         (_env(), dict(n_volumes=8, p_meas=0.01), ValueError), (_env(), dict(n_volumes=8, p_phys=-0.1), ValueError),
+                         (_env(), dict(n_volumes=8, seed=(1, 2, 3)), ValueError), (_env(), dict(n_volumes=8, env_id_base=-1), ValueError),
+                         (_env(), dict(n_volumes=8, chunk=0), ValueError), (_env(p_phys=2.0), dict(n_volumes=8), ValueError),
+                         (None, dict(n_volumes=8), ValueError), (_env(d=9, error_model="X"), dict(n_volumes=8), NotImplementedError),
+                         (_env(wide=True), dict(n_volumes=8), NotImplementedError), (_env(), dict(n_volumes=8), TypeError)]:
+        with pytest.raises(exc):
+            D.score_matching(env, **kw)
+
+
+def test_decode_benchmark_baseline_is_validated(dq, monkeypatch):
+    import shipped
+    _no_library(dq, monkeypatch)
+    agent_mod = __import__("importlib").import_module("deepq-decoding_amd.agent")
+    model = agent_mod.ConvQModel(shipped.C_LAYERS, shipped.FF_LAYERS, (7, 11, 11), 51)
+    agent = agent_mod.DQNAgent(model=model, nb_actions=51, memory=agent_mod.SequentialMemory(limit=100), nb_steps_warmup=10, target_model_update=10)
+    with pytest.raises(ValueError):
+        agent.decode_benchmark(_env(), n_volumes=8, baseline="mwpm")
+
+
+def test_eval_result_inexact_defaults_to_zero(dq):
+    E = dq.decoder.EvalResult
+    r = E([10, 1, 9, 8, 9, 10, 0, 0, 4])
+    assert r.inexact == 0 and "inexact" not in r.summary()
+    assert E([10, 1, 9, 8, 9, 10, 0, 0, 4], inexact=3).summary()["inexact"] == 3
+
+
+def test_matching_abi_is_declared_and_bound(dq):
+    import importlib
+    import os
+    L = importlib.import_module("deepq-decoding_amd._lib")
+    lib = L.lib()
+    assert lib.dq_version() >= 6
+    assert "dq_decode_match" in L.SIGNATURES and hasattr(lib, "dq_decode_match")
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "deepq_hip.h")).read()
+    assert "dq_status dq_decode_match(dq_decode_eval* ev, const uint8_t* volumes_dev, int n, uint8_t* frame_dev" in header

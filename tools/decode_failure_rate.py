@@ -4,7 +4,8 @@ DESIGN.md section 12).
     python tools/decode_failure_rate.py [--family d5_dp] [--weights 0.007] [--rates 0.003,0.007,0.011] [--n 1048576] [--chunk 262144] [--out profiles/NAME.json]
 
 Per rate: the failure rate (1 - success / volumes: the residual error is not a stabilizer) with its Wilson 95 % interval for the agent under
-the masked and the plain greedy policy and for no decoder at all (frame = 0), the death rate (the referee loses the residual's class), the
+the masked and the plain greedy policy, for space-time minimum-weight matching (the `matching` row, on the same volumes; its phases are sample /
+match / verdict, and `match_over_agent_decode` is its match time over the masked agent's decode time) and for no decoder at all (frame = 0), the death rate (the referee loses the residual's class), the
 share of all-zero volumes, corrections per volume, the status histogram, and the wall time of the phases (sample / decode / verdict, each
 closed by a synchronisation; the verdict phase of the masked run also carries the frame = 0 verdict).  Weights: tests/golden/keras_weights_<family>_<weights>.npz.
 One process, no retries: the first failing GPU call ends it.  On a shared box run it under a time limit, e.g. `timeout -k 10 600 python tools/...`."""
@@ -48,6 +49,7 @@ def main():
     agent.model.set_weights([fx[f"w{i}"] for i in range(12)])
     agent.decode_benchmark(env, min(a.n, a.chunk), rates=[rates[0]], chunk=a.chunk)            # warm-up: allocations, first launches
     out = {"family": a.family, "weights": a.weights, "volumes_per_rate": a.n, "chunk": a.chunk, "device": torch.cuda.get_device_name(0), "rates": {}}
+    mev = None
     for r in rates:
         row = {}
         for name, masked in (("masked", True), ("unmasked", False)):
@@ -66,6 +68,23 @@ def main():
                                                         "death_interval")}
             print(f"p = {r} {name:8s}: failure {res.failure_rate:.6f} [{res.failure_interval[0]:.6f}, {res.failure_interval[1]:.6f}]  death {res.death_rate:.6f}  "
                   f"trivial {res.trivial_share:.4f}  corrections / volume {res.mean_corrections:.4f}  {res.status_histogram}  ms {s['ms']}", flush=True)
+        # the space-time matching baseline on the same volumes (decoder.score_matching)
+        D = dq.decoder
+        if mev is None:                                                                                 # one scoring handle for every call: its matching tables are built once
+            mev = D.Evaluator(cfg["d"], cfg["error_model"], cfg["use_Y"], cfg["volume_depth"], chunk=a.chunk, device=env.device)
+        D.score_matching(env, min(a.n, a.chunk), rates=[r], evaluator=mev)                              # warm-up: the tables, first launch, allocations
+        timings = {}
+        t0 = time.perf_counter()
+        mres = D.score_matching(env, a.n, rates=[r], timings=timings, evaluator=mev)[r]
+        wall = time.perf_counter() - t0
+        s = mres.summary()
+        s["inexact"] = mres.inexact
+        s["ms"] = {k: round(1e3 * timings.get(k, 0.0), 3) for k in ("sample", "match", "verdict")}
+        s["ms"]["wall"] = round(1e3 * wall, 3)
+        s["match_over_agent_decode"] = round(s["ms"]["match"] / row["masked"]["ms"]["decode"], 4)
+        row["matching"] = s
+        print(f"p = {r} matching: failure {mres.failure_rate:.6f} [{mres.failure_interval[0]:.6f}, {mres.failure_interval[1]:.6f}]  death {mres.death_rate:.6f}  "
+              f"corrections / volume {mres.mean_corrections:.4f}  inexact {mres.inexact}  ms {s['ms']}  match / agent decode {s['match_over_agent_decode']}", flush=True)
         nd = row["no_decoder"]
         print(f"p = {r} frame = 0: failure {nd['failure_rate']:.6f} [{nd['failure_interval'][0]:.6f}, {nd['failure_interval'][1]:.6f}]  death {nd['death_rate']:.6f}",
               flush=True)
@@ -76,6 +95,8 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(out, f, indent=1)
+    if mev is not None:
+        mev.close()
     agent._decoder = None
     env.close()
 
