@@ -34,6 +34,7 @@ from collections import deque
 import numpy as np
 import torch
 
+from . import episodes
 from .core import DQNCore, MIN_FILLED
 from .env import Surface_Code_Environment_Multi_Decoding_Cycles, VectorEnv
 from .qnet import QNetwork, check_delta_clip
@@ -670,23 +671,24 @@ class DQNAgent:
              nb_max_start_steps=0, start_step_policy=None, verbose=1, episode_averaging_length=None, interval=100, single_cycle=True):
         """Greedy episodes (TRAIN:206).  With N lattices, lattice i contributes its first ceil-share of episodes, so the
         sample is not biased towards short episodes.  history keys: episode_reward, nb_steps, episode_lifetime,
-        episode_lifetimes_rolling_avg."""
+        episode_lifetimes_rolling_avg.  nb_max_episode_steps: the hard cap on the vector steps of the whole call (episodes.check_step_cap;
+        RuntimeError when it is reached with episodes outstanding)."""
         venv = self._bind(env)
         core, N = self._core, venv.n_envs
         self.training = False
         history = History()
         if verbose >= 1:
             print(f"Testing for {nb_episodes} episodes ...")
-        quota = np.full(N, nb_episodes // N, dtype=np.int64)
-        quota[:nb_episodes % N] += 1
+        quota = episodes.share_quota(N, nb_episodes)
+        episodes.check_step_cap(nb_max_episode_steps, quota)
         eps, masked = self.test_policy.current(False)
         core.begin_eval()                           # nothing of the evaluation reaches the replay memory (keras-rl: training=False)
         try:
-            return self._test_loop(core, venv, N, quota, eps, masked, history, verbose, interval)
+            return self._test_loop(core, venv, N, quota, eps, masked, history, verbose, interval, nb_max_episode_steps=nb_max_episode_steps)
         finally:
             core.end_eval()
 
-    def test_error_rates(self, env, error_rates, nb_episodes=1, p_meas=None, verbose=1, interval=100):
+    def test_error_rates(self, env, error_rates, nb_episodes=1, p_meas=None, verbose=1, interval=100, nb_max_episode_steps=None):
         """The evaluation sweep of TRAIN:164-222 -- `nb_episodes` greedy episodes at each rate of `error_rates` -- as ONE batched
         evaluation: the bound VectorEnv's N lattices are split into K = len(error_rates) contiguous blocks of m = N // K; block k runs at
         error_rates[k] (p_meas: None = the same rates, a scalar, or one rate per entry) and shares its nb_episodes over its m lattices by
@@ -695,34 +697,10 @@ class DQNAgent:
         same entries as test() on a VectorEnv holding that block's lattices alone (env_id_base = the block's first global id, same seed
         and history).  The environment's previous rates are restored on the way out."""
         venv = env._v if isinstance(env, Surface_Code_Environment_Multi_Decoding_Cycles) else env
-        rates = [float(r) for r in error_rates]
+        rates, m, ph, pm, quota = episodes.rate_blocks(venv.n_envs, error_rates, nb_episodes, p_meas)
+        episodes.check_step_cap(nb_max_episode_steps, quota)
         K, N = len(rates), int(venv.n_envs)
-        if K < 1:
-            raise ValueError("test_error_rates: no error rates")
-        if K > N:
-            raise ValueError(f"test_error_rates: {K} error rates need at least {K} lattices, the environment has {N}")
-        if len(set(rates)) != K:
-            raise ValueError("test_error_rates: the error rates must be distinct (they key the result)")
-        if p_meas is None:
-            meas = rates
-        elif np.ndim(p_meas) == 0:
-            meas = [float(p_meas)] * K
-        else:
-            meas = [float(r) for r in p_meas]
-            if len(meas) != K:
-                raise ValueError(f"test_error_rates: {len(meas)} measurement rates for {K} error rates")
-        for r in rates + meas:
-            if not (0.0 <= r <= 1.0):
-                raise ValueError(f"test_error_rates: rate {r!r} is not in [0, 1]")
         venv = self._bind(env)
-        m = N // K
-        ph, pm = np.empty(N), np.empty(N)
-        ph[:K * m] = np.repeat(rates, m); pm[:K * m] = np.repeat(meas, m)
-        ph[K * m:], pm[K * m:] = rates[-1], meas[-1]                 # (idle lattices: any valid rate)
-        quota = np.zeros(N, dtype=np.int64)
-        share = np.full(m, nb_episodes // m, dtype=np.int64)
-        share[:nb_episodes % m] += 1
-        quota[:K * m] = np.tile(share, K)
         core = self._core
         self.training = False
         if verbose >= 1:
@@ -732,51 +710,35 @@ class DQNAgent:
         venv.set_rates(ph, pm)
         core.begin_eval()
         try:
-            rec = self._test_records(core, venv, N, quota, eps, masked)
+            rec = self._test_records(core, venv, N, quota, eps, masked, nb_max_episode_steps=nb_max_episode_steps)
         finally:
             core.end_eval()
             venv.set_rates(*previous)
         out = {}
         for k, r in enumerate(rates):
-            sel = rec[(rec[:, 1] >= k * m) & (rec[:, 1] < (k + 1) * m)]
+            sel = episodes.block_records(rec, k, m)
             out[r] = self._history_from_records(sel, verbose >= 2, interval)
             if verbose >= 1 and len(sel):
                 print(f"p = {r}: {len(sel)} episodes, average lifetime {out[r].history['episode_lifetimes_rolling_avg'][-1]:.3f}")
         return out
 
-    def _test_loop(self, core, venv, N, quota, eps, masked, history, verbose, interval, sync_interval=None):
+    def _test_loop(self, core, venv, N, quota, eps, masked, history, verbose, interval, sync_interval=None, nb_max_episode_steps=None):
         """Device-resident: the episode records are appended on the device (dq_test_bookkeeping, one small launch per vector step); the host
         looks at the record counter every `sync_interval` steps only, so a batched evaluation costs what its kernels cost (rounds 1-2 did
         four device-to-host copies and a Python loop over the finished lattices per vector step)."""
-        rec = self._test_records(core, venv, N, quota, eps, masked, sync_interval)
+        rec = self._test_records(core, venv, N, quota, eps, masked, sync_interval, nb_max_episode_steps)
         return self._history_from_records(rec, verbose >= 2, interval, history)
 
-    def _test_records(self, core, venv, N, quota, eps, masked, sync_interval=None):
-        """_test_loop's device part: the episode records (vector step, lattice, reward bits, length, lifetime), sorted by vector step, then
-        lattice: the serial loop's order."""
-        from ._lib import check, ptr
-        dev = core.device
-        total = int(quota.sum())
-        quota_d = torch.from_numpy(quota.astype(np.int32)).to(dev)
-        ep_reward = torch.zeros(N, dtype=torch.float32, device=dev)
-        ep_len = torch.zeros(N, dtype=torch.int32, device=dev)
-        records = torch.zeros((max(total, 1), 5), dtype=torch.int32, device=dev)
-        counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        core.reset_env()
-        L = core.L
-        step = 0
-        if sync_interval is None:
-            sync_interval = 1 if N == 1 else 64
-        while total > 0:
+    def _test_records(self, core, venv, N, quota, eps, masked, sync_interval=None, nb_max_episode_steps=None):
+        """_test_loop's device part: the episode records of episodes.episode_records (the loop every policy runs) with the greedy agent's
+        vector step as its callback."""
+        def step(k):
             slot = core.cur
             core.act_and_step(eps, masked_greedy=masked, record_stats=False)
-            check(L.dq_test_bookkeeping(ptr(core.ring.terminal[slot]), ptr(venv.was_reset), ptr(core.ring.reward[slot]), ptr(venv.lifetime), N, step,
-                                        ptr(quota_d), ptr(ep_reward), ptr(ep_len), ptr(records), total, ptr(counter), core._stream()))
-            step += 1
-            if step % sync_interval == 0 and int(counter.item()) >= total:
-                break
-        rec = records.cpu().numpy()[:total]
-        rec = rec[np.lexsort((rec[:, 1], rec[:, 0]))]                     # by vector step, then lattice: the serial loop's order
+            return core.ring.terminal[slot], venv.was_reset, core.ring.reward[slot], venv.lifetime
+
+        core.reset_env()
+        rec = episodes.episode_records(core.L, core.device, core._stream, N, quota, step, sync_interval, nb_max_episode_steps)
         core.read_stats()
         return rec
 

@@ -14,5 +14,7 @@ struct dq_decode_eval {
     u64* xz;
     int32_t* no_action;
     u8* dec;
-    MatchStTables* match_st;    // dq_decode_match's tables (built and uploaded at its first call)
+    MatchStTables* match_st;    // dq_decode_match's / dq_env_match_select's tables (built and uploaded at the first call of either)
 };
+
+dq_status match_st_tables(dq_decode_eval* V);                    // match_st.hip: builds V->match_st unless it is there

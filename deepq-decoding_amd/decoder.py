@@ -535,6 +535,168 @@ def matching_decode(volumes, env, chunk=DEFAULT_CHUNK, to_host=False, evaluator=
     return MatchResult(*(tuple(x.cpu().numpy() for x in out) if to_host else out))
 
 
+# ---- the matching decoder as a policy of the environment (include/deepq_hip.h dq_env_match_select; csrc/env_match.hip) --------
+def frame_to_actions(frame, completed, d, error_model, use_Y):
+    """The rule of dq_env_match_select in numpy.  frame: hidden_state codes 0..3 [d, d] (or [d * d]) -- matching_decode's frame F for the lattice's
+    current volume, or [2, d, d] 0/1 components (X part, Z part); completed: the action indices in the lattice's completed_actions (any iterable;
+    completed_from_words reads them from an exported state), or None.  Returns (wanted, action): wanted = the ascending action indices whose index_to_move XOR to F --
+    X model: the X part on the one layer (the Z part is ignored: no action flips it); DP / IIDXZ with use_Y: code 1 / 2 / 3 -> layer 0 / 1 / 2 at
+    the qubit; without use_Y: X part -> layer 0, Z part -> layer 1, so a Y cell is the X action and, later, the Z action of its qubit -- and
+    action = the lowest wanted index not in `completed`, else the identity (num_actions - 1).  The legal set is not consulted: the environment
+    applies any action (Environments.py:131-136)."""
+    d = int(d)
+    layers = action_layers(error_model, use_Y)
+    d2 = d * d
+    f = np.asarray(frame)
+    if f.size == 2 * d2 and f.ndim >= 2 and f.shape[0] == 2:
+        fx, fz = (f[0].reshape(d2) != 0), (f[1].reshape(d2) != 0)
+    elif f.size == d2:
+        code = f.reshape(d2).astype(np.int64)
+        if ((code < 0) | (code > 3)).any():
+            raise ValueError("frame cells must be Pauli codes 0..3")
+        fx, fz = (code == 1) | (code == 2), (code == 2) | (code == 3)
+    else:
+        raise ValueError(f"frame must have shape [{d}, {d}] (codes) or [2, {d}, {d}] (components), got {f.shape}")
+    if error_model == "X":
+        parts = [fx]
+    elif use_Y:
+        parts = [fx & ~fz, fx & fz, fz & ~fx]
+    else:
+        parts = [fx, fz]
+    wanted = [int(l * d2 + q) for l in range(layers) for q in np.flatnonzero(parts[l])]
+    identity = layers * d2
+    have = set() if completed is None else {int(x) for x in completed}
+    for a in wanted:
+        if a not in have:
+            return wanted, a
+    return wanted, identity
+
+
+def completed_from_words(w0, w1):
+    """The set of action indices in a completed_actions mask (words 6, 7 of dq_env_export_state)."""
+    m = int(w0) & (2 ** 64 - 1) | (int(w1) & (2 ** 64 - 1)) << 64
+    return {i for i in range(128) if (m >> i) & 1}
+
+
+def check_match_policy_args(env, evaluator=None, chunk=DEFAULT_CHUNK):
+    """Validates the lattice of a matching-policy evaluation without touching the library: the narrow environment, d <= 7, volume_depth <= 16 (else
+    NotImplementedError), an evaluator of the same lattice (else ValueError).  Returns (d, error_model, use_Y, volume_depth)."""
+    if env is None:
+        raise ValueError("an environment is needed: the policy plays it")
+    v = getattr(env, "_v", env)
+    d, model, use_Y, depth = lattice_of(v)
+    if d < 3 or d % 2 == 0:
+        raise ValueError(f"d = {d}: the surface code lattices have odd d >= 3")
+    action_layers(model, use_Y)
+    if getattr(v, "wide", False) or d > 7:
+        raise NotImplementedError(f"the matching policy covers the narrow environment, d <= 7 (d = {d}, wide = {bool(getattr(v, 'wide', False))})")
+    if not 1 <= depth <= 16:
+        raise NotImplementedError(f"the matching policy covers volume_depth 1..16, not {depth}")
+    check_decode_args(d, model, use_Y, depth, (depth, d + 1, d + 1))
+    if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
+    if evaluator is not None:
+        theirs = (int(evaluator.d), str(evaluator.error_model), int(evaluator.volume_depth))
+        if theirs != (d, model, depth) or (model != "X" and bool(evaluator.use_Y) != use_Y):
+            raise ValueError(f"the evaluator's lattice (d, error model, use_Y, volume_depth) = "
+                             f"{(theirs[0], theirs[1], bool(evaluator.use_Y), theirs[2])} is not the environment's {(d, model, use_Y, depth)}")
+    return d, model, use_Y, depth
+
+
+class MatchingAgent:
+    """Plays the environment with the space-time matching decoder, behind DQNAgent's evaluation surface: per agent step one dq_env_match_select
+    launch (the next flip of the matching's frame for the lattice's current volume, then the identity) and one dq_env_step with auto-reset, the
+    episode records kept on the device by the loop DQNAgent.test runs (episodes.episode_records).  policy="identity": only ever the identity --
+    the "no decoder" row of the same table.  evaluator: an Evaluator of the environment's lattice to run on (it stays open); default: one per
+    call.  After a call last_inexact_steps holds the lattice-steps whose volume took the matching's 14 / 32 fallback (summed on the device; per
+    rate after test_error_rates: last_inexact_by_rate), last_vector_steps the vector steps made."""
+
+    def __init__(self, evaluator=None, chunk=DEFAULT_CHUNK, policy="matching"):
+        if policy not in ("matching", "identity"):
+            raise ValueError(f"policy must be 'matching' or 'identity', not {policy!r}")
+        if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+            raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
+        self.evaluator, self.chunk, self.policy = evaluator, int(chunk), policy
+        self.last_inexact_steps, self.last_inexact_by_rate, self.last_vector_steps = 0, {}, 0
+
+    def test(self, env, nb_episodes=1, verbose=1, interval=100, nb_max_episode_steps=None):
+        """DQNAgent.test for this policy: the same keys, ceil-share quota and record order (vector step, then lattice).  Returns History."""
+        from . import episodes
+        from .agent import DQNAgent, History
+        check_match_policy_args(env, self.evaluator, self.chunk)
+        v = getattr(env, "_v", env)
+        if isinstance(nb_episodes, (bool, np.bool_)) or not isinstance(nb_episodes, (int, np.integer)) or nb_episodes < 0:
+            raise ValueError(f"nb_episodes must be a non-negative integer, not {nb_episodes!r}")
+        quota = episodes.share_quota(int(v.n_envs), int(nb_episodes))
+        episodes.check_step_cap(nb_max_episode_steps, quota)
+        if verbose >= 1:
+            print(f"Testing for {nb_episodes} episodes ...")
+        rec, inexact = self._records(_narrow_env(env), quota, nb_max_episode_steps)
+        self.last_inexact_steps, self.last_inexact_by_rate = int(inexact.sum()), {}
+        return DQNAgent._history_from_records(rec, verbose >= 2, interval, History())
+
+    def test_error_rates(self, env, error_rates, nb_episodes=1, p_meas=None, verbose=1, interval=100, nb_max_episode_steps=None):
+        """DQNAgent.test_error_rates for this policy: the same block layout over the lattices, quotas, keys and record order; the environment's
+        previous rates are restored on the way out.  Returns {rate: History}."""
+        from . import episodes
+        from .agent import DQNAgent
+        check_match_policy_args(env, self.evaluator, self.chunk)
+        v = getattr(env, "_v", env)
+        rates, m, ph, pm, quota = episodes.rate_blocks(v.n_envs, error_rates, nb_episodes, p_meas)
+        episodes.check_step_cap(nb_max_episode_steps, quota)
+        venv = _narrow_env(env)
+        if verbose >= 1:
+            print(f"Testing for {nb_episodes} episodes at each of {len(rates)} error rates ({m} lattices each) ...")
+        previous = venv._rate_forms()
+        venv.set_rates(ph, pm)
+        try:
+            rec, inexact = self._records(venv, quota, nb_max_episode_steps)
+        finally:
+            venv.set_rates(*previous)
+        out = {}
+        self.last_inexact_steps, self.last_inexact_by_rate = int(inexact[:len(rates) * m].sum()), {}
+        for k, r in enumerate(rates):
+            sel = episodes.block_records(rec, k, m)
+            out[r] = DQNAgent._history_from_records(sel, verbose >= 2, interval)
+            self.last_inexact_by_rate[r] = int(inexact[k * m:(k + 1) * m].sum())
+            if verbose >= 1 and len(sel):
+                print(f"p = {r}: {len(sel)} episodes, average lifetime {out[r].history['episode_lifetimes_rolling_avg'][-1]:.3f}")
+        return out
+
+    def _records(self, venv, quota, nb_max_episode_steps):
+        """(records of episodes.episode_records, inexact lattice-steps per lattice int64 [N]) of one evaluation from a reset."""
+        import torch
+        from . import episodes
+        d, model, use_Y, depth = lattice_of(venv)
+        dev, N = venv.device, int(venv.n_envs)
+        matching = self.policy == "matching"
+        ev = self.evaluator
+        if matching and ev is None:
+            ev = Evaluator(d, model, use_Y, depth, chunk=min(self.chunk, N), device=dev)
+        try:
+            with torch.cuda.device(dev):
+                action = torch.full((N,), int(venv.identity_index), dtype=torch.int32, device=dev)
+                flag = torch.zeros(N, dtype=torch.uint8, device=dev)
+                inexact = torch.zeros(N, dtype=torch.int64, device=dev)
+                steps = [0]
+
+                def step(k):
+                    if matching:
+                        venv.match_select(ev, out=action, out_inexact=flag)
+                        inexact.add_(flag)
+                    venv.step(action, auto_reset=True, write_obs=False)
+                    steps[0] = k + 1
+                    return venv.done, venv.was_reset, venv.reward, venv.lifetime
+
+                venv.reset(write_obs=False)
+                rec = episodes.episode_records(venv.L, dev, venv._stream, N, quota, step, None, nb_max_episode_steps)
+                self.last_vector_steps = steps[0]
+                return rec, inexact.cpu().numpy()
+        finally:
+            if matching and self.evaluator is None:
+                ev.close()
+
+
 def expand_rates(lattice, env, n_volumes, rates, p_meas, seed, env_id_base, who):
     """rates=[...] of decode_benchmark / score_matching: n_volumes at EACH physical rate in one evaluation of K n_volumes volumes in blocks of
     n_volumes.  Validates without touching the library; returns (total, p_phys, p_meas, block, keys)."""

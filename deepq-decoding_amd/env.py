@@ -414,11 +414,12 @@ class VectorEnv:
             self.done.masked_fill_(w != 0, 0)
         return obs
 
-    def step(self, action, auto_reset=False, out_obs=None, out_patch=None):
-        """ENV:118-204 for every lattice.  `action`: int32 device tensor [n_envs].  Returns (obs, reward, done)."""
+    def step(self, action, auto_reset=False, out_obs=None, out_patch=None, write_obs=True):
+        """ENV:118-204 for every lattice.  `action`: int32 device tensor [n_envs].  Returns (obs, reward, done).  write_obs=False: no
+        observation is composed (a policy that reads the lattices' state instead, match_select); obs is then None."""
         if not (isinstance(action, torch.Tensor) and action.dtype == torch.int32 and action.is_cuda and action.is_contiguous()):
             action = torch.as_tensor(action, dtype=torch.int32, device=self.device).contiguous()
-        obs = self.obs if out_obs is None else out_obs
+        obs = (self.obs if out_obs is None else out_obs) if write_obs else None
         if out_patch is not None:
             self.arm_patch_output(out_patch)
         if self.wide:
@@ -473,6 +474,28 @@ class VectorEnv:
         else:
             check(self.L.dq_policy_select(ptr(q), ptr(self.legal), self.n_envs, self.num_actions, float(eps), int(masked_greedy),
                                           seed, self.env_id_base, int(t), ptr(out), self._stream()))
+        return out
+
+    def match_select(self, evaluator, out=None, out_inexact=None):
+        """The matching decoder's next action for every lattice (include/deepq_hip.h dq_env_match_select): the lowest action
+        index of the matching's Pauli frame for the lattice's current volume that is not in completed_actions, else the identity.  evaluator: a
+        decoder.Evaluator of this lattice (it owns the matching tables).  out: int32 [n_envs]; out_inexact: uint8 [n_envs] or None (the
+        fallback flag of each volume is then not written).  Returns the actions; step(actions, auto_reset=True) is the agent step."""
+        if self.wide or self.d > 7:
+            raise NotImplementedError("match_select covers the narrow environment, d <= 7 (the wide environment / d >= 9 is not supported)")
+        if self.volume_depth > 16:
+            raise NotImplementedError("match_select covers volume_depth <= 16")
+        mine = (self.d, self.error_model, self.volume_depth)
+        theirs = (evaluator.d, evaluator.error_model, evaluator.volume_depth)
+        if mine != theirs or (self.error_model != "X" and bool(self.use_Y) != bool(evaluator.use_Y)):
+            raise ValueError(f"the evaluator's lattice (d, error model, volume_depth) = {theirs}, use_Y = {evaluator.use_Y} is not the environment's "
+                             f"{mine}, use_Y = {self.use_Y}")
+        if out is None:
+            out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        for t, dt in ((out, torch.int32), (out_inexact, torch.uint8)):
+            if t is not None and not (t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (self.n_envs,)):
+                raise ValueError(f"match_select: outputs are contiguous device tensors of n_envs = {self.n_envs} entries (int32 actions, uint8 flags)")
+        check(self.L.dq_env_match_select(self._h, evaluator._h, ptr(out), ptr(out_inexact), self._stream()))
         return out
 
     # -- state views --------------------------------------------------------------------------------------

@@ -765,6 +765,17 @@ dq_status dq_decode_count(const uint8_t* verdict_dev, const uint8_t* trivial_dev
  * names MWPM as the benchmark). */
 dq_status dq_decode_match(dq_decode_eval* ev, const uint8_t* volumes_dev, int n, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev,
                           uint8_t* inexact_dev, void* stream);
+/* dq_env_match_select: the matching decoder as a policy of the narrow environment (csrc/env_match.hip; dq_version() >= 7).  For
+ * every lattice of `env`: F = the frame dq_decode_match returns for the lattice's current faulty volume (the record's volume_depth syndrome words,
+ * S_-1 = 0, so residual error of earlier volumes shows up as round-0 defects); wanted = the action indices whose moves XOR to F (X model: component 0
+ * on the one layer, component 1 is ignored; DP / IIDXZ with use_Y: code 1 / 2 / 3 -> layer 0 / 1 / 2; without: X part -> layer 0, Z part -> layer 1,
+ * a Y cell being both); action_dev[i] = the lowest wanted index not in completed_actions, else the identity; a lattice whose done flag is set gets the
+ * identity.  inexact_dev (nullable) uint8 [n_envs]: dq_decode_match's flag for the volume (0 for a done lattice).  A function of the lattice's state
+ * alone: nothing is kept between calls and the environment is not modified.  An agent step is this launch followed by
+ * dq_env_step(action_dev, auto_reset = 1); the legal set is not consulted (the step applies any action, Environments.py:131-136).  ev must have
+ * been created for the environment's d, error model, use_Y (X model: ignored) and volume_depth (DQ_ERR_INVALID otherwise); its matching tables are
+ * built at the first call of this or of dq_decode_match (the same thread rule).  One wavefront per lattice; action_dev int32 [n_envs]. */
+dq_status dq_env_match_select(dq_env* env, dq_decode_eval* ev, int32_t* action_dev, uint8_t* inexact_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Live kernel timing (measurement only; no reference counterpart).  dq_prof_arm(id, n) times up to n
