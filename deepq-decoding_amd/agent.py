@@ -160,10 +160,21 @@ class Policy:
 
 
 class EpsGreedyQPolicy(Policy):
-    """With probability eps a uniformly random LEGAL action, else argmax Q (over the legal set when masked_greedy)."""
+    """With probability eps a uniformly random LEGAL action, else argmax Q (over the legal set when masked_greedy).
+    guide (no keras-rl counterpart): a decoder.MatchingAgent(policy="matching") -- the teacher.  An exploring lattice then follows
+    the space-time matching decoder with probability guide_share (constant over the run; the teacher's rate eps * guide_share anneals with eps) and
+    draws uniformly over its legal set otherwise.  fit() reads `guide` and `guide_share` as attributes; current() is unchanged; test() ignores them."""
 
-    def __init__(self, eps=.1, masked_greedy=False):
-        self.eps, self.masked_greedy = eps, masked_greedy
+    def __init__(self, eps=.1, masked_greedy=False, guide=None, guide_share=1.0):
+        if guide is not None:
+            from .decoder import MatchingAgent
+            if not isinstance(guide, MatchingAgent):
+                raise TypeError(f"guide must be a decoder.MatchingAgent, not {type(guide).__name__}")
+            if guide.policy != "matching":
+                raise ValueError(f"guide must play the matching decoder (MatchingAgent(policy='matching')), not policy={guide.policy!r}")
+        if isinstance(guide_share, (bool, np.bool_)) or not isinstance(guide_share, (int, float, np.integer, np.floating)) or not 0.0 <= float(guide_share) <= 1.0:
+            raise ValueError(f"guide_share must be a number in [0, 1], not {guide_share!r}")
+        self.eps, self.masked_greedy, self.guide, self.guide_share = eps, masked_greedy, guide, float(guide_share)
 
     def current(self, training=True):
         return float(self.eps), bool(self.masked_greedy)
@@ -200,6 +211,10 @@ class LinearAnnealedPolicy(Policy):
     def current(self, training=True):
         setattr(self.inner_policy, self.attr, self.get_current_value(training))
         return self.inner_policy.current(training)
+
+    # the inner policy's teacher (EpsGreedyQPolicy(guide=..., guide_share=...)), passed through
+    guide = property(lambda self: getattr(self.inner_policy, "guide", None))
+    guide_share = property(lambda self: getattr(self.inner_policy, "guide_share", 1.0))
 
     @property
     def metrics_names(self):
@@ -317,6 +332,7 @@ class DQNAgent:
         self.step = 0
         self._core = self._net = self._env = None
         self._last_target_sync = 0
+        self.last_guided_steps = self.last_inexact_steps = 0      # of the last fit(): lattice-steps that followed the policy's guide / whose matching was inexact
         model._agent = self
 
     # -- keras-rl surface ---------------------------------------------------------------------------------------
@@ -523,6 +539,17 @@ class DQNAgent:
             warnings.warn("single_cycle=True is ignored: the environment is a multi-cycle one (Environments.py:97)")
         venv = self._bind(env)
         core, N = self._core, venv.n_envs
+        # A policy with a teacher (EpsGreedyQPolicy(guide=...)): every vector step is DQNCore.guided_act_and_step -- acting forward,
+        # dq_env_guided_select into the ring's action slot, dq_env_step into its reward / done / observation slots -- followed by _maybe_train(); the form in
+        # which the step rides on the update's launches (step_and_update) is taken only without one
+        guide, guide_share = getattr(self.policy, "guide", None), float(getattr(self.policy, "guide_share", 1.0))
+        guide_ev = guide_opened = None
+        if guide is not None:
+            if core.world_size > 1:
+                raise NotImplementedError("fit() with a guide runs on one GPU: several ranks are not supported")
+            guide_ev, guide_opened = guide.evaluator_for(venv)
+            core.guide_counts.zero_()
+        self.last_guided_steps = self.last_inexact_steps = 0
         self.training = True
         # Several ranks (one per GPU): every step-counted hyper-parameter -- nb_steps, nb_steps_warmup, the epsilon schedule, min_nb_steps,
         # target_model_update -- counts THIS RANK's environment steps (self.step); what is logged and printed ("Step: a/b", nb_steps in
@@ -557,7 +584,11 @@ class DQNAgent:
             while self.step - start_step < nb_steps and not stop:
                 loop_iter += 1
                 eps, masked = self.policy.current(True)
-                if self._will_train(self.step + N):
+                if guide is not None:
+                    core.guided_act_and_step(guide_ev, eps, guide_share, masked_greedy=masked)
+                    self.step += N
+                    trained = self._maybe_train()
+                elif self._will_train(self.step + N):
                     # acting forward + the update's forwards in one pair of launches; the environment launch draws the next minibatch
                     core.step_and_update(eps, masked_greedy=masked, presample_next=self._will_train(self.step + 2 * N),
                                          extra_updates=self.updates_per_vector_step - 1)
@@ -588,7 +619,10 @@ class DQNAgent:
                     # the all-reduced count -- only the ranks whose OWN lattice finished take the (uncounted) reset step, a rank whose
                     # lattice is still alive must not step it; the update is collective (gradient all-reduce), so every rank trains.
                     if core.local_stats[0] > 0:
-                        core.act_and_step(eps, masked_greedy=masked, record_stats=False)
+                        if guide is not None:
+                            core.guided_act_and_step(guide_ev, eps, guide_share, masked_greedy=masked, record_stats=False)
+                        else:
+                            core.act_and_step(eps, masked_greedy=masked, record_stats=False)
                     self._maybe_train()
                 now = timeit.default_timer()
                 # one log record per finished episode (N == 1) or per synchronisation chunk (N > 1)
@@ -629,7 +663,16 @@ class DQNAgent:
             core.close_comm(abort=True)
             self.training = False
             raise
+        finally:
+            if guide_opened:                # (an evaluator opened for this run; on the way out of an error its own must not replace the one that is unwinding)
+                try:
+                    guide_ev.close()
+                except Exception:
+                    pass
         torch.cuda.synchronize(core.device)
+        if guide is not None:
+            # lattice-steps of this run that followed the teacher / whose matching took its 14 / 32 fallback, summed on the device
+            self.last_guided_steps, self.last_inexact_steps = (int(x) for x in core.guide_counts.cpu().tolist())
         core.close_comm()               # (every rank, everything drained: before the process group that did its rendezvous can be destroyed)
         dt = timeit.default_timer() - t_start
         for cb in callbacks:

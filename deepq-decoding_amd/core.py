@@ -147,6 +147,10 @@ class DQNCore:
         self.local_stats = [0, 0, 0, 0]
         self.inexact_total = 0
         self._inexact_acc = torch.zeros((), dtype=torch.int64, device=dev) if self._wide else None
+        # guided exploration (guided_act_and_step): per-lattice flags of the step (row 0: followed the teacher, row 1: its matching took the fallback)
+        # and their running sums; the caller zeroes and reads the sums (DQNAgent.fit)
+        self._guide_flags = None
+        self.guide_counts = torch.zeros(2, dtype=torch.int64, device=dev)
         self.ar_events = None        # bench.py: a list here collects HIP-event pairs around the exposed part of the gradient all-reduce
         self.ar_pool = []            # ... taken from this pool of pre-created pairs (creating two timing events per step costs host time inside the timed region)
         self.ar_stride, self._ar_seen = 1, 0     # ... in every ar_stride-th step only (two marker packets in the stream cost the step ~4 us)
@@ -203,6 +207,34 @@ class DQNCore:
         self._launch_env(self._env_step(q, eps, masked_greedy, sj))
         # episode bookkeeping of this step: rides on the next update's TD launch (dq_td_update_stats) when an update follows, else
         # launched on its own
+        self._stats_pending = (cur,) if record_stats else None
+        if record_stats and not self.defer_stats:
+            self._flush_stats()
+        r.advance()
+        self.vector_steps += 1
+
+    def guided_act_and_step(self, evaluator, eps, guide_share, masked_greedy=False, record_stats=True):
+        """act_and_step() with a teacher: Q forward on the current observations, VectorEnv.guided_select -- an exploring lattice
+        follows the matching decoder with probability guide_share -- into the ring's action slot, then dq_env_step with auto-reset writing the ring's
+        reward / done slots and the successor observation; the episode bookkeeping is act_and_step's.  The lattice-steps that followed the teacher and
+        those whose matching took its fallback are added to self.guide_counts on the device.  evaluator: a decoder.Evaluator of the environment's
+        lattice.  One GPU, the narrow environment."""
+        if self._wide or self.world_size > 1:
+            raise NotImplementedError("guided_act_and_step: one GPU and the narrow environment (d <= 7)")
+        self._flush_stats()
+        r, env = self.ring, self.env
+        cur, nxt = r.cur, r.next_slot()
+        q = self.net.forward_multi([self._obs_job(params=self.params, slot=cur, batch=self.N, out=self.q_act, packed=self.params_pk)])[0]
+        if self._guide_flags is None:
+            self._guide_flags = torch.zeros((2, self.N), dtype=torch.uint8, device=self.device)
+        flags = self._guide_flags
+        env.guided_select(evaluator, self.vector_steps, q=q, eps=eps, guide_share=guide_share, masked_greedy=masked_greedy, out=r.action[cur],
+                          out_guided=flags[0], out_inexact=flags[1])
+        self.guide_counts += flags.sum(dim=1)
+        if r.compact:
+            env.arm_patch_output(r.store[nxt])
+        env._launch(self.L.dq_env_step, env._h, ptr(r.action[cur]), 1, None if r.compact else ptr(r.store[nxt]), ptr(r.reward[cur]), ptr(r.terminal[cur]),
+                    ptr(env.legal), ptr(env.lifetime), ptr(env.was_reset), self._stream())
         self._stats_pending = (cur,) if record_stats else None
         if record_stats and not self.defer_stats:
             self._flush_stats()

@@ -305,7 +305,7 @@ void dq_set_error(const char* fmt, ...) {
 
 extern "C" {
 
-int dq_version(void) { return 7; }
+int dq_version(void) { return 8; }
 const char* dq_last_error(void) { return g_err; }
 long dq_struct_size(int id) {
     switch (id) {
@@ -873,12 +873,12 @@ dq_status env_referee_view(const dq_env* E, bool need_referee, EnvRefereeView* v
     return DQ_OK;
 }
 
-// ---- the lattices' records, for csrc/env_match.hip (the matching policy reads the current volume and completed_actions where they are) -----------
+// ---- the lattices' records, for csrc/env_match.hip and csrc/env_guide.hip (the matching policy reads the current volume and completed_actions where they are) -----------
 dq_status env_state_view(const dq_env* E, EnvStateView* v) {
     DQ_REQUIRE(E && v, DQ_ERR_INVALID, "env_state_view: null argument");
     memset(v, 0, sizeof(*v));
     v->state = E->d_state; v->sw = E->sw; v->n_envs = E->cfg.n_envs; v->d = E->cfg.d; v->depth = E->cfg.volume_depth; v->model = E->cfg.error_model;
-    v->use_Y = E->cfg.use_Y; v->identity = E->info.identity_index;
+    v->use_Y = E->cfg.use_Y; v->identity = E->info.identity_index; v->n_actions = E->info.num_actions; v->env_id_base = E->cfg.env_id_base;
     return DQ_OK;
 }
 

@@ -791,9 +791,11 @@ struct EnvRefereeView {
 dq_status env_referee_view(const dq_env* E, bool need_referee, EnvRefereeView* v);
 dq_status env_referee_mlp_classes(dq_env* E, const u64* records_dev, int sw, int n, const int32_t* action_dev, u8* dec_dev, hipStream_t st);
 
-// env.hip, for env_match.hip: the lattices' internal records where they are (STATE_FIXED words, then the current volume's syndrome words; `sw` words apart).
+// env.hip, for env_match.hip / env_guide.hip: the lattices' internal records where they are (STATE_FIXED words, then the current volume's syndrome words; `sw`
+// words apart), and what a selection kernel needs beside them (the action count, the first lattice's global id of the policy's Philox counter).
 struct EnvStateView {
     const u64* state;
-    int sw, n_envs, d, depth, model, use_Y, identity;
+    int sw, n_envs, d, depth, model, use_Y, identity, n_actions;
+    u32 env_id_base;
 };
 dq_status env_state_view(const dq_env* E, EnvStateView* v);

@@ -10,10 +10,8 @@
 // The environment keeps a volume until the identity and clears completed_actions with the new volume, so calling this in front of every step applies
 // F one flip per step in ascending index order and then asks for the next volume; nothing is remembered between calls and nothing is written but the
 // action (and the flag).  A lattice whose done flag is set gets the identity.  Like match_st_kernel: no scratch pool, no lock, no loop whose exit
-// depends on another wave.
-#include "match_st_dev.h"
-#include "env_dev.h"
-#include "decode_eval.h"
+// depends on another wave.  The wave's work is env_match_dev.h env_match_wave, shared with env_guide.hip.
+#include "env_match_dev.h"
 
 namespace {
 
@@ -24,47 +22,23 @@ __global__ __launch_bounds__(64) void env_match_kernel(MatchStComp c0, MatchStCo
     const int i = blockIdx.x, lane = threadIdx.x;
     if (i >= n_envs) return;
     const u64 word = lane < sw ? state[(size_t)i * sw + lane] : 0;             // the whole record in one load (sw = 16 or 32 words)
-    const u64 done0 = wave_bcast64(word, 4), done1 = wave_bcast64(word, 5);     // completed_actions
-    if ((wave_bcast64(word, 8) >> 32) & 1) {                                   // done: the step resets this lattice, whatever the action (wave-uniform)
-        if (lane == 0) { action[i] = identity; if (inexact) inexact[i] = 0; }
-        return;
-    }
-    volatile u32* s_dw = reinterpret_cast<volatile u32*>(smem + MST_O_DW);
-    // lanes 0 .. n - 1 pick component 0's nodes out of the round's syndrome word, lanes 32 .. 32 + n - 1 component 1's: a ballot is the round's two words
-    const int my_bit = stab[lane];
-    u64 prev = 0;
-    for (int t = 0; t < depth; ++t) {
-        const u64 sword = wave_bcast64(word, STATE_FIXED + t);
-        const u64 cur = __ballot(my_bit < 64 && ((sword >> (my_bit & 63)) & 1));
-        const u64 D = cur ^ prev;
-        prev = cur;
-        if (lane == 0) { s_dw[t] = (u32)D; s_dw[MST_MAX_DEPTH + t] = (u32)(D >> 32); }
-    }
-    match_wave_sync();
-    int flag = 0, w[2], nd[2];
-    u64 m[2];
-    mst_component(c0, depth, s_dw, smem, lane, w[0], m[0], nd[0], &flag);
-    mst_component(c1, depth, s_dw + MST_MAX_DEPTH, smem, lane, w[1], m[1], nd[1], &flag);
-    // the frame as action indices (decode.hip's layer-to-Pauli map: X model 1; use_Y: layer + 1; else layer 0 -> X, layer 1 -> Z)
-    const u64 qubits = d2 < 64 ? (1ull << d2) - 1 : ~0ull;
-    const u64 fx = m[0] & qubits, fz = model == DQ_MODEL_X ? 0ull : m[1] & qubits;      // (X model: no action layer for component 1)
-    u64 want0 = 0, want1 = 0;
-    if (model == DQ_MODEL_X) {
-        want0 = fx;
-    } else if (use_Y) {
-        or_shl128(want0, want1, fx & ~fz, 0);
-        or_shl128(want0, want1, fx & fz, d2);
-        or_shl128(want0, want1, fz & ~fx, 2 * d2);
-    } else {
-        or_shl128(want0, want1, fx, 0);
-        or_shl128(want0, want1, fz, d2);
-    }
-    want0 &= ~done0; want1 &= ~done1;
-    const int a = want0 ? __builtin_ctzll(want0) : (want1 ? 64 + __builtin_ctzll(want1) : identity);
+    int flag;
+    const int a = env_match_wave(c0, c1, stab, word, d2, depth, model, use_Y, identity, smem, lane, flag);      // env_match_dev.h
     if (lane == 0) { action[i] = a; if (inexact) inexact[i] = (u8)flag; }
 }
 
 }  // namespace
+
+dq_status env_match_prepare(const dq_env* env, dq_decode_eval* V, EnvStateView* S, const char* who) {
+    dq_status rc = env_state_view(env, S);
+    if (rc != DQ_OK) return rc;
+    DQ_REQUIRE(S->d == V->d && S->model == V->model && (S->model == DQ_MODEL_X || (S->use_Y != 0) == (V->use_Y != 0)) && S->depth == V->depth, DQ_ERR_INVALID,
+               "%s: the environment's lattice (d = %d, model %d, use_Y = %d, volume_depth = %d) is not the evaluator's (d = %d, model %d, "
+               "use_Y = %d, volume_depth = %d)", who, S->d, S->model, S->use_Y, S->depth, V->d, V->model, V->use_Y, V->depth);
+    DQ_REQUIRE(V->d <= 7 && V->depth >= 1 && V->depth <= MST_MAX_DEPTH && STATE_FIXED + V->depth <= S->sw && S->sw <= 64, DQ_ERR_UNSUPPORTED,
+               "%s: d = %d, volume_depth = %d: matching covers d <= 7, depth <= %d", who, V->d, V->depth, MST_MAX_DEPTH);
+    return match_st_tables(V);
+}
 
 extern "C" {
 
@@ -72,14 +46,7 @@ dq_status dq_env_match_select(dq_env* env, dq_decode_eval* V, int32_t* action_de
     DQ_REQUIRE(env && V && action_dev, DQ_ERR_INVALID, "dq_env_match_select: null argument");
     DQ_REQUIRE((reinterpret_cast<uintptr_t>(action_dev) & 3) == 0, DQ_ERR_INVALID, "dq_env_match_select: action_dev must be 4-byte aligned");
     EnvStateView S;
-    dq_status rc = env_state_view(env, &S);
-    if (rc != DQ_OK) return rc;
-    DQ_REQUIRE(S.d == V->d && S.model == V->model && (S.model == DQ_MODEL_X || (S.use_Y != 0) == (V->use_Y != 0)) && S.depth == V->depth, DQ_ERR_INVALID,
-               "dq_env_match_select: the environment's lattice (d = %d, model %d, use_Y = %d, volume_depth = %d) is not the evaluator's (d = %d, model %d, "
-               "use_Y = %d, volume_depth = %d)", S.d, S.model, S.use_Y, S.depth, V->d, V->model, V->use_Y, V->depth);
-    DQ_REQUIRE(V->d <= 7 && V->depth >= 1 && V->depth <= MST_MAX_DEPTH && STATE_FIXED + V->depth <= S.sw && S.sw <= 64, DQ_ERR_UNSUPPORTED,
-               "dq_env_match_select: d = %d, volume_depth = %d: matching covers d <= 7, depth <= %d", V->d, V->depth, MST_MAX_DEPTH);
-    rc = match_st_tables(V);
+    const dq_status rc = env_match_prepare(env, V, &S, "dq_env_match_select");
     if (rc != DQ_OK) return rc;
     static unsigned long long attr_devs = 0;                          // per device (common.h dq_device_bit)
     const unsigned long long dev_bit = dq_device_bit();

@@ -578,6 +578,55 @@ def completed_from_words(w0, w1):
     return {i for i in range(128) if (m >> i) & 1}
 
 
+def rate_threshold(p):
+    """T of csrc/common.h dq_rate_threshold: W / 2^32 < p  <=>  W < T for every 32-bit W, T = ceil(p 2^32) clamped to [0, 2^32]."""
+    return max(0, min(math.ceil(float(p) * 4294967296.0), 1 << 32))
+
+
+def guided_actions(q, legal, teacher_actions, eps, guide_share, masked_greedy, seed, env_id_base, t):
+    """The rule of dq_env_guided_select in numpy.  q: float32 [n, num_actions] or None (every lattice explores); legal: the
+    lattices' legal sets as two 64-bit words each [n, 2] (VectorEnv.legal; bit a = action a); teacher_actions: int [n], what match_select emits for the
+    lattices as they stand; seed: the policy's key (the environment's seed); lattice i has global id env_id_base + i; t: the policy counter.  With
+    w[0..3] = Philox4x32-10(counter (t_lo, t_hi, id, STREAM_POLICY << 16), key seed) -- the words select_actions draws -- and T = rate_threshold:
+        explore = q is None or w[1] < T(eps);    guided = explore and w[2] < T(guide_share)
+        guided: the teacher's action;  else explore: the k-th (0-based, ascending) legal action, k = (w[0] * n_legal) >> 32 (-1 for an empty set);
+        else: the first maximum of the Q row, over the legal set when masked_greedy.
+    Returns (actions int32 [n], guided_flags uint8 [n])."""
+    from . import _lib, _philox
+    for name, v in (("eps", eps), ("guide_share", guide_share)):
+        if not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"guided_actions: {name} must lie in [0, 1], not {v!r}")
+    words = np.ascontiguousarray(np.asarray(legal)).astype(np.int64, copy=False).view(np.uint64).reshape(-1, 2)
+    n = len(words)
+    teacher = np.asarray(teacher_actions).reshape(-1)
+    if len(teacher) != n:
+        raise ValueError(f"guided_actions: {len(teacher)} teacher actions for {n} legal sets")
+    t = int(t)
+    ids = (int(env_id_base) + np.arange(n, dtype=np.uint64)) & np.uint64(0xFFFFFFFF)
+    w0, w1, w2, _ = _philox.philox4x32(t & 0xFFFFFFFF, t >> 32, ids, _lib.STREAM_POLICY << 16, seed)
+    explore = np.ones(n, dtype=bool) if q is None else w1.astype(np.uint64) < np.uint64(rate_threshold(eps))
+    guided = explore & (w2.astype(np.uint64) < np.uint64(rate_threshold(guide_share)))
+    if q is not None:
+        q = np.asarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[0] != n or not 1 <= q.shape[1] <= 128:
+            raise ValueError(f"guided_actions: q must have shape [{n}, num_actions <= 128], got {q.shape}")
+    actions = np.empty(n, dtype=np.int32)
+    for i in range(n):
+        if guided[i]:
+            actions[i] = teacher[i]
+            continue
+        mask = int(words[i, 0]) | int(words[i, 1]) << 64
+        if explore[i]:
+            members = [a for a in range(128) if (mask >> a) & 1]
+            k = (int(w0[i]) * len(members)) >> 32
+            actions[i] = members[k] if members else -1
+        else:
+            row = q[i]
+            cand = [a for a in range(len(row)) if not masked_greedy or (mask >> a) & 1]
+            actions[i] = max(cand, key=lambda a: (row[a], -a))                  # the larger value, the lower index among equals
+    return actions, guided.astype(np.uint8)
+
+
 def check_match_policy_args(env, evaluator=None, chunk=DEFAULT_CHUNK):
     """Validates the lattice of a matching-policy evaluation without touching the library: the narrow environment, d <= 7, volume_depth <= 16 (else
     NotImplementedError), an evaluator of the same lattice (else ValueError).  Returns (d, error_model, use_Y, volume_depth)."""
@@ -618,6 +667,16 @@ class MatchingAgent:
             raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
         self.evaluator, self.chunk, self.policy = evaluator, int(chunk), policy
         self.last_inexact_steps, self.last_inexact_by_rate, self.last_vector_steps = 0, {}, 0
+
+    def evaluator_for(self, env):
+        """(an Evaluator of env's lattice, whether it was opened here and is the caller's to close): the agent's own where it was given one.  Validates
+        like test(): the narrow environment, d <= 7, volume_depth <= 16 (NotImplementedError), an evaluator of the same lattice (ValueError), before any
+        library call.  For a caller that plays the matching itself over many steps (DQNAgent.fit with this agent as the policy's guide)."""
+        d, model, use_Y, depth = check_match_policy_args(env, self.evaluator, self.chunk)
+        if self.evaluator is not None:
+            return self.evaluator, False
+        venv = _narrow_env(env)
+        return Evaluator(d, model, use_Y, depth, chunk=min(self.chunk, int(venv.n_envs)), device=venv.device), True
 
     def test(self, env, nb_episodes=1, verbose=1, interval=100, nb_max_episode_steps=None):
         """DQNAgent.test for this policy: the same keys, ceil-share quota and record order (vector step, then lattice).  Returns History."""

@@ -481,21 +481,52 @@ class VectorEnv:
         index of the matching's Pauli frame for the lattice's current volume that is not in completed_actions, else the identity.  evaluator: a
         decoder.Evaluator of this lattice (it owns the matching tables).  out: int32 [n_envs]; out_inexact: uint8 [n_envs] or None (the
         fallback flag of each volume is then not written).  Returns the actions; step(actions, auto_reset=True) is the agent step."""
+        self._check_matching(evaluator, "match_select")
+        if out is None:
+            out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        self._check_outputs("match_select", (out, torch.int32), (out_inexact, torch.uint8))
+        check(self.L.dq_env_match_select(self._h, evaluator._h, ptr(out), ptr(out_inexact), self._stream()))
+        return out
+
+    def _check_matching(self, evaluator, who):
+        """What match_select and guided_select require of the lattice and the evaluator, before any library call."""
         if self.wide or self.d > 7:
-            raise NotImplementedError("match_select covers the narrow environment, d <= 7 (the wide environment / d >= 9 is not supported)")
+            raise NotImplementedError(f"{who} covers the narrow environment, d <= 7 (the wide environment / d >= 9 is not supported)")
         if self.volume_depth > 16:
-            raise NotImplementedError("match_select covers volume_depth <= 16")
+            raise NotImplementedError(f"{who} covers volume_depth <= 16")
         mine = (self.d, self.error_model, self.volume_depth)
         theirs = (evaluator.d, evaluator.error_model, evaluator.volume_depth)
         if mine != theirs or (self.error_model != "X" and bool(self.use_Y) != bool(evaluator.use_Y)):
             raise ValueError(f"the evaluator's lattice (d, error model, volume_depth) = {theirs}, use_Y = {evaluator.use_Y} is not the environment's "
                              f"{mine}, use_Y = {self.use_Y}")
+
+    def _check_outputs(self, who, *pairs):
+        for t, dt in pairs:
+            if t is not None and not (t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (self.n_envs,)):
+                raise ValueError(f"{who}: outputs are contiguous device tensors of n_envs = {self.n_envs} entries (int32 actions, uint8 flags)")
+
+    def guided_select(self, evaluator, t, q=None, eps=1.0, guide_share=1.0, masked_greedy=False, out=None, out_guided=None, out_inexact=None):
+        """Epsilon-greedy selection whose exploring lattices follow the matching decoder with probability guide_share (include/deepq_hip.h
+        dq_env_guided_select; the rule in numpy: decoder.guided_actions).  With select_actions' Philox words w of policy counter t:
+        explore = q is None or w[1] < T(eps); guided = explore and w[2] < T(guide_share); a guided lattice gets match_select's action, another exploring
+        one the k-th legal action, the rest the first maximum of their row of q (float32 [n_envs, num_actions]; over the legal set when masked_greedy).
+        guide_share = 0: select_actions' actions bit for bit; eps = 1 with guide_share = 1: match_select's.  The matching runs for the guided lattices
+        only.  out: int32 [n_envs]; out_guided / out_inexact: uint8 [n_envs] or None (1 where the lattice followed the matching / match_select's flag
+        for it, 0 for every other lattice).  Returns the actions; step(actions, auto_reset=True) is the agent step."""
+        self._check_matching(evaluator, "guided_select")
+        for name, v in (("eps", eps), ("guide_share", guide_share)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+                raise ValueError(f"guided_select: {name} must be a number in [0, 1], not {v!r}")
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) or t < 0:
+            raise ValueError(f"guided_select: the policy counter t must be a non-negative integer, not {t!r}")
+        if q is not None and not (q.dtype == torch.float32 and q.is_cuda and q.is_contiguous() and tuple(q.shape) == (self.n_envs, self.num_actions)):
+            raise ValueError(f"guided_select: q is a contiguous float32 device tensor [{self.n_envs}, {self.num_actions}] or None")
         if out is None:
             out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
-        for t, dt in ((out, torch.int32), (out_inexact, torch.uint8)):
-            if t is not None and not (t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (self.n_envs,)):
-                raise ValueError(f"match_select: outputs are contiguous device tensors of n_envs = {self.n_envs} entries (int32 actions, uint8 flags)")
-        check(self.L.dq_env_match_select(self._h, evaluator._h, ptr(out), ptr(out_inexact), self._stream()))
+        self._check_outputs("guided_select", (out, torch.int32), (out_guided, torch.uint8), (out_inexact, torch.uint8))
+        seed = (ctypes.c_uint32 * 2)(*self.seed)
+        check(self.L.dq_env_guided_select(self._h, evaluator._h, ptr(q), float(eps), float(guide_share), int(masked_greedy), seed, int(t), ptr(out),
+                                          ptr(out_guided), ptr(out_inexact), self._stream()))
         return out
 
     # -- state views --------------------------------------------------------------------------------------

@@ -776,6 +776,22 @@ dq_status dq_decode_match(dq_decode_eval* ev, const uint8_t* volumes_dev, int n,
  * been created for the environment's d, error model, use_Y (X model: ignored) and volume_depth (DQ_ERR_INVALID otherwise); its matching tables are
  * built at the first call of this or of dq_decode_match (the same thread rule).  One wavefront per lattice; action_dev int32 [n_envs]. */
 dq_status dq_env_match_select(dq_env* env, dq_decode_eval* ev, int32_t* action_dev, uint8_t* inexact_dev, void* stream);
+/* dq_env_guided_select: epsilon-greedy selection whose exploring lattices follow the matching decoder with probability guide_share (csrc/env_guide.hip;
+ * DESIGN.md section 15; dq_version() >= 8).  For lattice i, with w[0..3] the Philox words dq_policy_select draws for (seed, t, the environment's
+ * env_id_base + i, DQ_STREAM_POLICY) and T the threshold both rates go through (W / 2^32 < p  <=>  W < ceil(p 2^32)):
+ *   explore = q_dev == NULL || w[1] < T(eps);      guided = explore && w[2] < T(guide_share)
+ *   guided:        action_dev[i] = what dq_env_match_select writes for the lattice as it stands (the identity for a lattice whose done flag is set; the legal
+ *                  set is not consulted)
+ *   else explore:  the k-th legal action, k = (w[0] * n_legal) >> 32                                     (dq_policy_select's rule)
+ *   else:          the first maximum of row i of q_dev float [n_envs][num_actions], over the legal set when masked_greedy  (dq_policy_select's rule)
+ * The legal set is the one the lattice's record holds (what the last dq_env_reset / dq_env_step also wrote to its legal_dev).  guide_share = 0: the actions
+ * of dq_policy_select bit for bit; eps = 1 (or q_dev NULL) with guide_share = 1: those of dq_env_match_select.  guided_dev (nullable) uint8 [n_envs]: 1
+ * where the lattice followed the matching; inexact_dev (nullable) uint8 [n_envs]: dq_env_match_select's flag for a guided lattice, 0 for every other.  The
+ * matching runs only in the wavefronts of guided lattices.  eps and guide_share must lie in [0, 1] (DQ_ERR_INVALID); ev as for dq_env_match_select (same
+ * checks, tables and thread rule); the narrow environment, d <= 7, volume_depth <= 16.  Nothing is kept between calls and the environment is not
+ * modified: an agent step is this launch followed by dq_env_step(action_dev, auto_reset = 1).  No reference counterpart. */
+dq_status dq_env_guided_select(dq_env* env, dq_decode_eval* ev, const float* q_dev, double eps, double guide_share, int masked_greedy, const uint32_t seed[2],
+                               uint64_t t, int32_t* action_dev, uint8_t* guided_dev, uint8_t* inexact_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Live kernel timing (measurement only; no reference counterpart).  dq_prof_arm(id, n) times up to n
