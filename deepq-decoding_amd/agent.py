@@ -466,12 +466,14 @@ class DQNAgent:
         scalar, or one per rate) in one batched evaluation; returns {rate: EvalResult}, rate k's volumes being lattices env_id_base + k n_volumes
         + i: the result of its own call with that env_id_base.  no_decoder: EvalResult.no_decoder counts the verdict for frame = 0.
         baseline="matching": returns (the result above, decoder.score_matching's result for the same volumes) -- the space-time minimum-weight
-        matching decoder of DESIGN.md section 13 beside the agent."""
+        matching decoder of DESIGN.md section 13 beside the agent.  baseline="union_find": the same pair with the union-find decoder of section 16;
+        baseline=("matching", "union_find"): (agent, matching, union-find), all scored on the same volumes."""
         from . import decoder as D
         if env is None:
             raise ValueError("decode_benchmark() needs the environment: it supplies the lattice and the referee")
-        if baseline not in (None, "matching"):
-            raise ValueError(f"decode_benchmark: baseline must be None or 'matching', not {baseline!r}")
+        methods = () if baseline is None else ((baseline,) if isinstance(baseline, str) else baseline)
+        if not isinstance(methods, (tuple, list)) or (baseline is not None and not methods) or any(not isinstance(m, str) or m not in D.METHODS for m in methods):
+            raise ValueError(f"decode_benchmark: baseline must be None, one of {D.METHODS} or a tuple of them, not {baseline!r}")
         d, model, use_Y, depth = D.check_eval_lattice(None, env)
         D.check_decode_args(d, model, use_Y, depth, (depth, d + 1, d + 1), "environment", max_actions, obs_form)
         layers = D.action_layers(model, use_Y)
@@ -493,9 +495,9 @@ class DQNAgent:
         if baseline is None:
             return out
         # (p_meas without rates was refused above; the decoder's own scoring handle serves the baseline, so its matching tables are built once)
-        match = D.score_matching(env, n_volumes, rates=rates, p_meas=p_meas if rates is not None else None, seed=seed, env_id_base=env_id_base,
-                                 evaluator=dec._eval)
-        return out, match
+        rows = [D.score_matching(env, n_volumes, rates=rates, p_meas=p_meas if rates is not None else None, seed=seed, env_id_base=env_id_base,
+                                 evaluator=dec._eval, method=m) for m in methods]
+        return (out,) + tuple(rows)
 
     def compute_q_values(self, observation):
         obs = torch.as_tensor(np.asarray(observation), dtype=torch.uint8, device=self._core.device).reshape((1,) + tuple(self.model.input_shape)).contiguous()
@@ -548,6 +550,7 @@ class DQNAgent:
             if core.world_size > 1:
                 raise NotImplementedError("fit() with a guide runs on one GPU: several ranks are not supported")
             guide_ev, guide_opened = guide.evaluator_for(venv)
+            guide_method = getattr(guide, "method", "matching")
             core.guide_counts.zero_()
         self.last_guided_steps = self.last_inexact_steps = 0
         self.training = True
@@ -585,7 +588,7 @@ class DQNAgent:
                 loop_iter += 1
                 eps, masked = self.policy.current(True)
                 if guide is not None:
-                    core.guided_act_and_step(guide_ev, eps, guide_share, masked_greedy=masked)
+                    core.guided_act_and_step(guide_ev, eps, guide_share, masked_greedy=masked, method=guide_method)
                     self.step += N
                     trained = self._maybe_train()
                 elif self._will_train(self.step + N):
@@ -620,7 +623,7 @@ class DQNAgent:
                     # lattice is still alive must not step it; the update is collective (gradient all-reduce), so every rank trains.
                     if core.local_stats[0] > 0:
                         if guide is not None:
-                            core.guided_act_and_step(guide_ev, eps, guide_share, masked_greedy=masked, record_stats=False)
+                            core.guided_act_and_step(guide_ev, eps, guide_share, masked_greedy=masked, record_stats=False, method=guide_method)
                         else:
                             core.act_and_step(eps, masked_greedy=masked, record_stats=False)
                     self._maybe_train()

@@ -213,12 +213,12 @@ class DQNCore:
         r.advance()
         self.vector_steps += 1
 
-    def guided_act_and_step(self, evaluator, eps, guide_share, masked_greedy=False, record_stats=True):
+    def guided_act_and_step(self, evaluator, eps, guide_share, masked_greedy=False, record_stats=True, method="matching"):
         """act_and_step() with a teacher: Q forward on the current observations, VectorEnv.guided_select -- an exploring lattice
         follows the matching decoder with probability guide_share -- into the ring's action slot, then dq_env_step with auto-reset writing the ring's
         reward / done slots and the successor observation; the episode bookkeeping is act_and_step's.  The lattice-steps that followed the teacher and
         those whose matching took its fallback are added to self.guide_counts on the device.  evaluator: a decoder.Evaluator of the environment's
-        lattice.  One GPU, the narrow environment."""
+        lattice.  method: the teacher, "matching" or "union_find" (VectorEnv.guided_select's).  One GPU, the narrow environment."""
         if self._wide or self.world_size > 1:
             raise NotImplementedError("guided_act_and_step: one GPU and the narrow environment (d <= 7)")
         self._flush_stats()
@@ -229,7 +229,7 @@ class DQNCore:
             self._guide_flags = torch.zeros((2, self.N), dtype=torch.uint8, device=self.device)
         flags = self._guide_flags
         env.guided_select(evaluator, self.vector_steps, q=q, eps=eps, guide_share=guide_share, masked_greedy=masked_greedy, out=r.action[cur],
-                          out_guided=flags[0], out_inexact=flags[1])
+                          out_guided=flags[0], out_inexact=flags[1], method=method)
         self.guide_counts += flags.sum(dim=1)
         if r.compact:
             env.arm_patch_output(r.store[nxt])

@@ -16,12 +16,13 @@
 
 namespace {
 
-__global__ __launch_bounds__(64) void env_guided_select_kernel(MatchStComp c0, MatchStComp c1, const u8* __restrict__ stab, const u64* __restrict__ state, int sw,
-                                                               int n_envs, int d2, int depth, int model, int use_Y, int identity, int n_actions,
-                                                               const float* __restrict__ q, u64 T_eps, u64 T_share, int masked_greedy, u32 seed0, u32 seed1,
-                                                               u32 env_id_base, u64 t, int32_t* __restrict__ action, u8* __restrict__ guided,
-                                                               u8* __restrict__ inexact) {
-    extern __shared__ __attribute__((aligned(16))) u8 smem[];
+// One lattice by one wave, for either teacher (Solver: env_match_dev.h); smem: the solver's LDS bytes, touched by a guided wave only.
+template <class Solver>
+static __device__ __forceinline__ void env_guided_select_wave(const typename Solver::Comp& c0, const typename Solver::Comp& c1, const u8* __restrict__ stab,
+                                                              const u64* __restrict__ state, int sw, int n_envs, int d2, int depth, int model, int use_Y, int identity,
+                                                              int n_actions, const float* __restrict__ q, u64 T_eps, u64 T_share, int masked_greedy, u32 seed0,
+                                                              u32 seed1, u32 env_id_base, u64 t, int32_t* __restrict__ action, u8* __restrict__ guided,
+                                                              u8* __restrict__ inexact, u8* smem) {
     const int i = blockIdx.x, lane = threadIdx.x;
     if (i >= n_envs) return;
     const u64 word = lane < sw ? state[(size_t)i * sw + lane] : 0;             // the whole record in one load (sw = 16 or 32 words)
@@ -33,7 +34,7 @@ __global__ __launch_bounds__(64) void env_guided_select_kernel(MatchStComp c0, M
     const bool follow = explore && (u64)w2 < T_share;
     int a, flag = 0;
     if (follow) {
-        a = env_match_wave(c0, c1, stab, word, d2, depth, model, use_Y, identity, smem, lane, flag);
+        a = env_match_wave<Solver>(c0, c1, stab, word, d2, depth, model, use_Y, identity, smem, lane, flag);
     } else {
         const u64 lo = wave_bcast64(word, 6), hi = wave_bcast64(word, 7);       // legal_actions
         if (explore) {
@@ -59,6 +60,27 @@ __global__ __launch_bounds__(64) void env_guided_select_kernel(MatchStComp c0, M
         if (guided) guided[i] = follow ? 1 : 0;
         if (inexact) inexact[i] = (u8)flag;
     }
+}
+
+__global__ __launch_bounds__(64) void env_guided_select_kernel(MatchStComp c0, MatchStComp c1, const u8* __restrict__ stab, const u64* __restrict__ state, int sw,
+                                                               int n_envs, int d2, int depth, int model, int use_Y, int identity, int n_actions,
+                                                               const float* __restrict__ q, u64 T_eps, u64 T_share, int masked_greedy, u32 seed0, u32 seed1,
+                                                               u32 env_id_base, u64 t, int32_t* __restrict__ action, u8* __restrict__ guided,
+                                                               u8* __restrict__ inexact) {
+    extern __shared__ __attribute__((aligned(16))) u8 smem[];
+    env_guided_select_wave<EnvSolveMatching>(c0, c1, stab, state, sw, n_envs, d2, depth, model, use_Y, identity, n_actions, q, T_eps, T_share, masked_greedy, seed0,
+                                             seed1, env_id_base, t, action, guided, inexact, smem);
+}
+
+// The union-find teacher (dq_env_guided_select_uf): UF_LDS bytes per wave; the flag it writes is 0.
+__global__ __launch_bounds__(64) void env_guided_select_uf_kernel(UfComp c0, UfComp c1, const u8* __restrict__ stab, const u64* __restrict__ state, int sw, int n_envs,
+                                                                  int d2, int depth, int model, int use_Y, int identity, int n_actions,
+                                                                  const float* __restrict__ q, u64 T_eps, u64 T_share, int masked_greedy, u32 seed0, u32 seed1,
+                                                                  u32 env_id_base, u64 t, int32_t* __restrict__ action, u8* __restrict__ guided,
+                                                                  u8* __restrict__ inexact) {
+    __shared__ __attribute__((aligned(16))) u8 smem[UF_LDS];
+    env_guided_select_wave<EnvSolveUnionFind>(c0, c1, stab, state, sw, n_envs, d2, depth, model, use_Y, identity, n_actions, q, T_eps, T_share, masked_greedy, seed0,
+                                              seed1, env_id_base, t, action, guided, inexact, smem);
 }
 
 }  // namespace
@@ -87,6 +109,26 @@ dq_status dq_env_guided_select(dq_env* env, dq_decode_eval* V, const float* q_de
     env_guided_select_kernel<<<S.n_envs, 64, MST_LDS, (hipStream_t)stream>>>(
         T->comp[0], T->comp[1], T->stab, S.state, S.sw, S.n_envs, S.d * S.d, S.depth, S.model, S.use_Y, S.identity, S.n_actions, q_dev, T_eps, T_share,
         masked_greedy, seed[0], seed[1], S.env_id_base, t, action_dev, guided_dev, inexact_dev);
+    DQ_LAUNCH_CHECK();
+    return DQ_OK;
+}
+
+dq_status dq_env_guided_select_uf(dq_env* env, dq_decode_eval* V, const float* q_dev, double eps, double guide_share, int masked_greedy, const uint32_t seed[2],
+                                  uint64_t t, int32_t* action_dev, uint8_t* guided_dev, uint8_t* inexact_dev, void* stream) {
+    DQ_REQUIRE(env && V && seed && action_dev, DQ_ERR_INVALID, "dq_env_guided_select_uf: null argument");
+    DQ_REQUIRE((reinterpret_cast<uintptr_t>(action_dev) & 3) == 0 && (reinterpret_cast<uintptr_t>(q_dev) & 3) == 0, DQ_ERR_INVALID,
+               "dq_env_guided_select_uf: action_dev and q_dev must be 4-byte aligned");
+    DQ_REQUIRE(eps >= 0.0 && eps <= 1.0, DQ_ERR_INVALID, "dq_env_guided_select_uf: eps must be in [0,1]");
+    DQ_REQUIRE(guide_share >= 0.0 && guide_share <= 1.0, DQ_ERR_INVALID, "dq_env_guided_select_uf: guide_share must be in [0,1]");
+    EnvStateView S;
+    const dq_status rc = env_match_prepare(env, V, &S, "dq_env_guided_select_uf");
+    if (rc != DQ_OK) return rc;
+    DQ_REQUIRE(S.n_actions >= 1 && S.n_actions <= 128, DQ_ERR_UNSUPPORTED, "dq_env_guided_select_uf: %d actions do not fit the two-word legal set", S.n_actions);
+    const u64 T_eps = dq_rate_threshold(eps), T_share = dq_rate_threshold(guide_share);
+    const MatchStTables* T = V->match_st;
+    env_guided_select_uf_kernel<<<S.n_envs, 64, 0, (hipStream_t)stream>>>(
+        T->uf[0], T->uf[1], T->stab, S.state, S.sw, S.n_envs, S.d * S.d, S.depth, S.model, S.use_Y, S.identity, S.n_actions, q_dev, T_eps, T_share, masked_greedy,
+        seed[0], seed[1], S.env_id_base, t, action_dev, guided_dev, inexact_dev);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
 }

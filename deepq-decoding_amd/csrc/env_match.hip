@@ -23,8 +23,20 @@ __global__ __launch_bounds__(64) void env_match_kernel(MatchStComp c0, MatchStCo
     if (i >= n_envs) return;
     const u64 word = lane < sw ? state[(size_t)i * sw + lane] : 0;             // the whole record in one load (sw = 16 or 32 words)
     int flag;
-    const int a = env_match_wave(c0, c1, stab, word, d2, depth, model, use_Y, identity, smem, lane, flag);      // env_match_dev.h
+    const int a = env_match_wave<EnvSolveMatching>(c0, c1, stab, word, d2, depth, model, use_Y, identity, smem, lane, flag);      // env_match_dev.h
     if (lane == 0) { action[i] = a; if (inexact) inexact[i] = (u8)flag; }
+}
+
+// The union-find instantiation (dq_env_uf_select): the same rule around uf_dev.h's uf_component, UF_LDS bytes per wave, no flag.
+__global__ __launch_bounds__(64) void env_match_uf_kernel(UfComp c0, UfComp c1, const u8* __restrict__ stab, const u64* __restrict__ state, int sw, int n_envs, int d2,
+                                                          int depth, int model, int use_Y, int identity, int32_t* __restrict__ action) {
+    __shared__ __attribute__((aligned(16))) u8 smem[UF_LDS];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n_envs) return;
+    const u64 word = lane < sw ? state[(size_t)i * sw + lane] : 0;
+    int flag;
+    const int a = env_match_wave<EnvSolveUnionFind>(c0, c1, stab, word, d2, depth, model, use_Y, identity, smem, lane, flag);
+    if (lane == 0) action[i] = a;
 }
 
 }  // namespace
@@ -57,6 +69,19 @@ dq_status dq_env_match_select(dq_env* env, dq_decode_eval* V, int32_t* action_de
     const MatchStTables* T = V->match_st;
     env_match_kernel<<<S.n_envs, 64, MST_LDS, (hipStream_t)stream>>>(T->comp[0], T->comp[1], T->stab, S.state, S.sw, S.n_envs, S.d * S.d, S.depth, S.model, S.use_Y,
                                                                     S.identity, action_dev, inexact_dev);
+    DQ_LAUNCH_CHECK();
+    return DQ_OK;
+}
+
+dq_status dq_env_uf_select(dq_env* env, dq_decode_eval* V, int32_t* action_dev, void* stream) {
+    DQ_REQUIRE(env && V && action_dev, DQ_ERR_INVALID, "dq_env_uf_select: null argument");
+    DQ_REQUIRE((reinterpret_cast<uintptr_t>(action_dev) & 3) == 0, DQ_ERR_INVALID, "dq_env_uf_select: action_dev must be 4-byte aligned");
+    EnvStateView S;
+    const dq_status rc = env_match_prepare(env, V, &S, "dq_env_uf_select");
+    if (rc != DQ_OK) return rc;
+    const MatchStTables* T = V->match_st;
+    env_match_uf_kernel<<<S.n_envs, 64, 0, (hipStream_t)stream>>>(T->uf[0], T->uf[1], T->stab, S.state, S.sw, S.n_envs, S.d * S.d, S.depth, S.model, S.use_Y, S.identity,
+                                                                 action_dev);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
 }

@@ -59,12 +59,12 @@ void match_st_free(MatchStTables* t) {
     delete t;
 }
 
-// The handle's tables: built on the host and uploaded in one piece at the first dq_decode_match / dq_env_match_select of the handle.
+// The handle's tables: built on the host and uploaded in one piece at the first dq_decode_match / dq_decode_uf / dq_env_*_select of the handle.
 dq_status match_st_tables(dq_decode_eval* V) {
     if (V->match_st) return DQ_OK;
     LatticeHost L;
     lattice_build(V->d, &L);
-    std::vector<u8> dist[2], distB[2], cell(64, 255), stab(64, 255);
+    std::vector<u8> dist[2], distB[2], cell(64, 255), stab(64, 255), ends(256, 255);      // ends: [comp][eu, ev][64] (uf_dev.h UfComp)
     std::vector<u64> path[2], pathB[2];
     size_t off64[2][2], off8[2][2], bytes = 0;
     for (int c = 0; c < 2; ++c) {
@@ -74,6 +74,11 @@ dq_status match_st_tables(dq_decode_eval* V) {
         const int n = (int)L.typed[c].size();
         DQ_REQUIRE(n <= 32 && V->d * V->d <= 64, DQ_ERR_UNSUPPORTED, "dq_decode_match: d = %d: a component's %d nodes do not fit half a wavefront", V->d, n);
         for (int j = 0; j < n; ++j) { const int s = L.typed[c][j]; cell[32 * c + j] = (u8)(L.sa[s] * (V->d + 1) + L.sb[s]); stab[32 * c + j] = (u8)s; }
+        const int typ = c == 0 ? 3 : 1;
+        for (int q = 0; q < V->d * V->d; ++q) {                           // the qubit's plaquettes of the component, as lattice_match_tables walks them
+            int ne = 0;
+            for (int s : L.qubit_stabs[q]) if (L.stab_type[s] == typ && ne < 2) ends[128 * c + 64 * ne++ + q] = (u8)L.ref_bit[s];
+        }
         off64[c][0] = bytes; bytes += path[c].size() * sizeof(u64);
         off64[c][1] = bytes; bytes += pathB[c].size() * sizeof(u64);
     }
@@ -85,6 +90,8 @@ dq_status match_st_tables(dq_decode_eval* V) {
     bytes += cell.size();
     const size_t off_stab = bytes;
     bytes += stab.size();
+    const size_t off_ends = bytes;
+    bytes += ends.size();
     std::vector<u8> host(bytes);
     for (int c = 0; c < 2; ++c) {
         memcpy(host.data() + off64[c][0], path[c].data(), path[c].size() * sizeof(u64));
@@ -94,6 +101,7 @@ dq_status match_st_tables(dq_decode_eval* V) {
     }
     memcpy(host.data() + off_cell, cell.data(), cell.size());
     memcpy(host.data() + off_stab, stab.data(), stab.size());
+    memcpy(host.data() + off_ends, ends.data(), ends.size());
     static unsigned long long attr_devs = 0;                          // per device (common.h dq_device_bit)
     const unsigned long long dev_bit = dq_device_bit();
     if (!(attr_devs & dev_bit)) {
@@ -118,6 +126,7 @@ dq_status match_st_tables(dq_decode_eval* V) {
     }
     T->cell = T->blob + off_cell;
     T->stab = T->blob + off_stab;
+    for (int c = 0; c < 2; ++c) T->uf[c] = UfComp{T->blob + off_ends + 128 * c, T->blob + off_ends + 128 * c + 64, (int)L.typed[c].size(), V->d * V->d};
     V->match_st = T;
     return DQ_OK;
 }

@@ -4,6 +4,7 @@
 // fallback are stated at the top of match_st.hip.
 #pragma once
 #include "match_dev.h"
+#include "uf_dev.h"
 
 #define MST_O_T DQ_MATCH_LDS                    // [32] round of defect i (its node sits in match_dev.h's list bytes)
 #define MST_O_DW (MST_O_T + 32)                 // [2][16] defect words: bit u of word [comp][t] = defect (u, t)
@@ -23,6 +24,7 @@ struct MatchStTables {
     MatchStComp comp[2];
     const u8* cell;         // [64] lane 32 c + j -> grid cell a (d + 1) + b of node j of component c (255: none)
     const u8* stab;         // [64] lane 32 c + j -> bit of node j of component c in a syndrome word of the environment (measurement order; 255: none)
+    UfComp uf[2];           // uf_dev.h: the union-find decoder's endpoint tables, qubit -> (u, v or none), [2][64] bytes per component
 };
 
 static __device__ __forceinline__ u64 mst_bcast(u64 x) {

@@ -28,6 +28,14 @@ PLANES = {"environment": 0, "readme": 1}
 OBS_FORMS = {"uint8": 0, "patch": 1}
 MODELS = {"X": 0, "DP": 1, "IIDXZ": 2}
 DEFAULT_CHUNK = 65536
+METHODS = ("matching", "union_find")                             # the baseline decoders: DESIGN.md sections 13 and 16
+
+
+def check_method(method, who="method"):
+    """The baseline decoder's name, validated before any library call."""
+    if not isinstance(method, str) or method not in METHODS:
+        raise ValueError(f"{who} must be one of {METHODS}, not {method!r}")
+    return method
 
 
 def action_layers(error_model, use_Y):
@@ -341,6 +349,12 @@ class Evaluator:
         _lib.check(self.L.dq_decode_match(self._h, _lib.ptr(volumes), m, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(inexact),
                                           self._stream()))
 
+    def uf_into(self, volumes, m, frame, weight=None, n_defects=None, rounds=None):
+        """The union-find baseline (dq_decode_uf) on m <= chunk volumes already on the device."""
+        from . import _lib
+        _lib.check(self.L.dq_decode_uf(self._h, _lib.ptr(volumes), m, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
+                                       self._stream()))
+
     def verdict_into(self, venv, hidden, frame, m, out):
         from . import _lib
         _lib.check(self.L.dq_decode_verdict(self._h, venv._h, _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), self._stream()))
@@ -479,10 +493,11 @@ def verdict(hidden, frame, env, chunk=DEFAULT_CHUNK, to_host=False):
 class MatchResult:
     """Per-volume results of matching_decode, in input order: frame uint8 [N, d, d] (the matching's net correction as hidden_state codes 0..3, what
     verdict() takes), weight int32 [N, 2] (the matching's weight per Pauli component: 0 = X errors / type-3 plaquettes, 1 = Z errors / type-1),
-    n_defects int32 [N, 2], inexact uint8 [N] (1: a cluster beyond 14 defects or defects beyond the first 32 took the nearest-boundary fallback)."""
+    n_defects int32 [N, 2], inexact uint8 [N] (1: a cluster beyond 14 defects or defects beyond the first 32 took the nearest-boundary fallback; all 0
+    for method="union_find", which has none), rounds int32 [N, 2] (union-find: growth rounds per component; None for matching)."""
 
-    def __init__(self, frame, weight, n_defects, inexact):
-        self.frame, self.weight, self.n_defects, self.inexact = frame, weight, n_defects, inexact
+    def __init__(self, frame, weight, n_defects, inexact, rounds=None):
+        self.frame, self.weight, self.n_defects, self.inexact, self.rounds = frame, weight, n_defects, inexact, rounds
 
     def __repr__(self):
         return f"MatchResult(volumes={int(self.frame.shape[0])})"
@@ -504,13 +519,15 @@ def check_match_args(env, volumes, chunk=DEFAULT_CHUNK):
     return d, model, use_Y, depth, shape[0]
 
 
-def matching_decode(volumes, env, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None):
+def matching_decode(volumes, env, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None, method="matching"):
     """Minimum-weight matching on the space-time volume, unit weights, both Pauli components independently.  volumes: uint8
     [N, volume_depth, d+1, d+1] with 0/1 cells (sample_volumes' output, decode's input), numpy or torch; env supplies the lattice (d <= 7, the narrow
     environment).  Returns a MatchResult of device tensors (numpy arrays with to_host).  The result of a volume does not depend on the batch
     around it or on `chunk`.  evaluator: an Evaluator of this lattice to run on (its chunk is used and it stays open, so that repeated calls build
-    the matching tables once); default: one for this call."""
+    the matching tables once); default: one for this call.  method="union_find": the union-find decoder of DESIGN.md section 16 on the same graph
+    (weight = edges of its correction, inexact all 0, rounds = its growth rounds per component)."""
     import torch
+    check_method(method)
     d, model, use_Y, depth, n = check_match_args(env, volumes, chunk)
     venv = _narrow_env(env)
     dev = venv.device
@@ -522,16 +539,21 @@ def matching_decode(volumes, env, chunk=DEFAULT_CHUNK, to_host=False, evaluator=
         frame = torch.empty((n, d, d), dtype=torch.uint8, device=dev)
         weight = torch.empty((n, 2), dtype=torch.int32, device=dev)
         ndef = torch.empty((n, 2), dtype=torch.int32, device=dev)
-        inexact = torch.empty(n, dtype=torch.uint8, device=dev)
+        uf = method == "union_find"
+        inexact = torch.zeros(n, dtype=torch.uint8, device=dev) if uf else torch.empty(n, dtype=torch.uint8, device=dev)
+        rounds = torch.empty((n, 2), dtype=torch.int32, device=dev) if uf else None
         with torch.cuda.device(dev):
             for s in range(0, n, ev.chunk):
                 m = min(ev.chunk, n - s)
-                ev.match_into(vol[s:s + m], m, frame[s:s + m], weight[s:s + m], ndef[s:s + m], inexact[s:s + m])
+                if uf:
+                    ev.uf_into(vol[s:s + m], m, frame[s:s + m], weight[s:s + m], ndef[s:s + m], rounds[s:s + m])
+                else:
+                    ev.match_into(vol[s:s + m], m, frame[s:s + m], weight[s:s + m], ndef[s:s + m], inexact[s:s + m])
             torch.cuda.current_stream(dev).synchronize()
     finally:
         if evaluator is None:
             ev.close()
-    out = (frame, weight, ndef, inexact)
+    out = (frame, weight, ndef, inexact) + ((rounds,) if uf else ())
     return MatchResult(*(tuple(x.cpu().numpy() for x in out) if to_host else out))
 
 
@@ -658,11 +680,18 @@ class MatchingAgent:
     episode records kept on the device by the loop DQNAgent.test runs (episodes.episode_records).  policy="identity": only ever the identity --
     the "no decoder" row of the same table.  evaluator: an Evaluator of the environment's lattice to run on (it stays open); default: one per
     call.  After a call last_inexact_steps holds the lattice-steps whose volume took the matching's 14 / 32 fallback (summed on the device; per
-    rate after test_error_rates: last_inexact_by_rate), last_vector_steps the vector steps made."""
+    rate after test_error_rates: last_inexact_by_rate), last_vector_steps the vector steps made.  method="union_find": the union-find decoder of
+    DESIGN.md section 16 plays instead (dq_env_uf_select; it has no fallback, so the inexact counts are 0) -- in test, test_error_rates and, through
+    evaluator_for and this attribute, as the guide of a policy in DQNAgent.fit."""
 
-    def __init__(self, evaluator=None, chunk=DEFAULT_CHUNK, policy="matching"):
+    def __init__(self, evaluator=None, chunk=DEFAULT_CHUNK, policy="matching", method=None):
         if policy not in ("matching", "identity"):
             raise ValueError(f"policy must be 'matching' or 'identity', not {policy!r}")
+        if method is not None:
+            check_method(method)
+            if policy == "identity":
+                raise ValueError("policy='identity' plays no decoder: it takes no method")
+        self.method = "matching" if method is None else method
         if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
             raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
         self.evaluator, self.chunk, self.policy = evaluator, int(chunk), policy
@@ -741,8 +770,11 @@ class MatchingAgent:
 
                 def step(k):
                     if matching:
-                        venv.match_select(ev, out=action, out_inexact=flag)
-                        inexact.add_(flag)
+                        if self.method == "matching":
+                            venv.match_select(ev, out=action, out_inexact=flag)
+                            inexact.add_(flag)
+                        else:
+                            venv.match_select(ev, out=action, method=self.method)
                     venv.step(action, auto_reset=True, write_obs=False)
                     steps[0] = k + 1
                     return venv.done, venv.was_reset, venv.reward, venv.lifetime
@@ -776,15 +808,17 @@ def expand_rates(lattice, env, n_volumes, rates, p_meas, seed, env_id_base, who)
 
 
 def score_matching(env, n_volumes, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, chunk=DEFAULT_CHUNK, no_decoder=False, timings=None,
-                   evaluator=None):
+                   evaluator=None, method="matching"):
     """The matching baseline scored like DQNAgent.decode_benchmark scores the agent, on the SAME volumes for the same env, n_volumes, rates, seed and
     env_id_base (both run score_chunks): sample -> dq_decode_match -> verdict -> counts on the device.  Returns an EvalResult ({rate: EvalResult}
     with rates=[...]; p_meas then as in decode_benchmark; without rates p_phys / p_meas are scalars, default the environment's).  Counters: every
     volume counts as status identity, corrections = the frame's non-zero cells; EvalResult.inexact = volumes that took the fallback.  no_decoder:
     EvalResult.no_decoder counts the verdict for frame = 0.  timings: a dict that receives the wall seconds of the phases (sample / match /
     verdict).  evaluator: an Evaluator of this lattice to run on (its chunk is used, it stays open: its matching tables are built once);
-    default: one of `chunk` volumes for this call."""
+    default: one of `chunk` volumes for this call.  method="union_find": dq_decode_uf in place of dq_decode_match (inexact = 0; the phase key of
+    `timings` stays "match")."""
     import torch
+    check_method(method)
     lat = check_eval_lattice(None, env)
     if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
         raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
@@ -805,11 +839,14 @@ def score_matching(env, n_volumes, rates=None, p_phys=None, p_meas=None, seed=No
     try:
         rows = min(ev.chunk, n)
         frame = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
-        inexact = torch.empty(rows, dtype=torch.uint8, device=dev)
+        inexact = torch.zeros(rows, dtype=torch.uint8, device=dev)
         status = torch.full((rows,), STATUS_IDENTITY, dtype=torch.uint8, device=dev)
 
         def decode(vol, m, o):
-            ev.match_into(vol, m, frame[:m], None, None, inexact[:m])
+            if method == "union_find":
+                ev.uf_into(vol, m, frame[:m])
+            else:
+                ev.match_into(vol, m, frame[:m], None, None, inexact[:m])
             return frame[:m], status[:m], (frame[:m] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), inexact[:m]
 
         with torch.cuda.device(dev):

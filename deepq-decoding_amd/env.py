@@ -476,17 +476,29 @@ class VectorEnv:
                                           seed, self.env_id_base, int(t), ptr(out), self._stream()))
         return out
 
-    def match_select(self, evaluator, out=None, out_inexact=None):
+    def match_select(self, evaluator, out=None, out_inexact=None, method="matching"):
         """The matching decoder's next action for every lattice (include/deepq_hip.h dq_env_match_select): the lowest action
         index of the matching's Pauli frame for the lattice's current volume that is not in completed_actions, else the identity.  evaluator: a
         decoder.Evaluator of this lattice (it owns the matching tables).  out: int32 [n_envs]; out_inexact: uint8 [n_envs] or None (the
-        fallback flag of each volume is then not written).  Returns the actions; step(actions, auto_reset=True) is the agent step."""
+        fallback flag of each volume is then not written).  Returns the actions; step(actions, auto_reset=True) is the agent step.
+        method="union_find": the union-find decoder's frame instead (dq_env_uf_select); out_inexact, if given, is zero-filled."""
+        self._check_method(method, "match_select")
         self._check_matching(evaluator, "match_select")
         if out is None:
             out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
         self._check_outputs("match_select", (out, torch.int32), (out_inexact, torch.uint8))
-        check(self.L.dq_env_match_select(self._h, evaluator._h, ptr(out), ptr(out_inexact), self._stream()))
+        if method == "union_find":
+            check(self.L.dq_env_uf_select(self._h, evaluator._h, ptr(out), self._stream()))
+            if out_inexact is not None:
+                out_inexact.zero_()
+        else:
+            check(self.L.dq_env_match_select(self._h, evaluator._h, ptr(out), ptr(out_inexact), self._stream()))
         return out
+
+    @staticmethod
+    def _check_method(method, who):
+        if not isinstance(method, str) or method not in ("matching", "union_find"):
+            raise ValueError(f"{who}: method must be 'matching' or 'union_find', not {method!r}")
 
     def _check_matching(self, evaluator, who):
         """What match_select and guided_select require of the lattice and the evaluator, before any library call."""
@@ -505,14 +517,17 @@ class VectorEnv:
             if t is not None and not (t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (self.n_envs,)):
                 raise ValueError(f"{who}: outputs are contiguous device tensors of n_envs = {self.n_envs} entries (int32 actions, uint8 flags)")
 
-    def guided_select(self, evaluator, t, q=None, eps=1.0, guide_share=1.0, masked_greedy=False, out=None, out_guided=None, out_inexact=None):
+    def guided_select(self, evaluator, t, q=None, eps=1.0, guide_share=1.0, masked_greedy=False, out=None, out_guided=None, out_inexact=None,
+                      method="matching"):
         """Epsilon-greedy selection whose exploring lattices follow the matching decoder with probability guide_share (include/deepq_hip.h
         dq_env_guided_select; the rule in numpy: decoder.guided_actions).  With select_actions' Philox words w of policy counter t:
         explore = q is None or w[1] < T(eps); guided = explore and w[2] < T(guide_share); a guided lattice gets match_select's action, another exploring
         one the k-th legal action, the rest the first maximum of their row of q (float32 [n_envs, num_actions]; over the legal set when masked_greedy).
         guide_share = 0: select_actions' actions bit for bit; eps = 1 with guide_share = 1: match_select's.  The matching runs for the guided lattices
         only.  out: int32 [n_envs]; out_guided / out_inexact: uint8 [n_envs] or None (1 where the lattice followed the matching / match_select's flag
-        for it, 0 for every other lattice).  Returns the actions; step(actions, auto_reset=True) is the agent step."""
+        for it, 0 for every other lattice).  Returns the actions; step(actions, auto_reset=True) is the agent step.  method="union_find": the teacher is the
+        union-find decoder (dq_env_guided_select_uf: match_select(method="union_find")'s action for a guided lattice; out_inexact all 0)."""
+        self._check_method(method, "guided_select")
         self._check_matching(evaluator, "guided_select")
         for name, v in (("eps", eps), ("guide_share", guide_share)):
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
@@ -525,8 +540,9 @@ class VectorEnv:
             out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
         self._check_outputs("guided_select", (out, torch.int32), (out_guided, torch.uint8), (out_inexact, torch.uint8))
         seed = (ctypes.c_uint32 * 2)(*self.seed)
-        check(self.L.dq_env_guided_select(self._h, evaluator._h, ptr(q), float(eps), float(guide_share), int(masked_greedy), seed, int(t), ptr(out),
-                                          ptr(out_guided), ptr(out_inexact), self._stream()))
+        fn = self.L.dq_env_guided_select_uf if method == "union_find" else self.L.dq_env_guided_select
+        check(fn(self._h, evaluator._h, ptr(q), float(eps), float(guide_share), int(masked_greedy), seed, int(t), ptr(out),
+                 ptr(out_guided), ptr(out_inexact), self._stream()))
         return out
 
     # -- state views --------------------------------------------------------------------------------------

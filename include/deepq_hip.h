@@ -792,6 +792,26 @@ dq_status dq_env_match_select(dq_env* env, dq_decode_eval* ev, int32_t* action_d
  * modified: an agent step is this launch followed by dq_env_step(action_dev, auto_reset = 1).  No reference counterpart. */
 dq_status dq_env_guided_select(dq_env* env, dq_decode_eval* ev, const float* q_dev, double eps, double guide_share, int masked_greedy, const uint32_t seed[2],
                                uint64_t t, int32_t* action_dev, uint8_t* guided_dev, uint8_t* inexact_dev, void* stream);
+/* The union-find decoder (Delfosse and Nickerson; csrc/uf_dev.h, csrc/uf_st.hip): the second baseline and a teacher without a
+ * cluster-size limit.  dq_version() stays 8: the capability is discovered by the presence of these three symbols.  Per Pauli component, on
+ * dq_decode_match's defects and unit-weight graph with the spatial and the open future boundary merged into one boundary node: clusters grow in
+ * synchronous half-edge rounds until each holds an even number of defects or the boundary, then a breadth-first forest over the full edges is peeled.
+ * There is no fallback: nothing is inexact.
+ * dq_decode_uf: dq_decode_match's contract (n <= max_volumes volumes in dq_decode_run's input layout, frame_dev uint8 [n][d][d] as hidden_state codes,
+ * weight_dev int32 [n][2] = edges of the correction per component, time edges and the edge to the future boundary included, n_defects_dev int32 [n][2]) with
+ * rounds_dev int32 [n][2] = growth rounds per component in place of inexact_dev; weight_dev / n_defects_dev / rounds_dev may be NULL.  Deterministic per
+ * volume: no dependence on the batch.
+ * dq_env_uf_select: dq_env_match_select with F = dq_decode_uf's frame of the lattice's current volume (no flag output).
+ * dq_env_guided_select_uf: dq_env_guided_select whose guided lattices get dq_env_uf_select's action; inexact_dev, if given, is zero-filled.
+ * All three make dq_decode_match's / dq_env_match_select's checks of the lattice and the evaluator and return the same error codes (d <= 7,
+ * volume_depth <= 16, the narrow environment; an evaluator of another lattice: DQ_ERR_INVALID).  The endpoint tables live in the handle's table blob beside the
+ * matching's, built at the handle's first call of any of the six entry points, which therefore MODIFIES the handle: a dq_decode_eval serves one host
+ * thread at a time and the calls on it are ordered on one stream at a time; it is not thread-safe. */
+dq_status dq_decode_uf(dq_decode_eval* ev, const uint8_t* volumes_dev, int n, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev,
+                       int32_t* rounds_dev, void* stream);
+dq_status dq_env_uf_select(dq_env* env, dq_decode_eval* ev, int32_t* action_dev, void* stream);
+dq_status dq_env_guided_select_uf(dq_env* env, dq_decode_eval* ev, const float* q_dev, double eps, double guide_share, int masked_greedy, const uint32_t seed[2],
+                                  uint64_t t, int32_t* action_dev, uint8_t* guided_dev, uint8_t* inexact_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Live kernel timing (measurement only; no reference counterpart).  dq_prof_arm(id, n) times up to n

@@ -5,7 +5,8 @@ DESIGN.md section 12).
 
 Per rate: the failure rate (1 - success / volumes: the residual error is not a stabilizer) with its Wilson 95 % interval for the agent under
 the masked and the plain greedy policy, for space-time minimum-weight matching (the `matching` row, on the same volumes; its phases are sample /
-match / verdict, and `match_over_agent_decode` is its match time over the masked agent's decode time) and for no decoder at all (frame = 0), the death rate (the referee loses the residual's class), the
+match / verdict, and `match_over_agent_decode` is its match time over the masked agent's decode time), for the union-find decoder (the `union_find` row, the
+same volumes and phases) and for no decoder at all (frame = 0), the death rate (the referee loses the residual's class), the
 share of all-zero volumes, corrections per volume, the status histogram, and the wall time of the phases (sample / decode / verdict, each
 closed by a synchronisation; the verdict phase of the masked run also carries the frame = 0 verdict).  Weights: tests/golden/keras_weights_<family>_<weights>.npz.
 One process, no retries: the first failing GPU call ends it.  On a shared box run it under a time limit, e.g. `timeout -k 10 600 python tools/...`."""
@@ -72,19 +73,20 @@ def main():
         D = dq.decoder
         if mev is None:                                                                                 # one scoring handle for every call: its matching tables are built once
             mev = D.Evaluator(cfg["d"], cfg["error_model"], cfg["use_Y"], cfg["volume_depth"], chunk=a.chunk, device=env.device)
-        D.score_matching(env, min(a.n, a.chunk), rates=[r], evaluator=mev)                              # warm-up: the tables, first launch, allocations
-        timings = {}
-        t0 = time.perf_counter()
-        mres = D.score_matching(env, a.n, rates=[r], timings=timings, evaluator=mev)[r]
-        wall = time.perf_counter() - t0
-        s = mres.summary()
-        s["inexact"] = mres.inexact
-        s["ms"] = {k: round(1e3 * timings.get(k, 0.0), 3) for k in ("sample", "match", "verdict")}
-        s["ms"]["wall"] = round(1e3 * wall, 3)
-        s["match_over_agent_decode"] = round(s["ms"]["match"] / row["masked"]["ms"]["decode"], 4)
-        row["matching"] = s
-        print(f"p = {r} matching: failure {mres.failure_rate:.6f} [{mres.failure_interval[0]:.6f}, {mres.failure_interval[1]:.6f}]  death {mres.death_rate:.6f}  "
-              f"corrections / volume {mres.mean_corrections:.4f}  inexact {mres.inexact}  ms {s['ms']}  match / agent decode {s['match_over_agent_decode']}", flush=True)
+        for method in D.METHODS:                                                                        # the same volumes for either baseline
+            D.score_matching(env, min(a.n, a.chunk), rates=[r], evaluator=mev, method=method)           # warm-up: the tables, first launch, allocations
+            timings = {}
+            t0 = time.perf_counter()
+            mres = D.score_matching(env, a.n, rates=[r], timings=timings, evaluator=mev, method=method)[r]
+            wall = time.perf_counter() - t0
+            s = mres.summary()
+            s["inexact"] = mres.inexact
+            s["ms"] = {k: round(1e3 * timings.get(k, 0.0), 3) for k in ("sample", "match", "verdict")}
+            s["ms"]["wall"] = round(1e3 * wall, 3)
+            s["match_over_agent_decode"] = round(s["ms"]["match"] / row["masked"]["ms"]["decode"], 4)
+            row[method] = s
+            print(f"p = {r} {method}: failure {mres.failure_rate:.6f} [{mres.failure_interval[0]:.6f}, {mres.failure_interval[1]:.6f}]  death {mres.death_rate:.6f}  "
+                  f"corrections / volume {mres.mean_corrections:.4f}  inexact {mres.inexact}  ms {s['ms']}  match / agent decode {s['match_over_agent_decode']}", flush=True)
         nd = row["no_decoder"]
         print(f"p = {r} frame = 0: failure {nd['failure_rate']:.6f} [{nd['failure_interval'][0]:.6f}, {nd['failure_interval'][1]:.6f}]  death {nd['death_rate']:.6f}",
               flush=True)

@@ -2,7 +2,10 @@
 count): the selection launches alone (device events over repeated calls on one fixed set of lattice states) and whole vector steps with an update
 (host clock around a synchronised loop), every variant in this one process, the variants interleaved over several rounds.
 
-    python tools/guided_step_timing.py [--lattices 4096] [--minibatch 0] [--steps 300] [--rounds 3] [--out profiles/guided_step_timing.json]
+    python tools/guided_step_timing.py [--lattices 4096] [--minibatch 0] [--steps 300] [--rounds 3] [--method matching|union_find] [--out FILE]
+
+--method union_find: every variant with a teacher is timed for BOTH teachers, interleaved (the union-find ones carry the suffix " [union_find]"; DESIGN.md
+section 16), and the record goes to profiles/union_find_step_timing.json.
 """
 import argparse
 import importlib
@@ -43,8 +46,10 @@ def main():
     ap.add_argument("--minibatch", type=int, default=0, help="0: the lattice count (bench.py's default)")
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--method", default="matching", choices=["matching", "union_find"])
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    methods = [("matching", "")] + ([("union_find", " [union_find]")] if a.method == "union_find" else [])
     N = a.lattices
     a.minibatch = a.minibatch or N
     env = dq.VectorEnv(n_envs=N, seed=(24301, 57005), **C3)
@@ -61,10 +66,14 @@ def main():
     flags = torch.zeros((2, N), dtype=torch.uint8, device=env.device)
     select = {"select_actions eps=1": lambda: env.select_actions(7, q=q, eps=1.0, out=act),
               "select_actions eps=0": lambda: env.select_actions(7, q=q, eps=0.0, out=act),
-              "match_select": lambda: env.match_select(ev, out=act, out_inexact=flags[1])}
-    for x in FRACTIONS:
-        select[f"guided_select eps=1 share={x}"] = lambda x=x: env.guided_select(ev, 7, q=q, eps=1.0, guide_share=x, out=act, out_guided=flags[0], out_inexact=flags[1])
-    select["guided_select eps=0 (greedy)"] = lambda: env.guided_select(ev, 7, q=q, eps=0.0, guide_share=1.0, out=act, out_guided=flags[0], out_inexact=flags[1])
+              }
+    for m, tag in methods:
+        select["match_select" + tag] = lambda m=m: env.match_select(ev, out=act, out_inexact=flags[1], method=m)
+        for x in FRACTIONS:
+            select[f"guided_select eps=1 share={x}" + tag] = lambda x=x, m=m: env.guided_select(ev, 7, q=q, eps=1.0, guide_share=x, out=act, out_guided=flags[0],
+                                                                                                  out_inexact=flags[1], method=m)
+        select["guided_select eps=0 (greedy)" + tag] = lambda m=m: env.guided_select(ev, 7, q=q, eps=0.0, guide_share=1.0, out=act, out_guided=flags[0],
+                                                                                    out_inexact=flags[1], method=m)
     sel_us = {k: [] for k in select}
     for _ in range(a.rounds):
         for k, fn in select.items():
@@ -82,28 +91,29 @@ def main():
         torch.cuda.synchronize()
         return 1e6 * (time.perf_counter() - t0) / a.steps
 
-    def match_then_step():                                                    # section 14's form inside the loop: the matching for EVERY lattice, then a selection
-        env.match_select(ev, out=act, out_inexact=flags[1])
-        core.guided_act_and_step(ev, 1.0, 0.0)
+    def match_then_step(m):                                                   # section 14's form inside the loop: the matching for EVERY lattice, then a selection
+        env.match_select(ev, out=act, out_inexact=flags[1], method=m)
+        core.guided_act_and_step(ev, 1.0, 0.0, method=m)
 
     steps = {"act_and_step + update (eps=1)": lambda: core.act_and_step(1.0),
-             "act_and_step + update (eps=0.1)": lambda: core.act_and_step(0.1),
-             "full match_select + guided step(share=0) + update": match_then_step}
-    for x in FRACTIONS:
-        steps[f"guided_act_and_step(eps=1, share={x}) + update"] = lambda x=x: core.guided_act_and_step(ev, 1.0, x)
+             "act_and_step + update (eps=0.1)": lambda: core.act_and_step(0.1)}
+    for m, tag in methods:
+        steps["full match_select + guided step(share=0) + update" + tag] = lambda m=m: match_then_step(m)
+        for x in FRACTIONS:
+            steps[f"guided_act_and_step(eps=1, share={x}) + update" + tag] = lambda x=x, m=m: core.guided_act_and_step(ev, 1.0, x, method=m)
     step_us = {k: [] for k in steps}
     for _ in range(a.rounds):
         for k, fn in steps.items():
             step_us[k].append(loop(fn))
     summary = lambda d: {k: dict(median_us=float(np.median(v)), runs_us=[float(x) for x in v]) for k, v in d.items()}
-    record = dict(config=dict(C3, lattices=N, minibatch=a.minibatch), calls_per_selection_timing=200,
+    record = dict(config=dict(C3, lattices=N, minibatch=a.minibatch), method=a.method, calls_per_selection_timing=200,
                   steps_per_loop=a.steps, rounds=a.rounds, selection_launch_us=summary(sel_us), vector_step_us=summary(step_us),
                   guided_counts=[int(x) for x in core.guide_counts.cpu().tolist()], device=torch.cuda.get_device_name(0))
     for name, d in (("selection launch, us", record["selection_launch_us"]), ("vector step with update, us", record["vector_step_us"])):
         print(name)
         for k, v in d.items():
             print(f"  {k:60s} {v['median_us']:9.2f}   {['%.2f' % x for x in v['runs_us']]}")
-    path = a.out or os.path.join(ROOT, "profiles", "guided_step_timing.json")
+    path = a.out or os.path.join(ROOT, "profiles", "guided_step_timing.json" if a.method == "matching" else "union_find_step_timing.json")
     with open(path, "w") as f:
         json.dump(record, f, indent=1)
         f.write("\n")

@@ -2,7 +2,9 @@
 once with plain epsilon-greedy exploration, once with EpsGreedyQPolicy(guide=MatchingAgent(), guide_share=...) -- and scores both trained agents with
 DQNAgent.test_error_rates on the same lattice ids.
 
-    python tools/guided_training.py --family d5_dp|d5_x --steps N [--guide-share 0.5] [--lattices 64] [--updates-per-step 0] [--out FILE]
+    python tools/guided_training.py --family d5_dp|d5_x --steps N [--guide-share 0.5] [--method matching|union_find] [--lattices 64] [--updates-per-step 0] [--out FILE]
+
+--method union_find: the teacher is the union-find decoder; the record then goes to profiles/union_find_training_<family>.json.
 
 The configuration: the hyper-parameters of tests/golden/fixed_config_d5_dp.p (network, batch 32, buffer 50 000, no masked greedy; d5_x: the same with
 bit-flip noise) at p = 0.007, the variable ones of tests/golden/variable_config_d5_dp_0.011_92.p (Adam 5e-6, gamma 0.99, target copy every 2500 steps,
@@ -44,9 +46,9 @@ def lattice(cfg):
     return dict(d=cfg["d"], error_model=cfg["error_model"], use_Y=cfg["use_Y"], volume_depth=cfg["volume_depth"])
 
 
-def train_and_score(cfg, steps, lattices, updates, guide_share, seed, episodes, eval_lattices):
+def train_and_score(cfg, steps, lattices, updates, guide_share, seed, episodes, eval_lattices, method="matching"):
     env = dq.VectorEnv(n_envs=lattices, p_phys=cfg["p_phys"], p_meas=cfg["p_meas"], seed=seed, **lattice(cfg))
-    guide = None if guide_share is None else dq.decoder.MatchingAgent()
+    guide = None if guide_share is None else dq.decoder.MatchingAgent(method=method)
     inner = dq.EpsGreedyQPolicy(masked_greedy=cfg["masked_greedy"], guide=guide, guide_share=1.0 if guide_share is None else guide_share)
     policy = dq.LinearAnnealedPolicy(inner, attr="eps", value_max=cfg["max_eps"], value_min=cfg["final_eps"], value_test=0.0, nb_steps=max(1, steps // 5))
     model = dq.build_convolutional_nn(cfg["c_layers"], cfg["ff_layers"], env.obs_shape, env.num_actions)
@@ -80,6 +82,7 @@ def main():
     ap.add_argument("--family", required=True, choices=["d5_dp", "d5_x"])
     ap.add_argument("--steps", type=int, required=True, help="environment steps (lattice-steps) of each training run")
     ap.add_argument("--guide-share", type=float, default=0.5)
+    ap.add_argument("--method", default="matching", choices=["matching", "union_find"], help="the teacher of the guided run")
     ap.add_argument("--lattices", type=int, default=64)
     ap.add_argument("--updates-per-step", type=int, default=0)
     ap.add_argument("--episodes", type=int, default=101)
@@ -94,7 +97,7 @@ def main():
     updates = a.updates_per_step or a.lattices
     runs = {}
     for tag, share in (("plain", None), ("guided", a.guide_share)):
-        runs[tag] = train_and_score(cfg, a.steps, a.lattices, updates, share, seed, a.episodes, a.eval_lattices)
+        runs[tag] = train_and_score(cfg, a.steps, a.lattices, updates, share, seed, a.episodes, a.eval_lattices, a.method)
         r = runs[tag]
         print(f"{tag:>7}: {r['env_steps']} steps, {r['updates']} updates, {r['train_seconds']:.1f} s ({r['ms_per_vector_step']:.3f} ms per vector step), "
               f"guided {r['guided_steps']}, inexact {r['inexact_steps']}")
@@ -102,10 +105,10 @@ def main():
     print(f"{'p':>7} {'plain':>10} {'guided':>10} {'1/p':>8}")
     for p in TEST_RATES:
         print(f"{p:7.3f} {runs['plain']['lifetimes'][str(p)]:10.1f} {runs['guided']['lifetimes'][str(p)]:10.1f} {1.0 / p:8.0f}")
-    record = dict(family=a.family, p_train=P_TRAIN, steps=a.steps, lattices=a.lattices, updates_per_vector_step=updates, guide_share=a.guide_share,
+    record = dict(family=a.family, p_train=P_TRAIN, steps=a.steps, lattices=a.lattices, updates_per_vector_step=updates, guide_share=a.guide_share, method=a.method,
                   seed=list(seed), test_rates=TEST_RATES, episodes_per_rate=a.episodes, eval_lattices_per_rate=a.eval_lattices,
                   configuration={k: v for k, v in cfg.items() if isinstance(v, (int, float, str, bool, list))}, runs=runs)
-    path = a.out or os.path.join(ROOT, "profiles", f"guided_training_{a.family}.json")
+    path = a.out or os.path.join(ROOT, "profiles", f"{'guided' if a.method == 'matching' else a.method}_training_{a.family}.json")
     with open(path, "w") as f:
         json.dump(record, f, indent=1, default=lambda o: o.item() if isinstance(o, np.generic) else str(o))
         f.write("\n")

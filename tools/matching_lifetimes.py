@@ -1,5 +1,5 @@
-"""Episode lifetimes of three policies in the same environment: the shipped agent (DQNAgent.test_error_rates), the
-space-time matching decoder (decoder.MatchingAgent) and a policy that only ever sends the identity (no decoder), each on a fresh VectorEnv with the
+"""Episode lifetimes of four policies in the same environment (DESIGN.md sections 14 and 16): the shipped agent (DQNAgent.test_error_rates), the
+space-time matching decoder (decoder.MatchingAgent), the union-find decoder (MatchingAgent(method="union_find")) and a policy that only ever sends the identity (no decoder), each on a fresh VectorEnv with the
 same seed, global ids and rates, so that every policy meets the same noise streams.
 
     python tools/matching_lifetimes.py --family d5_dp|d5_x [--rates 0.001,...] [--episodes 101] [--lattices M] [--trained-at 0.007] [--out FILE]
@@ -43,6 +43,8 @@ def run(policy, family, trained_at, rates, episodes, m, seed):
     env = dq.VectorEnv(n_envs=len(rates) * m, p_phys=rates[0], p_meas=rates[0], seed=seed, **FAMILIES[family])
     if policy == "agent":
         who = shipped_agent(env, family, trained_at)
+    elif policy == "union_find":
+        who = dq.decoder.MatchingAgent(method="union_find")
     else:
         who = dq.decoder.MatchingAgent(policy=policy)
     torch.cuda.synchronize()
@@ -53,7 +55,7 @@ def run(policy, family, trained_at, rates, episodes, m, seed):
     out = dict(wall_seconds=seconds, avg_lifetime=[hist[p].history["episode_lifetimes_rolling_avg"][-1] for p in rates],
                episodes=[len(hist[p].history["episode_lifetime"]) for p in rates],
                agent_steps=[int(np.sum(hist[p].history["nb_steps"])) for p in rates])
-    if policy == "matching":
+    if policy in ("matching", "union_find"):
         out["inexact_steps"] = [who.last_inexact_by_rate[p] for p in rates]
         out["inexact_share"] = [who.last_inexact_by_rate[p] / max(1, who.last_vector_steps * m) for p in rates]
         out["vector_steps"] = who.last_vector_steps
@@ -74,11 +76,12 @@ def main():
     rates = [float(x) for x in a.rates.split(",")] if a.rates else [round(j * 0.001, 3) for j in range(1, 21)]
     m = a.lattices or a.episodes
     seed = tuple(int(x) for x in a.seed.split(","))
-    res = {p: run(p, a.family, a.trained_at, rates, a.episodes, m, seed) for p in ("agent", "matching", "identity")}
+    res = {p: run(p, a.family, a.trained_at, rates, a.episodes, m, seed) for p in ("agent", "matching", "union_find", "identity")}
     print(f"{a.family}, agent trained at p = {a.trained_at}: average lifetime over {a.episodes} episodes per rate ({m} lattices per rate)")
-    print(f"{'p':>7} {'agent':>10} {'matching':>10} {'identity':>10} {'1/p':>8} {'inexact share':>14}")
+    print(f"{'p':>7} {'agent':>10} {'matching':>10} {'union-find':>10} {'identity':>10} {'1/p':>8} {'inexact share':>14}")
     for k, p in enumerate(rates):
-        print(f"{p:7.3f} {res['agent']['avg_lifetime'][k]:10.1f} {res['matching']['avg_lifetime'][k]:10.1f} {res['identity']['avg_lifetime'][k]:10.1f} "
+        print(f"{p:7.3f} {res['agent']['avg_lifetime'][k]:10.1f} {res['matching']['avg_lifetime'][k]:10.1f} {res['union_find']['avg_lifetime'][k]:10.1f} "
+              f"{res['identity']['avg_lifetime'][k]:10.1f} "
               f"{1.0 / p:8.0f} {res['matching']['inexact_share'][k]:14.2e}")
     print("wall seconds: " + ", ".join(f"{p} {res[p]['wall_seconds']:.2f}" for p in res))
     record = dict(family=a.family, trained_at=a.trained_at, rates=rates, inverse_rate=[1.0 / p for p in rates], episodes_per_rate=a.episodes,
