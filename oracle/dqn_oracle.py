@@ -178,26 +178,75 @@ def forward(spec, flat_params, obs, training=False, keep_masks=None):
     return q, cache
 
 
-def fragile_samples(cache, thr=2e-6, rel=None):
-    """Samples with a ReLU pre-activation within `thr` of 0: an fp32 implementation may put it on the other side of the ReLU, which
-    changes that sample's gradient by a finite amount (not a round-off).  Tests on large batches give such samples dq = 0.  thr is the
-    pre-activation error bound of the HIP paths on unit-scale weights (2e-6 at |z| <~ 4: ten times their measured error against float64); with rel the threshold is rel * max |z|
-    per layer instead -- the error of an fp32 contraction is relative to the layer's magnitude (trained weights: |z| up to ~70; the
-    measured error of the HIP paths there is ~4e-7 of the largest value, tests/test_shipped_weights.py)."""
-    bad = None
-    for C in cache["layers"]:
+def _near_zero_units(cache, thr, rel):
+    """(layer index, boolean (B, units)) per ReLU layer: the pre-activations within the threshold of 0.  A layer's units are numbered in the oracle's own
+    layout of that layer's output: (oh, ow, cout) flattened for a convolution, the unit index for a dense layer."""
+    for li, C in enumerate(cache["layers"]):
         if C["kind"] == "conv" or C["relu"]:
             z = np.abs(C["z"])
             t = rel * float(z.max()) if rel else thr
-            b = (z.reshape(z.shape[0], -1) < t).any(axis=1)
-            bad = b if bad is None else (bad | b)
+            yield li, z.reshape(z.shape[0], -1) < t
+
+
+def fragile_units(cache, thr=2e-6, rel=None):
+    """The ReLU units behind fragile_samples, same thresholds: the sorted list of (sample, layer, unit) whose pre-activation is within the threshold of 0
+    (layer = index into spec.layers, unit as in _near_zero_units).  Each is one bit of freedom of an fp32 implementation -- on or off -- and
+    backward(relu_on=...) evaluates the gradient under either choice."""
+    out = []
+    for li, near in _near_zero_units(cache, thr, rel):
+        out += [(int(s), li, int(u)) for s, u in zip(*np.nonzero(near))]
+    return sorted(out)
+
+
+def fragile_samples(cache, thr=2e-6, rel=None):
+    """Samples with a ReLU pre-activation within `thr` of 0: an fp32 implementation may put it on the other side of the ReLU, which
+    changes that sample's gradient by a finite amount (not a round-off).  thr is the
+    pre-activation error bound of the HIP paths on unit-scale weights (2e-6 at |z| <~ 4: ten times their measured error against float64); with rel the threshold is rel * max |z|
+    per layer instead -- the error of an fp32 contraction is relative to the layer's magnitude (trained weights: |z| up to ~70; the
+    measured error of the HIP paths there is ~4e-7 of the largest value, tests/test_shipped_weights.py).  Which side the device took is read back per
+    sample by tests/relu_choices.py (fragile_units, backward(relu_on=...)), so the large-batch tests compare these samples too."""
+    bad = None
+    for _, near in _near_zero_units(cache, thr, rel):
+        b = near.any(axis=1)
+        bad = b if bad is None else (bad | b)
     return bad
 
 
-def backward(spec, flat_params, cache, dq):
-    """Gradient of sum(dq * Q) w.r.t. the flat parameters (float64)."""
+def sample_cache(cache, samples):
+    """The forward cache restricted to the given samples, in that order: backward() on it is the gradient those samples contribute (the "row" dueling
+    mean only -- the "batch" form couples the samples of a minibatch)."""
+    idx = np.asarray(samples, dtype=np.int64)
+    B = cache["head_in"].shape[0]
+    cut = lambda v: v[idx] if isinstance(v, np.ndarray) and v.ndim >= 1 and v.shape[0] == B else v
+    out = dict(layers=[{k: cut(v) for k, v in C.items()} for C in cache["layers"]], head_in=cache["head_in"][idx])
+    for C in out["layers"]:
+        if "x_shape" in C:
+            C["x_shape"] = (len(idx),) + tuple(C["x_shape"][1:])
+    return out
+
+
+def _relu_mask(C, li, relu_on):
+    """y > 0, with the units of layer li named in relu_on set to the given bit instead."""
+    on = C["y"] > 0.0
+    if relu_on:
+        flat_on = on.reshape(on.shape[0], -1)                                 # a view: `on` is a fresh contiguous array
+        for (s, l, u), bit in relu_on.items():
+            if l == li:
+                flat_on[s, u] = bool(bit)
+    return on
+
+
+def backward(spec, flat_params, cache, dq, relu_on=None):
+    """Gradient of sum(dq * Q) w.r.t. the flat parameters (float64).  relu_on: {(sample, layer, unit): bool} (fragile_units' numbering) replaces the
+    ReLU's own on / off bit `y > 0` for exactly those units -- the gradient an implementation computes whose pre-activation fell on that side of 0;
+    None (or empty) keeps the oracle's own bits."""
     P = spec.split(np.asarray(flat_params, dtype=np.float64))
     dq = np.asarray(dq, dtype=np.float64)
+    if relu_on:
+        for (s, l, u) in relu_on:
+            C = cache["layers"][l]
+            assert C["kind"] == "conv" or C["relu"], (s, l, u)
+            assert 0 <= s < C["y"].shape[0] and 0 <= u < C["y"][0].size, (s, l, u)
     if spec.dueling:
         A = spec.n_actions
         g = np.zeros((dq.shape[0], A + 1))
@@ -215,14 +264,14 @@ def backward(spec, flat_params, cache, dq):
             if C["keep"] is not None:
                 g = np.where(C["keep"], g / (1.0 - C["rate"]), 0.0)
             if C["relu"]:
-                g = g * (C["y"] > 0.0)
+                g = g * _relu_mask(C, li, relu_on)
             grads[li] = (C["x"].T @ g, g.sum(axis=0))
             g = g @ Wk.T
         else:
             B = C["y"].shape[0]
             if g.ndim == 2:                                                    # coming from Flatten: (B, C*OH*OW)
                 g = g.reshape(B, L["cout"], L["oh"], L["ow"]).transpose(0, 2, 3, 1)
-            g = g * (C["y"] > 0.0)                                             # (B,OH,OW,Cout)
+            g = g * _relu_mask(C, li, relu_on)                                 # (B,OH,OW,Cout)
             K = L["k"] * L["k"] * L["cin"]
             grads[li] = ((C["cols"].reshape(-1, K).T @ g.reshape(-1, L["cout"])).reshape(Wk.shape), g.sum(axis=(0, 1, 2)))
             if li > 0:

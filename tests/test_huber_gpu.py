@@ -9,6 +9,7 @@ import pytest
 
 import shipped
 from oracle import c_oracle, dqn_oracle as O, philox
+from relu_choices import device_relu_choices
 
 pytestmark = pytest.mark.gpu
 
@@ -218,7 +219,11 @@ def test_finite_delta_carries_any_td_error_with_the_host_known_scale(dq, torch_m
     seed, t = (1, 2), 7
     keep = O.dropout_keep_mask(seed, t, np.arange(B), 512, 0.2)
     _, cache = O.forward(spec, flat, obs, training=True, keep_masks=[keep])
-    fragile = O.fragile_samples(cache, rel=1e-6)
+    # dq is formed inside the launch, so no sample can be given dq = 0: the oracle takes the fused path's own side of every ReLU whose pre-activation is
+    # within fp32 round-off of 0 instead (tests/relu_choices.py), read back once from the training forward every launch below repeats
+    assert O.fragile_samples(cache, rel=1e-6).any()
+    choices = device_relu_choices(net, params, spec, flat, obs, keep, lambda: net.forward(params, obs_t, training=True, seed=seed, t=t), rel=1e-6,
+                                  cache=cache, label="d5_dp/0.011 B=256 fused")
 
     def run(td_size, q1=None):
         """td_backward_adam with Q_target(s1) = -td_size / gamma everywhere (a TD error of Q(s0)[a] + td_size), delta = 1, auto_scale = 0."""
@@ -239,11 +244,10 @@ def test_finite_delta_carries_any_td_error_with_the_host_known_scale(dq, torch_m
         assert torch.isfinite(g_).all() and torch.isfinite(p_).all() and not torch.equal(p_, params)
         dq_np = dq_.cpu().numpy().astype(np.float64)
         assert np.abs(dq_np).max() <= 1.0 / B
-        dq_np[fragile] = 0.0
-        g_ref = O.backward(spec, flat, cache, dq_np)
-        if not fragile.any():
-            err = np.abs(g_.cpu().numpy() - g_ref).max()
-            assert err < 1e-5 * np.abs(g_ref).max(), (td_size, err)
+        g_ref = O.backward(spec, flat, cache, dq_np, relu_on=choices)
+        err = np.abs(g_.cpu().numpy() - g_ref).max()
+        print(f"TD error ~{td_size:g}, delta 1, host-known scale: max |g| {np.abs(g_ref).max():.3e}, max abs error {err:.2e}")
+        assert err < 1e-5 * np.abs(g_ref).max(), (td_size, err)
     # a NaN TD error is still the guard's: the whole update discarded and reported
     q1 = torch.zeros((B, A), dtype=torch.float32, device="cuda")
     q1[17] = float("nan")

@@ -14,20 +14,22 @@ SPECS = {
 C_LAYERS, FF_LAYERS = [[64, 3, 2], [32, 2, 1], [32, 2, 1]], [[512, 0.2]]
 
 
-def torch_forward(spec, flat, obs, keep=None):
-    """Same network in torch float64 (weights converted HWIO -> OIHW)."""
+def torch_forward(spec, flat, obs, keep=None, act=None):
+    """Same network in torch, in the dtype of `flat` (float64 unless stated; weights converted HWIO -> OIHW).  act(layer index, z) replaces the ReLU
+    (z in torch's layout: (B, C, H, W) behind a convolution)."""
     P = spec.split(flat)
     x = obs
     mi = 0
-    for (kind, L), (Wk, bk) in zip(spec.layers, P):
+    relu = (lambda li, z: torch.relu(z)) if act is None else act
+    for li, ((kind, L), (Wk, bk)) in enumerate(zip(spec.layers, P)):
         if kind == "conv":
-            x = torch.relu(torch.nn.functional.conv2d(x, Wk.permute(3, 2, 0, 1), bk, stride=L["s"]))
+            x = relu(li, torch.nn.functional.conv2d(x, Wk.permute(3, 2, 0, 1), bk, stride=L["s"]))
         else:
             if x.dim() == 4:
                 x = x.flatten(1)
             x = x @ Wk + bk
             if L["relu"]:
-                x = torch.relu(x)
+                x = relu(li, x)
             if L["dropout"] > 0 and keep is not None:
                 x = torch.where(keep[mi], x / (1.0 - L["dropout"]), torch.zeros_like(x))
                 mi += 1
@@ -280,3 +282,161 @@ def test_dueling_mean_row_and_batch_forms():
     print(f"dueling mean, B = 32, random weights: max |Q_batch - Q_row| = {np.abs(shift).max():.3e}; gradient difference max {diff:.3e}, "
           f"relative (2-norm) {rel:.3e}")
     assert diff > 0.0          # the forms ARE different at B = 32: the choice is documented, not immaterial
+
+
+# ---- the ReLU's on / off bit as a parameter of the oracle's backward (fragile_units, backward(relu_on=...), tests/relu_choices.py) ---------------------
+def _torch_unit(spec, li, s, u):
+    """Index of the oracle's (sample, layer, unit) in torch's layout of that layer's pre-activation."""
+    kind, L = spec.layers[li]
+    if kind == "dense":
+        return (s, u)
+    oy, ox, c = np.unravel_index(u, (L["oh"], L["ow"], L["cout"]))
+    return (s, int(c), int(oy), int(ox))
+
+
+def test_relu_on_with_the_oracle_own_bits_changes_nothing():
+    shape, A = SPECS["c3"]
+    spec = O.QNetSpec(shape, C_LAYERS, FF_LAYERS, A)
+    rng = np.random.RandomState(4)
+    flat = O.glorot_init(spec, (1, 2)).astype(np.float64) + rng.randn(spec.n_params) * 0.01
+    B = 6
+    obs = (rng.rand(B, *shape) < 0.3).astype(np.float64)
+    keep = [O.dropout_keep_mask((1, 2), 7, np.arange(B), 512, 0.2)]
+    _, cache = O.forward(spec, flat, obs, training=True, keep_masks=keep)
+    dq = rng.randn(B, A)
+    g0 = O.backward(spec, flat, cache, dq)
+    assert np.array_equal(g0, O.backward(spec, flat, cache, dq, relu_on=None)) and np.array_equal(g0, O.backward(spec, flat, cache, dq, relu_on={}))
+    units = O.fragile_units(cache, thr=1e-2)                                   # a loose threshold: a few hundred units over all four ReLU layers
+    assert len(units) > 50 and set(l for _, l, _ in units) == {0, 1, 2, 3}
+    own = {(s, l, u): bool(cache["layers"][l]["y"].reshape(B, -1)[s, u] > 0.0) for s, l, u in units}
+    assert any(own.values()) and not all(own.values())
+    assert np.array_equal(g0, O.backward(spec, flat, cache, dq, relu_on=own))
+    # fragile_samples is the projection of fragile_units, for both forms of the threshold
+    for kw in (dict(thr=1e-2), dict(thr=1e-4), dict(rel=1e-3), dict()):
+        assert sorted(set(s for s, _, _ in O.fragile_units(cache, **kw))) == np.nonzero(O.fragile_samples(cache, **kw))[0].tolist(), kw
+    # the restriction to some samples is those samples' share of the gradient
+    parts = sum(O.backward(spec, flat, O.sample_cache(cache, [b]), dq[b:b + 1]) for b in range(B))
+    assert np.allclose(parts, g0, rtol=0, atol=1e-12 * np.abs(g0).max())
+    with pytest.raises(AssertionError):
+        O.backward(spec, flat, cache, dq, relu_on={(0, 4, 0): True})           # Dense(|A|) is linear: it has no bit to set
+
+
+@pytest.mark.parametrize("layer", [0, 1, 2, 3])
+def test_forced_relu_bit_equals_autograd_with_the_pre_activation_nudged(layer):
+    """backward(relu_on={unit: on / off}) against torch float64 autograd of the same network with that unit's pre-activation nudged to +-1e-3: the unit's bias
+    is shifted so that its pre-activation is 0 (to round-off), torch evaluates relu(z + d) - relu(d) with the constant d = +-1e-3 on that unit only -- the
+    gate of the nudged pre-activation, the activation value of the un-nudged one -- and the whole gradient agrees to 1e-11.  The two bits give different
+    gradients (the unit chosen is kept by dropout and feeds units that are on)."""
+    shape, A = SPECS["c3"]
+    spec = O.QNetSpec(shape, C_LAYERS, FF_LAYERS, A)
+    rng = np.random.RandomState(8)
+    flat = O.glorot_init(spec, (1, 2)).astype(np.float64) + rng.randn(spec.n_params) * 0.01
+    B, s = 4, 2
+    obs = (rng.rand(B, *shape) < 0.3).astype(np.float64)
+    keep = [O.dropout_keep_mask((1, 2), 7, np.arange(B), 512, 0.2)]
+    _, cache = O.forward(spec, flat, obs, training=True, keep_masks=keep)
+    z = cache["layers"][layer]["z"].reshape(B, -1)
+    ok = keep[0][s] if layer == 3 else np.ones(z.shape[1], bool)
+    u = int(np.nonzero(ok)[0][np.argmin(np.abs(z[s][ok]))])                    # the unit nearest to 0: the smallest shift
+    shapes, o = spec.param_shapes(), 0
+    for k, b in shapes[:layer]:
+        o += int(np.prod(k)) + int(np.prod(b))
+    flat[o + int(np.prod(shapes[layer][0])) + u % shapes[layer][1][0]] -= z[s, u]      # the unit's channel is the fastest index of both layouts
+    _, cache = O.forward(spec, flat, obs, training=True, keep_masks=keep)
+    assert abs(cache["layers"][layer]["z"].reshape(B, -1)[s, u]) < 1e-14
+    dq = rng.randn(B, A)
+    grads = {}
+    for bit in (True, False):
+        def act(li, zt, bit=bit):
+            d = torch.zeros_like(zt)
+            if li == layer:
+                d[_torch_unit(spec, layer, s, u)] = 1e-3 if bit else -1e-3
+            return torch.relu(zt + d) - torch.relu(d)
+        tp = torch.tensor(flat, dtype=torch.float64, requires_grad=True)
+        tq = torch_forward(spec, tp, torch.tensor(obs), [torch.tensor(k) for k in keep], act=act)
+        (tq * torch.tensor(dq)).sum().backward()
+        grads[bit] = O.backward(spec, flat, cache, dq, relu_on={(s, layer, u): bit})
+        assert np.allclose(grads[bit], tp.grad.numpy(), rtol=0, atol=1e-11), (layer, bit)
+    assert np.abs(grads[True] - grads[False]).max() > 1e-4 * np.abs(grads[True]).max()
+
+
+@pytest.fixture(scope="module")
+def stand_in():
+    """An fp32 implementation standing in for the device: oracle/torch_dqn.py's forward (torch-CPU fp32, autograd) on the GPU tests' random c3 network
+    and observations, a batch of 450 (five fragile samples, one in each ReLU layer at least) with the training forward's dropout; backward_one(dq) is its gradient of sum(dq * Q)."""
+    from oracle import torch_dqn
+    shape, A = SPECS["c3"]
+    spec = O.QNetSpec(shape, C_LAYERS, FF_LAYERS, A)
+    rng = np.random.RandomState(5)
+    flat = O.glorot_init(spec, (11, 22))
+    flat = flat + (rng.randn(flat.size) * 0.02).astype(np.float32)
+    B = 450
+    obs = (rng.rand(B, *shape) < 0.3).astype(np.uint8)
+    keep = O.dropout_keep_mask((3, 4), 99, 12345 + np.arange(B), 512, 0.2)
+    _, cache = O.forward(spec, flat, obs, training=True, keep_masks=[keep])
+    learner = torch_dqn.TorchDQN(spec, flat)
+    q = learner.forward(learner.params, obs, keep=keep)
+
+    def backward_one(dq):
+        return learner.flat(torch.autograd.grad((q * torch.from_numpy(np.asarray(dq, np.float32))).sum(), learner.params, retain_graph=True))
+
+    def flipped(dq, flip):
+        """The same fp32 gradient with the gate of the one unit flip = (sample, layer, unit) inverted (activation values unchanged)."""
+        def act(li, zt):
+            gate = (zt > 0)
+            if li == flip[1]:
+                gate = gate.clone()
+                i = _torch_unit(spec, *((flip[1], flip[0], flip[2])))
+                gate[i] = ~gate[i]
+            return torch.relu(zt).detach() + (zt - zt.detach()) * gate.to(zt.dtype)
+        tp = torch.tensor(flat, dtype=torch.float32, requires_grad=True)
+        tq = torch_forward(spec, tp, torch.from_numpy(obs).float(), [torch.from_numpy(keep)], act=act)
+        (tq * torch.from_numpy(np.asarray(dq, np.float32))).sum().backward()
+        return tp.grad.numpy().astype(np.float64)
+
+    return dict(spec=spec, flat=flat, obs=obs, keep=keep, cache=cache, B=B, A=A, backward_one=backward_one, flipped=flipped,
+                units=O.fragile_units(cache, thr=1e-6))
+
+
+def test_relu_choices_of_an_fp32_stand_in_are_identified_and_the_full_gradient_matches(stand_in):
+    """The method of the large-batch GPU gradient tests, with torch-CPU fp32 in the device's place: every fragile sample's on / off bits are identified from
+    one-sample backwards, and the gradient of the FULL minibatch -- no sample zeroed -- equals the oracle's under those bits at the GPU tests' tolerances."""
+    import relu_choices
+    S = stand_in
+    spec, flat, cache, B, A = S["spec"], S["flat"], S["cache"], S["B"], S["A"]
+    fragile = O.fragile_samples(cache, thr=1e-6)
+    assert fragile.sum() >= 3 and sorted(set(u[0] for u in S["units"])) == np.nonzero(fragile)[0].tolist()
+    choices = relu_choices.identify_relu_choices(S["backward_one"], spec, flat, cache, S["units"], label="torch fp32, c3 B=450")
+    assert sorted(choices) == S["units"] and choices.n_samples == fragile.sum()
+    assert choices.worst_accepted < 1e-5 < 1e-4 < choices.smallest_rejected        # (rejected assignments are off by a finite share of the gradient)
+    dq = (np.random.RandomState(6).randn(B, A) / B).astype(np.float32)
+    g = S["backward_one"](dq)
+    g_ref = O.backward(spec, flat, cache, dq.astype(np.float64), relu_on=choices)
+    assert np.abs(g - g_ref).max() < 1e-5 * max(np.abs(g_ref).max(), 1.0), (np.abs(g - g_ref).max(), np.abs(g_ref).max())
+    for li, ((gk, gb), (rk, rb)) in enumerate(zip(spec.split(g), spec.split(g_ref))):
+        for a, b in ((gk, rk), (gb, rb)):
+            assert np.abs(a - b).max() <= 1e-4 * np.abs(b).max() + 1e-7, (li, np.abs(a - b).max(), np.abs(b).max())
+    # the stand-in is torch_forward in fp32 too (the form the mutation below flips a gate of)
+    assert np.abs(S["flipped"](dq, (-1, -1, -1)) - g).max() < 1e-5 * max(np.abs(g_ref).max(), 1.0)
+
+
+def test_relu_choice_identification_rejects_wrong_gradients(stand_in):
+    """Two mutations of the stand-in that the identification must not accept: a fragile sample whose gradient comes back as zero, and a fragile sample with
+    the gate of one of its NON-fragile units inverted (a finite error that no assignment of the near-zero units explains)."""
+    import relu_choices
+    S = stand_in
+    spec, flat, cache = S["spec"], S["flat"], S["cache"]
+    s = S["units"][0][0]
+    mine = [u for u in S["units"] if u[0] == s]
+    one = relu_choices.probe_dq(s, S["B"], S["A"])
+    assert np.abs(O.backward(spec, flat, cache, one.astype(np.float64))).max() > 0
+    with pytest.raises(AssertionError, match="fits the oracle under no"):
+        relu_choices.identify_relu_choices(lambda dq: np.zeros(spec.n_params), spec, flat, cache, mine)
+    # a kept Dense(512) unit of the same sample, far from 0 on either side
+    z, keep = cache["layers"][3]["z"][s], S["keep"][s]
+    for u in (int(np.nonzero(keep & (z > 0.05))[0][0]), int(np.nonzero(keep & (z < -0.05))[0][0])):
+        assert (s, 3, u) not in S["units"]
+        with pytest.raises(AssertionError, match="fits the oracle under no"):
+            relu_choices.identify_relu_choices(lambda dq: S["flipped"](dq, (s, 3, u)), spec, flat, cache, mine)
+    # ... and the un-mutated gradient of that sample is accepted
+    assert sorted(relu_choices.identify_relu_choices(S["backward_one"], spec, flat, cache, mine)) == mine

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import dqn_oracle as O, philox
+from relu_choices import device_relu_choices
 
 pytestmark = pytest.mark.gpu
 
@@ -156,12 +157,14 @@ def test_backward_at_baseline_batch_matches_oracle(dq, torch_mod, name, batch):
     dq_ = (rng.randn(batch, spec.n_actions) / batch).astype(np.float32)
     # A ReLU pre-activation within fp32 round-off of 0 may fall on the other side in another summation order, which changes that
     # sample's gradient by a finite amount; with ~3000 units x thousands of samples some always are.  Such samples (a few per cent)
-    # get dq = 0: they still run through every kernel, but their masks cannot matter.
+    # get dq = 0 first: they still run through every kernel, but their masks cannot matter.  Further down the same dq WITHOUT the zeroing is compared,
+    # against the oracle evaluated with the side of each such ReLU that the path under test took (tests/relu_choices.py).
     # (round 6: the threshold halved to 1e-6 -- five times the HIP paths' measured pre-activation error on unit-scale weights -- and the bound set at the measured
     # share: 1.1-2.9 % of a minibatch on these random weights (the largest: d = 7, X noise), where 2e-6 zeroed 2.6-4.3 %; profiles/r06_test_printed_lines.txt)
     fragile = O.fragile_samples(cache, thr=1e-6)
     print(f"{name} B={batch}: {fragile.mean():.3%} of the samples have a ReLU pre-activation within 1e-6 of 0")
     assert fragile.mean() < 0.032
+    dq_full = dq_.copy()
     dq_[fragile] = 0.0
     dq_t = torch.from_numpy(dq_).cuda()
     g = net.backward(params, dq_t).cpu().numpy()
@@ -188,6 +191,21 @@ def test_backward_at_baseline_batch_matches_oracle(dq, torch_mod, name, batch):
     net.forward(params, obs_t, training=True, seed=seed, t=t, sample_base=base)
     g_pl = net.backward(params, dq_t).cpu().numpy()
     assert np.abs(g_pl - g_ref).max() < 1e-5 * max(np.abs(g_ref).max(), 1.0)
+    # every sample compared: the full dq on both paths, the oracle taking each path's own side of the near-zero ReLUs (identified per path from
+    # one-sample backwards; a sample whose gradient fits no assignment fails there)
+    dq_full_t = torch.from_numpy(dq_full).cuda()
+    for fused in (True, False):
+        net.set_fused(fused)
+        path = "fused" if fused else "per-layer"
+        choices = device_relu_choices(net, params, spec, flat, obs, keep, lambda: net.forward(params, obs_t, training=True, seed=seed, t=t, sample_base=base),
+                                      thr=1e-6, cache=cache, label=f"{name} B={batch} {path}")
+        assert choices.n_samples == fragile.sum()
+        g = net.backward(params, dq_full_t).cpu().numpy()
+        g_ref = O.backward(spec, flat, cache, dq_full.astype(np.float64), relu_on=choices)
+        assert np.abs(g - g_ref).max() < 1e-5 * max(np.abs(g_ref).max(), 1.0), (path, np.abs(g - g_ref).max(), np.abs(g_ref).max())
+        for li, ((gk, gb), (rk, rb)) in enumerate(zip(spec.split(g), spec.split(g_ref))):
+            for a, b in ((gk, rk), (gb, rb)):
+                assert np.abs(a - b).max() <= 1e-4 * np.abs(b).max() + 1e-7, (path, li, np.abs(a - b).max(), np.abs(b).max())
 
 
 def test_packed_weights_are_equivalent_and_must_follow_the_parameters(dq, torch_mod):

@@ -15,6 +15,7 @@ import pytest
 
 import shipped
 from oracle import dqn_oracle as O
+from relu_choices import device_relu_choices
 
 AGENTS = [("d5_x", "0.007", (6, 11, 11), 26), ("d5_dp", "0.007", (7, 11, 11), 51), ("d5_dp", "0.011", (7, 11, 11), 51)]
 
@@ -172,7 +173,8 @@ def _td_like_dq(rng, B, A, lo=1.0, hi=50.0):
 def test_backward_parity_on_shipped_weights(dq, torch_mod, family, p, shape, A):
     """Training forward (dropout on) + backward on the shipped agent with TD errors of 1 - 50: both HIP paths against the float64 oracle,
     1e-5 of the largest gradient element overall and 1e-4 per layer.  Samples with a ReLU pre-activation within fp32 round-off of zero
-    (scale-aware threshold, a few per cent) get dq = 0."""
+    (scale-aware threshold, a few per cent) get dq = 0 in the first comparison; the second takes the full dq, against the oracle evaluated with the side
+    of each such ReLU that the path under test took (tests/relu_choices.py)."""
     torch = torch_mod
     _, flat = shipped.shipped_weights(family, p)
     spec = _spec(shape, A)
@@ -186,25 +188,35 @@ def test_backward_parity_on_shipped_weights(dq, torch_mod, family, p, shape, A):
     fragile = O.fragile_samples(cache, rel=1e-6)
     print(f"{family}/{p}: {fragile.mean():.2%} fragile samples")
     assert fragile.mean() < 0.02                                                            # (measured 0.7 - 1.3 %)
+    dq_full = dq_.copy()
     dq_[fragile] = 0.0
     g_ref = O.backward(spec, flat, cache, dq_.astype(np.float64))
     net, params = _net(dq, torch, shape, A, flat, B)
-    obs_t, dq_t = torch.from_numpy(obs).cuda(), torch.from_numpy(dq_).cuda()
+    obs_t, dq_t, dq_full_t = torch.from_numpy(obs).cuda(), torch.from_numpy(dq_).cuda(), torch.from_numpy(dq_full).cuda()
+
+    def compare(fused, what, ref, dq_dev):
+        for declared in ((1.0 / B, 0.0) if fused else (0.0,)):              # S from the declared loss scale (the loop's) / from max |dq|
+            net.set_grad_scale(declared)
+            g = net.backward(params, dq_dev).cpu().numpy()
+            net.set_grad_scale(0.0)
+            net.check_range()
+            err = np.abs(g - ref).max()
+            print(f"  {'fused' if fused else 'per-layer'} (declared scale {declared:g}, {what}): max |g| {np.abs(ref).max():.3e}  max abs error {err:.2e}")
+            assert err < 1e-5 * max(np.abs(ref).max(), 1.0)
+            for li, ((gk, gb), (rk, rb)) in enumerate(zip(spec.split(g), spec.split(ref))):
+                for a, b in ((gk, rk), (gb, rb)):
+                    assert np.abs(a - b).max() <= 1e-4 * np.abs(b).max() + 1e-7, (fused, what, li, np.abs(a - b).max(), np.abs(b).max())
+
     for fused in (True, False):
         net.set_fused(fused)
         q = net.forward(params, obs_t, training=True, seed=seed, t=t, sample_base=base).cpu().numpy()
         assert np.abs(q - q_ref).max() < scale_tol(q_ref)
-        for declared in ((1.0 / B, 0.0) if fused else (0.0,)):              # S from the declared loss scale (the loop's) / from max |dq|
-            net.set_grad_scale(declared)
-            g = net.backward(params, dq_t).cpu().numpy()
-            net.set_grad_scale(0.0)
-            net.check_range()
-            err = np.abs(g - g_ref).max()
-            print(f"  {'fused' if fused else 'per-layer'} (declared scale {declared:g}): max |g| {np.abs(g_ref).max():.3e}  max abs error {err:.2e}")
-            assert err < 1e-5 * max(np.abs(g_ref).max(), 1.0)
-            for li, ((gk, gb), (rk, rb)) in enumerate(zip(spec.split(g), spec.split(g_ref))):
-                for a, b in ((gk, rk), (gb, rb)):
-                    assert np.abs(a - b).max() <= 1e-4 * np.abs(b).max() + 1e-7, (fused, li, np.abs(a - b).max(), np.abs(b).max())
+        compare(fused, "fragile samples zeroed", g_ref, dq_t)
+        # every sample compared: the oracle takes this path's own side of the near-zero ReLUs
+        choices = device_relu_choices(net, params, spec, flat, obs, keep, lambda: net.forward(params, obs_t, training=True, seed=seed, t=t, sample_base=base),
+                                      rel=1e-6, cache=cache, label=f"{family}/{p} B={B} {'fused' if fused else 'per-layer'}")
+        assert choices.n_samples == fragile.sum()
+        compare(fused, "every sample", O.backward(spec, flat, cache, dq_full.astype(np.float64), relu_on=choices), dq_full_t)
 
 
 @pytest.mark.gpu
@@ -231,7 +243,12 @@ def test_td_errors_beyond_the_fused_range_raise_range_error(dq, torch_mod):
     seed, t = (1, 2), 7
     keep = O.dropout_keep_mask(seed, t, np.arange(B), 512, 0.2)
     q0_ref, cache = O.forward(spec, flat, obs, training=True, keep_masks=[keep])
-    fragile = O.fragile_samples(cache, rel=1e-6)
+    # dq is formed inside the launch, so no sample can be given dq = 0: the oracle takes the fused path's own side of every ReLU whose pre-activation is
+    # within fp32 round-off of 0 instead (8 of the 256 samples have one), read back once from the training forward every launch below repeats
+    assert O.fragile_samples(cache, rel=1e-6).any()
+    net.set_fused(True)
+    choices = device_relu_choices(net, params, spec, flat, obs, keep, lambda: net.forward(params, obs_t, training=True, seed=seed, t=t), rel=1e-6,
+                                  cache=cache, label="d5_dp/0.011 B=256 fused")
 
     def run(td_size, fused, auto_scale=False):
         """One td_backward_adam with Q_target(s1) = -td_size / gamma everywhere, i.e. a TD error of Q(s0)[a] + td_size."""
@@ -250,28 +267,25 @@ def test_td_errors_beyond_the_fused_range_raise_range_error(dq, torch_mod):
     for td_size in (1e-3, 1.0, 1000.0, 1e4, 1e6):
         p_, g_, dq_ = run(td_size, True, auto_scale=True)
         net.check_range()
-        dq_np = dq_.cpu().numpy().astype(np.float64)
-        dq_np[fragile] = 0.0
-        g_ref = O.backward(spec, flat, cache, dq_np)
+        g_ref = O.backward(spec, flat, cache, dq_.cpu().numpy().astype(np.float64), relu_on=choices)
         assert torch.isfinite(g_).all() and torch.isfinite(p_).all() and not torch.equal(p_, params)
-        if not fragile.any():
-            err = np.abs(g_.cpu().numpy() - g_ref).max()
-            print(f"TD error ~{td_size:g}, measured scale: max |g| {np.abs(g_ref).max():.3e}, max abs error {err:.2e}")
-            assert err < 1e-5 * np.abs(g_ref).max()
-            for (gk, gb), (rk, rb) in zip(spec.split(g_.cpu().numpy()), spec.split(g_ref)):
-                for a_, b_ in ((gk, rk), (gb, rb)):
-                    assert np.abs(a_ - b_).max() <= 1e-4 * np.abs(b_).max() + 1e-7 * np.abs(g_ref).max()
+        err = np.abs(g_.cpu().numpy() - g_ref).max()
+        print(f"TD error ~{td_size:g}, measured scale: max |g| {np.abs(g_ref).max():.3e}, max abs error {err:.2e}")
+        assert err < 1e-5 * np.abs(g_ref).max()
+        for (gk, gb), (rk, rb) in zip(spec.split(g_.cpu().numpy()), spec.split(g_ref)):
+            for a_, b_ in ((gk, rk), (gb, rb)):
+                assert np.abs(a_ - b_).max() <= 1e-4 * np.abs(b_).max() + 1e-7 * np.abs(g_ref).max()
     # ... and with the HOST-KNOWN scale (auto_scale = 0, S x grad_scale in [4, 8)):
 
     # inside the range: handled, equal to the oracle
     p_, g_, dq_ = run(1000.0, True)
     net.check_range()
     dq_np = dq_.cpu().numpy().astype(np.float64)
-    dq_np[fragile] = 0.0
     assert np.abs(dq_np).max() * B > 900.0
-    g_ref = O.backward(spec, flat, cache, dq_np)
-    if not fragile.any():
-        assert np.abs(g_.cpu().numpy() - g_ref).max() < 1e-5 * np.abs(g_ref).max()
+    g_ref = O.backward(spec, flat, cache, dq_np, relu_on=choices)
+    err = np.abs(g_.cpu().numpy() - g_ref).max()
+    print(f"TD error ~1000, host-known scale: max |g| {np.abs(g_ref).max():.3e}, max abs error {err:.2e}")
+    assert err < 1e-5 * np.abs(g_ref).max()
     assert torch.isfinite(p_).all() and not torch.equal(p_, params)
     # beyond it: reported, not applied, flag cleared by the report
     for td_size in (1e4, 1e6):
