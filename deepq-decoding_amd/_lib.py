@@ -159,6 +159,7 @@ SIGNATURES = {
     "dq_qnet_range_check": (_i, [_vp, _vp]),
     "dq_qnet_range_discarded": (_i, [_vp, ctypes.POINTER(ctypes.c_uint), _vp]),
     "dq_qnet_fused_supported": (_i, [_vp]),
+    "dq_qnet_fused_backward_supported": (_i, [_vp]),
     "dq_qnet_set_patch_input": (_i, [_vp, _i, _i]),
     "dq_qnet_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _seedp, _u64, _u32, _vp, _vp]),
     "dq_qnet_forward_multi": (_i, [_vp, _i, ctypes.POINTER(QNetJob), _vp]),

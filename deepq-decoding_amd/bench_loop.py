@@ -133,6 +133,16 @@ class FullLoop:
         if self.mode == "act":
             assert self.net.fused_supported
             return {"conv_chain_kernel": (1, 2.0 * conv * fwd_samples, "mfma"), "dense_chain_kernel": (1, 2.0 * dense * fwd_samples, "mfma")}
+        if self.net.fused_supported and not self.net.fused_backward_supported:
+            # forward fused, backward not (QNetwork.fused_backward_supported): the acting, target and online forwards share one fused launch pair per update;
+            # the training forward, the data gradients and the weight gradients are the per-layer kernels'
+            train = self.B * k
+            return {
+                "conv_chain_kernel": (k, 2.0 * conv * (fwd_samples - train), "mfma"),
+                "dense_chain_kernel": (k, 2.0 * dense * (fwd_samples - train), "mfma"),
+                "gemm_fwd_kernel": ((2 * len(lm) - 1) * k, 2.0 * self.macs * train + 2.0 * (self.macs - lm[0]) * train, "mfma"),
+                "gemm_wgrad_kernel": (len(lm) * k, 2.0 * self.macs * train, "mfma"),
+            }
         if self.net.fused_supported:
             # one forward launch pair per step (the acting forward and the update's three forwards share it), one launch per
             # backward kernel
@@ -182,6 +192,8 @@ class FullLoop:
             if os.environ.get("DQ_CONV_FORM", "w")[:1] != "g" and os.environ.get("DQ_CONV_BWD_A1", "r")[:1] != "s":
                 # round 6: a1 recomputed from the patch words (26 rows per sample x K 32 x 64 channels, one MFMA per weight piece) instead of read back from HBM
                 conv_bwd += 2.0 * 26 * 32 * 64 / (conv + rest)
+        if not self.net.fused_backward_supported:                    # (the backward runs per layer, on the f32 pipe)
+            return {"conv_chain_kernel": conv_fwd, "dense_chain_kernel": 3.0}
         return {"conv_chain_kernel": conv_fwd,
                 "conv_bwd_chain_kernel": conv_bwd,
                 "dense_chain_kernel": 3.0, "dense_bwd_chain_kernel": 3.0, "dense_wgrad_kernel": 3.0}

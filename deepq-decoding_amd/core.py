@@ -95,7 +95,7 @@ class DQNCore:
         # configuration; DQ_COMPACT_OBS=0 (or compact=False) keeps the uint8 ring.
         if compact is None:
             compact = os.environ.get("DQ_COMPACT_OBS", "1") != "0"
-        compact = bool(compact and not self._wide and getattr(env, "patch_supported", False) and net.fused_supported
+        compact = bool(compact and not self._wide and getattr(env, "patch_supported", False) and net.fused_backward_supported
                        and net.fused_enabled and C == env.volume_depth + env.n_action_layers and net.c_layers[0][1:] == [3, 2])
         if compact:
             try:
@@ -159,6 +159,12 @@ class DQNCore:
     # ------------------------------------------------------------------------------------------------------
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _fused_update(self):
+        """The update's launches run on the fused chains: they cover the network's BACKWARD (a narrower set than the forward's,
+        QNetwork.fused_backward_supported) and are switched on.  What the riding environment step, the paired / ahead-of-time target forwards and the
+        compact ring are decided on: each of them is a property of the fused training forward or backward."""
+        return self.net.fused_backward_supported and self.net.fused_enabled
 
     # the ring's fields under the names bench.py, agent.py, the tests and tools/ use (obs_ring: uint8 [T, N, C, H, W], the tensor or -- compact
     # ring -- an ObsRingView; patch_ring: the compact ring's words, else None)
@@ -353,12 +359,12 @@ class DQNCore:
         r = self.ring
         _q.replay_sample_multi(r.terminal, self.N, r.T, r.cur, r.filled, B, self.seed, self.updates + 1, k - 1,
                                sample_base=sample_base, out=self._index_multi)
-        if not (self.target_ahead and self.net.fused_supported and self.net.fused_enabled):
+        if not (self.target_ahead and self._fused_update()):
             # The target network does not change inside a vector step and the rows of all these updates are known, so Q_target(s1) of update i + 1 needs
             # nothing update i produces: updates go in PAIRS -- the first one's launch pair carries four forwards (its own three and the second's target
             # forward), the second one's two.  At c3 the wave-private convolution kernel then runs 2 + 1 whole trips per pair of updates where three
             # forwards per launch are 1.5 trips timed as 2 each, and the dense kernel fills the chip (256 workgroups) instead of 192.
-            if self.pair_targets and self.net.fused_supported and self.net.fused_enabled:
+            if self.pair_targets and self._fused_update():
                 if self._q1_pair is None:
                     self._q1_pair = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
                 i = 0
@@ -585,15 +591,14 @@ class DQNCore:
         self.last_index = self.index
         jobs = self._update_jobs(t, sample_base)
         jobs.append(self._obs_job(params=self.params, slot=cur, batch=N, out=self.q_act, packed=self.params_pk))
-        self.net.forward_multi(jobs)
+        self.net.forward_multi(jobs)      # (fused forward, per-layer backward: the inference jobs share one fused launch pair, the training job runs per layer)
         sj = None
         if extra_updates > 0:                    # the next update runs on THIS step's ring: the environment launch draws its minibatch
             sj = self._sample_job(t + 1, nxt, filled)
         elif presample_next:
             sj = self._sample_job(t + 1, r.next_slot(2), r.filled_after(2))
         side = self._env_side
-        ride = self.ride_env and side is None and self.net.fused_supported and self.net.fused_enabled and not self._wide \
-            and not getattr(env, "mlp_referee", False)
+        ride = self.ride_env and side is None and self._fused_update() and not self._wide and not getattr(env, "mlp_referee", False)
         # riding: one launch fewer per step -- the environment step (+ look-ahead sampling + this step's episode bookkeeping) rides on the
         # dense backward's first kernel (dq_qnet_td_backward_adam_env / _phase0_env): neither needs the other's results
         step = self._env_step(self.q_act, eps, masked_greedy, sj, self.stats if ride and record_stats else None)

@@ -1795,7 +1795,8 @@ bool fused_backward_supported(const dq_qnet* Q) {
 static inline size_t dense_pstride(const dq_qnet* Q) { return (Q->n_params + 31) & ~(size_t)31; }
 // floats of workspace the fused backward needs: [DENSE_WGRAD_SLICES][n_params] dense partials, then [CONV_BWD_MAX_WGS][conv params]
 size_t fused_backward_workspace_floats(const dq_qnet* Q) {
-    if (!fused_backward_supported(Q)) return 0;
+    // (forward fused, backward not: the eight tail words only -- the fused FORWARD's range guard reports through the range word whatever path the backward takes)
+    if (!fused_backward_supported(Q)) return fused_forward_supported(Q) ? 8 : 0;
     return (size_t)DENSE_WGRAD_SLICES * dense_pstride(Q) + (size_t)CONV_BWD_MAX_WGS * Q->L[Q->cfg.n_conv].w_off + 8;     // + {S, 1/S}: GradScale, the range flag, a spare word, td_scale_kernel's two work words, two spare
 }
 
@@ -1806,7 +1807,7 @@ bool conv_bwd16_applies(const dq_qnet* Q, int B, bool patch) {
 
 unsigned* fused_range_flag(const dq_qnet* Q) {
     if (!Q->fpartial) return nullptr;
-    return reinterpret_cast<unsigned*>(Q->fpartial + (size_t)DENSE_WGRAD_SLICES * dense_pstride(Q) + (size_t)CONV_BWD_MAX_WGS * Q->L[Q->cfg.n_conv].w_off) + 2;
+    return reinterpret_cast<unsigned*>(Q->ftail) + 2;
 }
 
 typedef void (*conv_bwd_kernel_t)(ConvBwdArgs);

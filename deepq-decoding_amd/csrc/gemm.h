@@ -47,9 +47,11 @@ struct Epilogue {
     float mask_scale;
     float keep_scale;                 // EPI_DROPOUT: y = keep ? y * keep_scale : 0  (keep_scale = 1/(1-rate))
     u32 drop_T;                       //   dropped iff the unit's 16-bit draw < drop_T (dq_rate_threshold16)
-    u32 seed0, seed1;                 //   word = Philox(key=seed, ctr=(t_lo, t_hi, sample_base + m, (n>>2) | DROPOUT<<16))[n&3]
+    u32 seed0, seed1;                 //   half-word n & 7 of Philox(key=seed, ctr=(t_lo, t_hi, sample_base + m, (n>>3) | DROPOUT<<16 | drop_layer<<24))
     u64 t;
     u32 sample_base;
+    u32 drop_layer;                   //   ordinal of this dropout layer among the network's (0 for the first: its draws are what they were before the
+                                      //   ordinal existed, and what the fused chains and keep_bits draw); two layers of equal rate drop independent units
 };
 
 struct RowRef { unsigned off; int yx; };   // yx = y << 16 | x, or -1 for a row past M
@@ -134,7 +136,7 @@ __device__ __forceinline__ void epilogue_store(const Epilogue& e, int m, int n, 
     if (e.flags & EPI_DROPOUT) {
         u32 w[4];
         // one Philox call = eight consecutive units of a sample: unit n draws half-word n & 7 (word (n & 7) >> 1, low half first)
-        philox4x32_10((u32)e.t, (u32)(e.t >> 32), e.sample_base + (u32)m, ((u32)n >> 3) | ((u32)DQ_STREAM_DROPOUT << 16), e.seed0, e.seed1, w);
+        philox4x32_10((u32)e.t, (u32)(e.t >> 32), e.sample_base + (u32)m, ((u32)n >> 3) | ((u32)DQ_STREAM_DROPOUT << 16) | (e.drop_layer << 24), e.seed0, e.seed1, w);
         const int wi = (n & 7) >> 1;
         const u32 word = wi == 0 ? w[0] : wi == 1 ? w[1] : wi == 2 ? w[2] : w[3];
         v = (((word >> (16 * (n & 1))) & 0xffffu) < e.drop_T) ? 0.f : v * e.keep_scale;

@@ -51,6 +51,7 @@ struct dq_qnet {
     void* pk_scratch[FWD_MAX_JOBS];  // packed weights of jobs that did not bring their own (dq_qnet_job.packed_dev == NULL)
     const void* last_train_packed;   // packed weights of the last training forward (the backward's data gradients read them)
     float* fpartial;             // fused backward workspace (fused_backward_workspace_floats)
+    float* ftail;                // its last eight words ({S, 1/S}, the range word, ...: fused_range_flag); all there is of it where only the forward is fused
     unsigned short* planes;      // f16 piece planes (h plane, then l plane) of the training forward's / backward's operands of the dense
                                  // weight gradients, row-major [max_batch][ld]: x (ld K1), h1 (512), gh1 (512), then gy2, g3, y2 (ld
                                  // dq_planes_small_ld: 64 or 128; columns past the tensor's width hold anything finite or not -- they only
@@ -355,7 +356,7 @@ dq_status layer_dgrad(dq_qnet* Q, const float* params_dev, int layer, hipStream_
 // fused_bwd.hip: fused backward (data-gradient chains + all-layer weight gradients) for the same configurations
 bool fused_backward_supported(const dq_qnet* Q);
 size_t fused_backward_workspace_floats(const dq_qnet* Q);
-unsigned* fused_range_flag(const dq_qnet* Q);     // device word of the range guard (dq_qnet_range_check), NULL without the fused backward
+unsigned* fused_range_flag(const dq_qnet* Q);     // device word of the range guard (dq_qnet_range_check), NULL without the fused chains
 // opt != NULL (phases == 3 only): the final reduction also applies the Adam update to p/m/v (one launch fewer per update)
 struct AdamOpt { float* p; float* m; float* v; float lr_t, b1, b2, eps; };
 // td != NULL: the TD step (dq_td_update's arithmetic) runs in the dense backward's prologue instead of reading dq_dev, and the episode

@@ -244,6 +244,17 @@ static void wgrad_slices(int M, int K, int N, int* rows_per_slice, int* slices) 
     *slices = (M + rows - 1) / rows;
 }
 
+// The most slices wgrad_slices gives for ANY M <= M_max (create() sizes the workspace with it).  The count is not monotonic in M -- it jumps up wherever
+// ceil(M / want) falls back to a lower multiple of BK --, so the count at M_max is no bound for a smaller minibatch; rows >= ceil(M / want) gives slices <= want,
+// and rows >= 2 BK gives slices <= ceil(M / (2 BK)).
+static int wgrad_max_slices(int M_max, int K, int N) {
+    const int tiles = ((K + BM - 1) / BM) * ((N + 63) / 64);
+    int want = (768 + tiles - 1) / tiles;
+    if (want < 1) want = 1;
+    const int by_rows = (M_max + 2 * BK - 1) / (2 * BK);
+    return want < by_rows ? want : by_rows;
+}
+
 static Gather dense_gather(const float* src, int K) {
     Gather g;
     memset(&g, 0, sizeof(g));
@@ -405,9 +416,7 @@ dq_status dq_qnet_create(const dq_qnet_cfg* cfg, dq_qnet** out) {
         // (+ 16 bytes: the dense weight gradient reads rows as dwordx4 that may straddle the last row's end, fused_bwd.hip)
         for (int s = 0; s < 2 && e == hipSuccess; ++s) e = hipMalloc(&Q->act[s][i], floats * sizeof(float) + 16);
         if (e == hipSuccess) e = hipMalloc(&Q->gz[i], floats * sizeof(float) + 16);
-        int rps, slices;
-        wgrad_slices(cfg->max_batch * L.rows, L.K, L.N, &rps, &slices);
-        const size_t p = (size_t)slices * ((size_t)L.K * L.N + L.N);
+        const size_t p = (size_t)wgrad_max_slices(cfg->max_batch * L.rows, L.K, L.N) * ((size_t)L.K * L.N + L.N);
         max_partial = p > max_partial ? p : max_partial;
     }
     if (e == hipSuccess) e = hipMalloc(&Q->partial, max_partial * sizeof(float));
@@ -440,7 +449,8 @@ dq_status dq_qnet_create(const dq_qnet_cfg* cfg, dq_qnet** out) {
     const size_t fws = fused_backward_workspace_floats(Q);
     if (e == hipSuccess && fused_forward_supported(Q)) e = hipMalloc(&Q->keep_bits, (size_t)Q->cfg.max_batch * 16 * sizeof(u32));
     if (e == hipSuccess && fws) e = hipMalloc(&Q->fpartial, fws * sizeof(float));
-    if (e == hipSuccess && fws) e = hipMemset(Q->fpartial + fws - 8, 0, 8 * sizeof(float));       // {S, 1/S}, range flag, skip word; td_scale_kernel's two work words, discarded-update count, spare
+    if (e == hipSuccess && fws) Q->ftail = Q->fpartial + fws - 8;
+    if (e == hipSuccess && fws) e = hipMemset(Q->ftail, 0, 8 * sizeof(float));       // {S, 1/S}, range flag, skip word; td_scale_kernel's two work words, discarded-update count, spare
     Q->partial_floats = max_partial;
     if (e != hipSuccess) { dq_set_error("dq_qnet_create: %s", hipGetErrorString(e)); dq_qnet_destroy(Q); return DQ_ERR_HIP; }
     *out = Q;
@@ -540,6 +550,7 @@ dq_status dq_qnet_range_discarded(dq_qnet* Q, unsigned* count, void* stream) {
 }
 
 int dq_qnet_fused_supported(const dq_qnet* Q) { return Q && fused_forward_supported(Q) ? 1 : 0; }
+int dq_qnet_fused_backward_supported(const dq_qnet* Q) { return Q && fused_backward_supported(Q) ? 1 : 0; }
 
 dq_status dq_qnet_set_patch_input(dq_qnet* Q, int n_syndrome_planes, int stride_words) {
     DQ_REQUIRE(Q, DQ_ERR_INVALID, "dq_qnet_set_patch_input: null handle");
@@ -583,6 +594,7 @@ dq_status dq_qnet_forward(dq_qnet* Q, const float* params_dev, const uint8_t* ob
         jb.t = t; jb.sample_base = sample_base; jb.q_dev = q_dev;
         return fused_forward_multi(Q, 1, &jb, st);
     }
+    u32 drop_layer = 0;                                             // dropout layers met so far (Epilogue.drop_layer)
     for (int i = 0; i < Q->n_layers; ++i) {
         const Layer& L = Q->L[i];
         const int M = batch * L.rows;
@@ -615,7 +627,9 @@ dq_status dq_qnet_forward(dq_qnet* Q, const float* params_dev, const uint8_t* ob
             ep.keep_scale = (float)(1.0 / (1.0 - (double)L.dropout));
             ep.drop_T = dq_rate_threshold16((double)L.dropout);
             ep.seed0 = seed[0]; ep.seed1 = seed[1]; ep.t = t; ep.sample_base = sample_base;
+            ep.drop_layer = drop_layer;
         }
+        if (L.dropout > 0.f) ++drop_layer;                          // (counted in inference too: the ordinal belongs to the layer, not to the call)
         launch_fwd(ga, gb, ep, M, L.N, L.K, st);
         DQ_LAUNCH_CHECK();
         x = Q->act[set][i];
@@ -648,6 +662,24 @@ dq_status dq_qnet_forward_multi(dq_qnet* Q, int n_jobs, const dq_qnet_job* jobs,
     int n_train = 0;
     for (int i = 0; i < n_jobs; ++i) n_train += jobs[i].training ? 1 : 0;
     DQ_REQUIRE(n_train <= 1, DQ_ERR_INVALID, "dq_qnet_forward_multi: at most one training job per launch");
+    if (Q->use_fused && fused_forward_supported(Q) && any_train && n_jobs <= FWD_MAX_JOBS + 1) {
+        // Forward fused, backward not (dq_qnet_fused_backward_supported): the INFERENCE jobs of the call share one fused launch pair, with the packed weights
+        // they brought -- each the kernels and the bits of a call of its own --, and the training job alone runs per layer, the path its backward will take.
+        dq_qnet_job inf[FWD_MAX_JOBS];
+        const dq_qnet_job* tr = nullptr;
+        int n_inf = 0;
+        for (int i = 0; i < n_jobs; ++i) {
+            if (jobs[i].training) tr = &jobs[i];
+            else inf[n_inf++] = jobs[i];
+        }
+        DQ_REQUIRE(!(tr->reserved & 1u), DQ_ERR_UNSUPPORTED, "dq_qnet_forward_multi: patch-word input is read by the fused chains only");
+        if (n_inf) {
+            const dq_status rc = fused_forward_multi(Q, n_inf, inf, (hipStream_t)stream);
+            if (rc != DQ_OK) return rc;
+        }
+        return dq_qnet_forward(Q, tr->params_dev, tr->obs_dev, tr->index_dev, tr->index_off, tr->index_mod, tr->batch, 1, tr->seed, tr->t, tr->sample_base,
+                               tr->q_dev, stream);
+    }
     for (int i = 0; i < n_jobs; ++i)
         DQ_REQUIRE(!(jobs[i].reserved & 1u), DQ_ERR_UNSUPPORTED, "dq_qnet_forward_multi: patch-word input is read by the fused chains only");
     for (int i = 0; i < n_jobs; ++i) {                             // per-layer path: one forward after the other
@@ -833,7 +865,10 @@ dq_status dq_qnet_td_backward_adam_env(dq_qnet* Q, float* params_dev, const dq_t
 dq_status dq_qnet_adam_step(dq_qnet* Q, float* params_dev, const float* grads_dev, float* m_dev, float* v_dev, double lr, double beta_1, double beta_2,
                             double epsilon, uint64_t t, void* stream) {
     DQ_REQUIRE(Q, DQ_ERR_INVALID, "dq_qnet_adam_step: null handle");
-    return adam_step_flagged(params_dev, grads_dev, m_dev, v_dev, Q->n_params, lr, beta_1, beta_2, epsilon, t, fused_range_flag(Q), (hipStream_t)stream);
+    // (the guard belongs to the fused BACKWARD's gradients: a handle whose backward runs per layer -- f32 throughout -- propagates a non-finite gradient as
+    // dq_adam_step and Keras do, also where its fused forward has a range word of its own)
+    unsigned* flag = Q->fpartial != Q->ftail ? fused_range_flag(Q) : nullptr;
+    return adam_step_flagged(params_dev, grads_dev, m_dev, v_dev, Q->n_params, lr, beta_1, beta_2, epsilon, t, flag, (hipStream_t)stream);
 }
 
 dq_status dq_qnet_td_backward_adam(dq_qnet* Q, float* params_dev, const dq_td_job* td, float* grads_dev, float* m_dev, float* v_dev, double lr,

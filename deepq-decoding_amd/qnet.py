@@ -47,6 +47,9 @@ class QNetwork:
         self.n_params = int(self.L.dq_qnet_param_count(self._h))
         self.n_conv_params = int(self.L.dq_qnet_conv_param_count(self._h))     # flat layout: convolutions first, then the dense layers
         self.packed_bytes = int(self.L.dq_qnet_packed_bytes(self._h))          # 0 when the fused chains do not cover the architecture
+        # (properties of the configuration, asked once: DQNCore reads them in every step)
+        self._fused_fwd = bool(self.L.dq_qnet_fused_supported(self._h))
+        self._fused_bwd = bool(self.L.dq_qnet_fused_backward_supported(self._h))
         self.layers = []
         for i in range(self.L.dq_qnet_num_layers(self._h)):
             ko, bo, shape, nd = ctypes.c_int64(), ctypes.c_int64(), (ctypes.c_int32 * 4)(), ctypes.c_int32()
@@ -99,7 +102,15 @@ class QNetwork:
 
     @property
     def fused_supported(self):
-        return bool(self.L.dq_qnet_fused_supported(self._h))
+        """The fused chains cover this network's forward: inference jobs run on them (as long as set_fused() leaves them on)."""
+        return self._fused_fwd
+
+    @property
+    def fused_backward_supported(self):
+        """... and its backward too (a narrower set, include/deepq_hip.h dq_qnet_fused_backward_supported).  Where only the forward is covered, every
+        training forward and every backward runs per layer -- the inference jobs of a forward_multi call with a training job still share one fused
+        launch pair --, and the calls that carry the environment step are refused."""
+        return self._fused_bwd
 
     def close(self):
         if getattr(self, "_h", None):

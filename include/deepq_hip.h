@@ -370,7 +370,15 @@ dq_status dq_qnet_set_fused(dq_qnet* net, int enable);
  * (=8 -> 1, =16 -> 2) / DQ_CONV_BWD_A1 (=saved -> 1) read ONCE by dq_qnet_create; nothing re-reads the environment per call, so every rank that created its handle
  * under the same environment sums in the same order.  A/B measurements and tests.  No reference counterpart. */
 dq_status dq_qnet_set_kernel_forms(dq_qnet* net, int conv_forward_form, int conv_backward_form, int conv_backward_a1);
+/* 1 when the fused chains cover this configuration's FORWARD (inference jobs run on them, dq_qnet_pack applies). */
 int dq_qnet_fused_supported(const dq_qnet* net);
+/* 1 when they cover its BACKWARD as well -- a narrower set: at most 112 outputs in the widest head layer (111 actions with a dueling head) and observations of
+ * at most 2045 bytes.  Only then do training forwards, dq_qnet_backward* and the dq_qnet_td_backward_*_env calls take the fused chains.  Where the forward alone is
+ * covered ("mixed": e.g. d = 7 lattices with 10 input planes, 112..127 actions) every inference forward stays fused, every training forward and every backward
+ * runs per layer (f32), and the *_env calls return DQ_ERR_UNSUPPORTED.  A dq_qnet_forward_multi call with a training job then runs its inference jobs as ONE
+ * fused launch pair (with the packed weights they bring) and the training job per layer: every job gives the bits of a dq_qnet_forward call of its own.
+ * dq_qnet_range_check on such a handle reports the fused FORWARD's guard only; dq_qnet_adam_step does not guard there (it propagates like dq_adam_step). */
+int dq_qnet_fused_backward_supported(const dq_qnet* net);
 
 /* model.predict_on_batch (training == 0) / the forward half of train_on_batch (training != 0: dropout
  * active, activations kept for dq_qnet_backward).
@@ -382,9 +390,10 @@ int dq_qnet_fused_supported(const dq_qnet* net);
  *              allocation: both round sizes up to at least 256 bytes; views at arbitrary byte offsets inside it are fine);
  *   q_dev      float [batch, n_actions];
  *   dropout    one Philox call covers eight consecutive units of a sample, 16 bits per decision:
- *              keep(b, j) <=> half-word (j & 7) of Philox(key=seed, ctr=(t_lo, t_hi, sample_base + b, (j>>3) | DQ_STREAM_DROPOUT<<16))
+ *              keep(b, j) <=> half-word (j & 7) of Philox(key=seed, ctr=(t_lo, t_hi, sample_base + b, (j>>3) | DQ_STREAM_DROPOUT<<16 | l<<24))
  *              >= ceil(rate * 2^16)   (half-word h = bits 16 (h & 1) .. + 15 of word h >> 1);  kept units are scaled by
- *              1/(1-rate) (Keras K.dropout). */
+ *              1/(1-rate) (Keras K.dropout).  l = the ordinal of the dropout layer among the hidden layers with a rate > 0 (0 for the first, the only
+ *              one of the reference's stack): every dropout layer draws a mask of its own, as Keras does. */
 dq_status dq_qnet_forward(dq_qnet* net, const float* params_dev, const uint8_t* obs_dev, const int32_t* index_dev,
                           int index_off, int index_mod, int batch, int training, const uint32_t seed[2], uint64_t t,
                           uint32_t sample_base, float* q_dev, void* stream);

@@ -107,14 +107,16 @@ def glorot_init(spec, seed, stream=philox.STREAM_INIT):
     return flat
 
 
-def dropout_keep_mask(seed, t, sample_ids, n_units, rate):
+def dropout_keep_mask(seed, t, sample_ids, n_units, rate, layer=0):
     """keep[b, j] for update counter t.  One Philox call covers eight consecutive units, 16 bits per decision: unit j draws half-word
-    j & 7 (bits 16 (h & 1) .. + 15 of word h >> 1) of Philox(key=seed, ctr=(t_lo, t_hi, sample_id, (j>>3) | DROPOUT<<16)); dropped iff
-    the draw < ceil(rate * 2^16)."""
+    j & 7 (bits 16 (h & 1) .. + 15 of word h >> 1) of Philox(key=seed, ctr=(t_lo, t_hi, sample_id, (j>>3) | DROPOUT<<16 | layer<<24)); dropped
+    iff the draw < ceil(rate * 2^16).  layer: the ordinal of the dropout layer among the network's layers with a rate > 0 (0 for the first,
+    the only one of the reference's stack): Keras draws every Dropout layer's mask independently, so each gets a counter range of its own."""
+    assert 0 <= int(layer) < 4
     sample_ids = np.asarray(sample_ids, dtype=np.uint32)
     j = np.arange(n_units, dtype=np.uint32)
     words = philox.philox4x32_np(int(t) & philox.MASK, (int(t) >> 32) & philox.MASK, sample_ids[:, None],
-                                 (j[None, :] >> 3) | (philox.STREAM_DROPOUT << 16), seed)
+                                 (j[None, :] >> 3) | (philox.STREAM_DROPOUT << 16) | (int(layer) << 24), seed)
     w = np.stack(words, axis=-1)
     h = (j & 7).astype(np.int64)
     sel = np.take_along_axis(w, np.broadcast_to((h >> 1)[None, :, None], w.shape[:2] + (1,)), axis=-1)[..., 0]

@@ -40,6 +40,7 @@ def test_python_binding_covers_header(dq, built_lib):
     from importlib import import_module
     _lib = import_module("deepq-decoding_amd._lib")
     assert sorted(_lib.SIGNATURES) == _declared_functions()
+    assert "dq_qnet_fused_backward_supported" in _lib.SIGNATURES       # (what DQNCore decides the riding step, the paired targets and the compact ring on)
     L = _lib.lib()
     assert L.dq_version() >= 1
     assert isinstance(L.dq_device_count(), int)

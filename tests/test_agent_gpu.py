@@ -673,7 +673,7 @@ def test_driver_style_script_on_the_dropin_tree(dq, torch_mod, tmp_path):
         sys.path.pop(0)
 
 
-@pytest.mark.parametrize("name", ["c3", "c5", "c2", "c3-ragged", "per-layer"])
+@pytest.mark.parametrize("name", ["c3", "c5", "c2", "c3-ragged", "per-layer", "mixed"])
 def test_fused_step_equals_separate_calls_at_baseline_size(dq, torch_mod, name):
     """BASELINE.json sizes (c3 / c2: 4096 lattices and a 4096-sample minibatch; c5: d = 7, 1024 per GPU): DQNCore.step_and_update (four forwards in one pair of launches with
     32-row dense workgroups, next minibatch drawn on the environment launch, TD step inside the backward, Adam on its reduction) leaves
@@ -684,14 +684,19 @@ def test_fused_step_equals_separate_calls_at_baseline_size(dq, torch_mod, name):
               "c2": (4096, dict(d=5, error_model="X", use_Y=False, volume_depth=5, p_phys=0.007, p_meas=0.007)),
               "c3-ragged": (1003, dict(d=5, error_model="DP", use_Y=False, volume_depth=5, p_phys=0.011, p_meas=0.011)),
               # 18 input planes: outside what the fused chains cover -> the per-layer GEMM path behind the same calls
-              "per-layer": (96, dict(d=7, error_model="DP", use_Y=False, volume_depth=16, p_phys=0.004, p_meas=0.004))}[name]
+              "per-layer": (96, dict(d=7, error_model="DP", use_Y=False, volume_depth=16, p_phys=0.004, p_meas=0.004)),
+              # 10 input planes on the d = 7 image: 2250-byte observations -- the fused chains cover the forward, not the backward: the acting, target and online forwards
+              # fused, the training forward and the backward per layer, no environment step riding on the backward
+              "mixed": (96, dict(d=7, error_model="DP", use_Y=False, volume_depth=8, p_phys=0.004, p_meas=0.004))}[name]
     B = 777 if name == "c3-ragged" else N                           # neither a multiple of the 8 / 16 / 32 samples a workgroup takes
     cores = []
     for _ in range(2):
         env = dq.VectorEnv(n_envs=N, **cfg)
         net = dq.QNetwork(env.obs_shape, C_LAYERS, FF_LAYERS, env.num_actions, max_batch=N)
         assert net.fused_supported == (name != "per-layer")
+        assert net.fused_backward_supported == (name not in ("per-layer", "mixed"))
         core = dq.DQNCore(env, net, batch_size=B, memory_limit=N * 12, gamma=0.99, lr=1e-3)
+        assert core._fused_update() == net.fused_backward_supported and (name != "mixed" or not core.compact)
         core.reset_env()
         for _ in range(4):
             core.act_and_step(0.2)
@@ -709,6 +714,28 @@ def test_fused_step_equals_separate_calls_at_baseline_size(dq, torch_mod, name):
         assert torch.equal(x, y)                # (obs_ring[:]: the tensor, or the compact ring's words decoded -- core.ObsRingView)
     assert a.read_stats() == b.read_stats() and a.read_stats()[3] == 0
     assert not torch.equal(a.params, a.target)
+
+
+def test_the_loop_runs_where_only_the_forward_is_fused(dq, torch_mod):
+    """d = 7 with X noise at volume_depth 9: 10 input planes again (9 syndrome planes + 1 action plane), the other configuration whose forward is fused and
+    whose backward is not.  Three steps of the loop with two extra updates each (the paired-target form must not be taken either): finite parameters that moved,
+    a loss, and the range word clear."""
+    torch = torch_mod
+    env = dq.VectorEnv(n_envs=64, d=7, error_model="X", use_Y=False, volume_depth=9, p_phys=0.005, p_meas=0.005)
+    assert tuple(env.obs_shape) == (10, 15, 15)
+    net = dq.QNetwork(env.obs_shape, C_LAYERS, FF_LAYERS, env.num_actions, max_batch=64)
+    assert net.fused_supported and not net.fused_backward_supported
+    core = dq.DQNCore(env, net, batch_size=48, memory_limit=64 * 12, gamma=0.99, lr=1e-3)
+    assert not core.compact and not core._fused_update()
+    core.reset_env()
+    for _ in range(4):
+        core.act_and_step(0.3)
+    p0 = core.params.clone()
+    for _ in range(3):
+        core.step_and_update(0.3, extra_updates=2)
+    loss, mean_q = core.read_metrics()
+    assert core.updates == 9 and core.vector_steps == 7
+    assert torch.isfinite(core.params).all() and not torch.equal(core.params, p0) and np.isfinite(loss) and np.isfinite(mean_q)
 
 
 @pytest.mark.parametrize("name,cfg,n,R", [("c4", C3, 4096, 8), ("c5", C5, 1024, 8), ("c3-ragged", C3, 1003, 3)])

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import architectures
 from oracle import dqn_oracle as O
 
 SPECS = {
@@ -65,6 +66,47 @@ def test_forward_backward_vs_torch_autograd(name, training):
     g = O.backward(spec, flat, cache, dq)
     (tq * torch.tensor(dq)).sum().backward()
     assert np.allclose(g, tp.grad.numpy(), atol=1e-11)
+
+
+@pytest.mark.parametrize("name", sorted(architectures.ARCHITECTURES))
+def test_oracle_matches_autograd_on_the_architecture_list(name):
+    """The float64 oracle against torch float64 autograd on every entry of tests/architectures.py, at the entry's own batch, inputs and dropout masks
+    (one per dropout layer): the reference of tests/test_arch_gpu.py is checked at these shapes before any kernel is judged by it.  Bound: 1e-12 of
+    the largest element, on Q and on the flat gradient (measured: 1e-15 and 1e-14)."""
+    spec, B, flat, obs, rng, keep = architectures.entry(name)
+    flat, obs = flat.astype(np.float64), obs.astype(np.float64)
+    assert len(keep) == sum(1 for _, r in spec.ff_layers if r > 0)
+    q, cache = O.forward(spec, flat, obs, training=True, keep_masks=keep)
+    tp = torch.tensor(flat, dtype=torch.float64, requires_grad=True)
+    tq = torch_forward(spec, tp, torch.tensor(obs), [torch.tensor(k) for k in keep])
+    q_t = tq.detach().numpy()
+    assert q.shape == (B, spec.n_actions)
+    assert np.abs(q - q_t).max() <= 1e-12 * np.abs(q_t).max(), (np.abs(q - q_t).max(), np.abs(q_t).max())
+    dq = rng.randn(B, spec.n_actions) / B
+    g = O.backward(spec, flat, cache, dq)
+    (tq * torch.tensor(dq)).sum().backward()
+    g_t = tp.grad.numpy()
+    assert np.abs(g_t).max() > 0
+    assert np.abs(g - g_t).max() <= 1e-12 * np.abs(g_t).max(), (np.abs(g - g_t).max(), np.abs(g_t).max())
+    # the inference forward (no dropout) too
+    assert np.abs(O.forward(spec, flat, obs)[0] - torch_forward(spec, tp.detach(), torch.tensor(obs)).numpy()).max() <= 1e-12 * max(1.0, np.abs(q_t).max())
+    # the count of samples with a ReLU pre-activation within 1e-6 of 0 that the GPU tests rely on
+    fragile = O.fragile_samples(cache, thr=1e-6)
+    assert int(fragile.sum()) == architectures.FRAGILE[name]
+
+
+def test_dropout_layers_draw_independent_masks():
+    """dropout_keep_mask(layer=l): ordinal 0 is the mask as it was before the ordinal existed (the fused chains' and keep_bits' draw); another ordinal is
+    another counter range -- two layers of equal width and rate keep different units, each at the requested rate."""
+    ids = 1000 + np.arange(400)
+    k0 = O.dropout_keep_mask((3, 4), 99, ids, 64, 0.3)
+    assert np.array_equal(k0, O.dropout_keep_mask((3, 4), 99, ids, 64, 0.3, layer=0))
+    masks = [O.dropout_keep_mask((3, 4), 99, ids, 64, 0.3, layer=l) for l in range(4)]
+    for a in range(4):
+        assert abs(masks[a].mean() - 0.7) < 0.02
+        for b in range(a):
+            # independent Bernoulli(0.7) masks agree on 0.49 + 0.09 = 0.58 of the units
+            assert abs((masks[a] == masks[b]).mean() - 0.58) < 0.03, (a, b)
 
 
 def test_td_loss_adam_vs_torch():
