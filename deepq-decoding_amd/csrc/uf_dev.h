@@ -1,5 +1,5 @@
-// Device side of the union-find decoder, shared by uf_st.hip (uf_st_kernel: volumes given as cells, dq_decode_uf) and the
-// union-find forms of env_match.hip / env_guide.hip: one Pauli component of one volume by one wavefront.
+// Device side of the union-find decoder, shared by uf_st.hip (uf_st_kernel: volumes given as cells, dq_decode_uf), the
+// union-find forms of env_match.hip / env_guide.hip and uf_stream.hip (the sliding window of section 17): one Pauli component of one volume by one wavefront.
 //
 // Graph, unit weights, n nodes per round: node (u, t) = t n + u, the boundary node B = depth n (spatial and future boundary merged).  Edges of round t have
 // ids t (d^2 + n) + k: k = q < d^2 the space edge of qubit q (its two plaquettes of the component in slice t, or its one plaquette and B), k = d^2 + u the
@@ -39,8 +39,11 @@ struct UfComp {
 #define UF_NOLEVEL 0xffffu
 
 // One component of one volume: W = edges of the correction, M = XOR of the qubits of its space edges, rounds = growth rounds made; wave-uniform.
-static __device__ __forceinline__ void uf_component(const UfComp& G, int depth, volatile u32* dw, u8* __restrict__ s, int lane, int& Wout, u64& Mout, int& ndef,
-                                                    int& rounds_out) {
+// Commit (the sliding window of uf_stream.hip): unless `final`, only the edges of rounds t < commit count into W and M, and
+// carry = the set of u (bit u) whose time edge of round commit - 1 is in the correction.  Without Commit the two arguments are not read.
+template <bool Commit>
+static __device__ __forceinline__ void uf_component_impl(const UfComp& G, int depth, volatile u32* dw, u8* __restrict__ s, int lane, int commit, bool final, int& Wout,
+                                                         u64& Mout, u32& carry_out, int& ndef, int& rounds_out) {
     u32* s_label = reinterpret_cast<u32*>(s + UF_O_LABEL);
     u32* s_par = reinterpret_cast<u32*>(s + UF_O_PAR);
     u32* s_parent = reinterpret_cast<u32*>(s + UF_O_PARENT);
@@ -57,6 +60,7 @@ static __device__ __forceinline__ void uf_component(const UfComp& G, int depth, 
     for (int t = 0; t < depth; ++t) total += __popc(dw[t]);       // wave-uniform
     ndef = total;
     Wout = 0; Mout = 0; rounds_out = 0;
+    if (Commit) carry_out = 0;
     if (total == 0) return;                                       // wave-uniform: nothing to correct, `s` untouched
     auto defect = [&](int x) -> u32 { const int t = x / n; return x < B ? (dw[t] >> (x - t * n)) & 1u : 0u; };
     // ---- edges and singleton clusters --------------------------------------------------------------------------------------------------------
@@ -140,6 +144,7 @@ static __device__ __forceinline__ void uf_component(const UfComp& G, int depth, 
     // ---- peeling: from the deepest level down ---------------------------------------------------------------------------------------------------------
     int w = 0;
     u64 m = 0;
+    u32 cr = 0;
     for (int lev = deepest; lev >= 1; --lev) {
         for (int x = lane; x < B; x += 64) {
             if (s_level[x] != (u32)lev || !(v_par[x] & 1u)) continue;
@@ -147,6 +152,11 @@ static __device__ __forceinline__ void uf_component(const UfComp& G, int depth, 
             const int a = s_ea[e], up = a == x ? (int)s_eb[e] : a;
             __hip_atomic_fetch_xor(s_par + up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             const int k = e % per_round;
+            if (Commit && !final) {                               // (an edge is in the correction once: its lower end has one parent edge)
+                const int t = e / per_round;
+                if (t >= commit) continue;
+                if (k >= d2 && t == commit - 1) cr |= 1u << (k - d2);
+            }
             ++w;
             if (k < d2) m ^= 1ull << k;
         }
@@ -154,9 +164,28 @@ static __device__ __forceinline__ void uf_component(const UfComp& G, int depth, 
     }
 #pragma unroll
     for (int k = 32; k >= 1; k >>= 1) { w += __shfl_xor(w, k); m ^= (u64)__shfl_xor((unsigned long long)m, k); }
+    if (Commit) {
+#pragma unroll
+        for (int k = 32; k >= 1; k >>= 1) cr |= (u32)__shfl_xor((int)cr, k);
+        carry_out = __builtin_amdgcn_readfirstlane(cr);
+    }
     match_wave_sync();                                            // every lane is through with `s` before the next component reuses it
     Wout = __builtin_amdgcn_readfirstlane(w);
     const u32 lo = __builtin_amdgcn_readfirstlane((u32)m), hi = __builtin_amdgcn_readfirstlane((u32)(m >> 32));
     Mout = (u64)lo | (u64)hi << 32;
     rounds_out = rounds;
+}
+
+static __device__ __forceinline__ void uf_component(const UfComp& G, int depth, volatile u32* dw, u8* __restrict__ s, int lane, int& Wout, u64& Mout, int& ndef,
+                                                    int& rounds_out) {
+    u32 carry;
+    uf_component_impl<false>(G, depth, dw, s, lane, depth, true, Wout, Mout, carry, ndef, rounds_out);
+}
+
+// One component of one window of a stream: uf_component on the depth-`depth` graph, of whose correction the rounds t < commit are committed (all of it when
+// `final`: W and M are then uf_component's); carry: a wave-uniform word, bit u = the time edge (u, commit - 1) is in the correction.  ndef counts the window's
+// defect rows as they stand in `dw`.
+static __device__ __forceinline__ void uf_component_commit(const UfComp& G, int depth, volatile u32* dw, u8* __restrict__ s, int lane, int commit, bool final, int& Wout,
+                                                           u64& Mout, u32& carry, int& ndef, int& rounds_out) {
+    uf_component_impl<true>(G, depth, dw, s, lane, commit, final, Wout, Mout, carry, ndef, rounds_out);
 }

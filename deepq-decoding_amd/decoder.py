@@ -355,6 +355,22 @@ class Evaluator:
         _lib.check(self.L.dq_decode_uf(self._h, _lib.ptr(volumes), m, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
                                        self._stream()))
 
+    def stream_uf_into(self, syndromes, m, T, commit, frame, weight=None, n_defects=None, rounds=None):
+        """The sliding-window union-find decode (dq_stream_decode_uf) of m <= chunk streams of T rounds already on the device; the window is volume_depth."""
+        from . import _lib
+        _lib.check(self.L.dq_stream_decode_uf(self._h, _lib.ptr(syndromes), m, T, commit, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects),
+                                              _lib.ptr(rounds), self._stream()))
+
+    def stream_run_into(self, venv, m, T, commit, lattice_id, seed, p_phys, p_meas, hidden, trivial, frame, weight=None, n_defects=None, rounds=None,
+                        syndromes=None):
+        """m <= chunk streams of T rounds of lattices lattice_id .. lattice_id + m - 1 (mod 2^32), sampled and decoded in one kernel (dq_stream_run_uf)."""
+        from . import _lib
+        arr = (ctypes.c_uint32 * 2)(*seed)
+        each = not isinstance(p_phys, float)
+        _lib.check(self.L.dq_stream_run_uf(self._h, venv._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
+                                           p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, _lib.ptr(hidden), _lib.ptr(trivial),
+                                           _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), _lib.ptr(syndromes), self._stream()))
+
     def verdict_into(self, venv, hidden, frame, m, out):
         from . import _lib
         _lib.check(self.L.dq_decode_verdict(self._h, venv._h, _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), self._stream()))
@@ -857,6 +873,185 @@ def score_matching(env, n_volumes, rates=None, p_phys=None, p_meas=None, seed=No
             ev.close()
     results = block_results(host, host0, extras, -(-n // blk), blk, ph, pm)
     return results[0] if keys is None else dict(zip(keys, results))
+
+
+# ---- sliding-window union-find decoding of syndrome streams (include/deepq_hip.h dq_stream_decode_uf / dq_stream_run_uf) --------
+STREAM_MAX_ROUNDS = 1 << 20
+STREAM_MAX_WINDOW = 16
+
+
+class StreamResult:
+    """Per-stream results of stream_decode, in input order: frame uint8 [N, d, d] (the committed correction as hidden_state codes 0..3, what verdict()
+    takes), weight int32 [N, 2] (committed edges per Pauli component), n_defects int32 [N, 2] (the stream's own defects, carries not counted), rounds
+    int32 [N, 2] (growth rounds summed over the windows), windows (their number, the same for every stream)."""
+
+    def __init__(self, frame, weight, n_defects, rounds, windows):
+        self.frame, self.weight, self.n_defects, self.rounds, self.windows = frame, weight, n_defects, rounds, windows
+
+    def __repr__(self):
+        return f"StreamResult(streams={int(self.frame.shape[0])}, windows={self.windows})"
+
+
+def stream_windows(T, window, commit):
+    """The number of windows of a stream of T rounds."""
+    return 1 if window >= T else -(-(T - window) // commit) + 1
+
+
+def check_stream_method(method):
+    check_method(method)
+    if method != "union_find":
+        raise NotImplementedError("stream decoding is union-find only: the matching returns XORs of tabulated paths and not edges per round, so it cannot say "
+                                  "which part of a correction lies in the committed rounds")
+
+
+def check_stream_schedule(d, rounds, window, commit):
+    """(T, window, commit) with the defaults window = min(2 d, 16), commit = (window + 1) // 2; ValueError outside 1 <= commit <= window <= 16, 1 <= T <= 2^20."""
+    is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+    if window is None:
+        window = min(2 * d, STREAM_MAX_WINDOW)
+    if not is_int(window) or not 1 <= window <= STREAM_MAX_WINDOW:
+        raise ValueError(f"window must be an integer in 1..{STREAM_MAX_WINDOW}, not {window!r}")
+    if commit is None:
+        commit = (int(window) + 1) // 2
+    if not is_int(commit) or not 1 <= commit <= window:
+        raise ValueError(f"commit must be an integer in 1..window = {window}, not {commit!r}")
+    if not is_int(rounds) or not 1 <= rounds <= STREAM_MAX_ROUNDS:
+        raise ValueError(f"a stream has 1..{STREAM_MAX_ROUNDS} rounds, not {rounds!r}")
+    return int(rounds), int(window), int(commit)
+
+
+def check_stream_evaluator(evaluator, d, model, use_Y, window):
+    if evaluator is not None:
+        got = (evaluator.d, evaluator.error_model, evaluator.volume_depth)
+        if got != (d, model, window) or (model != "X" and bool(evaluator.use_Y) != use_Y):
+            raise ValueError(f"the evaluator's (d, error model, use_Y, volume_depth) = {got[:2] + (evaluator.use_Y, got[2])} is not the stream's lattice and window "
+                             f"{(d, model, use_Y, window)}")
+
+
+def check_stream_args(env, syndromes, window=None, commit=None, chunk=DEFAULT_CHUNK, evaluator=None, method="union_find"):
+    """Validates a stream_decode request without touching the library.  Returns (d, error_model, use_Y, n_streams, single, T, window, commit)."""
+    check_stream_method(method)
+    d, model, use_Y, _ = check_eval_lattice(None, env)
+    if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
+    if not hasattr(syndromes, "shape") or not hasattr(syndromes, "dtype"):
+        raise ValueError("syndromes must be a numpy array or a torch tensor")
+    if str(syndromes.dtype).replace("torch.", "") != "uint8":
+        raise ValueError(f"syndromes must be uint8, got dtype {syndromes.dtype}")
+    shape = tuple(int(x) for x in syndromes.shape)
+    single = len(shape) == 3
+    if len(shape) not in (3, 4) or shape[-2:] != (d + 1, d + 1) or min(shape[:-2]) < 1:
+        raise ValueError(f"syndromes must have shape [N, T, {d + 1}, {d + 1}] or [T, {d + 1}, {d + 1}], got {shape}")
+    T, window, commit = check_stream_schedule(d, shape[-3], window, commit)
+    check_binary(syndromes)
+    check_stream_evaluator(evaluator, d, model, use_Y, window)
+    return d, model, use_Y, 1 if single else shape[0], single, T, window, commit
+
+
+def stream_decode(syndromes, env, window=None, commit=None, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None, method="union_find"):
+    """Sliding-window union-find decoding of syndrome streams of any length.  syndromes: uint8 [N, T, d+1, d+1] with 0/1 cells, or
+    one stream [T, d+1, d+1], numpy or torch; T is free (1 .. 2^20), env supplies the lattice (d <= 7, the narrow environment) and its volume_depth is not
+    consulted.  Windows of `window` rounds (default min(2 d, 16)) are decoded by the union-find decoder of section 16; each commits its first `commit`
+    rounds (default (window + 1) // 2) and carries the crossing time edges into the next; the last one commits everything.  With window >= T the
+    result is matching_decode(method="union_find") at depth T.  Returns a StreamResult of device tensors (numpy arrays with to_host); the result of a
+    stream does not depend on the batch around it or on `chunk`.  evaluator: an Evaluator of this lattice with volume_depth = window to run on (its
+    chunk is used and it stays open); default: one for this call.  method="matching" raises NotImplementedError."""
+    import torch
+    d, model, use_Y, n, single, T, window, commit = check_stream_args(env, syndromes, window, commit, chunk, evaluator, method)
+    venv = _narrow_env(env)
+    dev = venv.device
+    syn = (syndromes if isinstance(syndromes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(syndromes))).to(device=dev).reshape(n, T, d + 1, d + 1).contiguous()
+    ev = Evaluator(d, model, use_Y, window, chunk=min(int(chunk), n), device=dev) if evaluator is None else evaluator
+    try:
+        frame = torch.empty((n, d, d), dtype=torch.uint8, device=dev)
+        weight, ndef, rounds = (torch.empty((n, 2), dtype=torch.int32, device=dev) for _ in range(3))
+        with torch.cuda.device(dev):
+            for s in range(0, n, ev.chunk):
+                m = min(ev.chunk, n - s)
+                ev.stream_uf_into(syn[s:s + m], m, T, commit, frame[s:s + m], weight[s:s + m], ndef[s:s + m], rounds[s:s + m])
+            torch.cuda.current_stream(dev).synchronize()
+    finally:
+        if evaluator is None:
+            ev.close()
+    out = (frame, weight, ndef, rounds)
+    return StreamResult(*(tuple(x.cpu().numpy() for x in out) if to_host else out), stream_windows(T, window, commit))
+
+
+def memory_experiment(env, n_runs, rounds, window=None, commit=None, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, chunk=DEFAULT_CHUNK,
+                      no_decoder=False, timings=None, evaluator=None, return_streams=False):
+    """The logical failure of a memory experiment of `rounds` rounds, decoded by the sliding-window union-find decoder: n_runs streams, stream i the first
+    `rounds` rounds of lattice env_id_base + i under sample_volumes' convention, sampled and decoded in ONE kernel per chunk (dq_stream_run_uf: the
+    syndromes never reach memory), then verdict -> counts on the device as score_matching does.  Returns what score_matching returns: an EvalResult
+    ({rate: EvalResult} with rates=[...], n_runs streams per rate, p_meas then as in decode_benchmark), every stream counted as status identity,
+    corrections = the frame's non-zero cells, inexact 0; no_decoder: EvalResult.no_decoder counts the verdict for frame = 0.  window / commit: as
+    stream_decode.  timings: a dict that receives the wall seconds of the phases run / verdict.  evaluator: an Evaluator of this lattice with
+    volume_depth = window.  return_streams: also returns dict(syndromes uint8 [N, rounds, d+1, d+1], hidden, frame uint8 [N, d, d], trivial uint8 [N]) of
+    device tensors; otherwise only the counters leave the device."""
+    import time
+    import torch
+    lat = check_eval_lattice(None, env)
+    d, model, use_Y, _ = lat
+    T, window, commit = check_stream_schedule(d, rounds, window, commit)
+    if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
+        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
+    if rates is None:
+        keys = None
+        n, ph, pm, seed, base, blk = check_eval_args(lat, env, n_runs, p_phys, p_meas, seed, env_id_base)
+    else:
+        if p_phys is not None:
+            raise ValueError("memory_experiment: rates=[...] are the physical rates; p_phys goes without them")
+        total, ph, pm, block, keys = expand_rates(lat, env, n_runs, rates, p_meas, seed, env_id_base, "memory_experiment")
+        n, ph, pm, seed, base, blk = check_eval_args(lat, env, total, ph, pm, seed, env_id_base, block)
+    check_stream_evaluator(evaluator, d, model, use_Y, window)
+    venv = _narrow_env(env)
+    dev = venv.device
+    ev = Evaluator(d, model, use_Y, window, chunk=min(int(chunk), n), device=dev) if evaluator is None else evaluator
+    each = not isinstance(ph, float)
+    try:
+        step = min(ev.chunk, n)
+        rows = n if return_streams else step
+        hid = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+        frame = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+        triv = torch.empty(rows, dtype=torch.uint8, device=dev)
+        syn = torch.empty((n, T, d + 1, d + 1), dtype=torch.uint8, device=dev) if return_streams else None
+        verd = torch.empty(step, dtype=torch.uint8, device=dev)
+        status = torch.full((step,), STATUS_IDENTITY, dtype=torch.uint8, device=dev)
+        n_blocks = -(-n // blk)
+        counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
+        counters0 = torch.zeros_like(counters) if no_decoder else None
+
+        def phase(name, t0):
+            if timings is None:
+                return t0
+            torch.cuda.current_stream(dev).synchronize()
+            t1 = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + (t1 - t0)
+            return t1
+
+        with torch.cuda.device(dev):
+            for s in range(0, n, step):
+                m = min(step, n - s)
+                o = s if return_streams else 0
+                sl = slice(o, o + m)
+                t = phase("setup", time.perf_counter()) if timings is not None else 0.0
+                a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
+                if each and (a == a[0]).all() and (b == b[0]).all():   # one rate pair in this chunk: the scalar form (the same thresholds, no table upload)
+                    a, b = float(a[0]), float(b[0])
+                ev.stream_run_into(venv, m, T, commit, base + s, seed, a, b, hid[sl], triv[sl], frame[sl], syndromes=None if syn is None else syn[s:s + m])
+                t = phase("run", t)
+                ev.verdict_into(venv, hid[sl], frame[sl], m, verd[:m])
+                ev.count_into(verd[:m], triv[sl], status[:m], (frame[sl] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), m, s, blk, counters)
+                if no_decoder:
+                    ev.verdict_into(venv, hid[sl], None, m, verd[:m])
+                    ev.count_into(verd[:m], triv[sl], None, None, m, s, blk, counters0)
+                t = phase("verdict", t)
+            host, host0 = counters.cpu().numpy(), counters0.cpu().numpy() if no_decoder else None
+    finally:
+        if evaluator is None:
+            ev.close()
+    results = block_results(host, host0, np.zeros(n_blocks, dtype=np.int64), n_blocks, blk, ph, pm)
+    out = results[0] if keys is None else dict(zip(keys, results))
+    return (out, dict(syndromes=syn, hidden=hid, frame=frame, trivial=triv)) if return_streams else out
 
 
 class DecodeResult:

@@ -821,6 +821,29 @@ dq_status dq_decode_uf(dq_decode_eval* ev, const uint8_t* volumes_dev, int n, ui
 dq_status dq_env_uf_select(dq_env* env, dq_decode_eval* ev, int32_t* action_dev, void* stream);
 dq_status dq_env_guided_select_uf(dq_env* env, dq_decode_eval* ev, const float* q_dev, double eps, double guide_share, int masked_greedy, const uint32_t seed[2],
                                   uint64_t t, int32_t* action_dev, uint8_t* guided_dev, uint8_t* inexact_dev, void* stream);
+/* Sliding-window union-find decoding of syndrome streams of any length (csrc/uf_stream.hip).  dq_version() stays 8: the capability is
+ * the presence of these two symbols.  Union-find only: the matching's tabulated paths do not say which part of a correction lies in the committed rounds.
+ * A stream is T rounds of faulty syndromes of one lattice, 1 <= T <= 2^20, with the defects D_t = S_t xor S_{t-1} (S_-1 = 0).  The window w is the handle's
+ * volume_depth, the commit c lies in 1 .. w.  Window k starts at round a = k c, is final iff a + w >= T and has l = T - a rounds when final, else w; its
+ * defect rows are D_a xor carry, D_{a+1} .. D_{a+l-1} (carry: empty at the start) and it is decoded by dq_decode_uf's algorithm, unchanged, on the depth-l
+ * graph.  With t = e / (d^2 + n) the round of an edge of the correction: the final window commits every edge and carries nothing; any other window commits
+ * the edges with t < c, and the next carry is the set of u whose time edge of round c - 1 is in the correction.  A committed space edge XORs its qubit
+ * into the frame, every committed edge adds 1 to the weight.  A function of the stream alone: one window (w >= T) is dq_decode_uf at depth T in every field.
+ * dq_stream_decode_uf: syndromes_dev uint8 [n][T][d+1][d+1] with 0/1 cells; frame_dev uint8 [n][d][d] as hidden_state codes; weight_dev / n_defects_dev /
+ * rounds_dev int32 [n][2], nullable, 4-byte aligned: committed edges, the stream's own defects (carries not counted), growth rounds summed over the windows.
+ * dq_stream_run_uf: the same schedule on rounds drawn in the kernel, so that the syndromes never reach memory: stream i is the first T rounds of lattice
+ * env_id_base + i under dq_decode_sample's convention (the same key, round counter, thresholds and per-stream rate arrays; for T <= 16 its syndromes are
+ * dq_decode_sample's).  hidden_dev uint8 [n][d][d] and trivial_dev uint8 [n] as dq_decode_sample writes them; weight_dev, n_defects_dev, rounds_dev and
+ * syndromes_dev (uint8 [n][T][d+1][d+1]) may be NULL.  `env` supplies the lattice tables and must be of the handle's d, error model and use_Y; its
+ * volume_depth is not consulted (dq_decode_verdict's check).
+ * Both: n in 1 .. max_volumes, T in 1 .. 2^20, commit in 1 .. volume_depth (DQ_ERR_INVALID); d <= 7, volume_depth <= 16 (DQ_ERR_UNSUPPORTED).  One
+ * wavefront per stream.  The endpoint tables are dq_decode_uf's, built at the handle's first call, which therefore MODIFIES the handle: a dq_decode_eval
+ * serves one host thread at a time and the calls on it are ordered on one stream at a time; it is not thread-safe.  No reference counterpart. */
+dq_status dq_stream_decode_uf(dq_decode_eval* ev, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
+                              int32_t* n_defects_dev, int32_t* rounds_dev, void* stream);
+dq_status dq_stream_run_uf(dq_decode_eval* ev, const dq_env* env, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys,
+                           double p_meas, const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev,
+                           int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Live kernel timing (measurement only; no reference counterpart).  dq_prof_arm(id, n) times up to n
