@@ -26,7 +26,10 @@ def __getattr__(name):
                 "FileLogger", "Adam", "build_convolutional_nn", "ConvQModel", "History"):
         from . import agent
         return getattr(agent, name)
-    if name in ("dist", "hdf5_reader", "weights_io", "function_library", "runner", "decoder"):
+    if name in ("WideEvaluator", "stream_decode_wide", "memory_experiment_wide"):
+        from . import decoder_wide
+        return getattr(decoder_wide, name)
+    if name in ("dist", "hdf5_reader", "weights_io", "function_library", "runner", "decoder", "decoder_wide"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "FeedForwardReferee":

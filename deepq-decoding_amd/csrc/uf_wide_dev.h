@@ -1,0 +1,198 @@
+// Device side of the wide union-find stream decoder (uf_wide.hip): section 16's component decode (uf_dev.h) inside section 17's
+// window schedule (uf_stream.hip), unchanged as an algorithm, for any odd d in 3 .. 15 and a window of up to 32 rounds -- one Pauli component of one window by
+// one WORKGROUP of UFW_THREADS threads (four waves) instead of one wavefront.
+//
+// Graph, unit weights, n = (d^2 - 1) / 2 nodes per round: node (u, t) = t n + u, B = depth n; edge ids t (d^2 + n) + k, k = q < d^2 the space edge of qubit q,
+// k = d^2 + u the time edge (u, t) -- (u, t + 1), in the last round (u, t) -- B.  Growth in synchronous rounds with g in {0, 1, 2}, min-labels (0 = holds B,
+// else lowest node + 1), peeling by levels with the lowest-edge-id parent: uf_dev.h's text applies word for word.  What differs is the shape:
+//   * the phases are separated by workgroup barriers, and every loop exit is decided by a barrier that reduces the predicate over the workgroup
+//     (__syncthreads_or) or by a value every thread computes alike from the kernel's arguments: no wave can leave a loop its siblings are still in;
+//   * the edges' ends are not stored: they follow from (t, k) and the component's endpoint table (UfwComp: d^2 bytes per end, read through the cache);
+//   * a defect row and the carry are UFW_ROW_WORDS x 32 bits (n <= 112), the frame of a component UFW_FRAME_WORDS x 32 bits (d^2 <= 225): LDS words,
+//     accumulated with LDS atomics;
+//   * the LDS is dynamic and sized from the call's (d, window) by ufw_layout, the same function on the host and on the device.
+// Every loop bound is a constant of (d, window, T, commit), which the host validates.  No scratch pool, no lock, no loop that waits on another workgroup.
+#pragma once
+#include "common.h"
+
+#define UFW_THREADS 256
+#define UFW_MAX_D 15
+#define UFW_MAX_WINDOW 32
+#define UFW_ROW_WORDS 4                                          // 32-bit words of a defect row / a carry: n <= 112
+#define UFW_FRAME_WORDS 8                                        // 32-bit words of a component's frame: d^2 <= 225
+#define UFW_NONE 0xffffffffu
+#define UFW_NOLEVEL 0xffffu
+
+struct UfwComp {
+    const u8* eu;           // [d^2] qubit -> its first plaquette of the component (node index)
+    const u8* ev;           // [d^2] ... its second one, 255: none (the edge goes to B)
+};
+
+// Byte offsets of a workgroup's dynamic LDS for (n, d2, window).  The head is fixed, the graph arrays follow.
+struct UfwLayout {
+    int o_frame, o_carry, o_acc, o_ring, o_label, o_par, o_parent, o_level, o_g, o_ex, o_ez, o_v, bytes;
+};
+
+static __host__ __device__ inline UfwLayout ufw_layout(int n, int d2, int window) {
+    UfwLayout L;
+    const int NN = window * n + 1, NE = window * (d2 + n);
+    int o = 0;
+    L.o_frame = o; o += 2 * UFW_FRAME_WORDS * 4;                 // u32 [2][8] committed space edges per component
+    L.o_carry = o; o += 2 * UFW_ROW_WORDS * 4;                   // u32 [2][4] the carry into the next window
+    L.o_acc = o; o += 8 * 4;                                     // int [2] weight, [2] defects, [2] growth rounds, [2] spare
+    L.o_ring = o; o += 2 * window * UFW_ROW_WORDS * 4;           // u32 [2][window][4] defect rows of the window
+    L.o_label = o; o += 4 * NN;                                  // u32 [NN] cluster label
+    L.o_par = o; o += 4 * NN;                                    // u32 [NN] defect parity per label; then subtree parity per node
+    L.o_parent = o; o += 4 * NN;                                 // u32 [NN] parent edge
+    L.o_level = o; o += (2 * NN + 3) & ~3;                       // u16 [NN]
+    L.o_g = o; o += (NE + 3) & ~3;                               // u8 [NE] growth
+    L.o_ex = o; o += 256;                                        // u8 [256] the sampler's X plane / the verdict's
+    L.o_ez = o; o += 256;                                        // u8 [256] ... Z plane
+    L.o_v = o; o += 256;                                         // u8 [256] the round's faulty syndrome bits, measurement order
+    L.bytes = o;
+    return L;
+}
+
+#ifdef __HIPCC__
+
+// x / p for x < 2^32 / p by one multiply: m = floor(2^32 / p) + 1
+static __device__ __forceinline__ u32 ufw_magic(int p) { return 0xffffffffu / (u32)p + 1u; }
+static __device__ __forceinline__ int ufw_div(int x, u32 magic) { return (int)__umulhi((u32)x, magic); }
+
+struct UfwGraph {
+    int n, d2, per_round, depth, B, NN, NE;
+    u32 mag_n, mag_pr;
+    const u8* eu;
+    const u8* ev;
+};
+
+static __device__ __forceinline__ void ufw_ends(const UfwGraph& G, int e, int& a, int& b, int& t, int& k) {
+    t = ufw_div(e, G.mag_pr);
+    k = e - t * G.per_round;
+    if (k < G.d2) {
+        const int u = G.eu[k], v = G.ev[k];
+        a = u == 255 ? G.B : t * G.n + u;
+        b = (u == 255 || v == 255) ? G.B : t * G.n + v;
+    } else {
+        a = t * G.n + (k - G.d2);
+        b = t + 1 < G.depth ? a + G.n : G.B;
+    }
+}
+
+// One component of one window by the whole workgroup; every thread calls it with the same arguments.  dw: the component's rows u32 [depth][4] in LDS.
+// Unless `final`, only the edges of rounds t < commit count; a committed space edge XORs its qubit into s_frame [8], a committed edge adds 1 to *s_weight, the
+// time edges of round commit - 1 set their bit of s_carry [4] (zero on entry).  The growth rounds made are added to *s_rounds.
+static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u32* dw, u8* __restrict__ s, const UfwLayout& L, int tid, int commit, bool final,
+                                                     u32* s_frame, u32* s_carry, int* s_weight, int* s_rounds) {
+    u32* s_label = reinterpret_cast<u32*>(s + L.o_label);
+    u32* s_par = reinterpret_cast<u32*>(s + L.o_par);
+    u32* s_parent = reinterpret_cast<u32*>(s + L.o_parent);
+    volatile u32* v_label = s_label;
+    volatile u32* v_par = s_par;
+    volatile u32* v_parent = s_parent;
+    volatile uint16_t* s_level = reinterpret_cast<volatile uint16_t*>(s + L.o_level);
+    volatile u8* s_g = s + L.o_g;
+    volatile const u32* v_dw = dw;
+    const int n = G.n, B = G.B, NN = G.NN, NE = G.NE;
+    // nothing to correct: workgroup-uniform, the graph arrays untouched
+    if (!__syncthreads_or(tid < G.depth * UFW_ROW_WORDS && v_dw[tid] != 0)) return;
+    auto defect = [&](int x) -> u32 {
+        if (x >= B) return 0u;
+        const int t = ufw_div(x, G.mag_n), u = x - t * n;
+        return (v_dw[t * UFW_ROW_WORDS + (u >> 5)] >> (u & 31)) & 1u;
+    };
+    for (int e = tid; e < NE; e += UFW_THREADS) s_g[e] = 0;
+    for (int x = tid; x < NN; x += UFW_THREADS) v_label[x] = x == B ? 0u : (u32)x + 1u;
+    __syncthreads();
+    // ---- growth ---------------------------------------------------------------------------------------------------------------------------------
+    int rounds = 0;
+    const int round_bound = 2 * NE;
+    for (int r = 0; r <= round_bound; ++r) {
+        for (int x = tid; x < NN; x += UFW_THREADS) v_par[x] = 0;
+        __syncthreads();
+        for (int x = tid; x < B; x += UFW_THREADS)
+            if (defect(x)) __hip_atomic_fetch_xor(s_par + v_label[x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __syncthreads();
+        bool any = false;
+        for (int x = tid; x < B; x += UFW_THREADS) { const u32 l = v_label[x]; any |= l != 0 && (v_par[l] & 1u); }
+        if (!__syncthreads_or(any) || r == round_bound) break;    // workgroup-uniform
+        ++rounds;
+        bool fresh = false;
+        for (int e = tid; e < NE; e += UFW_THREADS) {
+            const int g0 = s_g[e];
+            if (g0 == 2) continue;
+            int a, b, t, k;
+            ufw_ends(G, e, a, b, t, k);
+            const u32 la = v_label[a], lb = v_label[b];
+            const int inc = (int)(la != 0 && (v_par[la] & 1u)) + (int)(lb != 0 && (v_par[lb] & 1u));
+            const int g1 = min(2, g0 + inc);
+            if (g1 != g0) { s_g[e] = (u8)g1; fresh |= g1 == 2; }
+        }
+        if (!__syncthreads_or(fresh)) continue;                   // workgroup-uniform: no new full edge, the clusters stand
+        for (int pass = 0; pass < NN; ++pass) {                   // (a label travels at least one edge per pass)
+            bool changed = false;
+            for (int e = tid; e < NE; e += UFW_THREADS) {
+                if (s_g[e] != 2) continue;
+                int a, b, t, k;
+                ufw_ends(G, e, a, b, t, k);
+                const u32 la = v_label[a], lb = v_label[b];
+                if (la != lb) {
+                    const u32 m = la < lb ? la : lb;
+                    __hip_atomic_fetch_min(s_label + (la < lb ? b : a), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    changed = true;
+                }
+            }
+            if (!__syncthreads_or(changed)) break;                // workgroup-uniform
+        }
+    }
+    // ---- peeling: levels and parent edges ---------------------------------------------------------------------------------------------------------
+    for (int x = tid; x < NN; x += UFW_THREADS) {
+        s_level[x] = (uint16_t)((x == B || v_label[x] == (u32)x + 1u) ? 0u : UFW_NOLEVEL);
+        v_parent[x] = UFW_NONE;
+        v_par[x] = defect(x);
+    }
+    __syncthreads();
+    int deepest = 0;
+    for (int lev = 1; lev < NN; ++lev) {
+        for (int e = tid; e < NE; e += UFW_THREADS) {
+            if (s_g[e] != 2) continue;
+            int a, b, t, k;
+            ufw_ends(G, e, a, b, t, k);
+            const u32 va = s_level[a], vb = s_level[b];
+            if (va == (u32)(lev - 1) && vb == UFW_NOLEVEL) __hip_atomic_fetch_min(s_parent + b, (u32)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else if (vb == (u32)(lev - 1) && va == UFW_NOLEVEL) __hip_atomic_fetch_min(s_parent + a, (u32)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        __syncthreads();
+        bool reached = false;
+        for (int x = tid; x < B; x += UFW_THREADS)
+            if (s_level[x] == UFW_NOLEVEL && v_parent[x] != UFW_NONE) { s_level[x] = (uint16_t)lev; reached = true; }
+        if (!__syncthreads_or(reached)) break;                    // workgroup-uniform
+        deepest = lev;
+    }
+    // ---- peeling: from the deepest level down ---------------------------------------------------------------------------------------------------------
+    int w = 0;
+    for (int lev = deepest; lev >= 1; --lev) {
+        for (int x = tid; x < B; x += UFW_THREADS) {
+            if (s_level[x] != (u32)lev || !(v_par[x] & 1u)) continue;
+            const int e = (int)v_parent[x];
+            int a, b, t, k;
+            ufw_ends(G, e, a, b, t, k);
+            __hip_atomic_fetch_xor(s_par + (a == x ? b : a), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (!final) {                                         // (an edge is in the correction once: its lower end has one parent edge)
+                if (t >= commit) continue;
+                if (k >= G.d2 && t == commit - 1) {
+                    const int u = k - G.d2;
+                    __hip_atomic_fetch_or(s_carry + (u >> 5), 1u << (u & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+            ++w;
+            if (k < G.d2) __hip_atomic_fetch_xor(s_frame + (k >> 5), 1u << (k & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        __syncthreads();
+    }
+    if (w) __hip_atomic_fetch_add(s_weight, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (tid == 0) *s_rounds += rounds;
+    __syncthreads();                                              // every thread is through with the graph arrays before the next component reuses them
+}
+
+#endif  // __HIPCC__

@@ -1,0 +1,300 @@
+"""Union-find stream decoding for any odd d in 3 .. 15 with a window of up to 32 rounds (include/deepq_hip.h dq_wide_uf_*; csrc/uf_wide.hip; DESIGN.md
+section 18): the wide form of decoder.stream_decode / decoder.memory_experiment, which stay as they are and keep refusing d >= 9.
+
+The algorithm and the window schedule are section 17's; for d <= 7 and window <= 16 every field equals decoder.stream_decode's.  The handle
+(`WideEvaluator`) owns the lattice tables: no environment is needed, and no referee is consulted -- the verdict is "the residual is a stabilizer" (in the
+code space, trivial homology class).  EvalResult.death_rate therefore EQUALS failure_rate by construction at these sizes and means nothing more.
+"""
+import ctypes
+
+import numpy as np
+
+from .decoder import (COUNTER_NAMES, DEFAULT_CHUNK, MODELS, STATUS_IDENTITY, STREAM_MAX_ROUNDS, StreamResult, block_results, check_binary, check_rates,
+                      stream_windows)
+
+WIDE_MAX_D = 15
+WIDE_MAX_WINDOW = 32
+
+
+def _is_int(x):
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def check_wide_lattice(d, error_model):
+    """Odd d in 3 .. 15 and a known error model, else ValueError.  Returns (d, error_model)."""
+    if not _is_int(d) or d < 3 or d > WIDE_MAX_D or d % 2 == 0:
+        raise ValueError(f"d = {d!r}: the wide union-find decoder covers odd d in 3..{WIDE_MAX_D}")
+    if error_model not in MODELS:
+        raise ValueError(f"error model {error_model!r} is not one of X, DP, IIDXZ")
+    return int(d), str(error_model)
+
+
+def check_wide_schedule(d, rounds, window, commit):
+    """(T, window, commit) with the defaults window = min(2 d, 32), commit = (window + 1) // 2; ValueError outside 1 <= commit <= window <= 32,
+    1 <= T <= 2^20."""
+    if window is None:
+        window = min(2 * d, WIDE_MAX_WINDOW)
+    if not _is_int(window) or not 1 <= window <= WIDE_MAX_WINDOW:
+        raise ValueError(f"window must be an integer in 1..{WIDE_MAX_WINDOW}, not {window!r}")
+    if commit is None:
+        commit = (int(window) + 1) // 2
+    if not _is_int(commit) or not 1 <= commit <= window:
+        raise ValueError(f"commit must be an integer in 1..window = {window}, not {commit!r}")
+    if not _is_int(rounds) or not 1 <= rounds <= STREAM_MAX_ROUNDS:
+        raise ValueError(f"a stream has 1..{STREAM_MAX_ROUNDS} rounds, not {rounds!r}")
+    return int(rounds), int(window), int(commit)
+
+
+def check_chunk(chunk):
+    if not _is_int(chunk) or chunk < 1:
+        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
+    return int(chunk)
+
+
+def check_wide_evaluator(evaluator, d, error_model, window):
+    if evaluator is not None:
+        got = (evaluator.d, evaluator.error_model, evaluator.window)
+        if got != (d, error_model, window):
+            raise ValueError(f"the evaluator's (d, error model, window) = {got} is not the stream's {(d, error_model, window)}")
+
+
+def lattice_of_wide(lattice):
+    """`lattice`: (d, error_model), or an environment of either backend (the drop-in class, a VectorEnv, or any object with d and error_model).  Returns
+    (d, error_model, the environment's (p_phys, p_meas, seed) or None)."""
+    if isinstance(lattice, (tuple, list)):
+        if len(lattice) != 2:
+            raise ValueError(f"lattice must be (d, error_model) or an environment, not {lattice!r}")
+        d, model = check_wide_lattice(lattice[0], lattice[1])
+        return d, model, None
+    v = getattr(lattice, "_v", lattice)
+    if v is None or not hasattr(v, "d") or not hasattr(v, "error_model"):
+        raise ValueError(f"lattice must be (d, error_model) or an environment, not {lattice!r}")
+    d, model = check_wide_lattice(int(v.d), str(v.error_model))
+    return d, model, (getattr(v, "p_phys", None), getattr(v, "p_meas", None), getattr(v, "seed", None))
+
+
+def check_wide_stream_args(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHUNK, evaluator=None, error_model="DP"):
+    """Validates a stream_decode_wide request without touching the library.  Returns (d, n_streams, single, T, window, commit, chunk)."""
+    d, error_model = check_wide_lattice(d, error_model if evaluator is None else evaluator.error_model)
+    chunk = check_chunk(chunk)
+    if not hasattr(syndromes, "shape") or not hasattr(syndromes, "dtype"):
+        raise ValueError("syndromes must be a numpy array or a torch tensor")
+    if str(syndromes.dtype).replace("torch.", "") != "uint8":
+        raise ValueError(f"syndromes must be uint8, got dtype {syndromes.dtype}")
+    shape = tuple(int(x) for x in syndromes.shape)
+    single = len(shape) == 3
+    if len(shape) not in (3, 4) or shape[-2:] != (d + 1, d + 1) or min(shape[:-2]) < 1:
+        raise ValueError(f"syndromes must have shape [N, T, {d + 1}, {d + 1}] or [T, {d + 1}, {d + 1}], got {shape}")
+    T, window, commit = check_wide_schedule(d, shape[-3], window, commit)
+    check_binary(syndromes)
+    check_wide_evaluator(evaluator, d, error_model, window)
+    return d, 1 if single else shape[0], single, T, window, commit, chunk
+
+
+def check_wide_experiment_args(lattice, n_runs, rounds, window=None, commit=None, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0,
+                               chunk=DEFAULT_CHUNK, evaluator=None):
+    """Validates a memory_experiment_wide request without touching the library.  Returns (d, error_model, T, window, commit, n, p_phys, p_meas, seed, base,
+    block, keys, chunk): n streams in all, rates as floats or per-stream float64 arrays, block = streams per block of counters, keys = the rates of
+    rates=[...] or None."""
+    d, model, own = lattice_of_wide(lattice)
+    T, window, commit = check_wide_schedule(d, rounds, window, commit)
+    chunk = check_chunk(chunk)
+    if not _is_int(n_runs) or n_runs < 1:
+        raise ValueError(f"n_runs must be a positive integer, not {n_runs!r}")
+    keys = None
+    n = blk = int(n_runs)
+    if rates is not None:
+        if p_phys is not None:
+            raise ValueError("memory_experiment_wide: rates=[...] are the physical rates; p_phys goes without them")
+        keys = [float(r) for r in rates]
+        K = len(keys)
+        if K < 1:
+            raise ValueError("memory_experiment_wide: no error rates")
+        if len(set(keys)) != K:
+            raise ValueError("memory_experiment_wide: the error rates must be distinct (they key the result)")
+        meas = keys if p_meas is None else ([float(p_meas)] * K if np.ndim(p_meas) == 0 else [float(r) for r in p_meas])
+        if len(meas) != K:
+            raise ValueError(f"memory_experiment_wide: {len(meas)} measurement rates for {K} error rates")
+        n = blk * K
+        p_phys, p_meas = np.repeat(np.asarray(keys, dtype=np.float64), blk), np.repeat(np.asarray(meas, dtype=np.float64), blk)
+    if n >= 1 << 31:
+        raise ValueError("the number of streams must be below 2^31")
+    if p_phys is None:
+        if p_meas is not None:
+            raise ValueError("p_meas without p_phys: give both, p_phys alone (p_meas = p_phys), or neither (the environment's rates)")
+        if own is None or own[0] is None or own[1] is None:
+            raise ValueError("p_phys is required when the lattice is given as (d, error_model)")
+        p_phys, p_meas = own[0], own[1]
+    elif p_meas is None:
+        p_meas = p_phys
+    p_phys, p_meas = check_rates(p_phys, n, "p_phys"), check_rates(p_meas, n, "p_meas")
+    if isinstance(p_phys, float) != isinstance(p_meas, float):       # one array: the scalar becomes one too
+        full = lambda x: np.full(n, x, dtype=np.float64) if isinstance(x, float) else x
+        p_phys, p_meas = full(p_phys), full(p_meas)
+    if seed is None:
+        if own is None or own[2] is None:
+            raise ValueError("seed is required when the lattice is given as (d, error_model)")
+        seed = own[2]
+    try:
+        ok = len(seed) == 2 and all(_is_int(x) and 0 <= x < 1 << 32 for x in seed)
+    except (TypeError, IndexError):
+        ok = False
+    if not ok:
+        raise ValueError(f"seed must be a pair of 32-bit words, not {seed!r}")
+    seed = (int(seed[0]), int(seed[1]))
+    if not _is_int(env_id_base) or not 0 <= env_id_base < 1 << 32:
+        raise ValueError(f"env_id_base must be an integer in 0 .. 2^32 - 1, not {env_id_base!r}")
+    check_wide_evaluator(evaluator, d, model, window)
+    return d, model, T, window, commit, n, p_phys, p_meas, seed, int(env_id_base), blk, keys, chunk
+
+
+class WideEvaluator:
+    """Owns a dq_wide_uf handle for chunks of at most `chunk` streams of one lattice and one window: decode, sample-and-decode, verdict, counters.  One host
+    thread and one stream at a time."""
+
+    def __init__(self, d, error_model, window=None, chunk=DEFAULT_CHUNK, device=None):
+        d, error_model = check_wide_lattice(d, error_model)
+        _, window, _ = check_wide_schedule(d, 1, window, None)
+        self.d, self.error_model, self.window, self.chunk = d, error_model, window, check_chunk(chunk)
+        self._h = None
+        self._open(device)
+
+    def _open(self, device):
+        import torch
+        from . import _lib
+        self.L = _lib.lib()
+        _lib.require_gpu()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.dq_wide_uf_create(self.d, MODELS[self.error_model], self.window, self.chunk, ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.dq_wide_uf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def decode_into(self, syndromes, m, T, commit, frame, weight=None, n_defects=None, rounds=None):
+        """The sliding-window decode (dq_wide_uf_decode) of m <= chunk streams of T rounds already on the device."""
+        from . import _lib
+        _lib.check(self.L.dq_wide_uf_decode(self._h, _lib.ptr(syndromes), m, T, commit, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects),
+                                            _lib.ptr(rounds), self._stream()))
+
+    def run_into(self, m, T, commit, lattice_id, seed, p_phys, p_meas, hidden, trivial, frame, weight=None, n_defects=None, rounds=None, syndromes=None):
+        """m <= chunk streams of T rounds of lattices lattice_id .. lattice_id + m - 1 (mod 2^32), sampled and decoded in one kernel (dq_wide_uf_run)."""
+        from . import _lib
+        arr = (ctypes.c_uint32 * 2)(*seed)
+        each = not isinstance(p_phys, float)
+        _lib.check(self.L.dq_wide_uf_run(self._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
+                                         p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, _lib.ptr(hidden), _lib.ptr(trivial),
+                                         _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), _lib.ptr(syndromes), self._stream()))
+
+    def verdict_into(self, hidden, frame, m, out):
+        from . import _lib
+        _lib.check(self.L.dq_wide_uf_verdict(self._h, _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), self._stream()))
+
+    def count_into(self, verdict, trivial, status, n_corr, m, first, block, counters):
+        from . import _lib
+        _lib.check(self.L.dq_decode_count(_lib.ptr(verdict), _lib.ptr(trivial), _lib.ptr(status), _lib.ptr(n_corr), m, first, block,
+                                          counters.shape[0], _lib.ptr(counters), self._stream()))
+
+
+def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None):
+    """decoder.stream_decode for any odd d in 3 .. 15 and a window of up to 32 rounds.  syndromes: uint8 [N, T, d+1, d+1] with 0/1 cells, or one stream
+    [T, d+1, d+1], numpy or torch; window defaults to min(2 d, 32), commit to (window + 1) // 2.  Returns a decoder.StreamResult of device tensors (numpy
+    arrays with to_host); the result of a stream does not depend on the batch around it or on `chunk`.  evaluator: a WideEvaluator of this d and window to
+    run on (its chunk is used and it stays open); default: one for this call."""
+    import torch
+    d, n, single, T, window, commit, chunk = check_wide_stream_args(syndromes, d, window, commit, chunk, evaluator)
+    ev = WideEvaluator(d, "DP", window, chunk=min(chunk, n)) if evaluator is None else evaluator
+    dev = ev.device
+    try:
+        syn = (syndromes if isinstance(syndromes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(syndromes))).to(device=dev)
+        syn = syn.reshape(n, T, d + 1, d + 1).contiguous()
+        frame = torch.empty((n, d, d), dtype=torch.uint8, device=dev)
+        weight, ndef, rounds = (torch.empty((n, 2), dtype=torch.int32, device=dev) for _ in range(3))
+        with torch.cuda.device(dev):
+            for s in range(0, n, ev.chunk):
+                m = min(ev.chunk, n - s)
+                ev.decode_into(syn[s:s + m], m, T, commit, frame[s:s + m], weight[s:s + m], ndef[s:s + m], rounds[s:s + m])
+            torch.cuda.current_stream(dev).synchronize()
+    finally:
+        if evaluator is None:
+            ev.close()
+    out = (frame, weight, ndef, rounds)
+    return StreamResult(*(tuple(x.cpu().numpy() for x in out) if to_host else out), stream_windows(T, window, commit))
+
+
+def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0,
+                           chunk=DEFAULT_CHUNK, no_decoder=False, timings=None, evaluator=None, return_streams=False):
+    """decoder.memory_experiment for any odd d in 3 .. 15 and a window of up to 32 rounds: n_runs streams, stream i the first `rounds` rounds of lattice
+    env_id_base + i under sample_volumes' convention, sampled and decoded in ONE kernel per chunk (dq_wide_uf_run), then verdict -> counts on the device.
+    lattice: (d, error_model), or an environment of either backend, of which only d, error_model, the rates and the seed are read (the defaults of p_phys /
+    p_meas / seed; with a tuple p_phys and seed are required).  Returns what memory_experiment returns: an EvalResult ({rate: EvalResult} with
+    rates=[...], n_runs streams per rate), every stream counted as status identity, corrections = the frame's non-zero cells; no_decoder:
+    EvalResult.no_decoder counts the verdict for frame = 0.  No referee is consulted: alive := success, so death_rate equals failure_rate by construction.
+    timings: a dict that receives the wall seconds of the phases run / verdict.  evaluator: a WideEvaluator of this lattice and window.  return_streams:
+    also returns dict(syndromes uint8 [N, rounds, d+1, d+1], hidden, frame uint8 [N, d, d], trivial uint8 [N]) of device tensors."""
+    import time
+    import torch
+    d, model, T, window, commit, n, ph, pm, seed, base, blk, keys, chunk = check_wide_experiment_args(
+        lattice, n_runs, rounds, window, commit, rates, p_phys, p_meas, seed, env_id_base, chunk, evaluator)
+    ev = WideEvaluator(d, model, window, chunk=min(chunk, n)) if evaluator is None else evaluator
+    dev = ev.device
+    each = not isinstance(ph, float)
+    try:
+        step = min(ev.chunk, n)
+        rows = n if return_streams else step
+        hid = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+        frame = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+        triv = torch.empty(rows, dtype=torch.uint8, device=dev)
+        syn = torch.empty((n, T, d + 1, d + 1), dtype=torch.uint8, device=dev) if return_streams else None
+        verd = torch.empty(step, dtype=torch.uint8, device=dev)
+        status = torch.full((step,), STATUS_IDENTITY, dtype=torch.uint8, device=dev)
+        n_blocks = -(-n // blk)
+        counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
+        counters0 = torch.zeros_like(counters) if no_decoder else None
+
+        def phase(name, t0):
+            if timings is None:
+                return t0
+            torch.cuda.current_stream(dev).synchronize()
+            t1 = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + (t1 - t0)
+            return t1
+
+        with torch.cuda.device(dev):
+            for s in range(0, n, step):
+                m = min(step, n - s)
+                o = s if return_streams else 0
+                sl = slice(o, o + m)
+                t = time.perf_counter()                                  # (the previous chunk's verdict phase ended on a synchronisation)
+                a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
+                if each and (a == a[0]).all() and (b == b[0]).all():   # one rate pair in this chunk: the scalar form (the same thresholds, no table upload)
+                    a, b = float(a[0]), float(b[0])
+                ev.run_into(m, T, commit, base + s, seed, a, b, hid[sl], triv[sl], frame[sl], syndromes=None if syn is None else syn[s:s + m])
+                t = phase("run", t)
+                ev.verdict_into(hid[sl], frame[sl], m, verd[:m])
+                ev.count_into(verd[:m], triv[sl], status[:m], (frame[sl] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), m, s, blk, counters)
+                if no_decoder:
+                    ev.verdict_into(hid[sl], None, m, verd[:m])
+                    ev.count_into(verd[:m], triv[sl], None, None, m, s, blk, counters0)
+                t = phase("verdict", t)
+            host, host0 = counters.cpu().numpy(), counters0.cpu().numpy() if no_decoder else None
+    finally:
+        if evaluator is None:
+            ev.close()
+    results = block_results(host, host0, np.zeros(n_blocks, dtype=np.int64), n_blocks, blk, ph, pm)
+    out = results[0] if keys is None else dict(zip(keys, results))
+    return (out, dict(syndromes=syn, hidden=hid, frame=frame, trivial=triv)) if return_streams else out

@@ -845,6 +845,36 @@ dq_status dq_stream_run_uf(dq_decode_eval* ev, const dq_env* env, int n, int T, 
                            double p_meas, const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev,
                            int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
 
+/* Union-find stream decoding for any odd d in 3 .. 15 with a window of up to 32 rounds (csrc/uf_wide.hip).  dq_version() stays 8: the
+ * capability is the presence of these symbols.  The algorithm and the schedule are dq_stream_decode_uf's, word for word (for d <= 7 and window <= 16 every
+ * field equals its); what differs is the shape: one workgroup of 256 threads per stream, defect rows and carries of 4 x 32 bits, frames of 4 x 64 bits, and
+ * dynamic LDS sized from (d, window) -- at most 64 KiB at d = 15, window 32.  The handle owns the lattice tables (built on the host from d alone): no
+ * environment handle is needed, and no referee is consulted.
+ * dq_wide_uf_create: d odd in 3 .. 15, error_model a DQ_MODEL_*, window in 1 .. 32, max_streams >= 1 (else DQ_ERR_INVALID, before any device work); an LDS
+ * request the device refuses is DQ_ERR_UNSUPPORTED (the kernels' limit is set once per device to the largest shape's, so handles of different shapes live
+ * side by side); the table of per-stream rates is allocated for max_streams here (DQ_ERR_NOMEM), so a handle serves any n up to max_streams in any order.
+ * dq_wide_uf_decode: dq_stream_decode_uf's arguments and results (syndromes_dev uint8 [n][T][d+1][d+1], 0/1 cells; weight_dev / n_defects_dev / rounds_dev
+ * int32 [n][2], nullable, 4-byte aligned).
+ * dq_wide_uf_run: dq_stream_run_uf's arguments and results without the environment: stream i is the first T rounds of lattice env_id_base + i under
+ * dq_decode_sample's convention -- Philox4x32-10 under `seed` with the counter (round, 0, lattice id, q); for qubit q < d^2 word 0 below the physical
+ * threshold is a hit, word 1 gives the Pauli type (DP) or an independent Z flip (IIDXZ); for q < d^2 - 1 word 2 below the measurement threshold flips
+ * stabilizer q's measurement.  weight_dev, n_defects_dev, rounds_dev and syndromes_dev may be NULL; the rate arrays come as a pair or not at all.
+ * dq_wide_uf_verdict: residual = hidden XOR frame (frame_dev NULL: no correction); the byte is dq_decode_verdict's with no referee: DQ_VERDICT_IN_CODESPACE,
+ * the class field (X parity on column 0, + 2 x Z parity on row 0), DQ_VERDICT_SUCCESS = in code space and class 0, DQ_VERDICT_ALIVE := DQ_VERDICT_SUCCESS,
+ * decoded field 0.  dq_decode_count sums these bytes as they stand; its "alive" counter then equals "success" by construction and says nothing more.
+ * All: n in 1 .. max_streams, T in 1 .. 2^20, commit in 1 .. window; null handles and bad arguments are DQ_ERR_INVALID before any device work.  A
+ * dq_wide_uf serves one host thread at a time and its calls are ordered on one stream at a time (dq_wide_uf_run's rate arrays go through a staging buffer
+ * of the handle); it is not thread-safe.  No reference counterpart. */
+typedef struct dq_wide_uf dq_wide_uf;
+dq_status dq_wide_uf_create(int d, int error_model, int window, int max_streams, dq_wide_uf** out);
+void dq_wide_uf_destroy(dq_wide_uf* h);
+dq_status dq_wide_uf_decode(dq_wide_uf* h, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
+                            int32_t* n_defects_dev, int32_t* rounds_dev, void* stream);
+dq_status dq_wide_uf_run(dq_wide_uf* h, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
+                         const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev,
+                         int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
+dq_status dq_wide_uf_verdict(dq_wide_uf* h, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Live kernel timing (measurement only; no reference counterpart).  dq_prof_arm(id, n) times up to n
  * launches of kernel family `id` (0 <= id < dq_prof_kernel_count(), names from dq_prof_kernel_name) with HIP
