@@ -209,6 +209,8 @@ SIGNATURES = {
     "dq_wide_uf_decode": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_run": (_i, [_vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_verdict": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "dq_envb_uf_select": (_i, [_vp, _vp, _vp, _vp]),
+    "dq_envb_guided_select_uf": (_i, [_vp, _vp, _vp, _dbl, _dbl, _i, _seedp, _u64, _vp, _vp, _vp]),
     "dq_prof_kernel_count": (_i, []),
     "dq_prof_kernel_name": (ctypes.c_char_p, [_i]),
     "dq_prof_kernel_symbol": (ctypes.c_char_p, [_i]),

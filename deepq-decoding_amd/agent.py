@@ -24,6 +24,7 @@ masked_greedy) follow the README's description and log output (README.md:168,262
 With N lattices one "step" of the loop advances all of them, `self.step` advances by N, and episode statistics
 are gathered on the device and read back every `sync_interval` vector steps.
 """
+import functools
 import json
 import os
 import time
@@ -552,6 +553,8 @@ class DQNAgent:
             guide_ev, guide_opened = guide.evaluator_for(venv)
             guide_method = getattr(guide, "method", "matching")
             core.guide_counts.zero_()
+            # the wide environment's teacher (decoder_wide.WideUnionFindAgent) has a step of its own
+            guided_step = core.guided_act_and_step_wide if core._wide else functools.partial(core.guided_act_and_step, method=guide_method)
         self.last_guided_steps = self.last_inexact_steps = 0
         self.training = True
         # Several ranks (one per GPU): every step-counted hyper-parameter -- nb_steps, nb_steps_warmup, the epsilon schedule, min_nb_steps,
@@ -588,7 +591,7 @@ class DQNAgent:
                 loop_iter += 1
                 eps, masked = self.policy.current(True)
                 if guide is not None:
-                    core.guided_act_and_step(guide_ev, eps, guide_share, masked_greedy=masked, method=guide_method)
+                    guided_step(guide_ev, eps, guide_share, masked_greedy=masked)
                     self.step += N
                     trained = self._maybe_train()
                 elif self._will_train(self.step + N):
@@ -623,7 +626,7 @@ class DQNAgent:
                     # lattice is still alive must not step it; the update is collective (gradient all-reduce), so every rank trains.
                     if core.local_stats[0] > 0:
                         if guide is not None:
-                            core.guided_act_and_step(guide_ev, eps, guide_share, masked_greedy=masked, record_stats=False, method=guide_method)
+                            guided_step(guide_ev, eps, guide_share, masked_greedy=masked, record_stats=False)
                         else:
                             core.act_and_step(eps, masked_greedy=masked, record_stats=False)
                     self._maybe_train()

@@ -247,6 +247,34 @@ class DQNCore:
         r.advance()
         self.vector_steps += 1
 
+    def guided_act_and_step_wide(self, evaluator, eps, guide_share, masked_greedy=False, record_stats=True):
+        """guided_act_and_step() for the wide environment with the union-find teacher: Q forward on the current observations,
+        VectorEnv.guided_select_wide into the ring's action slot, then dq_envb_step with auto-reset writing the ring's reward / done slots and the successor
+        observation; the referee's inexact flags are accumulated as _launch_env does it, the lattice-steps that followed the teacher are added to
+        self.guide_counts[0].  Nothing rides on a wide launch: the update draws its own minibatch.  evaluator: a decoder_wide.WideEvaluator of the
+        environment's d and error model, window >= volume_depth.  One GPU, the wide environment."""
+        if not self._wide or self.world_size > 1:
+            raise NotImplementedError("guided_act_and_step_wide: one GPU and the wide environment (the narrow one: guided_act_and_step)")
+        self._flush_stats()
+        r, env = self.ring, self.env
+        cur, nxt = r.cur, r.next_slot()
+        q = self.net.forward_multi([self._obs_job(params=self.params, slot=cur, batch=self.N, out=self.q_act, packed=self.params_pk)])[0]
+        if self._guide_flags is None:
+            self._guide_flags = torch.zeros((2, self.N), dtype=torch.uint8, device=self.device)
+        flags = self._guide_flags
+        env.guided_select_wide(evaluator, self.vector_steps, q=q, eps=eps, guide_share=guide_share, masked_greedy=masked_greedy, out=r.action[cur],
+                               out_guided=flags[0])
+        self.guide_counts[0] += flags[0].sum()
+        r.presampled = None
+        check(self.L.dq_envb_step(env._h, ptr(r.action[cur]), 1, ptr(r.store[nxt]), ptr(r.reward[cur]), ptr(r.terminal[cur]), ptr(env.legal), ptr(env.lifetime),
+                                  ptr(env.was_reset), ptr(env.inexact), self._stream()))
+        self._inexact_acc += env.inexact.sum()                       # (read and reported at the next read_stats())
+        self._stats_pending = (cur,) if record_stats else None
+        if record_stats and not self.defer_stats:
+            self._flush_stats()
+        r.advance()
+        self.vector_steps += 1
+
     def _sample_job(self, t, head, filled):
         """dq_sample_job for update number t, to be run on a ring with `head` / `filled`, into the look-ahead buffer (the update in
         progress may still be reading self.index)."""

@@ -13,6 +13,7 @@
 #include <new>
 #include "match_dev.h"
 #include "lattice_host.h"
+#include "env_big_view.h"
 
 #define BIG_MAX_W 4
 #define BIG_EPB 4                       // lattices (waves) per block
@@ -534,6 +535,16 @@ dq_status dq_envb_set_rates_per_lattice(dq_envb* E, const double* p_phys, const 
 }
 
 }  // extern "C"
+
+// env_big_view.h: the records as they stand, for a kernel that reads them in place
+dq_status envb_state_view(const dq_envb* E, EnvbStateView* v) {
+    DQ_REQUIRE(E && v, DQ_ERR_INVALID, "envb_state_view: null argument");
+    memset(v, 0, sizeof(*v));
+    v->state = E->d_state; v->sw = E->sw; v->W = E->W; v->LW = E->LW; v->n_envs = E->cfg.n_envs; v->d = E->cfg.d; v->depth = E->cfg.volume_depth;
+    v->model = E->cfg.error_model; v->use_Y = E->cfg.use_Y; v->identity = E->info.identity_index; v->n_actions = E->info.num_actions;
+    v->env_id_base = E->cfg.env_id_base;
+    return DQ_OK;
+}
 
 static dq_status big_fill(dq_envb* E, BigParams& p) {
     DQ_REQUIRE(E, DQ_ERR_INVALID, "null environment");

@@ -1,0 +1,225 @@
+// The union-find decoder as a policy and as a teacher of the WIDE environment, any odd d in 3 .. 15 (include/deepq_hip.h dq_envb_uf_select,
+// dq_envb_guided_select_uf): env_match.hip's and env_guide.hip's rules on env_big.hip's lattice record, with uf_wide_dev.h's component
+// decode in the solver's place.  One workgroup of UFW_THREADS threads per lattice, dynamic LDS from ufw_layout(n, d^2, volume_depth).
+//   env_wide_uf_kernel          every lattice: the lowest action of the union-find frame of the lattice's current volume that is not in completed_actions,
+//                               else the identity; the identity for a lattice whose done bit is set
+//   env_wide_guided_uf_kernel   epsilon-greedy selection whose exploring lattices follow that action with probability guide_share
+// The record (x[W] z[W] acted[W] round meta completed[LW] legal[LW] volume[depth][W]) is read in place and never written.  Thread 128 c + j picks node j of
+// component c out of round t's words, D_t = S_t xor S_(t-1) goes into the LDS ring as stream_wide_uf_kernel stores it, and the whole volume is decoded as one
+// last window (final, commit = depth): union_find_ref on the volume.  Every exit in front of or between barriers is decided by a kernel argument, the record's
+// meta word or the Philox words every thread draws alike.  No scratch pool, no lock, no loop that waits on another workgroup.
+#include "uf_wide.h"
+#include "env_big_view.h"
+
+#define EWU_NONE 0x7fffffff
+#define EWU_MAX_DEPTH 16                                         // dq_envb_create's limit on volume_depth
+
+namespace {
+
+struct EnvUfArgs {
+    UfwComp c0, c1;
+    const u8* node_stab;        // [2][128] node -> stabilizer in measurement order
+    const u64* state;           // [n_envs][sw]
+    int sw, W, LW, n_envs, n, d2, depth, model, use_Y, identity, n_actions;
+    int32_t* action;            // [n_envs]
+    // the guided form
+    const float* q;             // [n_envs][n_actions] or NULL
+    u64 T_eps, T_share, t;
+    int masked_greedy;
+    u32 seed0, seed1, env_id_base;
+    u8* guided;                 // [n_envs] or NULL
+};
+
+// The select body for the lattice whose record is `rec`, by the whole workgroup; returns the action to every thread.
+static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, const u64* __restrict__ rec, u8* smem, int tid) {
+    int W = p.W, depth = p.depth, identity = p.identity;
+    const int O_META = 3 * W + 1;
+    int o_comp = 3 * W + 2;
+    if ((rec[O_META] >> 32) & 1) return identity;                   // done: workgroup-uniform, no barrier passed yet
+    UfwLayout L = ufw_layout(p.n, p.d2, depth);
+    ufw_layout_in_vgpr(L);
+    u32* s_frame = reinterpret_cast<u32*>(smem + L.o_frame);
+    u32* s_carry = reinterpret_cast<u32*>(smem + L.o_carry);
+    int* s_acc = reinterpret_cast<int*>(smem + L.o_acc);
+    u32* s_ring = reinterpret_cast<u32*>(smem + L.o_ring);
+    int row_stride = depth * UFW_ROW_WORDS;
+    const int my_stab = (tid & (UFW_NODE_SLOTS - 1)) < p.n ? p.node_stab[tid] : 255;
+    const bool mine = my_stab < 255;
+    const u64* vp = rec + o_comp + 2 * p.LW + (mine ? my_stab >> 6 : 0);       // (a thread without a node reads word 0 of its own volume and masks it)
+    const int my_bit = my_stab & 63;
+    const u64* comp = rec + o_comp;
+    int d2 = p.d2, model = p.model, use_Y = p.use_Y;
+    UFW_IN_VGPR(W); UFW_IN_VGPR(depth); UFW_IN_VGPR(identity); UFW_IN_VGPR(row_stride); UFW_IN_VGPR(comp); UFW_IN_VGPR(d2); UFW_IN_VGPR(model);
+    UFW_IN_VGPR(use_Y);
+    if (tid < 2 * UFW_FRAME_WORDS) s_frame[tid] = 0;
+    if (tid < 2 * UFW_ROW_WORDS) s_carry[tid] = 0;
+    if (tid < 8) s_acc[tid] = tid == 6 ? EWU_NONE : 0;             // [6]: the lowest wanted action that is not completed
+    int prev = 0, nd = 0;
+    for (int t = 0; t < depth; ++t) {
+        const int cur = (int)((vp[(size_t)t * W] >> my_bit) & 1);
+        wide_rows(mine ? cur : 0, prev, tid, s_ring + t * UFW_ROW_WORDS, s_ring + row_stride + t * UFW_ROW_WORDS, nd);
+    }
+    __syncthreads();
+    UfwGraph G;
+    G.n = p.n; G.d2 = p.d2; G.per_round = p.d2 + p.n;
+    G.mag_n = ufw_magic(G.n); G.mag_pr = ufw_magic(G.per_round);
+    UFW_IN_VGPR(G.n); UFW_IN_VGPR(G.d2); UFW_IN_VGPR(G.per_round); UFW_IN_VGPR(G.mag_n); UFW_IN_VGPR(G.mag_pr);
+    const u8 *eu0 = p.c0.eu, *ev0 = p.c0.ev, *eu1 = p.c1.eu, *ev1 = p.c1.ev;
+    UFW_IN_VGPR(eu0); UFW_IN_VGPR(ev0); UFW_IN_VGPR(eu1); UFW_IN_VGPR(ev1);
+    G.depth = depth; G.B = depth * G.n; G.NN = G.B + 1; G.NE = depth * G.per_round;
+    const int n_comp = model == DQ_MODEL_X ? 1 : 2;                 // the X model has no action layer for component 1: its frame is not asked for
+    for (int c = 0; c < n_comp; ++c) {
+        G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
+        ufw_component(G, s_ring + c * row_stride, smem, L, tid, depth, true, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c, s_acc + 4 + c);
+    }
+    // decoder.frame_to_actions' rule; thread q < d^2 holds qubit q's cell of the two frames (the component's last barrier is behind every thread, or its
+    // frame words still hold the zeros stored in front of the first one)
+    int best = EWU_NONE;
+    if (tid < d2) {
+        const int x = (s_frame[tid >> 5] >> (tid & 31)) & 1;
+        const int z = model == DQ_MODEL_X ? 0 : (s_frame[UFW_FRAME_WORDS + (tid >> 5)] >> (tid & 31)) & 1;
+        int a0 = -1, a1 = -1;                                      // this qubit's wanted actions, ascending
+        if (model == DQ_MODEL_X) { if (x) a0 = tid; }
+        else if (use_Y) { if (x | z) a0 = (x ? (z ? 1 : 0) : 2) * d2 + tid; }
+        else { if (x) a0 = tid; if (z) a1 = d2 + tid; }
+        if (a0 >= 0 && !((comp[a0 >> 6] >> (a0 & 63)) & 1)) best = a0;
+        else if (a1 >= 0 && !((comp[a1 >> 6] >> (a1 & 63)) & 1)) best = a1;
+    }
+    if (best != EWU_NONE) __hip_atomic_fetch_min(s_acc + 6, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __syncthreads();
+    const int a = s_acc[6];
+    return a == EWU_NONE ? identity : a;
+}
+
+__global__ __launch_bounds__(UFW_THREADS) void env_wide_uf_kernel(EnvUfArgs p) {
+    extern __shared__ __attribute__((aligned(16))) u8 smem[];
+    const int tid = threadIdx.x;
+    const size_t i = blockIdx.x;
+    if ((int)blockIdx.x >= p.n_envs) return;                        // workgroup-uniform
+    int32_t* out = p.action + i;
+    UFW_IN_VGPR(out);
+    const int a = env_wide_uf_action(p, p.state + i * p.sw, smem, tid);
+    if (tid == 0) *out = a;
+}
+
+__global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfArgs p) {
+    extern __shared__ __attribute__((aligned(16))) u8 smem[];
+    const int tid = threadIdx.x;
+    const size_t i = blockIdx.x;
+    if ((int)blockIdx.x >= p.n_envs) return;                        // workgroup-uniform
+    const u64* rec = p.state + i * p.sw;
+    u32 w[4];                                                       // the words dq_policy_select_wide draws for the lattice, drawn by every thread
+    philox4x32_10((u32)p.t, (u32)(p.t >> 32), p.env_id_base + (u32)blockIdx.x, (u32)DQ_STREAM_POLICY << 16, p.seed0, p.seed1, w);
+    const u32 w0 = (u32)__builtin_amdgcn_readfirstlane((int)w[0]), w1 = (u32)__builtin_amdgcn_readfirstlane((int)w[1]);
+    const u32 w2 = (u32)__builtin_amdgcn_readfirstlane((int)w[2]);
+    const bool explore = p.q == nullptr || (u64)w1 < p.T_eps;
+    const bool follow = explore && (u64)w2 < p.T_share;
+    int32_t* out = p.action + i;
+    u8* flag = p.guided ? p.guided + i : nullptr;
+    int a;
+    if (follow) {                                                   // workgroup-uniform: the only branch with barriers, the only one that touches LDS
+        UFW_IN_VGPR(out); UFW_IN_VGPR(flag);
+        a = env_wide_uf_action(p, rec, smem, tid);
+    } else {
+        if (tid >= 64) return;                                      // one wave suffices, and no barrier follows
+        const u64* lg = rec + 3 * p.W + 2 + p.LW;                   // the record's legal set: what the last reset / step also wrote to its legal_dev
+        if (explore) {                                              // policy_wide_kernel's rule
+            int n_legal = 0;
+            for (int k = 0; k < p.LW; ++k) n_legal += __popcll(lg[k]);
+            int kk = (int)__umulhi(w0, (u32)n_legal);
+            a = -1;
+            for (int k = 0; k < p.LW && a < 0; ++k) {
+                u64 m = lg[k];
+                const int c = __popcll(m);
+                if (kk < c) {
+                    for (int s = 0; s < kk; ++s) m &= m - 1;
+                    a = 64 * k + __ffsll((long long)m) - 1;
+                } else kk -= c;
+            }
+        } else {                                                    // larger value, the lower index among equals: independent of how many threads share the row
+            const float* row = p.q + i * p.n_actions;
+            float bv = -INFINITY;
+            int ba = EWU_NONE;
+            for (int k = tid; k < p.n_actions; k += 64) {
+                const bool ok = !p.masked_greedy || ((lg[k >> 6] >> (k & 63)) & 1);
+                const float v = row[k];
+                if (ok && (v > bv || ba == EWU_NONE)) { bv = v; ba = k; }
+            }
+            dq_wave_argmax(bv, ba);
+            a = __builtin_amdgcn_readfirstlane(ba);
+        }
+    }
+    if (tid == 0) {
+        *out = a;
+        if (flag) *flag = follow ? 1 : 0;
+    }
+}
+
+// What both entry points check alike, before any device work: the handles, the decoder's lattice and window (DQ_ERR_INVALID); then the kernels' LDS limit, once per
+// device (DQ_ERR_UNSUPPORTED).
+dq_status env_wide_uf_prepare(const dq_envb* E, const dq_wide_uf* H, const int32_t* action_dev, const float* q_dev, EnvUfArgs* a, int* lds, const char* who) {
+    DQ_REQUIRE(E && H && action_dev, DQ_ERR_INVALID, "%s: null argument", who);
+    DQ_REQUIRE((reinterpret_cast<uintptr_t>(action_dev) & 3) == 0 && (reinterpret_cast<uintptr_t>(q_dev) & 3) == 0, DQ_ERR_INVALID,
+               "%s: action_dev and q_dev must be 4-byte aligned", who);
+    EnvbStateView S;
+    const dq_status rc = envb_state_view(E, &S);
+    if (rc != DQ_OK) return rc;
+    DQ_REQUIRE(S.d == H->d && S.model == H->model, DQ_ERR_INVALID, "%s: the environment's lattice (d = %d, model %d) is not the decoder handle's (d = %d, model %d)", who,
+               S.d, S.model, H->d, H->model);
+    DQ_REQUIRE(S.depth >= 1 && S.depth <= EWU_MAX_DEPTH && H->window >= S.depth, DQ_ERR_INVALID,
+               "%s: the decoder handle's window %d is below the environment's volume_depth %d", who, H->window, S.depth);
+    DQ_REQUIRE(S.n_actions >= 1 && S.n_actions <= 64 * S.LW && S.sw == 3 * S.W + 2 + 2 * S.LW + S.depth * S.W, DQ_ERR_INVALID, "%s: inconsistent record", who);
+    static unsigned long long attr_devs = 0;                          // per device (common.h dq_device_bit)
+    const unsigned long long dev_bit = dq_device_bit();
+    if (!(attr_devs & dev_bit)) {
+        const int lds_max = ufw_layout((UFW_MAX_D * UFW_MAX_D - 1) / 2, UFW_MAX_D * UFW_MAX_D, EWU_MAX_DEPTH).bytes;
+        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(env_wide_uf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        if (ea == hipSuccess) ea = hipFuncSetAttribute(reinterpret_cast<const void*>(env_wide_guided_uf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        if (ea != hipSuccess) {
+            (void)hipGetLastError();
+            dq_set_error("%s: the device refuses %d bytes of LDS per workgroup: %s", who, lds_max, hipGetErrorString(ea));
+            return DQ_ERR_UNSUPPORTED;
+        }
+        attr_devs |= dev_bit;
+    }
+    memset(a, 0, sizeof(*a));
+    a->c0 = UfwComp{H->ends, H->ends + 256};
+    a->c1 = UfwComp{H->ends + 512, H->ends + 768};
+    a->node_stab = H->node_stab; a->state = S.state; a->sw = S.sw; a->W = S.W; a->LW = S.LW; a->n_envs = S.n_envs; a->n = H->n; a->d2 = H->d2; a->depth = S.depth;
+    a->model = S.model; a->use_Y = S.use_Y; a->identity = S.identity; a->n_actions = S.n_actions; a->env_id_base = S.env_id_base;
+    a->action = const_cast<int32_t*>(action_dev);
+    *lds = ufw_layout(H->n, H->d2, S.depth).bytes;
+    return DQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+dq_status dq_envb_uf_select(dq_envb* env, dq_wide_uf* H, int32_t* action_dev, void* stream) {
+    EnvUfArgs a;
+    int lds = 0;
+    const dq_status rc = env_wide_uf_prepare(env, H, action_dev, nullptr, &a, &lds, "dq_envb_uf_select");
+    if (rc != DQ_OK) return rc;
+    env_wide_uf_kernel<<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(a);
+    DQ_LAUNCH_CHECK();
+    return DQ_OK;
+}
+
+dq_status dq_envb_guided_select_uf(dq_envb* env, dq_wide_uf* H, const float* q_dev, double eps, double guide_share, int masked_greedy, const uint32_t seed[2],
+                                   uint64_t t, int32_t* action_dev, uint8_t* guided_dev, void* stream) {
+    DQ_REQUIRE(seed, DQ_ERR_INVALID, "dq_envb_guided_select_uf: null argument");
+    DQ_REQUIRE(eps >= 0.0 && eps <= 1.0, DQ_ERR_INVALID, "dq_envb_guided_select_uf: eps must be in [0,1]");                  // (NaN fails both compares)
+    DQ_REQUIRE(guide_share >= 0.0 && guide_share <= 1.0, DQ_ERR_INVALID, "dq_envb_guided_select_uf: guide_share must be in [0,1]");
+    EnvUfArgs a;
+    int lds = 0;
+    const dq_status rc = env_wide_uf_prepare(env, H, action_dev, q_dev, &a, &lds, "dq_envb_guided_select_uf");
+    if (rc != DQ_OK) return rc;
+    a.q = q_dev; a.T_eps = dq_rate_threshold(eps); a.T_share = dq_rate_threshold(guide_share); a.t = t; a.masked_greedy = masked_greedy;
+    a.seed0 = seed[0]; a.seed1 = seed[1]; a.guided = guided_dev;
+    env_wide_guided_uf_kernel<<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(a);
+    DQ_LAUNCH_CHECK();
+    return DQ_OK;
+}
+
+}  // extern "C"

@@ -723,11 +723,15 @@ class MatchingAgent:
         venv = _narrow_env(env)
         return Evaluator(d, model, use_Y, depth, chunk=min(self.chunk, int(venv.n_envs)), device=venv.device), True
 
+    def _check_env(self, env):
+        """What test() and test_error_rates() require of the environment and the agent's evaluator, before any library call."""
+        check_match_policy_args(env, self.evaluator, self.chunk)
+
     def test(self, env, nb_episodes=1, verbose=1, interval=100, nb_max_episode_steps=None):
         """DQNAgent.test for this policy: the same keys, ceil-share quota and record order (vector step, then lattice).  Returns History."""
         from . import episodes
         from .agent import DQNAgent, History
-        check_match_policy_args(env, self.evaluator, self.chunk)
+        self._check_env(env)
         v = getattr(env, "_v", env)
         if isinstance(nb_episodes, (bool, np.bool_)) or not isinstance(nb_episodes, (int, np.integer)) or nb_episodes < 0:
             raise ValueError(f"nb_episodes must be a non-negative integer, not {nb_episodes!r}")
@@ -744,7 +748,7 @@ class MatchingAgent:
         previous rates are restored on the way out.  Returns {rate: History}."""
         from . import episodes
         from .agent import DQNAgent
-        check_match_policy_args(env, self.evaluator, self.chunk)
+        self._check_env(env)
         v = getattr(env, "_v", env)
         rates, m, ph, pm, quota = episodes.rate_blocks(v.n_envs, error_rates, nb_episodes, p_meas)
         episodes.check_step_cap(nb_max_episode_steps, quota)

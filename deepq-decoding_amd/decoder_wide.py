@@ -9,8 +9,8 @@ import ctypes
 
 import numpy as np
 
-from .decoder import (COUNTER_NAMES, DEFAULT_CHUNK, MODELS, STATUS_IDENTITY, STREAM_MAX_ROUNDS, StreamResult, block_results, check_binary, check_rates,
-                      stream_windows)
+from .decoder import (COUNTER_NAMES, DEFAULT_CHUNK, MODELS, STATUS_IDENTITY, STREAM_MAX_ROUNDS, MatchingAgent, StreamResult, action_layers, block_results,
+                      check_binary, check_rates, lattice_of, rate_threshold, stream_windows)
 
 WIDE_MAX_D = 15
 WIDE_MAX_WINDOW = 32
@@ -298,3 +298,139 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
     results = block_results(host, host0, np.zeros(n_blocks, dtype=np.int64), n_blocks, blk, ph, pm)
     out = results[0] if keys is None else dict(zip(keys, results))
     return (out, dict(syndromes=syn, hidden=hid, frame=frame, trivial=triv)) if return_streams else out
+
+
+# ---- the union-find decoder as a policy and a teacher of the wide environment (include/deepq_hip.h dq_envb_uf_select, dq_envb_guided_select_uf;
+# ---- csrc/env_wide_uf.hip) -----------------------------------------------------------------------------------------------------
+WIDE_MAX_DEPTH = 16
+
+
+def completed_from_state(state_row, d, legal_words):
+    """The set of action indices in completed_actions of one lattice's row of VectorEnv.export_state() on the wide backend (dq_envb_export_state's layout:
+    x[W] z[W] true[W] summed[W] acted[W] round completed[LW] legal[LW] meta volume[depth][W], W = ceil(d^2 / 64))."""
+    W, LW = (int(d) * int(d) + 63) // 64, int(legal_words)
+    o = 5 * W + 1
+    words = [int(x) & (2 ** 64 - 1) for x in np.asarray(state_row).reshape(-1)[o:o + LW].tolist()]
+    if len(words) != LW:
+        raise ValueError(f"the state row is too short for d = {d} and {LW} legal words")
+    return {64 * k + b for k, w in enumerate(words) for b in range(64) if (w >> b) & 1}
+
+
+def guided_actions_wide(q, legal_words, teacher, eps, guide_share, masked_greedy, seed, env_id_base, t):
+    """decoder.guided_actions for legal sets of any number of 64-bit words: the rule of dq_envb_guided_select_uf in numpy.  legal_words: [n, LW] (VectorEnv.legal
+    of the wide backend; bit a of the set = action a); teacher: int [n], what uf_select_wide emits for the lattices as they stand; the other arguments and
+    the result (actions int32 [n], guided flags uint8 [n]) are guided_actions'.  With two words it returns exactly what that function returns."""
+    from . import _lib, _philox
+    for name, v in (("eps", eps), ("guide_share", guide_share)):
+        if not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"guided_actions_wide: {name} must lie in [0, 1], not {v!r}")
+    words = np.asarray(legal_words)
+    if words.ndim != 2 or words.shape[1] < 1:
+        raise ValueError(f"guided_actions_wide: legal_words must have shape [n, LW], got {words.shape}")
+    words = np.ascontiguousarray(words).astype(np.int64, copy=False).view(np.uint64)
+    n, LW = words.shape
+    teacher = np.asarray(teacher).reshape(-1)
+    if len(teacher) != n:
+        raise ValueError(f"guided_actions_wide: {len(teacher)} teacher actions for {n} legal sets")
+    t = int(t)
+    ids = (int(env_id_base) + np.arange(n, dtype=np.uint64)) & np.uint64(0xFFFFFFFF)
+    w0, w1, w2, _ = _philox.philox4x32(t & 0xFFFFFFFF, t >> 32, ids, _lib.STREAM_POLICY << 16, seed)
+    explore = np.ones(n, dtype=bool) if q is None else w1.astype(np.uint64) < np.uint64(rate_threshold(eps))
+    guided = explore & (w2.astype(np.uint64) < np.uint64(rate_threshold(guide_share)))
+    if q is not None:
+        q = np.asarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[0] != n or not 1 <= q.shape[1] <= 64 * LW:
+            raise ValueError(f"guided_actions_wide: q must have shape [{n}, num_actions <= {64 * LW}], got {q.shape}")
+    actions = np.empty(n, dtype=np.int32)
+    for i in range(n):
+        if guided[i]:
+            actions[i] = teacher[i]
+            continue
+        mask = sum(int(words[i, k]) << (64 * k) for k in range(LW))
+        if explore[i]:
+            members = [a for a in range(64 * LW) if (mask >> a) & 1]
+            k = (int(w0[i]) * len(members)) >> 32
+            actions[i] = members[k] if members else -1
+        else:
+            row = q[i]
+            cand = [a for a in range(len(row)) if not masked_greedy or (mask >> a) & 1]
+            actions[i] = max(cand, key=lambda a: (row[a], -a))                  # the larger value, the lower index among equals
+    return actions, guided.astype(np.uint8)
+
+
+def check_wide_policy_args(env, evaluator=None, chunk=DEFAULT_CHUNK):
+    """Validates the lattice of a wide union-find evaluation without touching the library: a wide handle (else NotImplementedError, naming the narrow agent),
+    odd d in 3 .. 15, volume_depth 1 .. 16, an evaluator of the same d and error model whose window covers the volume (else ValueError).  Returns
+    (d, error_model, use_Y, volume_depth)."""
+    if env is None:
+        raise ValueError("an environment is needed: the policy plays it")
+    v = getattr(env, "_v", env)
+    d, model, use_Y, depth = lattice_of(v)
+    if not getattr(v, "wide", False):
+        raise NotImplementedError("WideUnionFindAgent plays the wide environment (backend='wide' / d >= 9); on the narrow one use "
+                                  "decoder.MatchingAgent(method=\"union_find\")")
+    check_wide_lattice(d, model)
+    action_layers(model, use_Y)
+    if not 1 <= depth <= WIDE_MAX_DEPTH:
+        raise NotImplementedError(f"the wide union-find policy covers volume_depth 1..{WIDE_MAX_DEPTH}, not {depth}")
+    check_chunk(chunk)
+    if evaluator is not None:
+        theirs = (getattr(evaluator, "d", None), getattr(evaluator, "error_model", None))
+        window = getattr(evaluator, "window", None)
+        if window is None or theirs != (d, model):
+            raise ValueError(f"the evaluator must be a WideEvaluator of the environment's (d, error model) = {(d, model)}, not {theirs}")
+        if int(window) < depth:
+            raise ValueError(f"the evaluator's window {window} is below the environment's volume_depth {depth}")
+    return d, model, use_Y, depth
+
+
+class WideUnionFindAgent(MatchingAgent):
+    """decoder.MatchingAgent(method="union_find") for the wide environment, any odd d in 3 .. 15: per agent step one dq_envb_uf_select launch (the next flip of
+    the union-find frame of the lattice's current volume, then the identity) and one dq_envb_step with auto-reset.  test and test_error_rates return what
+    MatchingAgent's return -- the same keys, quotas, block layout, record order and step cap, through episodes.py.  policy="identity": only ever the identity,
+    the "no decoder" row on the same handle.  evaluator: a WideEvaluator of the environment's d and error model with window >= volume_depth (it stays
+    open); default: one per call.  The decoder has no fallback, so last_inexact_steps is 0.  As a subclass it is accepted by EpsGreedyQPolicy(guide=...):
+    DQNAgent.fit then runs DQNCore.guided_act_and_step_wide."""
+
+    def __init__(self, evaluator=None, chunk=DEFAULT_CHUNK, policy="matching"):
+        super().__init__(evaluator=evaluator, chunk=chunk, policy=policy)
+        self.method = "union_find"
+
+    def _check_env(self, env):
+        check_wide_policy_args(env, self.evaluator, self.chunk)
+
+    def evaluator_for(self, env):
+        """(a WideEvaluator(d, error_model, window=volume_depth) of env's lattice, whether it was opened here and is the caller's to close): the agent's own
+        where it was given one.  Validates like test(), before any library call."""
+        d, model, _, depth = check_wide_policy_args(env, self.evaluator, self.chunk)
+        if self.evaluator is not None:
+            return self.evaluator, False
+        v = getattr(env, "_v", env)
+        return WideEvaluator(d, model, window=depth, chunk=min(self.chunk, int(v.n_envs)), device=v.device), True
+
+    def _records(self, venv, quota, nb_max_episode_steps):
+        """(records of episodes.episode_records, zeros int64 [N]) of one evaluation from a reset."""
+        import torch
+        from . import episodes
+        dev, N = venv.device, int(venv.n_envs)
+        decode = self.policy == "matching"
+        ev, opened = self.evaluator_for(venv) if decode else (None, False)
+        try:
+            with torch.cuda.device(dev):
+                action = torch.full((N,), int(venv.identity_index), dtype=torch.int32, device=dev)
+                steps = [0]
+
+                def step(k):
+                    if decode:
+                        venv.uf_select_wide(ev, out=action)
+                    venv.step(action, auto_reset=True, write_obs=False)
+                    steps[0] = k + 1
+                    return venv.done, venv.was_reset, venv.reward, venv.lifetime
+
+                venv.reset(write_obs=False)
+                rec = episodes.episode_records(venv.L, dev, venv._stream, N, quota, step, None, nb_max_episode_steps)
+                self.last_vector_steps = steps[0]
+                return rec, np.zeros(N, dtype=np.int64)
+        finally:
+            if opened:
+                ev.close()

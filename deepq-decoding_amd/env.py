@@ -545,6 +545,56 @@ class VectorEnv:
                  ptr(out_guided), ptr(out_inexact), self._stream()))
         return out
 
+    def _check_wide_uf(self, evaluator, who):
+        """What uf_select_wide and guided_select_wide require of the handle and the evaluator, before any library call."""
+        if not self.wide:
+            raise NotImplementedError(f"{who} covers the wide environment (backend='wide' / d >= 9); on the narrow one use "
+                                      f"match_select(method=\"union_find\")")
+        theirs = (getattr(evaluator, "d", None), getattr(evaluator, "error_model", None))
+        window = getattr(evaluator, "window", None)
+        if window is None:
+            raise ValueError(f"{who}: the evaluator must be a decoder_wide.WideEvaluator, not {type(evaluator).__name__}")
+        if theirs != (self.d, self.error_model):
+            raise ValueError(f"{who}: the evaluator's lattice (d, error model) = {theirs} is not the environment's {(self.d, self.error_model)}")
+        if int(window) < int(self.volume_depth):
+            raise ValueError(f"{who}: the evaluator's window {window} is below the environment's volume_depth {self.volume_depth}")
+
+    def uf_select_wide(self, evaluator, out=None):
+        """match_select(method="union_find") for the wide environment, any odd d in 3 .. 15 (include/deepq_hip.h dq_envb_uf_select):
+        the lowest action index of the union-find decoder's Pauli frame for the lattice's current volume that is not in completed_actions, else the
+        identity; the identity for a lattice whose done flag is set.  evaluator: a decoder_wide.WideEvaluator of this d and error model whose window is at
+        least volume_depth (it owns the decoder's tables; its chunk does not bound n_envs).  out: int32 [n_envs].  Returns the actions;
+        step(actions, auto_reset=True) is the agent step.  A narrow handle raises NotImplementedError."""
+        self._check_wide_uf(evaluator, "uf_select_wide")
+        self._check_outputs("uf_select_wide", (out, torch.int32))
+        if out is None:
+            out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        check(self.L.dq_envb_uf_select(self._h, evaluator._h, ptr(out), self._stream()))
+        return out
+
+    def guided_select_wide(self, evaluator, t, q=None, eps=1.0, guide_share=1.0, masked_greedy=False, out=None, out_guided=None):
+        """guided_select(method="union_find") for the wide environment (include/deepq_hip.h dq_envb_guided_select_uf; the rule in
+        numpy: decoder_wide.guided_actions_wide).  With select_actions' Philox words w of policy counter t: explore = q is None or w[1] < T(eps);
+        guided = explore and w[2] < T(guide_share); a guided lattice gets uf_select_wide's action, another exploring one the k-th legal action, the rest the
+        first maximum of their row of q (float32 [n_envs, num_actions]; over the legal set when masked_greedy).  guide_share = 0: select_actions' actions bit
+        for bit; eps = 1 with guide_share = 1: uf_select_wide's.  The decoder runs for the guided lattices only.  out: int32 [n_envs]; out_guided: uint8
+        [n_envs] or None (1 where the lattice followed the decoder).  Returns the actions.  A narrow handle raises NotImplementedError."""
+        self._check_wide_uf(evaluator, "guided_select_wide")
+        for name, v in (("eps", eps), ("guide_share", guide_share)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+                raise ValueError(f"guided_select_wide: {name} must be a number in [0, 1], not {v!r}")
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) or t < 0:
+            raise ValueError(f"guided_select_wide: the policy counter t must be a non-negative integer, not {t!r}")
+        if q is not None and not (q.dtype == torch.float32 and q.is_cuda and q.is_contiguous() and tuple(q.shape) == (self.n_envs, self.num_actions)):
+            raise ValueError(f"guided_select_wide: q is a contiguous float32 device tensor [{self.n_envs}, {self.num_actions}] or None")
+        self._check_outputs("guided_select_wide", (out, torch.int32), (out_guided, torch.uint8))
+        if out is None:
+            out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        seed = (ctypes.c_uint32 * 2)(*self.seed)
+        check(self.L.dq_envb_guided_select_uf(self._h, evaluator._h, ptr(q), float(eps), float(guide_share), int(masked_greedy), seed, int(t), ptr(out),
+                                              ptr(out_guided), self._stream()))
+        return out
+
     # -- state views --------------------------------------------------------------------------------------
     def export_state(self):
         """int64 tensor [n_envs, 11 + depth] of uint64 words (layout: include/deepq_hip.h)."""

@@ -875,6 +875,26 @@ dq_status dq_wide_uf_run(dq_wide_uf* h, int n, int T, int commit, uint32_t env_i
                          int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
 dq_status dq_wide_uf_verdict(dq_wide_uf* h, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev, void* stream);
 
+/* The union-find decoder as a policy and as a teacher of the wide environment, any odd d in 3 .. 15 (csrc/env_wide_uf.hip).
+ * dq_version() stays 8: the capability is the presence of these two symbols.  The rules are dq_env_uf_select's and dq_env_guided_select_uf's on the wide
+ * handle's lattice records, which are read in place and never written; the decoder is dq_wide_uf's component decode on the lattice's current volume taken
+ * as one last window (window = commit = volume_depth), one workgroup of 256 threads per lattice, dynamic LDS sized from (d, volume_depth).
+ * dq_envb_uf_select: action_dev[i] = the lowest action index of the union-find frame of lattice i's volume that is not in its completed_actions, else the
+ * identity; the identity for a lattice whose done flag is set.  Frame to actions: X model: the X part on layer 0; use_Y: Pauli code 1 / 2 / 3 on layer
+ * 0 / 1 / 2; otherwise the X part on layer 0 and the Z part on layer 1.  The legal set is not consulted.
+ * dq_envb_guided_select_uf: with w[0..3] the Philox words dq_policy_select_wide draws for (seed, t, the environment's env_id_base + i):
+ * explore = q_dev == NULL || w[1] < T(eps); guided = explore && w[2] < T(guide_share); a guided lattice gets dq_envb_uf_select's action, another exploring
+ * one the k-th member of the record's legal set, k = umulhi(w[0], n_legal) (-1 for an empty set), the rest the first maximum of their row of q_dev
+ * (float32 [n_envs][num_actions]; over the legal set when masked_greedy).  guided_dev uint8 [n_envs] (nullable): 1 where the lattice followed the decoder.
+ * Only the guided lattices run the decoder.
+ * Both: DQ_ERR_INVALID before any device work for a null handle, action_dev or seed, an action_dev or q_dev that is not 4-byte aligned, eps or guide_share
+ * outside [0, 1], a decoder handle of another d or error model, or one whose window is below the environment's volume_depth; DQ_ERR_UNSUPPORTED if the
+ * device refuses the LDS.  The dq_wide_uf handle is only read: its max_streams does not bound n_envs.  One host thread and one stream at a time per handle,
+ * as for dq_wide_uf_*.  No reference counterpart. */
+dq_status dq_envb_uf_select(dq_envb* env, dq_wide_uf* h, int32_t* action_dev, void* stream);
+dq_status dq_envb_guided_select_uf(dq_envb* env, dq_wide_uf* h, const float* q_dev, double eps, double guide_share, int masked_greedy,
+                                   const uint32_t seed[2], uint64_t t, int32_t* action_dev, uint8_t* guided_dev, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Live kernel timing (measurement only; no reference counterpart).  dq_prof_arm(id, n) times up to n
  * launches of kernel family `id` (0 <= id < dq_prof_kernel_count(), names from dq_prof_kernel_name) with HIP

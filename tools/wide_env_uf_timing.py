@@ -1,0 +1,120 @@
+"""Launch times of the wide environment's union-find selection: recorded, not gated.
+
+    python tools/wide_env_uf_timing.py [--lattices 4096] [--p 0.006] [--rounds 5] [--play 8] [--out FILE]
+
+Per configuration (d = 9 / volume_depth 9 and d = 15 / volume_depth 5, DP) on --lattices mid-episode lattices (--play agent steps of the union-find policy
+from a reset): the select launch (env_wide_uf_kernel), dq_envb_step, dq_wide_uf_decode on the same volumes exported as grids with window = commit =
+volume_depth (stream_wide_uf_kernel), and the guided launch (env_wide_guided_uf_kernel) at guided fractions 0, 0.1 and 1 (eps = 1, guide_share = the
+fraction).  Device events around single launches; the configurations alternate within each of --rounds rounds, and every round ends with one untimed agent
+step and a fresh export, so that all launches of a round see the same volumes.  Median, min and max.  Writes profiles/wide_env_uf_timing.json."""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+dq = importlib.import_module("deepq-decoding_amd")
+
+SEED = (24301, 57005)
+SHAPES = ((9, 9), (15, 5))
+
+
+def timed_us(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return 1e3 * e0.elapsed_time(e1)
+
+
+class Config:
+    def __init__(self, d, depth, n, p):
+        from oracle import lattice
+        self.d, self.depth, self.n = d, depth, n
+        self.env = dq.VectorEnv(n_envs=n, seed=SEED, d=d, error_model="DP", use_Y=False, volume_depth=depth, p_phys=p, p_meas=p, backend="wide")
+        self.ev = dq.WideEvaluator(d, "DP", window=depth, chunk=n, device=self.env.device)
+        dev = self.env.device
+        self.action, self.other = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+        self.flag = torch.empty(n, dtype=torch.uint8, device=dev)
+        self.q = torch.randn((n, self.env.num_actions), device=dev, generator=torch.Generator(device=dev).manual_seed(5))
+        self.frame = torch.empty((n, d, d), dtype=torch.uint8, device=dev)
+        order = lattice.Masks(d).order
+        self.cell = torch.tensor([a * (d + 1) + b for a, b in order], device=dev)
+        self.word = torch.tensor([s >> 6 for s in range(len(order))], device=dev)
+        self.bit = torch.tensor([s & 63 for s in range(len(order))], device=dev)
+        self.grids = torch.zeros((n, depth, (d + 1) * (d + 1)), dtype=torch.uint8, device=dev)
+        self.t = 0
+        self.env.reset(write_obs=False)
+
+    def export(self):
+        """The lattices' current volumes as syndrome grids uint8 [n, depth, d+1, d+1] (dq_envb_export_state's layout)."""
+        W, LW = (self.d * self.d + 63) // 64, self.env.legal_words
+        o = 5 * W + 2 + 2 * LW
+        vol = self.env.export_state()[:, o:o + self.depth * W].reshape(self.n, self.depth, W)
+        self.grids[:, :, self.cell] = ((vol[:, :, self.word] >> self.bit) & 1).to(torch.uint8)
+
+    def play(self):
+        self.env.uf_select_wide(self.ev, out=self.action)
+        self.env.step(self.action, auto_reset=True, write_obs=False)
+        self.t += 1
+
+    def launches(self):
+        e, ev, n = self.env, self.ev, self.n
+        out = {"select": lambda: e.uf_select_wide(ev, out=self.action),
+               "decode": lambda: ev.decode_into(self.grids, n, self.depth, self.depth, self.frame)}
+        for share in (0.0, 0.1, 1.0):
+            out[f"guided_{share:g}"] = lambda share=share: e.guided_select_wide(ev, self.t, q=self.q, eps=1.0, guide_share=share, out=self.other, out_guided=self.flag)
+        out["step"] = lambda: e.step(self.action, auto_reset=True, write_obs=False)      # last: it moves the lattices on
+        return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lattices", type=int, default=4096)
+    ap.add_argument("--p", type=float, default=0.006)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--play", type=int, default=8)
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    cfgs = {f"d{d}_depth{depth}": Config(d, depth, a.lattices, a.p) for d, depth in SHAPES}
+    for c in cfgs.values():
+        for _ in range(a.play):
+            c.play()
+        c.export()
+        for name, fn in c.launches().items():                                           # first launches (the step included: one more agent step)
+            fn()
+        c.t += 1
+        c.export()
+    torch.cuda.synchronize()
+    t = {k: {name: [] for name in c.launches()} for k, c in cfgs.items()}
+    live = {k: [] for k in cfgs}
+    for _ in range(a.rounds):
+        for k, c in cfgs.items():
+            for name, fn in c.launches().items():
+                t[k][name].append(timed_us(fn))
+            live[k].append(float((c.action != c.env.identity_index).float().mean()))
+            c.t += 1
+            c.export()
+    record = dict(device=torch.cuda.get_device_name(0), lattices=a.lattices, p=a.p, model="DP", played_steps=a.play, timing_rounds=a.rounds, configurations={})
+    for k, c in cfgs.items():
+        rows = {name: dict(median_us=float(np.median(v)), min_us=float(np.min(v)), max_us=float(np.max(v))) for name, v in t[k].items()}
+        ratio = rows["select"]["median_us"] / rows["decode"]["median_us"]
+        record["configurations"][k] = dict(d=c.d, volume_depth=c.depth, flip_share=float(np.mean(live[k])), launches=rows, select_over_decode=ratio)
+        for name, r in rows.items():
+            print(f"{k:12s} {name:12s} median {r['median_us']:10.1f} us  [{r['min_us']:10.1f}, {r['max_us']:10.1f}]")
+        print(f"{k:12s} select / decode = {ratio:.3f}")
+    path = a.out or os.path.join(ROOT, "profiles", "wide_env_uf_timing.json")
+    with open(path, "w") as f:
+        json.dump(record, f, indent=1)
+        f.write("\n")
+    print("wrote", path)
+
+
+if __name__ == "__main__":
+    main()
