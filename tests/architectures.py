@@ -14,6 +14,22 @@ is there for the forms of those kernels it reaches (GEMM view of a layer: M = ba
   ref_cin11           the reference's stack on 11 input planes: K = 99 > 96, the first plane count past the fused chains
   big_rows            the 4-wave gemm_fwd_kernel<32, 4> and <64, 4> with ragged M (43 200 and 36 300 rows), 675 and 568 slices through
                       reduce_partials_kernel's 16-unrolled loop, a 4840-wide Flatten, 200 actions without a dueling head
+
+The wide entries are the reference's stack on the observations and actions of d = 11, 13 and 15 (tests/test_env_wide_gpu.py CONFIGS): what DQNAgent.fit
+creates there.  All of them run gemm_fwd_kernel<64, 1> / <32, 1> (at most 85 row tiles: far from the 256 blocks of the 4-wave forms) with a ragged last
+row tile in every convolution, more than one row tile per sample (so the batch of one and the ring gather span 3 to 8 blocks), one weight-gradient slice
+per dense layer (reduce_partials_kernel's tail loop alone, over up to 2.77 M elements) and a dueling head of 4 to 11 column tiles:
+
+  wide_d11_dpy        23 x 23 x 7 input; Flatten 2592: 81 K tiles forward, gemm_wgrad_kernel<64> on a (21, 1, 8) grid whose last K block holds 32 of 128
+                      rows, its data gradient over 41 column tiles (the last half full); head of 365 columns: 6 column tiles (45 in the last), K = 364 /
+                      365 (12 K tiles, 12 and 13 in the last), the dueling kernels' loops 6 times with 44 lanes in the last pass
+  wide_d13_dp         27 x 27 x 6 input, batch 7 (every dense row tile holds 7 of 32 rows); Flatten 3872: 121 K tiles, weight gradient on (31, 1, 8), data
+                      gradient over 61 column tiles; head of 340 columns: K = 339 / 340 (19 and 20 in the last K tile), 19 and 20 columns in the last tile
+  wide_d15_x          31 x 31 x 4 input (K = 36 in the first convolution, 85 / 74 / 64 row tiles, 43 / 37 / 32 weight-gradient slices); Flatten 5408: 169 K
+                      tiles, weight gradient on (43, 1, 8), data gradient over 85 column tiles; head of 227 columns: 4 column tiles, K = 226 / 227
+  wide_d15_dpy        the largest network the product creates (3.59 M parameters): the 5408-wide Flatten again, and a head of 677 columns: 11 column tiles
+                      forward and as grid z of the weight gradient, whose (6, 1, 11) grid has a ragged last K block (36 of 128) AND a ragged last column
+                      tile (37 of 64); K = 676 / 677: 22 K tiles (4 and 5 in the last); the dueling kernels' loops 11 times with 36 lanes in the last pass
 """
 import numpy as np
 
@@ -30,6 +46,11 @@ ARCHITECTURES = {
     "ref_hidden256": ((7, 11, 11), REF_CONV, [[256, 0.2]], 51, True, 45),
     "ref_cin11": ((11, 11, 11), REF_CONV, REF_FF, 51, True, 45),
     "big_rows": ((3, 13, 13), [[8, 2, 1], [40, 2, 1]], [[16, 0.0]], 200, False, 300),
+    # the observations and actions of four wide configurations of tests/test_env_wide_gpu.py (d11dpy, d13dp, d15x, d15dpy)
+    "wide_d11_dpy": ((7, 23, 23), REF_CONV, REF_FF, 364, True, 11),
+    "wide_d13_dp": ((6, 27, 27), REF_CONV, REF_FF, 339, True, 7),
+    "wide_d15_x": ((4, 31, 31), REF_CONV, REF_FF, 226, True, 12),
+    "wide_d15_dpy": ((6, 31, 31), REF_CONV, REF_FF, 676, True, 9),
 }
 
 # Seed of each entry's weight perturbation and observations (make_inputs): the first one from 5 upwards -- 5 is what tests/test_qnet_gpu.py's _setup
@@ -37,8 +58,10 @@ ARCHITECTURES = {
 # fragile_samples), so that every sample's gradient is compared with the float64 oracle as it stands.  big_rows has none among the first 55 seeds (300
 # samples x 5992 ReLU units): it keeps seed 5 and its FRAGILE[name] = 3 such samples are compared under the side of each near-zero ReLU that the device
 # took (tests/relu_choices.py).  The tests assert these counts; they do not rely on this table being right.
-INPUT_SEED = {"one_conv_no_hidden": 5, "k1_s1_two_hidden": 5, "four_convs": 6, "k5_s1_four_hidden": 9, "ref_hidden256": 5, "ref_cin11": 5, "big_rows": 5}
-FRAGILE = {"one_conv_no_hidden": 0, "k1_s1_two_hidden": 0, "four_convs": 0, "k5_s1_four_hidden": 0, "ref_hidden256": 0, "ref_cin11": 0, "big_rows": 3}
+INPUT_SEED = {"one_conv_no_hidden": 5, "k1_s1_two_hidden": 5, "four_convs": 6, "k5_s1_four_hidden": 9, "ref_hidden256": 5, "ref_cin11": 5, "big_rows": 5,
+              "wide_d11_dpy": 6, "wide_d13_dp": 5, "wide_d15_x": 9, "wide_d15_dpy": 5}
+FRAGILE = {"one_conv_no_hidden": 0, "k1_s1_two_hidden": 0, "four_convs": 0, "k5_s1_four_hidden": 0, "ref_hidden256": 0, "ref_cin11": 0, "big_rows": 3,
+           "wide_d11_dpy": 0, "wide_d13_dp": 0, "wide_d15_x": 0, "wide_d15_dpy": 0}
 
 INIT_SEED = (11, 22)                        # glorot_init
 DROPOUT = dict(seed=(3, 4), t=12345678901, sample_base=77)

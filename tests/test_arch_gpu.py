@@ -186,7 +186,22 @@ def full_td_update(dq, torch, net, params, spec, flat, obs, label, seed=(1, 2), 
     assert not torch.equal(p, p0)
 
 
-@pytest.mark.parametrize("name", ["one_conv_no_hidden", "k1_s1_two_hidden", "ref_cin11"])
+WIDE = sorted(n for n in AR.ARCHITECTURES if n.startswith("wide_"))
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_the_wide_entries_run_per_layer(dq, torch_mod, name):
+    """The networks of d = 11 .. 15 as created (the library chooses the path): A + 1 > 128 outputs, so neither fused chain covers them -- the support
+    queries say so, and a silent change of dispatch fails here."""
+    shape, c_layers, ff_layers, A, dueling, B = AR.ARCHITECTURES[name]
+    assert (c_layers, ff_layers, dueling) == (REF_CONV, REF_FF, True) and expected_dispatch(shape, c_layers, ff_layers, A, dueling) == (False, False)
+    net = dq.QNetwork(shape, c_layers, ff_layers, A, dueling=dueling, max_batch=B)
+    assert net.n_params == AR.spec_of(name).n_params
+    assert not net.fused_supported and not net.fused_backward_supported and net.packed_bytes == 0
+
+
+# (the wide pair: dq_td_step, the per-layer backward and dq_adam_step at 365 and 677 head columns, 1.66 M and 3.59 M parameters)
+@pytest.mark.parametrize("name", ["one_conv_no_hidden", "k1_s1_two_hidden", "ref_cin11", "wide_d11_dpy", "wide_d15_dpy"])
 def test_one_full_td_update_through_the_per_layer_route(dq, torch_mod, name):
     torch = torch_mod
     spec, B, flat, obs, _, _, _, _ = arch_reference(name)
@@ -250,19 +265,35 @@ SWEEPS = {
     "per-layer": (SUB_BATCH["dense1024"][0], 321, (1, 37, 200, 257, 319), [257, 319]),
     # the reference's stack on the fused chains (whose workspaces do not depend on the batch)
     "fused": (((4, 7, 7), REF_CONV, REF_FF, 10, True), 417, (1, 37, 193, 352, 416), None),
+    # the d = 15 stack with Y moves (architectures.py wide_d15_dpy) in an order that descends: after 64 samples the handle's activations, masks and
+    # partial sums hold the rows of a larger batch than the one being computed.  No size up to 64 needs more workspace than 64 does (one slice of the
+    # 2.77 M-element Dense(512) gradient at every size; the convolutions' slice counts grow with the batch up to 225, 196 and 169 at 64)
+    "wide": (AR.ARCHITECTURES["wide_d15_dpy"][:5], 64, (37, 64, 1, 33, 5), []),
 }
+
+
+def workspace_need(spec, batch):
+    """Floats of partial sums a backward on `batch` samples needs: the largest layer's slices * floats per slice."""
+    return max(s * f for s, f in slices_needed(spec, batch))
 
 
 @pytest.mark.parametrize("path", sorted(SWEEPS))
 def test_batch_sizes_below_max_batch_on_one_handle(dq, torch_mod, path):
-    """Five batch sizes below max_batch on ONE handle, uint8 input, on either path: Q and gradient against the oracle at each size."""
+    """Five batch sizes up to max_batch on ONE handle, uint8 input, on either path: Q and gradient against the oracle at each size."""
     torch = torch_mod
     (shape, c_layers, ff_layers, A, dueling), max_batch, sizes, short = SWEEPS[path]
     spec = O.QNetSpec(shape, c_layers, ff_layers, A, dueling=dueling)
     if short is not None:
         assert [b for b in sizes if parent_workspace_short(spec, max_batch, b)] == short
+    if path == "wide":
+        # the sweep holds the batch with the largest workspace need of all batches the handle accepts, and, layer by layer, the one with the most slices
+        every = range(1, max_batch + 1)
+        assert max(sizes) <= max_batch and max(workspace_need(spec, b) for b in sizes) == max(workspace_need(spec, b) for b in every)
+        for li in range(len(spec.layers)):
+            assert max(slices_needed(spec, b)[li][0] for b in sizes) == max(slices_needed(spec, b)[li][0] for b in every), li
+        assert any(a > b for a, b in zip(sizes, sizes[1:])) and any(a < b for a, b in zip(sizes, sizes[1:]))      # (it descends, and ascends again)
     flat, obs, rng = AR.make_inputs(spec, max(sizes), 5)
-    net, params = build(dq, torch, spec, flat, max_batch, per_layer=path == "per-layer")
+    net, params = build(dq, torch, spec, flat, max_batch, per_layer=path != "fused")
     assert (net.fused_supported and net.fused_backward_supported and net.fused_enabled) == (path == "fused")
     keep = AR.keep_masks(spec, max(sizes), **AR.DROPOUT)
     q_all, cache_all = O.forward(spec, flat, obs, training=True, keep_masks=keep)      # samples are independent: one oracle forward serves every size
