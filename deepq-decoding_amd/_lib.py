@@ -204,11 +204,15 @@ SIGNATURES = {
     "dq_env_guided_select_uf": (_i, [_vp, _vp, _vp, _dbl, _dbl, _i, _seedp, _u64, _vp, _vp, _vp, _vp]),
     "dq_stream_decode_uf": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dq_stream_run_uf": (_i, [_vp, _vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dq_stream_decode_uf_closed": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dq_stream_run_uf_closed": (_i, [_vp, _vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_create": (_i, [_i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "dq_wide_uf_destroy": (None, [_vp]),
     "dq_wide_uf_decode": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_run": (_i, [_vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_verdict": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "dq_wide_uf_decode_closed": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dq_wide_uf_run_closed": (_i, [_vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_envb_uf_select": (_i, [_vp, _vp, _vp, _vp]),
     "dq_envb_guided_select_uf": (_i, [_vp, _vp, _vp, _dbl, _dbl, _i, _seedp, _u64, _vp, _vp, _vp]),
     "dq_prof_kernel_count": (_i, []),

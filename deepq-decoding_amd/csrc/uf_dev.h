@@ -41,7 +41,10 @@ struct UfComp {
 // One component of one volume: W = edges of the correction, M = XOR of the qubits of its space edges, rounds = growth rounds made; wave-uniform.
 // Commit (the sliding window of uf_stream.hip): unless `final`, only the edges of rounds t < commit count into W and M, and
 // carry = the set of u (bit u) whose time edge of round commit - 1 is in the correction.  Without Commit the two arguments are not read.
-template <bool Commit>
+// Closed (a stream that ends on a round of perfect measurements): in a `final` window the time edges of the last round do not exist.
+// They are the last n edge ids, and the growth loop stops in front of them: never grown, they are never full, so no label crosses them, no level reaches
+// across them and they are never in the correction.
+template <bool Commit, bool Closed = false>
 static __device__ __forceinline__ void uf_component_impl(const UfComp& G, int depth, volatile u32* dw, u8* __restrict__ s, int lane, int commit, bool final, int& Wout,
                                                          u64& Mout, u32& carry_out, int& ndef, int& rounds_out) {
     u32* s_label = reinterpret_cast<u32*>(s + UF_O_LABEL);
@@ -56,6 +59,7 @@ static __device__ __forceinline__ void uf_component_impl(const UfComp& G, int de
     volatile u8* s_g = s + UF_O_G;
     const int n = G.n, d2 = G.d2, per_round = d2 + n;
     const int B = depth * n, NN = B + 1, NE = depth * per_round;
+    const int NE_grown = Closed && final ? NE - n : NE;
     int total = 0;
     for (int t = 0; t < depth; ++t) total += __popc(dw[t]);       // wave-uniform
     ndef = total;
@@ -93,7 +97,7 @@ static __device__ __forceinline__ void uf_component_impl(const UfComp& G, int de
         if (!__ballot(any) || r == round_bound) break;            // wave-uniform
         ++rounds;
         bool fresh = false;
-        for (int e = lane; e < NE; e += 64) {
+        for (int e = lane; e < NE_grown; e += 64) {
             const u32 la = v_label[s_ea[e]], lb = v_label[s_eb[e]];
             const int inc = (int)(la != 0 && (v_par[la] & 1u)) + (int)(lb != 0 && (v_par[lb] & 1u));
             const int g0 = s_g[e], g1 = min(2, g0 + inc);
@@ -184,8 +188,9 @@ static __device__ __forceinline__ void uf_component(const UfComp& G, int depth, 
 
 // One component of one window of a stream: uf_component on the depth-`depth` graph, of whose correction the rounds t < commit are committed (all of it when
 // `final`: W and M are then uf_component's); carry: a wave-uniform word, bit u = the time edge (u, commit - 1) is in the correction.  ndef counts the window's
-// defect rows as they stand in `dw`.
+// defect rows as they stand in `dw`.  Closed: see uf_component_impl.
+template <bool Closed = false>
 static __device__ __forceinline__ void uf_component_commit(const UfComp& G, int depth, volatile u32* dw, u8* __restrict__ s, int lane, int commit, bool final, int& Wout,
                                                            u64& Mout, u32& carry, int& ndef, int& rounds_out) {
-    uf_component_impl<true>(G, depth, dw, s, lane, commit, final, Wout, Mout, carry, ndef, rounds_out);
+    uf_component_impl<true, Closed>(G, depth, dw, s, lane, commit, final, Wout, Mout, carry, ndef, rounds_out);
 }

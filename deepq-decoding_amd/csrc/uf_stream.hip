@@ -6,6 +6,8 @@
 //   stream_uf_kernel      the rounds are read from memory with uf_st_kernel's ballot front end
 //   stream_run_uf_kernel  the rounds are drawn in the wave by eval_sample_kernel's round (decode_eval.hip): stream i is the first T rounds of lattice
 //                         env_id_base + i, and the syndromes never reach memory unless a buffer for them is given
+// Both kernels are templates on Closed (dq_stream_decode_uf_closed / dq_stream_run_uf_closed): the stream ends on a round of perfect
+// measurements -- the final window has no time edges in its last round, and the sampler leaves round T - 1's measurement flips out.
 // One wavefront per stream, one wave per block.  The ring of at most 16 defect words per component lives in UF_O_DW of the wave's UF_LDS bytes; the frame
 // words, weights, defect counts and growth rounds accumulate in registers.  No scratch, no lock, no loop whose exit depends on another wave: every loop bound
 // follows from (T, d, w, c), which the entry points validate.
@@ -22,13 +24,14 @@
 namespace {
 
 // The schedule around a source of rounds: next(j) returns round j's defect ballot D_j (lanes 0 .. n - 1 component 0's nodes, lanes 32 .. component 1's) and is
-// called once for every j = 0 .. T - 1, in order.
+// called once for every j = 0 .. T - 1, in order; `last` says j = T - 1 (the schedule knows it without T: the last row of the final window).
+// Closed: the stream ends on a round of perfect measurements, so the final window has no time edges in its last round.
 struct StreamOut {
     u64 m[2];
     int w[2], nd[2], rd[2];
 };
 
-template <class Next>
+template <bool Closed, class Next>
 static __device__ __forceinline__ void stream_windows(const UfComp& c0, const UfComp& c1, int T, int window, int commit, u8* smem, int lane, Next next, StreamOut& o) {
     volatile u32* s_dw = reinterpret_cast<volatile u32*>(smem + UF_O_DW);
     o.m[0] = o.m[1] = 0;
@@ -44,7 +47,7 @@ static __device__ __forceinline__ void stream_windows(const UfComp& c0, const Uf
         const bool final = a + window >= T;
         const int l = final ? T - a : window;                      // have < l <= window
         for (int t = have; t < l; ++t, ++j) {
-            const u64 D = next(j);
+            const u64 D = next(j, Closed && final && t == l - 1);
             o.nd[0] += __popc((u32)D);
             o.nd[1] += __popc((u32)(D >> 32));
             if (lane == 0) { s_dw[t] = (u32)D; s_dw[UF_MAX_DEPTH + t] = (u32)(D >> 32); }
@@ -57,7 +60,7 @@ static __device__ __forceinline__ void stream_windows(const UfComp& c0, const Uf
             int w, nd, rd;
             u64 m;
             u32 carry;
-            uf_component_commit(c ? c1 : c0, l, s_dw + c * UF_MAX_DEPTH, smem, lane, commit, final, w, m, carry, nd, rd);
+            uf_component_commit<Closed>(c ? c1 : c0, l, s_dw + c * UF_MAX_DEPTH, smem, lane, commit, final, w, m, carry, nd, rd);
             if (c) { o.w[1] += w; o.m[1] ^= m; o.rd[1] += rd; carry1 = carry; }
             else { o.w[0] += w; o.m[0] ^= m; o.rd[0] += rd; carry0 = carry; }
         }
@@ -104,6 +107,7 @@ static __device__ __forceinline__ void stream_store(const StreamOut& o, const St
     }
 }
 
+template <bool Closed>
 __global__ __launch_bounds__(64) void stream_uf_kernel(UfComp c0, UfComp c1, const u8* __restrict__ cell, const u8* __restrict__ syndromes, int n, int d, int T, int window,
                                                        int commit, u8* __restrict__ frame, int32_t* __restrict__ weight, int32_t* __restrict__ n_defects,
                                                        int32_t* __restrict__ rounds) {
@@ -119,7 +123,7 @@ __global__ __launch_bounds__(64) void stream_uf_kernel(UfComp c0, UfComp c1, con
     u64 prev = 0;
     STREAM_IN_VGPR(prev);
     StreamOut o;
-    stream_windows(c0, c1, T, window, commit, smem, lane, [&](int j) -> u64 {
+    stream_windows<Closed>(c0, c1, T, window, commit, smem, lane, [&](int j, bool) -> u64 {
         const u64 cur = __ballot(mine && vp[(size_t)j * G] != 0);
         const u64 D = cur ^ prev;
         prev = cur;
@@ -143,6 +147,7 @@ struct StreamRunArgs {
     u8* syndromes;              // [n][T][G] or NULL
 };
 
+template <bool Closed>
 __global__ __launch_bounds__(64) void stream_run_uf_kernel(StreamRunArgs p) {
     __shared__ __attribute__((aligned(16))) u8 smem[UF_LDS];
     const int i = blockIdx.x, lane = threadIdx.x;
@@ -175,7 +180,7 @@ __global__ __launch_bounds__(64) void stream_run_uf_kernel(StreamRunArgs p) {
     STREAM_IN_VGPR(syn); STREAM_IN_VGPR(hid); STREAM_IN_VGPR(triv);
     const StreamPtrs P = stream_ptrs((size_t)i, d2, lane, p.frame, p.weight, p.n_defects, p.rounds);
     StreamOut o;
-    stream_windows(p.c0, p.c1, p.T, p.window, p.commit, smem, lane, [&](int j) -> u64 {
+    stream_windows<Closed>(p.c0, p.c1, p.T, p.window, p.commit, smem, lane, [&](int j, bool last) -> u64 {
         u32 w[4];                                                  // eval_sample_kernel's round, round counter j
         philox4x32_10((u32)j, 0u, id, (u32)lane, seed0, seed1, w);
         const bool hit = (u64)w[0] < Tq;
@@ -183,7 +188,7 @@ __global__ __launch_bounds__(64) void stream_run_uf_kernel(StreamRunArgs p) {
         const bool zhit = (u64)w[1] < Tq;
         const u64 ex = __ballot(model == DQ_MODEL_IIDXZ ? hit : hit && typ != 3);
         const u64 ez = __ballot(model == DQ_MODEL_IIDXZ ? zhit : hit && typ != 1);
-        const u64 flips = __ballot((u64)w[2] < Tm);
+        const u64 flips = Closed && last ? 0ull : __ballot((u64)w[2] < Tm);        // (closed: the last round is read without error, its data errors land)
         xmask ^= ex;
         zmask ^= ez;
         const u64 tw = __ballot(__popcll(((xmask & selx) | (zmask & ~selx)) & sq) & 1);
@@ -215,38 +220,35 @@ dq_status stream_check(const dq_decode_eval* V, int n, int T, int commit, const 
     return DQ_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-dq_status dq_stream_decode_uf(dq_decode_eval* V, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
-                              int32_t* n_defects_dev, int32_t* rounds_dev, void* stream) {
-    DQ_REQUIRE(V && syndromes_dev && frame_dev, DQ_ERR_INVALID, "dq_stream_decode_uf: null argument");
-    dq_status rc = stream_check(V, n, T, commit, weight_dev, n_defects_dev, rounds_dev, "dq_stream_decode_uf");
+// The open and the closed entry points: one body, `who` names the caller in the messages.
+dq_status stream_decode(bool closed, const char* who, dq_decode_eval* V, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
+                        int32_t* n_defects_dev, int32_t* rounds_dev, void* stream) {
+    DQ_REQUIRE(V && syndromes_dev && frame_dev, DQ_ERR_INVALID, "%s: null argument", who);
+    dq_status rc = stream_check(V, n, T, commit, weight_dev, n_defects_dev, rounds_dev, who);
     if (rc != DQ_OK) return rc;
     rc = match_st_tables(V);
     if (rc != DQ_OK) return rc;
     const MatchStTables* M = V->match_st;
-    stream_uf_kernel<<<n, 64, 0, (hipStream_t)stream>>>(M->uf[0], M->uf[1], M->cell, syndromes_dev, n, V->d, T, V->depth, commit, frame_dev, weight_dev, n_defects_dev,
-                                                        rounds_dev);
+    auto* kernel = closed ? stream_uf_kernel<true> : stream_uf_kernel<false>;
+    kernel<<<n, 64, 0, (hipStream_t)stream>>>(M->uf[0], M->uf[1], M->cell, syndromes_dev, n, V->d, T, V->depth, commit, frame_dev, weight_dev, n_defects_dev, rounds_dev);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
 }
 
-dq_status dq_stream_run_uf(dq_decode_eval* V, const dq_env* env, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
-                           const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev,
-                           int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
-    DQ_REQUIRE(V && env && seed && hidden_dev && trivial_dev && frame_dev, DQ_ERR_INVALID, "dq_stream_run_uf: null argument");
-    dq_status rc = stream_check(V, n, T, commit, weight_dev, n_defects_dev, rounds_dev, "dq_stream_run_uf");
+dq_status stream_run(bool closed, const char* who, dq_decode_eval* V, const dq_env* env, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys,
+                     double p_meas, const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev,
+                     int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
+    DQ_REQUIRE(V && env && seed && hidden_dev && trivial_dev && frame_dev, DQ_ERR_INVALID, "%s: null argument", who);
+    dq_status rc = stream_check(V, n, T, commit, weight_dev, n_defects_dev, rounds_dev, who);
     if (rc != DQ_OK) return rc;
-    DQ_REQUIRE((p_phys_each != nullptr) == (p_meas_each != nullptr), DQ_ERR_INVALID, "dq_stream_run_uf: per-stream rates come as a pair of arrays");
+    DQ_REQUIRE((p_phys_each != nullptr) == (p_meas_each != nullptr), DQ_ERR_INVALID, "%s: per-stream rates come as a pair of arrays", who);
     EnvRefereeView R;
     rc = env_referee_view(env, false, &R);
     if (rc != DQ_OK) return rc;
     // the lattice without the depth (dq_decode_verdict's check): the stream's length is T, the handle's volume_depth is the window
     DQ_REQUIRE(R.d == V->d && R.model == V->model && (R.model == DQ_MODEL_X || (R.use_Y != 0) == (V->use_Y != 0)), DQ_ERR_INVALID,
-               "dq_stream_run_uf: the environment's lattice (d = %d, model %d, use_Y = %d) is not the decoder's (d = %d, model %d, use_Y = %d)", R.d, R.model,
-               R.use_Y, V->d, V->model, V->use_Y);
+               "%s: the environment's lattice (d = %d, model %d, use_Y = %d) is not the decoder's (d = %d, model %d, use_Y = %d)", who, R.d, R.model, R.use_Y, V->d,
+               V->model, V->use_Y);
     rc = match_st_tables(V);
     if (rc != DQ_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -257,7 +259,7 @@ dq_status dq_stream_run_uf(dq_decode_eval* V, const dq_env* env, int n, int T, i
         if (rc != DQ_OK) return rc;
         a.T_each = V->rates.dev;
     } else {
-        DQ_REQUIRE(p_phys >= 0.0 && p_phys <= 1.0 && p_meas >= 0.0 && p_meas <= 1.0, DQ_ERR_INVALID, "dq_stream_run_uf: rates must be in [0,1]");
+        DQ_REQUIRE(p_phys >= 0.0 && p_phys <= 1.0 && p_meas >= 0.0 && p_meas <= 1.0, DQ_ERR_INVALID, "%s: rates must be in [0,1]", who);
         a.T_phys = dq_rate_threshold(p_phys); a.T_meas = dq_rate_threshold(p_meas);
     }
     const MatchStTables* M = V->match_st;
@@ -266,9 +268,38 @@ dq_status dq_stream_run_uf(dq_decode_eval* V, const dq_env* env, int n, int T, i
     a.env_id_base = env_id_base; a.seed0 = seed[0]; a.seed1 = seed[1];
     a.hidden = hidden_dev; a.trivial = trivial_dev; a.frame = frame_dev; a.weight = weight_dev; a.n_defects = n_defects_dev; a.rounds = rounds_dev;
     a.syndromes = syndromes_dev;
-    stream_run_uf_kernel<<<n, 64, 0, st>>>(a);
+    if (closed) stream_run_uf_kernel<true><<<n, 64, 0, st>>>(a);
+    else stream_run_uf_kernel<false><<<n, 64, 0, st>>>(a);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+dq_status dq_stream_decode_uf(dq_decode_eval* V, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
+                              int32_t* n_defects_dev, int32_t* rounds_dev, void* stream) {
+    return stream_decode(false, "dq_stream_decode_uf", V, syndromes_dev, n, T, commit, frame_dev, weight_dev, n_defects_dev, rounds_dev, stream);
+}
+
+dq_status dq_stream_decode_uf_closed(dq_decode_eval* V, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
+                                     int32_t* n_defects_dev, int32_t* rounds_dev, void* stream) {
+    return stream_decode(true, "dq_stream_decode_uf_closed", V, syndromes_dev, n, T, commit, frame_dev, weight_dev, n_defects_dev, rounds_dev, stream);
+}
+
+dq_status dq_stream_run_uf(dq_decode_eval* V, const dq_env* env, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
+                           const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev,
+                           int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
+    return stream_run(false, "dq_stream_run_uf", V, env, n, T, commit, env_id_base, seed, p_phys, p_meas, p_phys_each, p_meas_each, hidden_dev, trivial_dev, frame_dev,
+                      weight_dev, n_defects_dev, rounds_dev, syndromes_dev, stream);
+}
+
+dq_status dq_stream_run_uf_closed(dq_decode_eval* V, const dq_env* env, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys,
+                                  double p_meas, const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev,
+                                  int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
+    return stream_run(true, "dq_stream_run_uf_closed", V, env, n, T, commit, env_id_base, seed, p_phys, p_meas, p_phys_each, p_meas_each, hidden_dev, trivial_dev,
+                      frame_dev, weight_dev, n_defects_dev, rounds_dev, syndromes_dev, stream);
 }
 
 }  // extern "C"

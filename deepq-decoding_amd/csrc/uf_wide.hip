@@ -4,6 +4,7 @@
 //   stream_run_wide_uf_kernel  the rounds are drawn in the workgroup by tests/decode_eval_ref.sample_volumes' rule (thread q owns qubit q and, for
 //                              q < n_stab, stabilizer q's measurement flip): the syndromes never reach memory unless a buffer for them is given
 //   verdict_wide_kernel        residual = hidden XOR frame: in code space, homology class, success; no referee is consulted
+// The two stream kernels are templates on Closed (dq_wide_uf_decode_closed / dq_wide_uf_run_closed), as uf_stream.hip's are.
 // The lattice tables come from LatticeHost inside the handle; no environment handle is needed.
 #include "uf_wide.h"
 #include "lattice_host.h"
@@ -28,8 +29,9 @@ struct WideArgs {
 };
 
 // The schedule around a source of rounds: next(j, row0, row1) is called once for every j = 0 .. T - 1, in order, by every thread; it leaves round j's defect
-// rows of the two components in the given LDS words (all UFW_ROW_WORDS of each) and may use barriers.
-template <class Next>
+// rows of the two components in the given LDS words (all UFW_ROW_WORDS of each) and may use barriers; `last` says j = T - 1 (the last row of the final window).
+// Closed: the stream ends on a round of perfect measurements, so the final window has no time edges in its last round.
+template <bool Closed, class Next>
 static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem, const UfwLayout& L, int tid, Next next) {
     u32* s_frame = reinterpret_cast<u32*>(smem + L.o_frame);
     u32* s_carry = reinterpret_cast<u32*>(smem + L.o_carry);
@@ -54,7 +56,7 @@ static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem,
         const int a = k * commit;
         const bool final = a + window >= T;
         const int l = final ? T - a : window;                      // have < l <= window
-        for (int t = have; t < l; ++t, ++j) next(j, s_ring + t * UFW_ROW_WORDS, s_ring + row_stride + t * UFW_ROW_WORDS);
+        for (int t = have; t < l; ++t, ++j) next(j, Closed && final && t == l - 1, s_ring + t * UFW_ROW_WORDS, s_ring + row_stride + t * UFW_ROW_WORDS);
         __syncthreads();
         if (tid < 2 * UFW_ROW_WORDS) {                             // row 0 ^= carry (row 0 leaves the ring with this window: commit >= 1)
             s_ring[(tid >> 2) * row_stride + (tid & 3)] ^= s_carry[tid];
@@ -64,7 +66,7 @@ static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem,
         G.depth = l; G.B = l * G.n; G.NN = G.B + 1; G.NE = l * G.per_round;
         for (int c = 0; c < 2; ++c) {
             G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
-            ufw_component(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c,
+            ufw_component<Closed>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c,
                           s_acc + 4 + c);
         }
         if (final) break;
@@ -116,6 +118,7 @@ static __device__ __forceinline__ void wide_store(const WidePtrs& P, u8* smem, c
     }
 }
 
+template <bool Closed>
 __global__ __launch_bounds__(UFW_THREADS) void stream_wide_uf_kernel(WideArgs p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
@@ -129,13 +132,14 @@ __global__ __launch_bounds__(UFW_THREADS) void stream_wide_uf_kernel(WideArgs p)
     const WidePtrs P = wide_ptrs(p, i, tid);
     int prev = 0, nd = 0, G = p.G;
     UFW_IN_VGPR(vp); UFW_IN_VGPR(prev); UFW_IN_VGPR(nd); UFW_IN_VGPR(G);
-    wide_windows(p, smem, L, tid, [&](int j, u32* row0, u32* row1) {
+    wide_windows<Closed>(p, smem, L, tid, [&](int j, bool, u32* row0, u32* row1) {
         const int cur = vp[(size_t)j * G] != 0;                    // (a thread without a node reads cell 0 of its own stream and masks it)
         wide_rows(mine ? cur : 0, prev, tid, row0, row1, nd);
     });
     wide_store(P, smem, L, tid, nd);
 }
 
+template <bool Closed>
 __global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArgs p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
@@ -168,7 +172,7 @@ __global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArg
     int x = 0, z = 0, prev = 0, seen = 0, nd = 0;
     UFW_IN_VGPR(has_q); UFW_IN_VGPR(has_s); UFW_IN_VGPR(isx); UFW_IN_VGPR(x); UFW_IN_VGPR(z); UFW_IN_VGPR(prev); UFW_IN_VGPR(seen); UFW_IN_VGPR(nd);
     UFW_IN_VGPR(hid); UFW_IN_VGPR(triv); UFW_IN_VGPR(syn);
-    wide_windows(p, smem, L, tid, [&](int j, u32* row0, u32* row1) {
+    wide_windows<Closed>(p, smem, L, tid, [&](int j, bool last, u32* row0, u32* row1) {
         u32 w[4];                                                  // sample_volumes' round, round counter j
         philox4x32_10((u32)j, 0u, id, (u32)tid, seed0, seed1, w);
         const bool hit = has_q && (u64)w[0] < T_phys;
@@ -183,7 +187,7 @@ __global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArg
             int par = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) par ^= q4[k] < 255 ? plane[q4[k]] : 0;
-            const int v = (par & 1) ^ (int)((u64)w[2] < T_meas);
+            const int v = (par & 1) ^ (int)(!(Closed && last) && (u64)w[2] < T_meas);      // (closed: the last round is read without error, its data errors land)
             seen |= v;
             s_v[tid] = (u8)v;
         }
@@ -253,6 +257,49 @@ void wide_args(const dq_wide_uf* H, int n, int T, int commit, WideArgs* a) {
     a->commit = commit;
 }
 
+
+// The open and the closed entry points: one body, `who` names the caller in the messages.
+dq_status wide_decode(bool closed, const char* who, dq_wide_uf* H, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
+                      int32_t* n_defects_dev, int32_t* rounds_dev, void* stream) {
+    DQ_REQUIRE(H && syndromes_dev && frame_dev, DQ_ERR_INVALID, "%s: null argument", who);
+    const dq_status rc = wide_check(H, n, T, commit, weight_dev, n_defects_dev, rounds_dev, who);
+    if (rc != DQ_OK) return rc;
+    WideArgs a;
+    wide_args(H, n, T, commit, &a);
+    a.syn_in = syndromes_dev; a.frame = frame_dev; a.weight = weight_dev; a.n_defects = n_defects_dev; a.rounds = rounds_dev;
+    if (closed) stream_wide_uf_kernel<true><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(a);
+    else stream_wide_uf_kernel<false><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(a);
+    DQ_LAUNCH_CHECK();
+    return DQ_OK;
+}
+
+dq_status wide_run(bool closed, const char* who, dq_wide_uf* H, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
+                   const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev,
+                   int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
+    DQ_REQUIRE(H && seed && hidden_dev && trivial_dev && frame_dev, DQ_ERR_INVALID, "%s: null argument", who);
+    dq_status rc = wide_check(H, n, T, commit, weight_dev, n_defects_dev, rounds_dev, who);
+    if (rc != DQ_OK) return rc;
+    DQ_REQUIRE((p_phys_each != nullptr) == (p_meas_each != nullptr), DQ_ERR_INVALID, "%s: per-stream rates come as a pair of arrays", who);
+    hipStream_t st = (hipStream_t)stream;
+    WideArgs a;
+    wide_args(H, n, T, commit, &a);
+    if (p_phys_each) {
+        rc = dq_rate_table_upload(H->rates, n, p_phys_each, p_meas_each, st);
+        if (rc != DQ_OK) return rc;
+        a.T_each = H->rates.dev;
+    } else {
+        DQ_REQUIRE(p_phys >= 0.0 && p_phys <= 1.0 && p_meas >= 0.0 && p_meas <= 1.0, DQ_ERR_INVALID, "%s: rates must be in [0,1]", who);
+        a.T_phys = dq_rate_threshold(p_phys); a.T_meas = dq_rate_threshold(p_meas);
+    }
+    a.env_id_base = env_id_base; a.seed0 = seed[0]; a.seed1 = seed[1];
+    a.hidden = hidden_dev; a.trivial = trivial_dev; a.frame = frame_dev; a.weight = weight_dev; a.n_defects = n_defects_dev; a.rounds = rounds_dev;
+    a.syn_out = syndromes_dev;
+    if (closed) stream_run_wide_uf_kernel<true><<<n, UFW_THREADS, H->lds, st>>>(a);
+    else stream_run_wide_uf_kernel<false><<<n, UFW_THREADS, H->lds, st>>>(a);
+    DQ_LAUNCH_CHECK();
+    return DQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -295,8 +342,10 @@ dq_status dq_wide_uf_create(int d, int error_model, int window, int max_streams,
     const unsigned long long dev_bit = dq_device_bit();
     if (!(attr_devs & dev_bit)) {
         const int lds_max = ufw_layout((UFW_MAX_D * UFW_MAX_D - 1) / 2, UFW_MAX_D * UFW_MAX_D, UFW_MAX_WINDOW).bytes;
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(stream_wide_uf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        if (ea == hipSuccess) ea = hipFuncSetAttribute(reinterpret_cast<const void*>(stream_run_wide_uf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        const void* kernels[4] = {reinterpret_cast<const void*>(stream_wide_uf_kernel<false>), reinterpret_cast<const void*>(stream_run_wide_uf_kernel<false>),
+                                  reinterpret_cast<const void*>(stream_wide_uf_kernel<true>), reinterpret_cast<const void*>(stream_run_wide_uf_kernel<true>)};
+        hipError_t ea = hipSuccess;
+        for (int k = 0; k < 4 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
         if (ea != hipSuccess) {
             (void)hipGetLastError();
             dq_set_error("dq_wide_uf_create: the device refuses %d bytes of LDS per workgroup: %s", lds_max, hipGetErrorString(ea));
@@ -334,41 +383,26 @@ void dq_wide_uf_destroy(dq_wide_uf* H) {
 
 dq_status dq_wide_uf_decode(dq_wide_uf* H, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev,
                             int32_t* rounds_dev, void* stream) {
-    DQ_REQUIRE(H && syndromes_dev && frame_dev, DQ_ERR_INVALID, "dq_wide_uf_decode: null argument");
-    const dq_status rc = wide_check(H, n, T, commit, weight_dev, n_defects_dev, rounds_dev, "dq_wide_uf_decode");
-    if (rc != DQ_OK) return rc;
-    WideArgs a;
-    wide_args(H, n, T, commit, &a);
-    a.syn_in = syndromes_dev; a.frame = frame_dev; a.weight = weight_dev; a.n_defects = n_defects_dev; a.rounds = rounds_dev;
-    stream_wide_uf_kernel<<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(a);
-    DQ_LAUNCH_CHECK();
-    return DQ_OK;
+    return wide_decode(false, "dq_wide_uf_decode", H, syndromes_dev, n, T, commit, frame_dev, weight_dev, n_defects_dev, rounds_dev, stream);
+}
+
+dq_status dq_wide_uf_decode_closed(dq_wide_uf* H, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
+                                   int32_t* n_defects_dev, int32_t* rounds_dev, void* stream) {
+    return wide_decode(true, "dq_wide_uf_decode_closed", H, syndromes_dev, n, T, commit, frame_dev, weight_dev, n_defects_dev, rounds_dev, stream);
 }
 
 dq_status dq_wide_uf_run(dq_wide_uf* H, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
                          const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev,
                          int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
-    DQ_REQUIRE(H && seed && hidden_dev && trivial_dev && frame_dev, DQ_ERR_INVALID, "dq_wide_uf_run: null argument");
-    dq_status rc = wide_check(H, n, T, commit, weight_dev, n_defects_dev, rounds_dev, "dq_wide_uf_run");
-    if (rc != DQ_OK) return rc;
-    DQ_REQUIRE((p_phys_each != nullptr) == (p_meas_each != nullptr), DQ_ERR_INVALID, "dq_wide_uf_run: per-stream rates come as a pair of arrays");
-    hipStream_t st = (hipStream_t)stream;
-    WideArgs a;
-    wide_args(H, n, T, commit, &a);
-    if (p_phys_each) {
-        rc = dq_rate_table_upload(H->rates, n, p_phys_each, p_meas_each, st);
-        if (rc != DQ_OK) return rc;
-        a.T_each = H->rates.dev;
-    } else {
-        DQ_REQUIRE(p_phys >= 0.0 && p_phys <= 1.0 && p_meas >= 0.0 && p_meas <= 1.0, DQ_ERR_INVALID, "dq_wide_uf_run: rates must be in [0,1]");
-        a.T_phys = dq_rate_threshold(p_phys); a.T_meas = dq_rate_threshold(p_meas);
-    }
-    a.env_id_base = env_id_base; a.seed0 = seed[0]; a.seed1 = seed[1];
-    a.hidden = hidden_dev; a.trivial = trivial_dev; a.frame = frame_dev; a.weight = weight_dev; a.n_defects = n_defects_dev; a.rounds = rounds_dev;
-    a.syn_out = syndromes_dev;
-    stream_run_wide_uf_kernel<<<n, UFW_THREADS, H->lds, st>>>(a);
-    DQ_LAUNCH_CHECK();
-    return DQ_OK;
+    return wide_run(false, "dq_wide_uf_run", H, n, T, commit, env_id_base, seed, p_phys, p_meas, p_phys_each, p_meas_each, hidden_dev, trivial_dev, frame_dev, weight_dev,
+                    n_defects_dev, rounds_dev, syndromes_dev, stream);
+}
+
+dq_status dq_wide_uf_run_closed(dq_wide_uf* H, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
+                                const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev,
+                                int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
+    return wide_run(true, "dq_wide_uf_run_closed", H, n, T, commit, env_id_base, seed, p_phys, p_meas, p_phys_each, p_meas_each, hidden_dev, trivial_dev, frame_dev,
+                    weight_dev, n_defects_dev, rounds_dev, syndromes_dev, stream);
 }
 
 dq_status dq_wide_uf_verdict(dq_wide_uf* H, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev, void* stream) {

@@ -82,6 +82,10 @@ static __device__ __forceinline__ void ufw_ends(const UfwGraph& G, int e, int& a
 // One component of one window by the whole workgroup; every thread calls it with the same arguments.  dw: the component's rows u32 [depth][4] in LDS.
 // Unless `final`, only the edges of rounds t < commit count; a committed space edge XORs its qubit into s_frame [8], a committed edge adds 1 to *s_weight, the
 // time edges of round commit - 1 set their bit of s_carry [4] (zero on entry).  The growth rounds made are added to *s_rounds.
+// Closed (a stream that ends on a round of perfect measurements): in a `final` window the time edges of the last round do not exist.
+// They are the last n edge ids, and the growth loop stops in front of them: never grown, they are never full, so no label crosses them, no level reaches
+// across them and they are never in the correction.
+template <bool Closed = false>
 static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u32* dw, u8* __restrict__ s, const UfwLayout& L, int tid, int commit, bool final,
                                                      u32* s_frame, u32* s_carry, int* s_weight, int* s_rounds) {
     u32* s_label = reinterpret_cast<u32*>(s + L.o_label);
@@ -94,6 +98,7 @@ static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u3
     volatile u8* s_g = s + L.o_g;
     volatile const u32* v_dw = dw;
     const int n = G.n, B = G.B, NN = G.NN, NE = G.NE;
+    const int NE_grown = Closed && final ? NE - n : NE;
     // nothing to correct: workgroup-uniform, the graph arrays untouched
     if (!__syncthreads_or(tid < G.depth * UFW_ROW_WORDS && v_dw[tid] != 0)) return;
     auto defect = [&](int x) -> u32 {
@@ -118,7 +123,7 @@ static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u3
         if (!__syncthreads_or(any) || r == round_bound) break;    // workgroup-uniform
         ++rounds;
         bool fresh = false;
-        for (int e = tid; e < NE; e += UFW_THREADS) {
+        for (int e = tid; e < NE_grown; e += UFW_THREADS) {
             const int g0 = s_g[e];
             if (g0 == 2) continue;
             int a, b, t, k;

@@ -355,21 +355,25 @@ class Evaluator:
         _lib.check(self.L.dq_decode_uf(self._h, _lib.ptr(volumes), m, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
                                        self._stream()))
 
-    def stream_uf_into(self, syndromes, m, T, commit, frame, weight=None, n_defects=None, rounds=None):
-        """The sliding-window union-find decode (dq_stream_decode_uf) of m <= chunk streams of T rounds already on the device; the window is volume_depth."""
+    def stream_uf_into(self, syndromes, m, T, commit, frame, weight=None, n_defects=None, rounds=None, final_round="faulty"):
+        """The sliding-window union-find decode (dq_stream_decode_uf) of m <= chunk streams of T rounds already on the device; the window is volume_depth.
+        final_round="perfect": dq_stream_decode_uf_closed."""
         from . import _lib
-        _lib.check(self.L.dq_stream_decode_uf(self._h, _lib.ptr(syndromes), m, T, commit, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects),
-                                              _lib.ptr(rounds), self._stream()))
+        fn = self.L.dq_stream_decode_uf_closed if check_final_round(final_round) else self.L.dq_stream_decode_uf
+        _lib.check(fn(self._h, _lib.ptr(syndromes), m, T, commit, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects),
+                      _lib.ptr(rounds), self._stream()))
 
     def stream_run_into(self, venv, m, T, commit, lattice_id, seed, p_phys, p_meas, hidden, trivial, frame, weight=None, n_defects=None, rounds=None,
-                        syndromes=None):
-        """m <= chunk streams of T rounds of lattices lattice_id .. lattice_id + m - 1 (mod 2^32), sampled and decoded in one kernel (dq_stream_run_uf)."""
+                        syndromes=None, final_round="faulty"):
+        """m <= chunk streams of T rounds of lattices lattice_id .. lattice_id + m - 1 (mod 2^32), sampled and decoded in one kernel (dq_stream_run_uf).
+        final_round="perfect": dq_stream_run_uf_closed."""
         from . import _lib
+        fn = self.L.dq_stream_run_uf_closed if check_final_round(final_round) else self.L.dq_stream_run_uf
         arr = (ctypes.c_uint32 * 2)(*seed)
         each = not isinstance(p_phys, float)
-        _lib.check(self.L.dq_stream_run_uf(self._h, venv._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
-                                           p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, _lib.ptr(hidden), _lib.ptr(trivial),
-                                           _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), _lib.ptr(syndromes), self._stream()))
+        _lib.check(fn(self._h, venv._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
+                      p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, _lib.ptr(hidden), _lib.ptr(trivial),
+                      _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), _lib.ptr(syndromes), self._stream()))
 
     def verdict_into(self, venv, hidden, frame, m, out):
         from . import _lib
@@ -908,6 +912,22 @@ def check_stream_method(method):
                                   "which part of a correction lies in the committed rounds")
 
 
+FINAL_ROUNDS = ("faulty", "perfect")
+
+
+def check_final_round(final_round):
+    """How a stream ends: "faulty", the last round is read like every other one, or "perfect", a last round of reliable syndromes
+    as a data-qubit readout gives it (the closed entry points).  Returns whether the stream is closed; ValueError for anything else."""
+    if not isinstance(final_round, str) or final_round not in FINAL_ROUNDS:
+        raise ValueError(f"final_round must be one of {FINAL_ROUNDS}, not {final_round!r}")
+    return final_round == "perfect"
+
+
+def closed_kw(final_round):
+    """The keyword an evaluator's decode / run takes for a closed stream; none for an open one, which is called as ever."""
+    return dict(final_round="perfect") if check_final_round(final_round) else {}
+
+
 def check_stream_schedule(d, rounds, window, commit):
     """(T, window, commit) with the defaults window = min(2 d, 16), commit = (window + 1) // 2; ValueError outside 1 <= commit <= window <= 16, 1 <= T <= 2^20."""
     is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
@@ -952,15 +972,18 @@ def check_stream_args(env, syndromes, window=None, commit=None, chunk=DEFAULT_CH
     return d, model, use_Y, 1 if single else shape[0], single, T, window, commit
 
 
-def stream_decode(syndromes, env, window=None, commit=None, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None, method="union_find"):
+def stream_decode(syndromes, env, window=None, commit=None, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None, method="union_find", final_round="faulty"):
     """Sliding-window union-find decoding of syndrome streams of any length.  syndromes: uint8 [N, T, d+1, d+1] with 0/1 cells, or
     one stream [T, d+1, d+1], numpy or torch; T is free (1 .. 2^20), env supplies the lattice (d <= 7, the narrow environment) and its volume_depth is not
     consulted.  Windows of `window` rounds (default min(2 d, 16)) are decoded by the union-find decoder of section 16; each commits its first `commit`
     rounds (default (window + 1) // 2) and carries the crossing time edges into the next; the last one commits everything.  With window >= T the
     result is matching_decode(method="union_find") at depth T.  Returns a StreamResult of device tensors (numpy arrays with to_host); the result of a
     stream does not depend on the batch around it or on `chunk`.  evaluator: an Evaluator of this lattice with volume_depth = window to run on (its
-    chunk is used and it stays open); default: one for this call.  method="matching" raises NotImplementedError."""
+    chunk is used and it stays open); default: one for this call.  method="matching" raises NotImplementedError.  final_round="perfect": the stream ends on
+    a round of reliable syndromes, so the final window has no time edges in its last round; then the frame's syndrome is the
+    stream's last syndrome, and T = 1 is code-capacity decoding."""
     import torch
+    closed = closed_kw(final_round)
     d, model, use_Y, n, single, T, window, commit = check_stream_args(env, syndromes, window, commit, chunk, evaluator, method)
     venv = _narrow_env(env)
     dev = venv.device
@@ -972,7 +995,7 @@ def stream_decode(syndromes, env, window=None, commit=None, chunk=DEFAULT_CHUNK,
         with torch.cuda.device(dev):
             for s in range(0, n, ev.chunk):
                 m = min(ev.chunk, n - s)
-                ev.stream_uf_into(syn[s:s + m], m, T, commit, frame[s:s + m], weight[s:s + m], ndef[s:s + m], rounds[s:s + m])
+                ev.stream_uf_into(syn[s:s + m], m, T, commit, frame[s:s + m], weight[s:s + m], ndef[s:s + m], rounds[s:s + m], **closed)
             torch.cuda.current_stream(dev).synchronize()
     finally:
         if evaluator is None:
@@ -982,7 +1005,7 @@ def stream_decode(syndromes, env, window=None, commit=None, chunk=DEFAULT_CHUNK,
 
 
 def memory_experiment(env, n_runs, rounds, window=None, commit=None, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, chunk=DEFAULT_CHUNK,
-                      no_decoder=False, timings=None, evaluator=None, return_streams=False):
+                      no_decoder=False, timings=None, evaluator=None, return_streams=False, final_round="faulty"):
     """The logical failure of a memory experiment of `rounds` rounds, decoded by the sliding-window union-find decoder: n_runs streams, stream i the first
     `rounds` rounds of lattice env_id_base + i under sample_volumes' convention, sampled and decoded in ONE kernel per chunk (dq_stream_run_uf: the
     syndromes never reach memory), then verdict -> counts on the device as score_matching does.  Returns what score_matching returns: an EvalResult
@@ -990,9 +1013,12 @@ def memory_experiment(env, n_runs, rounds, window=None, commit=None, rates=None,
     corrections = the frame's non-zero cells, inexact 0; no_decoder: EvalResult.no_decoder counts the verdict for frame = 0.  window / commit: as
     stream_decode.  timings: a dict that receives the wall seconds of the phases run / verdict.  evaluator: an Evaluator of this lattice with
     volume_depth = window.  return_streams: also returns dict(syndromes uint8 [N, rounds, d+1, d+1], hidden, frame uint8 [N, d, d], trivial uint8 [N]) of
-    device tensors; otherwise only the counters leave the device."""
+    device tensors; otherwise only the counters leave the device.  final_round="perfect": the last round is measured without error (its data errors
+    land, its measurement flips are not applied; the same Philox words are drawn) and decoded as stream_decode decodes it; hidden and rounds
+    0 .. rounds - 2 are those of the "faulty" run of the same seed and ids, and every residual is in the code space."""
     import time
     import torch
+    closed = closed_kw(final_round)
     lat = check_eval_lattice(None, env)
     d, model, use_Y, _ = lat
     T, window, commit = check_stream_schedule(d, rounds, window, commit)
@@ -1041,7 +1067,8 @@ def memory_experiment(env, n_runs, rounds, window=None, commit=None, rates=None,
                 a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
                 if each and (a == a[0]).all() and (b == b[0]).all():   # one rate pair in this chunk: the scalar form (the same thresholds, no table upload)
                     a, b = float(a[0]), float(b[0])
-                ev.stream_run_into(venv, m, T, commit, base + s, seed, a, b, hid[sl], triv[sl], frame[sl], syndromes=None if syn is None else syn[s:s + m])
+                ev.stream_run_into(venv, m, T, commit, base + s, seed, a, b, hid[sl], triv[sl], frame[sl], syndromes=None if syn is None else syn[s:s + m],
+                                   **closed)
                 t = phase("run", t)
                 ev.verdict_into(venv, hid[sl], frame[sl], m, verd[:m])
                 ev.count_into(verd[:m], triv[sl], status[:m], (frame[sl] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), m, s, blk, counters)

@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 from .decoder import (COUNTER_NAMES, DEFAULT_CHUNK, MODELS, STATUS_IDENTITY, STREAM_MAX_ROUNDS, MatchingAgent, StreamResult, action_layers, block_results,
-                      check_binary, check_rates, lattice_of, rate_threshold, stream_windows)
+                      check_binary, check_final_round, check_rates, closed_kw, lattice_of, rate_threshold, stream_windows)
 
 WIDE_MAX_D = 15
 WIDE_MAX_WINDOW = 32
@@ -185,20 +185,24 @@ class WideEvaluator:
         import torch
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def decode_into(self, syndromes, m, T, commit, frame, weight=None, n_defects=None, rounds=None):
-        """The sliding-window decode (dq_wide_uf_decode) of m <= chunk streams of T rounds already on the device."""
+    def decode_into(self, syndromes, m, T, commit, frame, weight=None, n_defects=None, rounds=None, final_round="faulty"):
+        """The sliding-window decode (dq_wide_uf_decode) of m <= chunk streams of T rounds already on the device.  final_round="perfect":
+        dq_wide_uf_decode_closed."""
         from . import _lib
-        _lib.check(self.L.dq_wide_uf_decode(self._h, _lib.ptr(syndromes), m, T, commit, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects),
-                                            _lib.ptr(rounds), self._stream()))
+        fn = self.L.dq_wide_uf_decode_closed if check_final_round(final_round) else self.L.dq_wide_uf_decode
+        _lib.check(fn(self._h, _lib.ptr(syndromes), m, T, commit, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), self._stream()))
 
-    def run_into(self, m, T, commit, lattice_id, seed, p_phys, p_meas, hidden, trivial, frame, weight=None, n_defects=None, rounds=None, syndromes=None):
-        """m <= chunk streams of T rounds of lattices lattice_id .. lattice_id + m - 1 (mod 2^32), sampled and decoded in one kernel (dq_wide_uf_run)."""
+    def run_into(self, m, T, commit, lattice_id, seed, p_phys, p_meas, hidden, trivial, frame, weight=None, n_defects=None, rounds=None, syndromes=None,
+                 final_round="faulty"):
+        """m <= chunk streams of T rounds of lattices lattice_id .. lattice_id + m - 1 (mod 2^32), sampled and decoded in one kernel (dq_wide_uf_run).
+        final_round="perfect": dq_wide_uf_run_closed."""
         from . import _lib
+        fn = self.L.dq_wide_uf_run_closed if check_final_round(final_round) else self.L.dq_wide_uf_run
         arr = (ctypes.c_uint32 * 2)(*seed)
         each = not isinstance(p_phys, float)
-        _lib.check(self.L.dq_wide_uf_run(self._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
-                                         p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, _lib.ptr(hidden), _lib.ptr(trivial),
-                                         _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), _lib.ptr(syndromes), self._stream()))
+        _lib.check(fn(self._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
+                      p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, _lib.ptr(hidden), _lib.ptr(trivial),
+                      _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), _lib.ptr(syndromes), self._stream()))
 
     def verdict_into(self, hidden, frame, m, out):
         from . import _lib
@@ -210,12 +214,14 @@ class WideEvaluator:
                                           counters.shape[0], _lib.ptr(counters), self._stream()))
 
 
-def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None):
+def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None, final_round="faulty"):
     """decoder.stream_decode for any odd d in 3 .. 15 and a window of up to 32 rounds.  syndromes: uint8 [N, T, d+1, d+1] with 0/1 cells, or one stream
     [T, d+1, d+1], numpy or torch; window defaults to min(2 d, 32), commit to (window + 1) // 2.  Returns a decoder.StreamResult of device tensors (numpy
     arrays with to_host); the result of a stream does not depend on the batch around it or on `chunk`.  evaluator: a WideEvaluator of this d and window to
-    run on (its chunk is used and it stays open); default: one for this call."""
+    run on (its chunk is used and it stays open); default: one for this call.  final_round="perfect": decoder.stream_decode's closed form (DESIGN.md
+    section 20)."""
     import torch
+    closed = closed_kw(final_round)
     d, n, single, T, window, commit, chunk = check_wide_stream_args(syndromes, d, window, commit, chunk, evaluator)
     ev = WideEvaluator(d, "DP", window, chunk=min(chunk, n)) if evaluator is None else evaluator
     dev = ev.device
@@ -227,7 +233,7 @@ def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHU
         with torch.cuda.device(dev):
             for s in range(0, n, ev.chunk):
                 m = min(ev.chunk, n - s)
-                ev.decode_into(syn[s:s + m], m, T, commit, frame[s:s + m], weight[s:s + m], ndef[s:s + m], rounds[s:s + m])
+                ev.decode_into(syn[s:s + m], m, T, commit, frame[s:s + m], weight[s:s + m], ndef[s:s + m], rounds[s:s + m], **closed)
             torch.cuda.current_stream(dev).synchronize()
     finally:
         if evaluator is None:
@@ -237,7 +243,7 @@ def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHU
 
 
 def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0,
-                           chunk=DEFAULT_CHUNK, no_decoder=False, timings=None, evaluator=None, return_streams=False):
+                           chunk=DEFAULT_CHUNK, no_decoder=False, timings=None, evaluator=None, return_streams=False, final_round="faulty"):
     """decoder.memory_experiment for any odd d in 3 .. 15 and a window of up to 32 rounds: n_runs streams, stream i the first `rounds` rounds of lattice
     env_id_base + i under sample_volumes' convention, sampled and decoded in ONE kernel per chunk (dq_wide_uf_run), then verdict -> counts on the device.
     lattice: (d, error_model), or an environment of either backend, of which only d, error_model, the rates and the seed are read (the defaults of p_phys /
@@ -245,9 +251,11 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
     rates=[...], n_runs streams per rate), every stream counted as status identity, corrections = the frame's non-zero cells; no_decoder:
     EvalResult.no_decoder counts the verdict for frame = 0.  No referee is consulted: alive := success, so death_rate equals failure_rate by construction.
     timings: a dict that receives the wall seconds of the phases run / verdict.  evaluator: a WideEvaluator of this lattice and window.  return_streams:
-    also returns dict(syndromes uint8 [N, rounds, d+1, d+1], hidden, frame uint8 [N, d, d], trivial uint8 [N]) of device tensors."""
+    also returns dict(syndromes uint8 [N, rounds, d+1, d+1], hidden, frame uint8 [N, d, d], trivial uint8 [N]) of device tensors.  final_round="perfect":
+    decoder.memory_experiment's closed form."""
     import time
     import torch
+    closed = closed_kw(final_round)
     d, model, T, window, commit, n, ph, pm, seed, base, blk, keys, chunk = check_wide_experiment_args(
         lattice, n_runs, rounds, window, commit, rates, p_phys, p_meas, seed, env_id_base, chunk, evaluator)
     ev = WideEvaluator(d, model, window, chunk=min(chunk, n)) if evaluator is None else evaluator
@@ -283,7 +291,7 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
                 a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
                 if each and (a == a[0]).all() and (b == b[0]).all():   # one rate pair in this chunk: the scalar form (the same thresholds, no table upload)
                     a, b = float(a[0]), float(b[0])
-                ev.run_into(m, T, commit, base + s, seed, a, b, hid[sl], triv[sl], frame[sl], syndromes=None if syn is None else syn[s:s + m])
+                ev.run_into(m, T, commit, base + s, seed, a, b, hid[sl], triv[sl], frame[sl], syndromes=None if syn is None else syn[s:s + m], **closed)
                 t = phase("run", t)
                 ev.verdict_into(hid[sl], frame[sl], m, verd[:m])
                 ev.count_into(verd[:m], triv[sl], status[:m], (frame[sl] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), m, s, blk, counters)

@@ -845,6 +845,22 @@ dq_status dq_stream_run_uf(dq_decode_eval* ev, const dq_env* env, int n, int T, 
                            double p_meas, const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev,
                            int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
 
+/* Streams closed by a final round of perfect measurements, as a memory experiment that ends on a data-qubit readout gives them.
+ * dq_version() stays 8: the capability is the presence of these four symbols.  The argument lists, the validation, the error codes, the nullable arrays
+ * and the one-host-thread, one-stream contract are those of the entry points without the suffix; so are all results but for this rule:
+ * decode: in the final window (the one with a + window >= T, of depth l) the time edges of round l - 1, (u, l - 1) -- B, do not exist: they are never grown,
+ *   never full and never in the correction.  Edge ids, node ids, the schedule, the commit filter, the carry, the growth rule, the min-labels and the
+ *   lowest-edge-id peeling are unchanged, and so is every window but the final one.  Per component the committed frame's syndrome then equals the stream's
+ *   last syndrome; with T = 1 the decode is code-capacity union-find on the 2-D graph.  Defined for any input stream.
+ * run: the same Philox words for every round j = 0 .. T - 1; in round T - 1 the measurement flip (word 2) is not applied, the data errors land as always.
+ *   hidden equals the open run's for the same seed and ids, the syndromes of rounds 0 .. T - 2 too; round T - 1 is the true syndrome, and trivial is
+ *   computed from the syndromes as drawn.  The residual of a closed run is therefore always in the code space. */
+dq_status dq_stream_decode_uf_closed(dq_decode_eval* ev, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
+                                     int32_t* n_defects_dev, int32_t* rounds_dev, void* stream);
+dq_status dq_stream_run_uf_closed(dq_decode_eval* ev, const dq_env* env, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys,
+                                  double p_meas, const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev,
+                                  uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
+
 /* Union-find stream decoding for any odd d in 3 .. 15 with a window of up to 32 rounds (csrc/uf_wide.hip).  dq_version() stays 8: the
  * capability is the presence of these symbols.  The algorithm and the schedule are dq_stream_decode_uf's, word for word (for d <= 7 and window <= 16 every
  * field equals its); what differs is the shape: one workgroup of 256 threads per stream, defect rows and carries of 4 x 32 bits, frames of 4 x 64 bits, and
@@ -874,6 +890,13 @@ dq_status dq_wide_uf_run(dq_wide_uf* h, int n, int T, int commit, uint32_t env_i
                          const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev,
                          int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
 dq_status dq_wide_uf_verdict(dq_wide_uf* h, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev, void* stream);
+/* The closed forms (a final round of perfect measurements): dq_stream_decode_uf_closed's and dq_stream_run_uf_closed's rule on this handle, with
+ * dq_wide_uf_decode's and dq_wide_uf_run's arguments, validation and contract.  For d <= 7 and window <= 16 every field equals the narrow closed forms'. */
+dq_status dq_wide_uf_decode_closed(dq_wide_uf* h, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
+                                   int32_t* n_defects_dev, int32_t* rounds_dev, void* stream);
+dq_status dq_wide_uf_run_closed(dq_wide_uf* h, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
+                                const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev,
+                                int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
 
 /* The union-find decoder as a policy and as a teacher of the wide environment, any odd d in 3 .. 15 (csrc/env_wide_uf.hip).
  * dq_version() stays 8: the capability is the presence of these two symbols.  The rules are dq_env_uf_select's and dq_env_guided_select_uf's on the wide

@@ -1,6 +1,6 @@
 """The sliding-window union-find decoder measured: one process per table, the forms compared interleaved, medians with spread.
 
-    python tools/memory_experiment.py fused    [--streams 16384] [--rounds 256] [--reps 5]
+    python tools/memory_experiment.py fused    [--streams 16384] [--rounds 256] [--reps 5] [--final-round faulty|perfect]
     python tools/memory_experiment.py schedule [--streams 65536] [--reps 5]
     python tools/memory_experiment.py rates    [--streams 16384] [--distances 3,5,7] [--rates 0.003,0.007,0.011] [--lengths 10,100,1000]
 
@@ -11,6 +11,8 @@ schedule  stream_uf_kernel at T = 16, window 16 against uf_st_kernel on the same
           (16, 1) on the same streams.
 rates     failure rates with Wilson intervals: depolarising noise, every row the same seed and ids, windows (2d, d) and (d, d), the no-decoder row beside
           them, and for T <= 16 the whole-history decode (window = T) on the same streams.
+--final-round perfect (fused, rates): the streams end on a round of perfect measurements.  `fused` then times the closed kernels
+beside the open ones on the same streams, launches alternating; `rates` gives the closed failure rates.  The record gets the suffix _closed.
 Writes profiles/memory_experiment_<table>.json (or --out)."""
 import argparse
 import importlib
@@ -58,6 +60,11 @@ def fused(a):
         "run_writing_syndromes": lambda: ev.stream_run_into(env, n, T, c, 0, SEED, p, p, hid, triv, frame, syndromes=syn),
         "decode_from_buffer": lambda: ev.stream_uf_into(syn, n, T, c, frame2),
     }
+    closed = a.final_round == "perfect"
+    if closed:                                                                   # the closed kernels beside the open ones, on buffers of their own
+        hid_c, frame_c, frame2_c = (torch.empty((n, d, d), dtype=torch.uint8, device=dev) for _ in range(3))
+        runs["fused_run_closed"] = lambda: ev.stream_run_into(env, n, T, c, 0, SEED, p, p, hid_c, triv, frame_c, final_round="perfect")
+        runs["decode_from_buffer_closed"] = lambda: ev.stream_uf_into(syn, n, T, c, frame2_c, final_round="perfect")
     for fn in runs.values():
         fn()
     torch.cuda.synchronize()
@@ -72,6 +79,9 @@ def fused(a):
     # decode_from_buffer alone a lower bound, of "sample then decode"
     rec["unfused_over_fused_upper"] = (med["run_writing_syndromes"] + med["decode_from_buffer"]) / med["fused_run"]
     rec["decode_from_buffer_over_fused"] = med["decode_from_buffer"] / med["fused_run"]
+    if closed:
+        assert torch.equal(hid, hid_c)
+        rec["closed_over_open"] = {k: med[k + "_closed"] / med[k] for k in ("fused_run", "decode_from_buffer")}
     print(json.dumps(rec))
     ev.close()
     return rec
@@ -115,7 +125,8 @@ def rates(a):
         for T in a.lengths:
             forms = [("2d_d", min(2 * d, 16), d), ("d_d", d, d)] + ([("whole", T, T)] if T <= 16 else [])
             for name, w, c in forms:
-                out = D.memory_experiment(env, a.streams, T, window=w, commit=c, rates=a.rates, seed=SEED, no_decoder=name == "2d_d", chunk=a.streams)
+                out = D.memory_experiment(env, a.streams, T, window=w, commit=c, rates=a.rates, seed=SEED, no_decoder=name == "2d_d", chunk=a.streams,
+                                          final_round=a.final_round)
                 for p, r in out.items():
                     fail = r.failure_rate
                     row = dict(d=d, rounds=T, p=p, form=name, window=w, commit=c, streams=r.counters["volumes"], failure_rate=fail,
@@ -126,7 +137,7 @@ def rates(a):
                     rows.append(row)
                     print(json.dumps(row), flush=True)
         env.close()
-    return dict(seed=list(SEED), model="DP", rows=rows)
+    return dict(seed=list(SEED), model="DP", final_round=a.final_round, rows=rows)
 
 
 def main():
@@ -138,14 +149,16 @@ def main():
     ap.add_argument("--distances", default="3,5,7")
     ap.add_argument("--rates", default="0.003,0.007,0.011")
     ap.add_argument("--lengths", default="10,100,1000")
+    ap.add_argument("--final-round", choices=("faulty", "perfect"), default="faulty")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    assert a.final_round == "faulty" or a.table != "schedule", "schedule compares with uf_st_kernel, which has no closed form"
     a.streams = a.streams or dict(fused=1 << 14, schedule=1 << 16, rates=1 << 14)[a.table]
     a.distances = [int(x) for x in a.distances.split(",")]
     a.rates = [float(x) for x in a.rates.split(",")]
     a.lengths = [int(x) for x in a.lengths.split(",")]
     rec = dict(device=torch.cuda.get_device_name(0), table=a.table, **dict(fused=fused, schedule=schedule, rates=rates)[a.table](a))
-    path = a.out or os.path.join(ROOT, "profiles", f"memory_experiment_{a.table}.json")
+    path = a.out or os.path.join(ROOT, "profiles", f"memory_experiment_{a.table}{'_closed' if a.final_round == 'perfect' else ''}.json")
     with open(path, "w") as f:
         json.dump(rec, f, indent=1)
         f.write("\n")

@@ -1,6 +1,6 @@
 """Logical failure of a memory experiment against the physical error rate for a family of distances: the threshold table.
 
-    python tools/threshold_sweep.py [--distances 3,5,...,15] [--rates 0.005,...] [--rounds 60,120] [--streams 4096] [--model DP] [--out FILE]
+    python tools/threshold_sweep.py [--distances 3,5,...,15] [--rates 0.005,...] [--rounds 60,120] [--streams 4096] [--model DP] [--final-round faulty|perfect] [--out FILE]
 
 Every cell (d, p) is memory_experiment_wide on --streams streams with p_meas = p, window min(2 d, 32), commit (window + 1) // 2, one seed and one range of
 lattice ids for every cell, at each of the one or two stream lengths of --rounds.  For d <= 7 the same streams also go through decoder.memory_experiment
@@ -10,7 +10,8 @@ not depend on T (a lone last-round defect beside the bound
 d; with two lengths T1 < T2 the cell therefore also records the failure per round BETWEEN them, 1 - ((1 - f2) / (1 - f1))^(1 / (T2 - T1)), from which a
 T-independent floor cancels, with the interval its two Wilson intervals span.  The threshold is read off that figure when it is there.  Writes
 profiles/threshold_sweep_<model>.json and prints, per pair of neighbouring distances, the rates between which their curves cross (or that the grid does not
-resolve it)."""
+resolve it).  --final-round perfect closes every stream with a round of perfect measurements, which removes that floor: the raw
+failure and its per-round figure can then be read directly; the record goes to profiles/threshold_sweep_<model>_closed.json."""
 import argparse
 import importlib
 import json
@@ -58,6 +59,7 @@ def main():
     ap.add_argument("--streams", type=int, default=4096)
     ap.add_argument("--model", default="DP")
     ap.add_argument("--env-id-base", type=int, default=0)
+    ap.add_argument("--final-round", choices=("faulty", "perfect"), default="faulty")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     distances = [int(x) for x in a.distances.split(",")]
@@ -66,7 +68,7 @@ def main():
     assert 1 <= len(lengths) <= 2 and len(set(lengths)) == len(lengths), "--rounds takes one or two distinct stream lengths"
     D, DW = dq.decoder, dq.decoder_wide
     record = dict(device=torch.cuda.get_device_name(0), model=a.model, rounds=lengths, streams_per_cell=a.streams, seed=list(SEED),
-                  env_id_base=a.env_id_base, p_meas="= p", cells={}, narrow_checked=[])
+                  env_id_base=a.env_id_base, p_meas="= p", final_round=a.final_round, cells={}, narrow_checked=[])
     table = {}
     for d in distances:
         _, window, commit = DW.check_wide_schedule(d, lengths[0], None, None)
@@ -77,14 +79,16 @@ def main():
             cell = dict(window=window, commit=commit, per_length={})
             for T in lengths:
                 t0 = time.perf_counter()
-                r = DW.memory_experiment_wide((d, a.model), a.streams, T, p_phys=p, seed=SEED, env_id_base=a.env_id_base, evaluator=ev)
+                r = DW.memory_experiment_wide((d, a.model), a.streams, T, p_phys=p, seed=SEED, env_id_base=a.env_id_base, evaluator=ev,
+                                              final_round=a.final_round)
                 torch.cuda.synchronize()
                 one = r.summary()
                 one.update(failure_per_round=per_round(r.failure_rate, T), failure_per_round_interval=[per_round(x, T) for x in r.failure_interval],
                            seconds=time.perf_counter() - t0)
                 cell["per_length"][str(T)] = one
                 if env is not None:                                               # the one-wavefront kernels on the same streams: the same counters
-                    narrow = D.memory_experiment(env, a.streams, T, window=window, commit=commit, p_phys=p, seed=SEED, env_id_base=a.env_id_base)
+                    narrow = D.memory_experiment(env, a.streams, T, window=window, commit=commit, p_phys=p, seed=SEED, env_id_base=a.env_id_base,
+                                                 final_round=a.final_round)
                     keys = ("volumes", "trivial", "in_codespace", "success", "identity", "repeat", "stopped", "corrections")
                     assert all(narrow.counters[k] == one[k] for k in keys), (d, p, T, narrow.counters, one)       # (alive: the narrow verdict asks a referee)
             last = cell["per_length"][str(lengths[-1])]
@@ -110,7 +114,7 @@ def main():
         where = (f"between p = {c['crossing_between'][0]} and {c['crossing_between'][1]}" if c["crossing_between"] else
                  "not inside the grid" + (" (the larger distance fails less at every rate)" if all(c["larger_distance_fails_less"]) else ""))
         print(f"{c['figure']}, d = {lo} / {hi}: the curves cross {where}; intervals disjoint at {sum(c['intervals_disjoint'])} of {len(rates)} rates")
-    path = a.out or os.path.join(ROOT, "profiles", f"threshold_sweep_{a.model.lower()}.json")
+    path = a.out or os.path.join(ROOT, "profiles", f"threshold_sweep_{a.model.lower()}{'_closed' if a.final_round == 'perfect' else ''}.json")
     with open(path, "w") as f:
         json.dump(record, f, indent=1)
         f.write("\n")
