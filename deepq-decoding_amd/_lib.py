@@ -14,6 +14,7 @@ DQ_MODEL_X, DQ_MODEL_DP, DQ_MODEL_IIDXZ = 0, 1, 2
 STREAM_ENV, STREAM_POLICY, STREAM_REPLAY, STREAM_DROPOUT, STREAM_INIT = range(5)
 
 
+DQ_ERR_INVALID, DQ_ERR_UNSUPPORTED, DQ_ERR_STATE = -1, -2, -5
 DQ_ERR_RANGE = -6
 
 
@@ -215,6 +216,14 @@ SIGNATURES = {
     "dq_wide_uf_run_closed": (_i, [_vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_envb_uf_select": (_i, [_vp, _vp, _vp, _vp]),
     "dq_envb_guided_select_uf": (_i, [_vp, _vp, _vp, _dbl, _dbl, _i, _seedp, _u64, _vp, _vp, _vp]),
+    "dq_decode_wide_create": (_i, [ctypes.POINTER(DecodeCfg), _i, ctypes.POINTER(_vp)]),
+    "dq_decode_wide_destroy": (None, [_vp]),
+    "dq_decode_wide_pack": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dq_decode_wide_step": (_i, [_vp, _vp, ctypes.POINTER(_i), _vp]),
+    "dq_decode_wide_run": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), _vp]),
+    "dq_decode_wide_rows": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i)]),
+    "dq_decode_wide_words": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i)]),
+    "dq_decode_wide_active": (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i)]),
     "dq_prof_kernel_count": (_i, []),
     "dq_prof_kernel_name": (ctypes.c_char_p, [_i]),
     "dq_prof_kernel_symbol": (ctypes.c_char_p, [_i]),

@@ -500,6 +500,70 @@ class DQNAgent:
                                  evaluator=dec._eval, method=m) for m in methods]
         return (out,) + tuple(rows)
 
+    # -- the same for any odd d in 3 .. 15 (decoder_wide.py; csrc/decode_wide.hip) ------------------------------------
+    def decode_wide(self, faulty_syndromes, env=None, masked_greedy=None, max_actions=None, chunk=None, to_host=True):
+        """decode() for any odd d in 3 .. 15 and volume_depth 1 .. 16, with the environment's action planes and uint8 observation rows; for d <= 7 every
+        field equals decode(obs_form="uint8")'s.  chunk: volumes per device launch sequence; default: the largest power of two whose rows, Q rows and
+        network workspaces fit decoder_wide.DECODE_WIDE_BUDGET."""
+        from . import decoder as D, decoder_wide as W
+        lattice_env = env if env is not None else self._env
+        if lattice_env is None:
+            raise RuntimeError("decode_wide() needs the lattice: pass env= or bind the agent to an environment first (fit()/test())")
+        d, model, use_Y, depth = D.lattice_of(lattice_env)
+        shape = tuple(getattr(faulty_syndromes, "shape", np.shape(faulty_syndromes)))
+        _, _, _, max_actions = W.check_decode_wide_args(d, model, use_Y, depth, shape, max_actions)
+        if chunk is not None:
+            W.check_chunk(chunk)
+        D.check_binary(faulty_syndromes)
+        if env is not None:
+            self._bind(env)
+        return self._wide_decoder_for(d, model, use_Y, depth, masked_greedy, max_actions, chunk).decode(self._core.params, faulty_syndromes,
+                                                                                                        to_host=to_host)
+
+    def _wide_decoder_for(self, d, model, use_Y, depth, masked_greedy, max_actions, chunk):
+        """The WideBatchDecoder of a validated request (kept until a request with other settings arrives)."""
+        from . import decoder_wide as W
+        if self._core is None:
+            raise RuntimeError("the agent has no weights on a device yet: bind it to an environment first (fit()/test(), or pass env=)")
+        if masked_greedy is None:
+            masked_greedy = self.test_policy.current(False)[1]
+        key = (d, model, use_Y, depth, bool(masked_greedy), max_actions, chunk, str(self._core.device))
+        if getattr(self, "_wide_decoder_key", None) != key:
+            old = getattr(self, "_wide_decoder", None)
+            self._wide_decoder = None
+            if old is not None:
+                old.close()
+            self._wide_decoder = W.WideBatchDecoder(self.model.input_shape, self.model.c_layers, self.model.ff_layers, self.nb_actions, d, model, use_Y,
+                                                    depth, dueling=self.enable_dueling_network, masked_greedy=bool(masked_greedy),
+                                                    max_actions=max_actions, chunk=chunk, device=self._core.device)
+            self._wide_decoder_key = key
+        return self._wide_decoder
+
+    def decode_benchmark_wide(self, lattice, n_volumes, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, masked_greedy=None,
+                              max_actions=None, chunk=None, baseline=None, no_decoder=False, final_round="faulty", return_volumes=False, timings=None):
+        """Scores decode_wide() on the device for any odd d in 3 .. 15 under decoder_wide.memory_experiment_wide's conventions:
+        volume i is the first volume_depth rounds of lattice env_id_base + i.  lattice: an environment of either backend (the defaults of the rates and
+        the seed; the agent is bound to a VectorEnv or drop-in environment given here), or (d, error_model, use_Y, volume_depth) with explicit rates and
+        seed on an agent already bound.  One sampling launch per chunk yields the agent's input, the hidden state and the union-find frame of the same
+        volumes.  Returns a decoder.EvalResult; {rate: EvalResult} with rates=[...] (n_volumes at each rate, p_meas as in memory_experiment_wide);
+        baseline="union_find": (that, the union-find decoder's result on the same volumes -- memory_experiment_wide's with rounds = window = commit =
+        volume_depth).  no_decoder: EvalResult.no_decoder counts the verdict for frame = 0.  final_round="perfect": the volume's last round is measured
+        perfectly.  return_volumes: the per-volume device tensors ride on the (first) result.  timings: a dict that receives the wall seconds of the
+        phases run / decode / verdict.  No referee is consulted: alive := success, so death_rate equals failure_rate by construction."""
+        from . import decoder as D, decoder_wide as W
+        d, model, use_Y, depth, max_actions, n, ph, pm, seed, base, blk, keys, _ = W.check_decode_benchmark_wide_args(
+            lattice, n_volumes, rates, p_phys, p_meas, seed, env_id_base, max_actions, chunk, baseline, final_round)
+        layers = D.action_layers(model, use_Y)
+        if int(self.nb_actions) != layers * d * d + 1 or tuple(self.model.input_shape) != (depth + layers, 2 * d + 1, 2 * d + 1):
+            raise ValueError(f"the network ({tuple(self.model.input_shape)} -> {self.nb_actions} actions) does not fit the lattice "
+                             f"(d = {d}, {model}, volume_depth = {depth})")
+        venv = getattr(lattice, "_v", lattice)
+        if isinstance(venv, VectorEnv):
+            self._bind(lattice)
+        dec = self._wide_decoder_for(d, model, use_Y, depth, masked_greedy, max_actions, chunk)
+        return W.score_decode_wide(dec, self._core.params, n, ph, pm, seed, base, blk, keys, baseline=baseline, no_decoder=no_decoder,
+                                   final_round=final_round, return_volumes=return_volumes, timings=timings)
+
     def compute_q_values(self, observation):
         obs = torch.as_tensor(np.asarray(observation), dtype=torch.uint8, device=self._core.device).reshape((1,) + tuple(self.model.input_shape)).contiguous()
         return self._net.forward(self._core.params, obs, batch=1)[0].cpu().numpy()

@@ -15,9 +15,9 @@
 #include "common.h"
 #include "qnet.h"
 #include "lattice_host.h"
+#include "decode_compact.h"
 
 #define DEC_THREADS 256          // select / pack: 16 lanes per volume, 16 volumes per workgroup
-#define DEC_PART 1024            // compaction partition: positions of the active list per compact workgroup (one per thread)
 
 namespace {
 
@@ -225,31 +225,9 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_select_kernel(DecArgs a) {
     }
 }
 
-// Partition b = positions [b DEC_PART, (b + 1) DEC_PART) of the active list, one per thread.
+// Partition b = positions [b DEC_PART, (b + 1) DEC_PART) of the active list, one per thread (decode_compact.h).
 __global__ __launch_bounds__(DEC_PART) void decode_compact_kernel(DecArgs a) {
-    __shared__ int s_pre[DEC_PART / 64];
-    __shared__ int s_cnt[DEC_PART / 64];
-    __shared__ int s_base[DEC_PART / 64];
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int pre = 0;                                                    // volumes of the partitions before this one that go on
-    for (int k = t; k < b; k += DEC_PART) pre += a.part[k];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) pre += __shfl_xor(pre, m);
-    const int pos = b * DEC_PART + t;
-    const int v = pos < a.n_active ? a.act_in[pos] : 0;
-    const bool keep = pos < a.n_active && a.status[v] == DQ_DECODE_ACTIVE;
-    const u64 bal = __ballot(keep);
-    if (lane == 0) { s_pre[wave] = pre; s_cnt[wave] = __popcll(bal); }
-    __syncthreads();
-    if (t == 0) {
-        int off = 0;
-        for (int w = 0; w < DEC_PART / 64; ++w) off += s_pre[w];
-        for (int w = 0; w < DEC_PART / 64; ++w) { s_base[w] = off; off += s_cnt[w]; }
-        if (b == (int)gridDim.x - 1) *a.count = off;
-        a.part_next[b] = 0;                                         // the next iteration's counts start from zero
-    }
-    __syncthreads();
-    if (keep) a.act_out[s_base[wave] + __popcll(bal & ((1ull << lane) - 1ull))] = v;
+    decode_compact_partition(a.part, a.part_next, a.act_in, a.n_active, a.status, a.act_out, a.count);
 }
 
 }  // namespace

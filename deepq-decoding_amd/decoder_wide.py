@@ -4,6 +4,10 @@ section 18): the wide form of decoder.stream_decode / decoder.memory_experiment,
 The algorithm and the window schedule are section 17's; for d <= 7 and window <= 16 every field equals decoder.stream_decode's.  The handle
 (`WideEvaluator`) owns the lattice tables: no environment is needed, and no referee is consulted -- the verdict is "the residual is a stabilizer" (in the
 code space, trivial homology class).  EvalResult.death_rate therefore EQUALS failure_rate by construction at these sizes and means nothing more.
+
+Further down: the union-find decoder as a policy and a teacher of the wide environment (section 19), and batched decoding by a trained agent at these
+sizes -- WideBatchDecoder, the wide form of decoder.BatchDecoder, and the scorer behind DQNAgent.decode_benchmark_wide (include/deepq_hip.h
+dq_decode_wide_*; csrc/decode_wide.hip).
 """
 import ctypes
 
@@ -442,3 +446,314 @@ class WideUnionFindAgent(MatchingAgent):
         finally:
             if opened:
                 ev.close()
+
+
+# ---- batched agent decoding for any odd d in 3 .. 15 (include/deepq_hip.h dq_decode_wide_*; csrc/decode_wide.hip) ---------------------
+DECODE_WIDE_BUDGET = 4 << 30                                      # device bytes a default chunk may ask for (rows + Q rows + the network's workspaces)
+DECODE_WIDE_MIN_CHUNK = 64
+
+
+def check_decode_wide_args(d, error_model, use_Y, volume_depth, shape, max_actions=None):
+    """Validates a decode_wide request without touching the library: odd d in 3 .. 15, volume_depth 1 .. 16, max_actions in 1 .. num_actions - 1, the
+    syndromes [N, depth, d+1, d+1] or one volume [depth, d+1, d+1] (else ValueError).  Returns (n_volumes, single, num_actions, max_actions)."""
+    d, error_model = check_wide_lattice(d, error_model)
+    layers = action_layers(error_model, use_Y)
+    if not _is_int(volume_depth) or not 1 <= volume_depth <= WIDE_MAX_DEPTH:
+        raise ValueError(f"decode_wide covers volume_depth 1..{WIDE_MAX_DEPTH}, not {volume_depth!r}")
+    volume_depth = int(volume_depth)
+    num_actions = layers * d * d + 1
+    if max_actions is None:
+        max_actions = num_actions - 1
+    if not _is_int(max_actions) or not 1 <= max_actions <= num_actions - 1:
+        raise ValueError(f"max_actions must be an integer in 1..{num_actions - 1}, not {max_actions!r}")
+    shape = tuple(int(x) for x in shape)
+    grid = (volume_depth, d + 1, d + 1)
+    if len(shape) == 3 and shape == grid:
+        return 1, True, num_actions, int(max_actions)
+    if len(shape) == 4 and shape[1:] == grid and shape[0] >= 1:
+        return shape[0], False, num_actions, int(max_actions)
+    raise ValueError(f"faulty syndromes must have shape [N, {volume_depth}, {d + 1}, {d + 1}] or [{volume_depth}, {d + 1}, {d + 1}], got {shape}")
+
+
+def decode_wide_footprint(input_shape, c_layers, ff_layers, num_actions, dueling=True):
+    """Device bytes one volume of a chunk costs: its observation row, its Q row, and the per-layer network's workspaces (csrc/qnet.hip keeps three float
+    buffers -- two activations and a gradient -- per layer output)."""
+    c, h, w = (int(x) for x in input_shape)
+    row, outs = c * h * w, 0
+    for cout, k, s in ((int(l[0]), int(l[1]), int(l[2])) for l in c_layers):
+        h, w = (h - k) // s + 1, (w - k) // s + 1
+        outs += cout * h * w
+    outs += sum(int(l[0]) for l in ff_layers) + int(num_actions) + (int(num_actions) + 1 if dueling else 0)
+    return row + 4 * int(num_actions) + 12 * outs
+
+
+def default_decode_wide_chunk(input_shape, c_layers, ff_layers, num_actions, dueling=True):
+    """The largest power of two of volumes whose footprint stays within DECODE_WIDE_BUDGET, between DECODE_WIDE_MIN_CHUNK and decoder.DEFAULT_CHUNK."""
+    fit = DECODE_WIDE_BUDGET // decode_wide_footprint(input_shape, c_layers, ff_layers, num_actions, dueling)
+    chunk = DECODE_WIDE_MIN_CHUNK
+    while 2 * chunk <= min(fit, DEFAULT_CHUNK):
+        chunk *= 2
+    return chunk
+
+
+class _DeviceView:
+    """A typed view of device memory the library owns, for torch.as_tensor (the __cuda_array_interface__ protocol); for reading."""
+
+    def __init__(self, pointer, shape, typestr):
+        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(pointer), False), version=2, strides=None)
+
+
+class WideBatchDecoder:
+    """decoder.BatchDecoder for any odd d in 3 .. 15: decodes syndrome volumes with a Q-network's weights in chunks of at most `chunk` volumes.  Owns a
+    QNetwork handle of max_batch = chunk and a dq_decode_wide handle.  The environment's action planes and uint8 observation rows only.  chunk=None: the
+    largest power of two whose rows, Q rows and network workspaces fit DECODE_WIDE_BUDGET (default_decode_wide_chunk).  Scoring is
+    DQNAgent.decode_benchmark_wide."""
+
+    def __init__(self, input_shape, c_layers, ff_layers, num_actions, d, error_model, use_Y, volume_depth, dueling=True, masked_greedy=False,
+                 max_actions=None, chunk=None, device=None):
+        import torch
+        from . import _lib
+        from .qnet import QNetwork
+        _, _, n_act, max_actions = check_decode_wide_args(d, error_model, use_Y, volume_depth, (volume_depth, d + 1, d + 1), max_actions)
+        layers = action_layers(error_model, use_Y)
+        if int(num_actions) != n_act or tuple(input_shape) != (volume_depth + layers, 2 * d + 1, 2 * d + 1):
+            raise ValueError(f"the network ({tuple(input_shape)} -> {num_actions} actions) does not fit the lattice (d = {d}, {error_model}, "
+                             f"volume_depth = {volume_depth})")
+        chunk = default_decode_wide_chunk(input_shape, c_layers, ff_layers, num_actions, dueling) if chunk is None else check_chunk(chunk)
+        self.d, self.error_model, self.use_Y, self.volume_depth = int(d), error_model, bool(use_Y), int(volume_depth)
+        self.masked_greedy, self.max_actions, self.chunk, self.num_actions = bool(masked_greedy), max_actions, chunk, n_act
+        self._h = None
+        self.net = QNetwork(input_shape, c_layers, ff_layers, num_actions, dueling=dueling, max_batch=self.chunk, device=device)
+        self.device = self.net.device
+        cfg = _lib.DecodeCfg(d=self.d, volume_depth=self.volume_depth, error_model=MODELS[error_model], use_Y=int(self.use_Y),
+                             masked_greedy=int(self.masked_greedy), max_actions=self.max_actions, action_planes=_lib.DECODE_PLANES_ENV,
+                             obs_form=_lib.DECODE_OBS_UINT8)
+        self.L = _lib.lib()
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.dq_decode_wide_create(ctypes.byref(cfg), self.chunk, ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.dq_decode_wide_destroy(self._h)
+            self._h = None
+        if getattr(self, "net", None) is not None:
+            self.net.close()
+            self.net = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _input(self, syndromes):
+        import torch
+        n, single, _, _ = check_decode_wide_args(self.d, self.error_model, self.use_Y, self.volume_depth, tuple(syndromes.shape), self.max_actions)
+        check_binary(syndromes)
+        t = syndromes if isinstance(syndromes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(syndromes)))
+        t = t.to(device=self.device, dtype=torch.uint8).reshape(n, self.volume_depth, self.d + 1, self.d + 1).contiguous()
+        return t, n, single
+
+    def outputs(self, n):
+        """Empty (corrections, n_corrections, frame, status) device tensors for n volumes."""
+        import torch
+        dev = self.device
+        return (torch.empty((n, self.max_actions), dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                torch.empty((n, self.d, self.d), dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.uint8, device=dev))
+
+    def decode_into(self, params, packed, syn, m, corr, ncorr, frame, status):
+        """One dq_decode_wide_run over m <= chunk volumes already on the device; returns the iterations."""
+        from . import _lib
+        it = ctypes.c_int(0)
+        _lib.check(self.L.dq_decode_wide_run(self._h, self.net._h, _lib.ptr(params), _lib.ptr(packed), _lib.ptr(syn), m, _lib.ptr(corr), _lib.ptr(ncorr),
+                                             _lib.ptr(frame), _lib.ptr(status), ctypes.byref(it), self._stream()))
+        return int(it.value)
+
+    def decode(self, params, syndromes, to_host=True):
+        """params: float32 device tensor of the network's flat parameters (Keras order).  syndromes: numpy or torch (CPU or device), 0/1 cells,
+        [N, volume_depth, d+1, d+1] or one volume.  Returns a decoder.DecodeResult; to_host=False leaves the outputs as device tensors."""
+        import torch
+        from .decoder import DecodeResult
+        syn, n, single = self._input(syndromes)
+        corr, ncorr, frame, status = self.outputs(n)
+        iters = []
+        with torch.cuda.device(self.device):
+            packed = self.net.pack(params)
+            for s in range(0, n, self.chunk):
+                m = min(self.chunk, n - s)
+                iters.append(self.decode_into(params, packed, syn[s:s + m], m, corr[s:s + m], ncorr[s:s + m], frame[s:s + m], status[s:s + m]))
+        out = [corr, ncorr, frame, status]
+        if to_host:
+            out = [x.cpu().numpy() for x in out]
+        if single:
+            out = [x[0] for x in out]
+        return DecodeResult(*out, iterations=iters)
+
+    # -- the stepping pair (dq_decode_wide_pack / dq_decode_wide_step): the bookkeeping driven by the caller's Q rows ------------------------------
+    def pack(self, syndromes):
+        """Starts a decode of n <= chunk volumes; returns the (corrections, n_corrections, frame, status) device tensors the steps write."""
+        import torch
+        from . import _lib
+        syn, n, _ = self._input(syndromes)
+        if n > self.chunk:
+            raise ValueError(f"pack takes at most chunk = {self.chunk} volumes, not {n}")
+        out = self.outputs(n)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.dq_decode_wide_pack(self._h, _lib.ptr(syn), n, *(_lib.ptr(x) for x in out), self._stream()))
+        self._stepping = (syn,) + out                             # (the handle writes them until the decode ends)
+        return out
+
+    def step(self, q):
+        """One select + compact with q float32 [n_active, num_actions], rows in active-list order; returns the next active count."""
+        import torch
+        from . import _lib
+        q = torch.as_tensor(q, dtype=torch.float32, device=self.device).contiguous()
+        _, n_active = self.active(count_only=True)
+        if n_active and tuple(q.shape) != (n_active, self.num_actions):       # (no volume active: the library says so, DQ_ERR_STATE)
+            raise ValueError(f"q must have shape {(n_active, self.num_actions)}, got {tuple(q.shape)}")
+        nxt = ctypes.c_int(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.dq_decode_wide_step(self._h, _lib.ptr(q), ctypes.byref(nxt), self._stream()))
+        return int(nxt.value)
+
+    def active(self, count_only=False):
+        """(the current active list as an int32 device tensor, its length)."""
+        import torch
+        from . import _lib
+        p, n = ctypes.c_void_p(), ctypes.c_int(0)
+        _lib.check(self.L.dq_decode_wide_active(self._h, ctypes.byref(p), ctypes.byref(n)))
+        if count_only or n.value == 0:
+            return None, int(n.value)
+        return torch.as_tensor(_DeviceView(p.value, (n.value,), "<i4"), device=self.device), int(n.value)
+
+    def rows(self, n):
+        """The observation rows of volumes 0 .. n - 1 as a uint8 device tensor [n, depth + layers, 2d+1, 2d+1] (a view of the handle's buffer)."""
+        import torch
+        from . import _lib
+        p, nb = ctypes.c_void_p(), ctypes.c_int(0)
+        _lib.check(self.L.dq_decode_wide_rows(self._h, ctypes.byref(p), ctypes.byref(nb)))
+        side = 2 * self.d + 1
+        return torch.as_tensor(_DeviceView(p.value, (int(n), nb.value // (side * side), side, side), "|u1"), device=self.device)
+
+    def words(self, n):
+        """(legal, completed) words of volumes 0 .. n - 1 as int64 device tensors [n, legal_words] (views; bit a of the set = action a)."""
+        import torch
+        from . import _lib
+        pl, pc, lw = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int(0)
+        _lib.check(self.L.dq_decode_wide_words(self._h, ctypes.byref(pl), ctypes.byref(pc), ctypes.byref(lw)))
+        return tuple(torch.as_tensor(_DeviceView(p.value, (int(n), lw.value), "<i8"), device=self.device) for p in (pl, pc))
+
+
+def decode_lattice_of(lattice):
+    """`lattice`: (d, error_model, use_Y, volume_depth), or an environment of either backend.  Returns (d, error_model, use_Y, volume_depth, what
+    check_wide_experiment_args takes as its lattice)."""
+    if isinstance(lattice, (tuple, list)):
+        if len(lattice) != 4:
+            raise ValueError(f"lattice must be (d, error_model, use_Y, volume_depth) or an environment, not {lattice!r}")
+        d, model = check_wide_lattice(lattice[0], lattice[1])
+        return d, model, bool(lattice[2]), lattice[3], (d, model)
+    v = getattr(lattice, "_v", lattice)
+    if v is None or not all(hasattr(v, k) for k in ("d", "error_model", "use_Y", "volume_depth")):
+        raise ValueError(f"lattice must be (d, error_model, use_Y, volume_depth) or an environment, not {lattice!r}")
+    d, model = check_wide_lattice(int(v.d), str(v.error_model))
+    return d, model, bool(v.use_Y), int(v.volume_depth), lattice
+
+
+def check_decode_benchmark_wide_args(lattice, n_volumes, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, max_actions=None, chunk=None,
+                                     baseline=None, final_round="faulty"):
+    """Validates a decode_benchmark_wide request without touching the library.  Returns (d, error_model, use_Y, depth, max_actions, n, p_phys, p_meas,
+    seed, base, block, keys, closed): memory_experiment_wide's conventions for the rates, the seed and the blocks (check_wide_experiment_args with
+    rounds = window = commit = volume_depth)."""
+    d, model, use_Y, depth, lat = decode_lattice_of(lattice)
+    _, _, _, max_actions = check_decode_wide_args(d, model, use_Y, depth, (depth, d + 1, d + 1), max_actions)
+    if baseline is not None and baseline != "union_find":
+        raise ValueError(f"decode_benchmark_wide: baseline must be None or 'union_find', not {baseline!r}")
+    closed = check_final_round(final_round)
+    _, _, _, _, _, n, ph, pm, seed, base, blk, keys, _ = check_wide_experiment_args(
+        lat, n_volumes, depth, depth, depth, rates, p_phys, p_meas, seed, env_id_base, DEFAULT_CHUNK if chunk is None else chunk)
+    return d, model, use_Y, int(depth), max_actions, n, ph, pm, seed, base, blk, keys, closed
+
+
+def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=None, no_decoder=False, final_round="faulty", return_volumes=False,
+                      timings=None):
+    """The loop behind DQNAgent.decode_benchmark_wide for a validated request: per chunk ONE dq_wide_uf_run (T = window = commit = volume_depth, with
+    syndromes) yields the agent's input, the hidden state and the union-find frame of the same volumes; then dq_decode_wide_run, dq_wide_uf_verdict
+    and dq_decode_count with the agent's status and correction count.  No referee is consulted: alive := success."""
+    import time
+    import torch
+    from .decoder import DecodeResult
+    d, depth, dev = dec.d, dec.volume_depth, dec.device
+    step = min(dec.chunk, n)
+    ev = WideEvaluator(d, dec.error_model, depth, chunk=step, device=dev)
+    each = not isinstance(ph, float)
+    closed = closed_kw(final_round)
+    try:
+        rows = n if return_volumes else step
+        syn = torch.empty((rows, depth, d + 1, d + 1), dtype=torch.uint8, device=dev)
+        hid = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+        uf_frame = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+        triv = torch.empty(rows, dtype=torch.uint8, device=dev)
+        verd = torch.empty(rows, dtype=torch.uint8, device=dev)
+        verd2 = torch.empty(step, dtype=torch.uint8, device=dev)
+        corr, ncorr, frame, status = dec.outputs(rows)
+        uf_status = torch.full((step,), STATUS_IDENTITY, dtype=torch.uint8, device=dev)
+        n_blocks = -(-n // blk)
+        counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
+        counters_uf = torch.zeros_like(counters) if baseline else None
+        counters0 = torch.zeros_like(counters) if no_decoder else None
+        iters = []
+
+        def phase(name, t0):
+            if timings is None:
+                return t0
+            torch.cuda.current_stream(dev).synchronize()
+            t1 = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + (t1 - t0)
+            return t1
+
+        with torch.cuda.device(dev):
+            packed = dec.net.pack(params)
+            for s in range(0, n, step):
+                m = min(step, n - s)
+                o = s if return_volumes else 0
+                sl = slice(o, o + m)
+                t = time.perf_counter()
+                a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
+                if each and (a == a[0]).all() and (b == b[0]).all():
+                    a, b = float(a[0]), float(b[0])
+                ev.run_into(m, depth, depth, base + s, seed, a, b, hid[sl], triv[sl], uf_frame[sl], syndromes=syn[sl], **closed)
+                t = phase("run", t)
+                iters.append(dec.decode_into(params, packed, syn[sl], m, corr[sl], ncorr[sl], frame[sl], status[sl]))
+                t = phase("decode", t)
+                ev.verdict_into(hid[sl], frame[sl], m, verd[sl])
+                ev.count_into(verd[sl], triv[sl], status[sl], ncorr[sl], m, s, blk, counters)
+                if baseline:
+                    ev.verdict_into(hid[sl], uf_frame[sl], m, verd2[:m])
+                    ev.count_into(verd2[:m], triv[sl], uf_status[:m], (uf_frame[sl] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), m, s, blk,
+                                  counters_uf)
+                if no_decoder:
+                    ev.verdict_into(hid[sl], None, m, verd2[:m])
+                    ev.count_into(verd2[:m], triv[sl], None, None, m, s, blk, counters0)
+                t = phase("verdict", t)
+            host = counters.cpu().numpy()
+            host_uf = counters_uf.cpu().numpy() if baseline else None
+            host0 = counters0.cpu().numpy() if no_decoder else None
+    finally:
+        ev.close()
+    zeros = np.zeros(n_blocks, dtype=np.int64)
+    results = block_results(host, host0, zeros, n_blocks, blk, ph, pm)
+    if return_volumes:
+        r = results[0]
+        r.volumes, r.hidden, r.trivial, r.verdict = syn, hid, triv, verd
+        r.decode = DecodeResult(corr, ncorr, frame, status, iterations=iters)
+    out = results[0] if keys is None else dict(zip(keys, results))
+    if not baseline:
+        return out
+    rows_uf = block_results(host_uf, host0, zeros, n_blocks, blk, ph, pm)
+    return out, (rows_uf[0] if keys is None else dict(zip(keys, rows_uf)))

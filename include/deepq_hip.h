@@ -68,7 +68,7 @@ int dq_version(void);
 const char* dq_build_digest(void);
 const char* dq_last_error(void);
 /* sizeof() of the public structs as THIS library was compiled: 0 dq_env_cfg, 1 dq_env_info, 2 dq_sample_job, 3 dq_qnet_cfg, 4 dq_qnet_job, 5 dq_td_job,
- * 6 dq_env_step_job, 7 dq_env_ring, 8 dq_decode_cfg; -1 for any other id.  A binding (the ctypes structures of _lib.py) checks its own layouts against it: a struct of the wrong size handed
+ * 6 dq_env_step_job, 7 dq_env_ring, 8 dq_decode_cfg (dq_decode_create's and dq_decode_wide_create's); -1 for any other id.  A binding (the ctypes structures of _lib.py) checks its own layouts against it: a struct of the wrong size handed
  * across the boundary is silent memory corruption (tests/test_abi.py).  No reference counterpart. */
 long dq_struct_size(int id);
 /* Number of visible HIP devices (0 if none / runtime unavailable).  Never fails. */
@@ -703,7 +703,7 @@ enum { DQ_DECODE_ACTIVE = 0, DQ_DECODE_IDENTITY = 1, DQ_DECODE_REPEAT = 2, DQ_DE
 enum { DQ_DECODE_PLANES_ENV = 0, DQ_DECODE_PLANES_README = 1 };
 enum { DQ_DECODE_OBS_UINT8 = 0, DQ_DECODE_OBS_PATCH = 1 };
 typedef struct {
-    int32_t d;              /* 3, 5 or 7 */
+    int32_t d;              /* 3, 5 or 7 (dq_decode_wide_create: odd, 3 .. 15) */
     int32_t volume_depth;   /* 1..16 */
     int32_t error_model;    /* DQ_MODEL_* */
     int32_t use_Y;
@@ -917,6 +917,38 @@ dq_status dq_wide_uf_run_closed(dq_wide_uf* h, int n, int T, int commit, uint32_
 dq_status dq_envb_uf_select(dq_envb* env, dq_wide_uf* h, int32_t* action_dev, void* stream);
 dq_status dq_envb_guided_select_uf(dq_envb* env, dq_wide_uf* h, const float* q_dev, double eps, double guide_share, int masked_greedy,
                                    const uint32_t seed[2], uint64_t t, int32_t* action_dev, uint8_t* guided_dev, void* stream);
+
+/* Batched agent decoding for any odd d in 3 .. 15 (csrc/decode_wide.hip).  dq_version() stays 8: the capability is the presence of
+ * these symbols.  The semantics are dq_decode_run's, statement for statement, with DQ_DECODE_PLANES_ENV and DQ_DECODE_OBS_UINT8 (patch words and the README
+ * quirk stay narrow-only); what differs is the state: LW = ceil(num_actions / 64) <= 11 legal and as many completed words per volume, ceil(d^2 / 64) <= 4
+ * words each for the acted-on qubits and the two frame components, grid masks of ceil((d+1)^2 / 64) <= 4 words per slice, one wavefront per volume.  For
+ * d <= 7 every output equals dq_decode_run's on uint8 rows, bit for bit (the same forward on the same rows in the same order).  dq_decode_cfg is reused
+ * (its d: odd, 3 .. 15), so dq_struct_size has no new id.
+ * dq_decode_wide_create: cfg->d odd in 3 .. 15, volume_depth 1 .. 16, a DQ_MODEL_*, max_actions 1 .. num_actions - 1, max_volumes >= 1 (else
+ * DQ_ERR_INVALID); action_planes != DQ_DECODE_PLANES_ENV or obs_form != DQ_DECODE_OBS_UINT8: DQ_ERR_UNSUPPORTED; all before any device work.
+ * dq_decode_wide_pack: starts a decode of n <= max_volumes volumes (syndromes_dev uint8 [n][volume_depth][d+1][d+1], 4-byte aligned): observation rows
+ * with empty action planes, reset_legal_moves' legal set of the summed volume, corrections = -1, the identity active list.  The four output arrays are
+ * dq_decode_run's; the handle keeps their pointers, and the steps that follow write them: they must stay valid until the decode ends.
+ * dq_decode_wide_step: one selection and one stable compaction over the current active list with the caller's Q rows, q_dev float32 [n_active][num_actions]
+ * in active-list order; *n_active_out (nullable) receives the next active count.  It synchronises `stream` (the one host wait of an iteration).  A chosen
+ * value that is not finite raises a sticky device word that is read together with the count: DQ_ERR_RANGE, and the decode is over (pack starts the next
+ * one).  DQ_ERR_STATE without a pack, with no volume active, or after max_actions steps.
+ * dq_decode_wide_run: pack, then dq_qnet_forward_multi (index gather over the active list) and step until no volume is active; dq_decode_run's arguments,
+ * checks of the network against the lattice, host waits and final dq_qnet_range_check.
+ * The accessors return device pointers of the handle's own buffers for reading (tests, diagnostics): the observation rows uint8 [max_volumes][row_bytes],
+ * row_bytes = (volume_depth + layers) (2d+1)^2, row v = volume v; the legal and completed words uint64 [max_volumes][legal_words]; the current active list
+ * int32 [n_active].  Out-pointers may be NULL.  One host thread and one stream at a time per handle.  No reference counterpart beyond README.md:786-829. */
+typedef struct dq_decode_wide dq_decode_wide;
+dq_status dq_decode_wide_create(const dq_decode_cfg* cfg, int max_volumes, dq_decode_wide** out);
+void dq_decode_wide_destroy(dq_decode_wide* h);
+dq_status dq_decode_wide_pack(dq_decode_wide* h, const uint8_t* syndromes_dev, int n, int32_t* corrections_dev, int32_t* n_corr_dev, uint8_t* frame_dev,
+                              uint8_t* status_dev, void* stream);
+dq_status dq_decode_wide_step(dq_decode_wide* h, const float* q_dev, int* n_active_out, void* stream);
+dq_status dq_decode_wide_run(dq_decode_wide* h, dq_qnet* net, const float* params_dev, const void* packed_dev, const uint8_t* syndromes_dev, int n,
+                             int32_t* corrections_dev, int32_t* n_corr_dev, uint8_t* frame_dev, uint8_t* status_dev, int* iterations, void* stream);
+dq_status dq_decode_wide_rows(const dq_decode_wide* h, const uint8_t** rows_dev, int* row_bytes);
+dq_status dq_decode_wide_words(const dq_decode_wide* h, const uint64_t** legal_dev, const uint64_t** completed_dev, int* legal_words);
+dq_status dq_decode_wide_active(const dq_decode_wide* h, const int32_t** active_dev, int* n_active);
 
 /* ---------------------------------------------------------------------------------------------
  * Live kernel timing (measurement only; no reference counterpart).  dq_prof_arm(id, n) times up to n

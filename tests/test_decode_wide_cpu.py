@@ -1,0 +1,163 @@
+"""Batched agent decoding at d = 9 .. 15, host side: argument validation before any library call, the narrow entry points'
+refusal of d >= 9 asserted again, the C ABI declared, bound and exported, the default chunk rule, and the numpy restatement (tests/decode_ref.py) at the
+wide shapes under the supplied Q rows the GPU stepping test uses."""
+import re
+import subprocess
+import types
+
+import numpy as np
+import pytest
+
+import decode_wide_ref as WR
+from conftest import ROOT
+from oracle import lattice
+
+NEW_SYMBOLS = ("dq_decode_wide_create", "dq_decode_wide_destroy", "dq_decode_wide_pack", "dq_decode_wide_step", "dq_decode_wide_run")
+ACCESSORS = ("dq_decode_wide_rows", "dq_decode_wide_words", "dq_decode_wide_active")
+
+
+def _agent_without_library(dq, monkeypatch, shape=(5, 19, 19), actions=163):
+    """An agent whose every library call fails: validation has to raise before one is made (tests/test_decode_cpu.py)."""
+    import importlib
+    _lib = importlib.import_module("deepq-decoding_amd._lib")
+    agent_mod = importlib.import_module("deepq-decoding_amd.agent")
+
+    def no_library(*a, **k):
+        raise AssertionError("a library call was made before the arguments were validated")
+    monkeypatch.setattr(_lib, "lib", no_library)
+    monkeypatch.setattr(_lib, "require_gpu", no_library)
+    model = agent_mod.ConvQModel(WR.C_LAYERS, WR.FF_LAYERS, shape, actions)
+    return agent_mod.DQNAgent(model=model, nb_actions=actions, memory=agent_mod.SequentialMemory(limit=100), nb_steps_warmup=10, target_model_update=10)
+
+
+D9 = dict(d=9, error_model="DP", use_Y=False, volume_depth=3)
+
+
+@pytest.mark.parametrize("lat,syn,kw", [
+    (dict(D9, d=8), np.zeros((1, 3, 9, 9), np.uint8), {}),                                   # even d
+    (dict(D9, d=17), np.zeros((1, 3, 18, 18), np.uint8), {}),                                # beyond the wide kernels
+    (D9, np.zeros((4, 3, 10, 9), np.uint8), {}),                                             # shape
+    (D9, np.zeros((4, 2, 10, 10), np.uint8), {}),                                            # depth of the input
+    (D9, np.full((2, 3, 10, 10), 2, np.uint8), {}),                                          # values
+    (D9, -np.ones((3, 10, 10), np.int64), {}),                                               # values
+    (dict(D9, volume_depth=17), np.zeros((1, 17, 10, 10), np.uint8), {}),                    # depth 17
+    (dict(D9, error_model="XZ"), np.zeros((1, 3, 10, 10), np.uint8), {}),                    # error model
+    (D9, np.zeros((1, 3, 10, 10), np.uint8), dict(max_actions=0)),
+    (D9, np.zeros((1, 3, 10, 10), np.uint8), dict(max_actions=163)),                         # n_actions - 1 = 162 is the last
+    (D9, np.zeros((1, 3, 10, 10), np.uint8), dict(max_actions=2.5)),
+    (D9, np.zeros((1, 3, 10, 10), np.uint8), dict(chunk=0)),
+])
+def test_decode_wide_arguments_are_validated_before_any_library_call(dq, monkeypatch, lat, syn, kw):
+    agent = _agent_without_library(dq, monkeypatch)
+    with pytest.raises(ValueError):
+        agent.decode_wide(syn, env=types.SimpleNamespace(**lat), **kw)
+
+
+def test_decode_wide_without_a_lattice_is_refused(dq, monkeypatch):
+    agent = _agent_without_library(dq, monkeypatch)
+    with pytest.raises(RuntimeError):
+        agent.decode_wide(np.zeros((1, 3, 10, 10), np.uint8))
+
+
+def test_the_narrow_decode_still_refuses_d9(dq, monkeypatch):
+    agent = _agent_without_library(dq, monkeypatch)
+    with pytest.raises(NotImplementedError):
+        agent.decode(np.zeros((1, 3, 10, 10), np.uint8), env=types.SimpleNamespace(**D9))
+
+
+TUPLE = (9, "DP", False, 3)
+RATED = dict(p_phys=0.01, seed=(1, 2))
+
+
+@pytest.mark.parametrize("lattice_arg,kw", [
+    (TUPLE, dict(seed=(1, 2))),                                                              # a tuple lattice without rates
+    (TUPLE, dict(p_phys=0.01)),                                                              # ... without a seed
+    (TUPLE, dict(RATED, baseline="matching")),                                               # the matching referee is not wide
+    (TUPLE, dict(RATED, baseline="uf")),
+    (TUPLE, dict(RATED, final_round="ideal")),
+    (TUPLE, dict(RATED, max_actions=163)),
+    (TUPLE, dict(RATED, rates=[0.01, 0.02])),                                                # rates=[...] are the physical rates: p_phys goes without
+    (TUPLE, dict(seed=(1, 2), rates=[0.01, 0.01])),                                          # they key the result
+    ((9, "DP", False), RATED),                                                               # not a lattice
+    ((10, "DP", False, 3), RATED),
+    ((9, "DP", False, 17), RATED),
+    (TUPLE, dict(RATED, env_id_base=-1)),
+    (TUPLE, dict(RATED, chunk=0)),
+    (types.SimpleNamespace(**D9), dict(seed=(1, 2))),                                        # an environment-like object without rates
+])
+def test_decode_benchmark_wide_arguments_are_validated_before_any_library_call(dq, monkeypatch, lattice_arg, kw):
+    agent = _agent_without_library(dq, monkeypatch)
+    with pytest.raises(ValueError):
+        agent.decode_benchmark_wide(lattice_arg, 64, **kw)
+    with pytest.raises(ValueError):
+        agent.decode_benchmark_wide(TUPLE, 0, **RATED)
+
+
+def test_decode_benchmark_wide_checks_the_network_against_the_lattice(dq, monkeypatch):
+    agent = _agent_without_library(dq, monkeypatch)
+    with pytest.raises(ValueError, match="does not fit"):
+        agent.decode_benchmark_wide((9, "DP", True, 3), 64, **RATED)
+    with pytest.raises(RuntimeError):                                                        # valid, but the agent has no weights on a device
+        agent.decode_benchmark_wide(TUPLE, 64, **RATED)
+
+
+def test_the_wide_decode_abi_is_declared_bound_and_exported(dq):
+    import ctypes
+    import importlib
+    L = importlib.import_module("deepq-decoding_amd._lib")
+    text = re.sub(r"/\*.*?\*/", "", open(f"{ROOT}/include/deepq_hip.h").read(), flags=re.S)
+    lib = L.lib()
+    assert lib.dq_version() == 8                                                             # the capability is the presence of the symbols
+    assert lib.dq_struct_size(8) == ctypes.sizeof(L.DecodeCfg) and lib.dq_struct_size(9) == -1
+    exported = set(re.findall(r" T (dq_[a-z0-9_]+)", subprocess.check_output(["nm", "-D", "--defined-only", dq.LIB_PATH], text=True)))
+    for name in NEW_SYMBOLS + ACCESSORS:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert name in L.SIGNATURES and hasattr(lib, name) and name in exported, name
+    for name in ("WideBatchDecoder", "decoder_wide"):
+        assert getattr(dq, name) is not None
+    assert hasattr(dq.DQNAgent, "decode_wide") and hasattr(dq.DQNAgent, "decode_benchmark_wide")
+
+
+def test_null_handles_are_refused_without_a_device(dq):
+    import ctypes
+    import importlib
+    L = importlib.import_module("deepq-decoding_amd._lib")
+    lib = L.lib()
+    out, n = ctypes.c_void_p(), ctypes.c_int(0)
+    assert lib.dq_decode_wide_create(None, 4, ctypes.byref(out)) == L.DQ_ERR_INVALID
+    for bad, code in ((dict(d=17), L.DQ_ERR_INVALID), (dict(d=8), L.DQ_ERR_INVALID), (dict(volume_depth=17), L.DQ_ERR_INVALID),
+                      (dict(max_actions=163), L.DQ_ERR_INVALID), (dict(action_planes=1), L.DQ_ERR_UNSUPPORTED), (dict(obs_form=1), L.DQ_ERR_UNSUPPORTED)):
+        cfg = L.DecodeCfg(**dict(dict(d=9, volume_depth=3, error_model=1, use_Y=0, masked_greedy=0, max_actions=5, action_planes=0, obs_form=0), **bad))
+        assert lib.dq_decode_wide_create(ctypes.byref(cfg), 4, ctypes.byref(out)) == code and not out.value, bad
+    assert lib.dq_decode_wide_step(None, None, ctypes.byref(n), None) == L.DQ_ERR_INVALID
+    assert lib.dq_decode_wide_active(None, ctypes.byref(out), ctypes.byref(n)) == L.DQ_ERR_INVALID
+    lib.dq_decode_wide_destroy(None)
+
+
+def test_the_default_chunk_follows_the_footprint(dq):
+    W = dq.decoder_wide
+    small = W.default_decode_wide_chunk((7, 19, 19), WR.C_LAYERS, WR.FF_LAYERS, 163)
+    big = W.default_decode_wide_chunk((19, 31, 31), WR.C_LAYERS, WR.FF_LAYERS, 676)
+    for chunk, shape, A in ((small, (7, 19, 19), 163), (big, (19, 31, 31), 676)):
+        per = W.decode_wide_footprint(shape, WR.C_LAYERS, WR.FF_LAYERS, A)
+        assert chunk & (chunk - 1) == 0 and W.DECODE_WIDE_MIN_CHUNK <= chunk <= dq.decoder.DEFAULT_CHUNK
+        assert chunk * per <= W.DECODE_WIDE_BUDGET and (2 * chunk * per > W.DECODE_WIDE_BUDGET or chunk == dq.decoder.DEFAULT_CHUNK)
+    assert big < small
+    assert W.decode_wide_footprint((19, 31, 31), WR.C_LAYERS, WR.FF_LAYERS, 676) * (1 << 18) > 40 << 30      # what a 2^18 chunk would have asked for
+
+
+def test_the_restatement_runs_at_676_actions_under_supplied_q_rows():
+    """d = 15, DP with Y, depth 16: decode_ref.decode_volume with the stepping test's Q rows gives sequences that stay inside their legal sets when
+    masked, never repeat an action, and end for the reason their status names."""
+    cfg = dict(d=15, error_model="DP", use_Y=True, volume_depth=16)
+    A, _ = lattice.num_actions(15, "DP", True)
+    assert A == 676
+    grids = WR.sparse_grids(cfg, 12, seed=15)
+    sup = WR.SuppliedQ(12, A, seed=3)
+    corr, frames, status = WR.reference_decode(cfg, grids, sup, True, 12)
+    for v in range(12):
+        assert len(set(corr[v])) == len(corr[v]) <= 12 and (status[v] == 3) == (len(corr[v]) == 12)
+        _, legal = WR.R.state_after(grids[v], corr[v], 15, "DP", True)
+        assert set(corr[v]) <= legal
+        assert int((frames[v] != 0).sum()) <= len(corr[v])
+    assert corr[0] == [] and status[0] == 1                          # the empty volume's legal set is the identity alone
