@@ -212,6 +212,7 @@ SIGNATURES = {
     "dq_wide_uf_decode": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_run": (_i, [_vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_verdict": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "dq_wide_uf_verdict_refereed": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "dq_wide_uf_decode_closed": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_run_closed": (_i, [_vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_envb_uf_select": (_i, [_vp, _vp, _vp, _vp]),

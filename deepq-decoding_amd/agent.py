@@ -540,7 +540,8 @@ class DQNAgent:
         return self._wide_decoder
 
     def decode_benchmark_wide(self, lattice, n_volumes, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, masked_greedy=None,
-                              max_actions=None, chunk=None, baseline=None, no_decoder=False, final_round="faulty", return_volumes=False, timings=None):
+                              max_actions=None, chunk=None, baseline=None, no_decoder=False, final_round="faulty", return_volumes=False, timings=None,
+                              referee=None):
         """Scores decode_wide() on the device for any odd d in 3 .. 15 under decoder_wide.memory_experiment_wide's conventions:
         volume i is the first volume_depth rounds of lattice env_id_base + i.  lattice: an environment of either backend (the defaults of the rates and
         the seed; the agent is bound to a VectorEnv or drop-in environment given here), or (d, error_model, use_Y, volume_depth) with explicit rates and
@@ -549,10 +550,15 @@ class DQNAgent:
         baseline="union_find": (that, the union-find decoder's result on the same volumes -- memory_experiment_wide's with rounds = window = commit =
         volume_depth).  no_decoder: EvalResult.no_decoder counts the verdict for frame = 0.  final_round="perfect": the volume's last round is measured
         perfectly.  return_volumes: the per-volume device tensors ride on the (first) result.  timings: a dict that receives the wall seconds of the
-        phases run / decode / verdict.  No referee is consulted: alive := success, so death_rate equals failure_rate by construction."""
+        phases run / decode / verdict.  referee=None: no referee is consulted, alive := success, so death_rate equals failure_rate by construction.
+        referee="matching": every verdict of the call -- the agent's row, the union-find row and no_decoder -- is the refereed one (DESIGN.md section
+        22): alive is what the wide environment's step would decide on the residual, and EvalResult.inexact counts the volumes on which the referee's
+        flagged fallback fired.  Anything else is a ValueError.  With no_decoder the refereed verdict of the uncorrected errors is the slow part at
+        d >= 13 (decoder_wide.refereed_uncorrected_into: launches of at most 2048 volumes, 0.24 s each at d = 15, depth 5, p = 0.006): keep n_volumes
+        modest there."""
         from . import decoder as D, decoder_wide as W
         d, model, use_Y, depth, max_actions, n, ph, pm, seed, base, blk, keys, _ = W.check_decode_benchmark_wide_args(
-            lattice, n_volumes, rates, p_phys, p_meas, seed, env_id_base, max_actions, chunk, baseline, final_round)
+            lattice, n_volumes, rates, p_phys, p_meas, seed, env_id_base, max_actions, chunk, baseline, final_round, referee)
         layers = D.action_layers(model, use_Y)
         if int(self.nb_actions) != layers * d * d + 1 or tuple(self.model.input_shape) != (depth + layers, 2 * d + 1, 2 * d + 1):
             raise ValueError(f"the network ({tuple(self.model.input_shape)} -> {self.nb_actions} actions) does not fit the lattice "
@@ -562,7 +568,7 @@ class DQNAgent:
             self._bind(lattice)
         dec = self._wide_decoder_for(d, model, use_Y, depth, masked_greedy, max_actions, chunk)
         return W.score_decode_wide(dec, self._core.params, n, ph, pm, seed, base, blk, keys, baseline=baseline, no_decoder=no_decoder,
-                                   final_round=final_round, return_volumes=return_volumes, timings=timings)
+                                   final_round=final_round, return_volumes=return_volumes, timings=timings, referee=referee)
 
     def compute_q_values(self, observation):
         obs = torch.as_tensor(np.asarray(observation), dtype=torch.uint8, device=self._core.device).reshape((1,) + tuple(self.model.input_shape)).contiguous()

@@ -2,8 +2,10 @@
 section 18): the wide form of decoder.stream_decode / decoder.memory_experiment, which stay as they are and keep refusing d >= 9.
 
 The algorithm and the window schedule are section 17's; for d <= 7 and window <= 16 every field equals decoder.stream_decode's.  The handle
-(`WideEvaluator`) owns the lattice tables: no environment is needed, and no referee is consulted -- the verdict is "the residual is a stabilizer" (in the
-code space, trivial homology class).  EvalResult.death_rate therefore EQUALS failure_rate by construction at these sizes and means nothing more.
+(`WideEvaluator`) owns the lattice tables: no environment is needed.  By default no referee is consulted -- the verdict is "the residual is a stabilizer"
+(in the code space, trivial homology class), and EvalResult.death_rate then EQUALS failure_rate by construction and means nothing more.  referee="matching"
+(verdict_wide, memory_experiment_wide, DQNAgent.decode_benchmark_wide) sends the residual's true syndrome through the matching referee,
+as the wide environment's step does: death_rate is then the share of volumes on which the environment would have ended the episode.
 
 Further down: the union-find decoder as a policy and a teacher of the wide environment (section 19), and batched decoding by a trained agent at these
 sizes -- WideBatchDecoder, the wide form of decoder.BatchDecoder, and the scorer behind DQNAgent.decode_benchmark_wide (include/deepq_hip.h
@@ -14,7 +16,7 @@ import ctypes
 import numpy as np
 
 from .decoder import (COUNTER_NAMES, DEFAULT_CHUNK, MODELS, STATUS_IDENTITY, STREAM_MAX_ROUNDS, MatchingAgent, StreamResult, action_layers, block_results,
-                      check_binary, check_final_round, check_rates, closed_kw, lattice_of, rate_threshold, stream_windows)
+                      check_binary, check_codes, check_final_round, check_rates, closed_kw, lattice_of, rate_threshold, stream_windows)
 
 WIDE_MAX_D = 15
 WIDE_MAX_WINDOW = 32
@@ -47,6 +49,14 @@ def check_wide_schedule(d, rounds, window, commit):
     if not _is_int(rounds) or not 1 <= rounds <= STREAM_MAX_ROUNDS:
         raise ValueError(f"a stream has 1..{STREAM_MAX_ROUNDS} rounds, not {rounds!r}")
     return int(rounds), int(window), int(commit)
+
+
+def check_referee(referee):
+    """None (no referee: alive := success) or "matching" (the matching referee on the residual's true syndrome), else ValueError.  Returns whether a
+    referee is asked for."""
+    if referee is not None and not (isinstance(referee, str) and referee == "matching"):
+        raise ValueError(f"referee must be None or 'matching', not {referee!r}")
+    return referee is not None
 
 
 def check_chunk(chunk):
@@ -160,7 +170,7 @@ class WideEvaluator:
         d, error_model = check_wide_lattice(d, error_model)
         _, window, _ = check_wide_schedule(d, 1, window, None)
         self.d, self.error_model, self.window, self.chunk = d, error_model, window, check_chunk(chunk)
-        self._h = None
+        self._h = self._m = None
         self._open(device)
 
     def _open(self, device):
@@ -175,6 +185,9 @@ class WideEvaluator:
         self._h = h
 
     def close(self):
+        if getattr(self, "_m", None):
+            self.L.dq_match_destroy(self._m)
+            self._m = None
         if getattr(self, "_h", None):
             self.L.dq_wide_uf_destroy(self._h)
             self._h = None
@@ -188,6 +201,17 @@ class WideEvaluator:
     def _stream(self):
         import torch
         return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _referee(self):
+        """The evaluator's own dq_match handle of its d, created at the first refereed verdict and destroyed by close()."""
+        import torch
+        from . import _lib
+        if not self._m:
+            m = ctypes.c_void_p()
+            with torch.cuda.device(self.device):
+                _lib.check(self.L.dq_match_create(self.d, ctypes.byref(m)))
+            self._m = m
+        return self._m
 
     def decode_into(self, syndromes, m, T, commit, frame, weight=None, n_defects=None, rounds=None, final_round="faulty"):
         """The sliding-window decode (dq_wide_uf_decode) of m <= chunk streams of T rounds already on the device.  final_round="perfect":
@@ -208,9 +232,17 @@ class WideEvaluator:
                       p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, _lib.ptr(hidden), _lib.ptr(trivial),
                       _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), _lib.ptr(syndromes), self._stream()))
 
-    def verdict_into(self, hidden, frame, m, out):
+    def verdict_into(self, hidden, frame, m, out, referee=None, inexact=None):
+        """The verdict bytes of m <= chunk volumes (frame None: no correction).  referee=None: dq_wide_uf_verdict (alive := success, decoded 0);
+        referee="matching": dq_wide_uf_verdict_refereed, with inexact (uint8 [m] or None) receiving the referee's fallback flags."""
         from . import _lib
-        _lib.check(self.L.dq_wide_uf_verdict(self._h, _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), self._stream()))
+        if not check_referee(referee):
+            if inexact is not None:
+                raise ValueError("inexact flags come from the referee: give referee='matching'")
+            _lib.check(self.L.dq_wide_uf_verdict(self._h, _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), self._stream()))
+            return
+        _lib.check(self.L.dq_wide_uf_verdict_refereed(self._h, self._referee(), _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), _lib.ptr(inexact),
+                                                      self._stream()))
 
     def count_into(self, verdict, trivial, status, n_corr, m, first, block, counters):
         from . import _lib
@@ -246,20 +278,101 @@ def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHU
     return StreamResult(*(tuple(x.cpu().numpy() for x in out) if to_host else out), stream_windows(T, window, commit))
 
 
+def check_verdict_wide_args(hidden, frame, d, error_model="DP", referee=None, chunk=DEFAULT_CHUNK, evaluator=None):
+    """Validates a verdict_wide request without touching the library.  Returns (d, error_model, n_volumes, refereed, chunk)."""
+    refereed = check_referee(referee)
+    d, error_model = check_wide_lattice(d, error_model if evaluator is None else evaluator.error_model)
+    chunk = check_chunk(chunk)
+    n = check_codes(hidden, d, "hidden")
+    if frame is not None and check_codes(frame, d, "frame") != n:
+        raise ValueError(f"hidden has {n} volumes, frame {int(frame.shape[0])}")
+    if evaluator is not None and evaluator.d != d:
+        raise ValueError(f"the evaluator's d = {evaluator.d} is not the volumes' {d}")
+    return d, error_model, n, refereed, chunk
+
+
+def verdict_wide(hidden, frame, d, error_model="DP", referee=None, chunk=DEFAULT_CHUNK, evaluator=None, to_host=False):
+    """decoder.verdict for any odd d in 3 .. 15, without an environment: what the step decides on the residual hidden XOR frame of each volume (hidden,
+    frame: Pauli codes 0..3 [N, d, d], numpy or torch; frame=None: no correction).  referee=None: the bytes of dq_wide_uf_verdict (in code space, class,
+    success; alive := success).  referee="matching": dq_decode_verdict's byte with the matching referee -- alive and the decoded class as the wide
+    environment's step has them (X model: the referee is asked for component 0 only) -- and the result is (bytes, inexact uint8 [N]: 1 where a
+    flagged fallback of the referee fired).  evaluator: a WideEvaluator of this d (its error model and chunk are used and it stays open).  Device
+    tensors unless to_host."""
+    import torch
+    d, error_model, n, refereed, chunk = check_verdict_wide_args(hidden, frame, d, error_model, referee, chunk, evaluator)
+    ev = WideEvaluator(d, error_model, 1, chunk=min(chunk, n)) if evaluator is None else evaluator
+    dev = ev.device
+    try:
+        on = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.array(x, order="C"))).to(       # (a copy: read-only arrays are welcome)
+            device=dev, dtype=torch.uint8).reshape(n, d, d).contiguous()
+        hid, frm = on(hidden), None if frame is None else on(frame)
+        out = torch.empty(n, dtype=torch.uint8, device=dev)
+        flags = torch.empty(n, dtype=torch.uint8, device=dev) if refereed else None
+        with torch.cuda.device(dev):
+            for s in range(0, n, ev.chunk):
+                m = min(ev.chunk, n - s)
+                if refereed and frm is None:
+                    refereed_uncorrected_into(ev, hid[s:s + m], m, out[s:s + m], flags[s:s + m])
+                else:
+                    ev.verdict_into(hid[s:s + m], None if frm is None else frm[s:s + m], m, out[s:s + m], referee=referee,
+                                    inexact=flags[s:s + m] if refereed else None)
+            torch.cuda.current_stream(dev).synchronize()
+    finally:
+        if evaluator is None:
+            ev.close()
+    if to_host:
+        out, flags = out.cpu().numpy(), flags.cpu().numpy() if refereed else None
+    return (out, flags) if refereed else out
+
+
+UNCORRECTED_REFEREE_D, UNCORRECTED_REFEREE_SLICE = 13, 2048
+
+
+def refereed_uncorrected_into(ev, hidden, m, out, flags):
+    """The refereed verdict of m volumes with NO correction (the no_decoder row).  Every error is then still on the lattice: nearly every volume reaches
+    the referee, and at d >= 13 a few in a hundred hold a cluster of 15 .. 20 defects that walks 2^15 .. 2^20 subsets in one of the referee's eight
+    scratch-pool slots.  Measured at d = 15: 2048 such volumes take 0.24 s in one launch, while one launch of 2^16 did not end within minutes (DESIGN.md
+    section 22), and a launch cannot be interrupted.  So at d >= UNCORRECTED_REFEREE_D the volumes go in launches of at most UNCORRECTED_REFEREE_SLICE, the
+    size that was measured; the bytes and flags of a volume do not depend on the launch around it."""
+    step = UNCORRECTED_REFEREE_SLICE if ev.d >= UNCORRECTED_REFEREE_D else m
+    for s in range(0, m, step):
+        k = min(step, m - s)
+        ev.verdict_into(hidden[s:s + k], None, k, out[s:s + k], referee="matching", inexact=flags[s:s + k])
+
+
+def add_flags(extras, flags, m, first, blk):
+    """extras int64 [n_blocks] += the flags uint8 [m] of volumes first .. first + m - 1, per block of blk volumes (dq_decode_count's block rule)."""
+    import torch
+    idx = torch.div(torch.arange(first, first + m, dtype=torch.int64, device=extras.device), blk, rounding_mode="floor")
+    extras.index_add_(0, idx, flags[:m].to(torch.int64))
+
+
+def set_no_decoder_inexact(results, extras0):
+    for r, x in zip(results, extras0):
+        if r.no_decoder is not None:
+            r.no_decoder.inexact = int(x)
+
+
 def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0,
-                           chunk=DEFAULT_CHUNK, no_decoder=False, timings=None, evaluator=None, return_streams=False, final_round="faulty"):
+                           chunk=DEFAULT_CHUNK, no_decoder=False, timings=None, evaluator=None, return_streams=False, final_round="faulty", referee=None):
     """decoder.memory_experiment for any odd d in 3 .. 15 and a window of up to 32 rounds: n_runs streams, stream i the first `rounds` rounds of lattice
     env_id_base + i under sample_volumes' convention, sampled and decoded in ONE kernel per chunk (dq_wide_uf_run), then verdict -> counts on the device.
     lattice: (d, error_model), or an environment of either backend, of which only d, error_model, the rates and the seed are read (the defaults of p_phys /
     p_meas / seed; with a tuple p_phys and seed are required).  Returns what memory_experiment returns: an EvalResult ({rate: EvalResult} with
     rates=[...], n_runs streams per rate), every stream counted as status identity, corrections = the frame's non-zero cells; no_decoder:
-    EvalResult.no_decoder counts the verdict for frame = 0.  No referee is consulted: alive := success, so death_rate equals failure_rate by construction.
+    EvalResult.no_decoder counts the verdict for frame = 0.  referee=None: no referee is consulted, alive := success, so death_rate equals failure_rate
+    by construction.  referee="matching": every verdict of the call goes through dq_wide_uf_verdict_refereed -- alive is what the
+    wide environment's step would decide on the residual, every other counter is unchanged, and EvalResult.inexact (of the no_decoder row too) counts
+    the volumes on which a flagged fallback of the referee fired.  With no_decoder the refereed verdict of the uncorrected errors is the slow part at
+    d >= 13 (refereed_uncorrected_into: launches of at most 2048 volumes, 0.24 s each at d = 15, depth 5, p = 0.006, more at higher rates): keep
+    n_runs modest there.
     timings: a dict that receives the wall seconds of the phases run / verdict.  evaluator: a WideEvaluator of this lattice and window.  return_streams:
     also returns dict(syndromes uint8 [N, rounds, d+1, d+1], hidden, frame uint8 [N, d, d], trivial uint8 [N]) of device tensors.  final_round="perfect":
     decoder.memory_experiment's closed form."""
     import time
     import torch
     closed = closed_kw(final_round)
+    refereed = check_referee(referee)
     d, model, T, window, commit, n, ph, pm, seed, base, blk, keys, chunk = check_wide_experiment_args(
         lattice, n_runs, rounds, window, commit, rates, p_phys, p_meas, seed, env_id_base, chunk, evaluator)
     ev = WideEvaluator(d, model, window, chunk=min(chunk, n)) if evaluator is None else evaluator
@@ -277,6 +390,10 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
         n_blocks = -(-n // blk)
         counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
         counters0 = torch.zeros_like(counters) if no_decoder else None
+        flags = torch.empty(step, dtype=torch.uint8, device=dev) if refereed else None
+        ref_kw = dict(referee=referee, inexact=flags) if refereed else {}     # (no referee: the call of before, argument for argument)
+        extras = torch.zeros(n_blocks, dtype=torch.int64, device=dev)
+        extras0 = torch.zeros_like(extras)
 
         def phase(name, t0):
             if timings is None:
@@ -297,17 +414,26 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
                     a, b = float(a[0]), float(b[0])
                 ev.run_into(m, T, commit, base + s, seed, a, b, hid[sl], triv[sl], frame[sl], syndromes=None if syn is None else syn[s:s + m], **closed)
                 t = phase("run", t)
-                ev.verdict_into(hid[sl], frame[sl], m, verd[:m])
+                ev.verdict_into(hid[sl], frame[sl], m, verd[:m], **ref_kw)
                 ev.count_into(verd[:m], triv[sl], status[:m], (frame[sl] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), m, s, blk, counters)
+                if refereed:
+                    add_flags(extras, flags, m, s, blk)
                 if no_decoder:
-                    ev.verdict_into(hid[sl], None, m, verd[:m])
+                    if refereed:
+                        refereed_uncorrected_into(ev, hid[sl], m, verd[:m], flags)
+                    else:
+                        ev.verdict_into(hid[sl], None, m, verd[:m])
                     ev.count_into(verd[:m], triv[sl], None, None, m, s, blk, counters0)
+                    if refereed:
+                        add_flags(extras0, flags, m, s, blk)
                 t = phase("verdict", t)
             host, host0 = counters.cpu().numpy(), counters0.cpu().numpy() if no_decoder else None
+            extras, extras0 = extras.cpu().numpy(), extras0.cpu().numpy()
     finally:
         if evaluator is None:
             ev.close()
-    results = block_results(host, host0, np.zeros(n_blocks, dtype=np.int64), n_blocks, blk, ph, pm)
+    results = block_results(host, host0, extras, n_blocks, blk, ph, pm)
+    set_no_decoder_inexact(results, extras0)
     out = results[0] if keys is None else dict(zip(keys, results))
     return (out, dict(syndromes=syn, hidden=hid, frame=frame, trivial=triv)) if return_streams else out
 
@@ -666,10 +792,11 @@ def decode_lattice_of(lattice):
 
 
 def check_decode_benchmark_wide_args(lattice, n_volumes, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, max_actions=None, chunk=None,
-                                     baseline=None, final_round="faulty"):
+                                     baseline=None, final_round="faulty", referee=None):
     """Validates a decode_benchmark_wide request without touching the library.  Returns (d, error_model, use_Y, depth, max_actions, n, p_phys, p_meas,
     seed, base, block, keys, closed): memory_experiment_wide's conventions for the rates, the seed and the blocks (check_wide_experiment_args with
     rounds = window = commit = volume_depth)."""
+    check_referee(referee)
     d, model, use_Y, depth, lat = decode_lattice_of(lattice)
     _, _, _, max_actions = check_decode_wide_args(d, model, use_Y, depth, (depth, d + 1, d + 1), max_actions)
     if baseline is not None and baseline != "union_find":
@@ -681,13 +808,16 @@ def check_decode_benchmark_wide_args(lattice, n_volumes, rates=None, p_phys=None
 
 
 def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=None, no_decoder=False, final_round="faulty", return_volumes=False,
-                      timings=None):
+                      timings=None, referee=None):
     """The loop behind DQNAgent.decode_benchmark_wide for a validated request: per chunk ONE dq_wide_uf_run (T = window = commit = volume_depth, with
     syndromes) yields the agent's input, the hidden state and the union-find frame of the same volumes; then dq_decode_wide_run, dq_wide_uf_verdict
-    and dq_decode_count with the agent's status and correction count.  No referee is consulted: alive := success."""
+    and dq_decode_count with the agent's status and correction count.  referee=None: no referee is consulted, alive := success; referee="matching":
+    the verdicts of all three rows (the agent's, the union-find baseline's, no_decoder's) go through dq_wide_uf_verdict_refereed and each row's
+    EvalResult.inexact counts its flagged volumes."""
     import time
     import torch
     from .decoder import DecodeResult
+    refereed = check_referee(referee)
     d, depth, dev = dec.d, dec.volume_depth, dec.device
     step = min(dec.chunk, n)
     ev = WideEvaluator(d, dec.error_model, depth, chunk=step, device=dev)
@@ -707,6 +837,10 @@ def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=No
         counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
         counters_uf = torch.zeros_like(counters) if baseline else None
         counters0 = torch.zeros_like(counters) if no_decoder else None
+        flags = torch.empty(step, dtype=torch.uint8, device=dev) if refereed else None
+        ref_kw = dict(referee=referee, inexact=flags) if refereed else {}     # (no referee: the call of before, argument for argument)
+        extras = torch.zeros(n_blocks, dtype=torch.int64, device=dev)
+        extras_uf, extras0 = torch.zeros_like(extras), torch.zeros_like(extras)
         iters = []
 
         def phase(name, t0):
@@ -731,23 +865,33 @@ def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=No
                 t = phase("run", t)
                 iters.append(dec.decode_into(params, packed, syn[sl], m, corr[sl], ncorr[sl], frame[sl], status[sl]))
                 t = phase("decode", t)
-                ev.verdict_into(hid[sl], frame[sl], m, verd[sl])
+                ev.verdict_into(hid[sl], frame[sl], m, verd[sl], **ref_kw)
                 ev.count_into(verd[sl], triv[sl], status[sl], ncorr[sl], m, s, blk, counters)
+                if refereed:
+                    add_flags(extras, flags, m, s, blk)
                 if baseline:
-                    ev.verdict_into(hid[sl], uf_frame[sl], m, verd2[:m])
+                    ev.verdict_into(hid[sl], uf_frame[sl], m, verd2[:m], **ref_kw)
                     ev.count_into(verd2[:m], triv[sl], uf_status[:m], (uf_frame[sl] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), m, s, blk,
                                   counters_uf)
+                    if refereed:
+                        add_flags(extras_uf, flags, m, s, blk)
                 if no_decoder:
-                    ev.verdict_into(hid[sl], None, m, verd2[:m])
+                    if refereed:
+                        refereed_uncorrected_into(ev, hid[sl], m, verd2[:m], flags)
+                    else:
+                        ev.verdict_into(hid[sl], None, m, verd2[:m])
                     ev.count_into(verd2[:m], triv[sl], None, None, m, s, blk, counters0)
+                    if refereed:
+                        add_flags(extras0, flags, m, s, blk)
                 t = phase("verdict", t)
             host = counters.cpu().numpy()
             host_uf = counters_uf.cpu().numpy() if baseline else None
             host0 = counters0.cpu().numpy() if no_decoder else None
+            extras, extras_uf, extras0 = extras.cpu().numpy(), extras_uf.cpu().numpy(), extras0.cpu().numpy()
     finally:
         ev.close()
-    zeros = np.zeros(n_blocks, dtype=np.int64)
-    results = block_results(host, host0, zeros, n_blocks, blk, ph, pm)
+    results = block_results(host, host0, extras, n_blocks, blk, ph, pm)
+    set_no_decoder_inexact(results, extras0)
     if return_volumes:
         r = results[0]
         r.volumes, r.hidden, r.trivial, r.verdict = syn, hid, triv, verd
@@ -755,5 +899,6 @@ def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=No
     out = results[0] if keys is None else dict(zip(keys, results))
     if not baseline:
         return out
-    rows_uf = block_results(host_uf, host0, zeros, n_blocks, blk, ph, pm)
+    rows_uf = block_results(host_uf, host0, extras_uf, n_blocks, blk, ph, pm)
+    set_no_decoder_inexact(rows_uf, extras0)
     return out, (rows_uf[0] if keys is None else dict(zip(keys, rows_uf)))

@@ -890,6 +890,19 @@ dq_status dq_wide_uf_run(dq_wide_uf* h, int n, int T, int commit, uint32_t env_i
                          const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev,
                          int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
 dq_status dq_wide_uf_verdict(dq_wide_uf* h, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev, void* stream);
+/* The refereed verdict at these sizes (csrc/verdict_wide.hip).  dq_version() stays 8: the capability is the presence of this symbol.
+ * dq_wide_uf_verdict_refereed: dq_decode_verdict's byte, every field, with the matching referee `m` (dq_match_create of the handle's d) as the referee: residual =
+ * hidden XOR frame (frame_dev NULL: no correction), true = its perfect syndrome, correct = its homology class (dq_wide_uf_verdict's two fields, bit for
+ * bit), decoded = the referee's class for true -- component 0 always, component 1 unless the handle's error model is DQ_MODEL_X, as the wide environment's
+ * step asks it -- DQ_VERDICT_SUCCESS = true == 0 and correct == 0 (the step's reward 1), DQ_VERDICT_ALIVE = success or decoded == correct (the step's
+ * done == False).  A residual in the code space is not sent to the referee: decoded = 0, which is the referee's class for the empty syndrome.
+ * inexact_dev (nullable) uint8 [n]: 1 where one of the referee's flagged fallbacks fired (a cluster beyond 20 defects, defects beyond the first 32 of a
+ * component), as dq_match_decode reports it.  One wavefront per volume.  n in 1 .. max_streams, null handles or arrays, and a referee of another d are
+ * DQ_ERR_INVALID before any device work; the referee's scratch-pool locks are re-zeroed on `stream` in front of the launch, as dq_match_decode does.  `m` is
+ * used by one stream at a time, like the handle.  dq_decode_count's "alive" counter of these bytes is the number of episodes the environment would not
+ * have ended.  No reference counterpart beyond the step's rule (Environments.py:139-151). */
+dq_status dq_wide_uf_verdict_refereed(dq_wide_uf* h, const dq_match* m, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev,
+                                      uint8_t* inexact_dev, void* stream);
 /* The closed forms (a final round of perfect measurements): dq_stream_decode_uf_closed's and dq_stream_run_uf_closed's rule on this handle, with
  * dq_wide_uf_decode's and dq_wide_uf_run's arguments, validation and contract.  For d <= 7 and window <= 16 every field equals the narrow closed forms'. */
 dq_status dq_wide_uf_decode_closed(dq_wide_uf* h, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,

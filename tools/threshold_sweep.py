@@ -1,17 +1,21 @@
 """Logical failure of a memory experiment against the physical error rate for a family of distances: the threshold table.
 
-    python tools/threshold_sweep.py [--distances 3,5,...,15] [--rates 0.005,...] [--rounds 60,120] [--streams 4096] [--model DP] [--final-round faulty|perfect] [--out FILE]
+    python tools/threshold_sweep.py [--distances 3,5,...,15] [--rates 0.005,...] [--rounds 60,120] [--streams 4096] [--model DP] [--final-round faulty|perfect] [--referee matching] [--out FILE]
 
 Every cell (d, p) is memory_experiment_wide on --streams streams with p_meas = p, window min(2 d, 32), commit (window + 1) // 2, one seed and one range of
 lattice ids for every cell, at each of the one or two stream lengths of --rounds.  For d <= 7 the same streams also go through decoder.memory_experiment
-(the one-wavefront kernels) under the same window and commit, and the counters are asserted equal.  A cell records per length the counters, the failure
+(the one-wavefront kernels) under the same window and commit, and the counters are asserted equal (with --referee matching `alive` too: the narrow
+verdict asks the look-up referee, which the matching referee equals at these sizes).  A cell records per length the counters, the failure
 rate f with its Wilson 95 % interval, 1 - (1 - f)^(1 / T) and the seconds it took.  A memory experiment that ends on a faulty round has a floor that does
 not depend on T (a lone last-round defect beside the boundary is a data error or a misreading, at equal cost), and the floor grows with
 d; with two lengths T1 < T2 the cell therefore also records the failure per round BETWEEN them, 1 - ((1 - f2) / (1 - f1))^(1 / (T2 - T1)), from which a
 T-independent floor cancels, with the interval its two Wilson intervals span.  The threshold is read off that figure when it is there.  Writes
 profiles/threshold_sweep_<model>.json and prints, per pair of neighbouring distances, the rates between which their curves cross (or that the grid does not
 resolve it).  --final-round perfect closes every stream with a round of perfect measurements, which removes that floor: the raw
-failure and its per-round figure can then be read directly; the record goes to profiles/threshold_sweep_<model>_closed.json."""
+failure and its per-round figure can then be read directly; the record goes to profiles/threshold_sweep_<model>_closed.json.  --referee matching sends
+every verdict through the matching referee: each cell then also records death_rate -- the share of streams on which the environment
+would have ended the episode, the referee having completed the residual under perfect measurement -- with its Wilson interval and the volumes flagged
+inexact, the crossings are also read on death_rate, and the record goes to profiles/threshold_sweep_<model>_refereed.json."""
 import argparse
 import importlib
 import json
@@ -60,6 +64,7 @@ def main():
     ap.add_argument("--model", default="DP")
     ap.add_argument("--env-id-base", type=int, default=0)
     ap.add_argument("--final-round", choices=("faulty", "perfect"), default="faulty")
+    ap.add_argument("--referee", choices=("matching",), default=None)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     distances = [int(x) for x in a.distances.split(",")]
@@ -68,7 +73,7 @@ def main():
     assert 1 <= len(lengths) <= 2 and len(set(lengths)) == len(lengths), "--rounds takes one or two distinct stream lengths"
     D, DW = dq.decoder, dq.decoder_wide
     record = dict(device=torch.cuda.get_device_name(0), model=a.model, rounds=lengths, streams_per_cell=a.streams, seed=list(SEED),
-                  env_id_base=a.env_id_base, p_meas="= p", final_round=a.final_round, cells={}, narrow_checked=[])
+                  env_id_base=a.env_id_base, p_meas="= p", final_round=a.final_round, referee=a.referee, cells={}, narrow_checked=[])
     table = {}
     for d in distances:
         _, window, commit = DW.check_wide_schedule(d, lengths[0], None, None)
@@ -80,7 +85,7 @@ def main():
             for T in lengths:
                 t0 = time.perf_counter()
                 r = DW.memory_experiment_wide((d, a.model), a.streams, T, p_phys=p, seed=SEED, env_id_base=a.env_id_base, evaluator=ev,
-                                              final_round=a.final_round)
+                                              final_round=a.final_round, referee=a.referee)
                 torch.cuda.synchronize()
                 one = r.summary()
                 one.update(failure_per_round=per_round(r.failure_rate, T), failure_per_round_interval=[per_round(x, T) for x in r.failure_interval],
@@ -90,10 +95,15 @@ def main():
                     narrow = D.memory_experiment(env, a.streams, T, window=window, commit=commit, p_phys=p, seed=SEED, env_id_base=a.env_id_base,
                                                  final_round=a.final_round)
                     keys = ("volumes", "trivial", "in_codespace", "success", "identity", "repeat", "stopped", "corrections")
-                    assert all(narrow.counters[k] == one[k] for k in keys), (d, p, T, narrow.counters, one)       # (alive: the narrow verdict asks a referee)
+                    if a.referee:                                                 # the narrow verdict asks the look-up referee, which the matching referee equals at d <= 7
+                        keys += ("alive",)
+                    assert all(narrow.counters[k] == one[k] for k in keys), (d, p, T, narrow.counters, one)       # (unrefereed: alive is not comparable)
             last = cell["per_length"][str(lengths[-1])]
             cell.update(failure_rate=last["failure_rate"], failure_interval=last["failure_interval"])
             line = "  ".join(f"T = {T}: {cell['per_length'][str(T)]['failure_rate']:.5f}" for T in lengths)
+            if a.referee:
+                cell.update(death_rate=last["death_rate"], death_interval=last["death_interval"], inexact=last.get("inexact", 0))
+                line += "  death " + "  ".join(f"T = {T}: {cell['per_length'][str(T)]['death_rate']:.5f}" for T in lengths)
             if len(lengths) == 2:
                 (T1, T2), first = lengths, cell["per_length"][str(lengths[0])]
                 cell["failure_per_round_between"] = between(first["failure_rate"], last["failure_rate"], T1, T2)
@@ -108,13 +118,15 @@ def main():
             env.close()
             record["narrow_checked"].append(d)
     figures = [("failure_rate", "failure_interval")] + ([("failure_per_round_between", "failure_per_round_between_interval")] if len(lengths) == 2 else [])
+    if a.referee:
+        figures.append(("death_rate", "death_interval"))
     record["crossings"] = [c for key, interval in figures for c in crossings(table, distances, rates, key, interval)]
     for c in record["crossings"]:
         lo, hi = c["distances"]
         where = (f"between p = {c['crossing_between'][0]} and {c['crossing_between'][1]}" if c["crossing_between"] else
                  "not inside the grid" + (" (the larger distance fails less at every rate)" if all(c["larger_distance_fails_less"]) else ""))
         print(f"{c['figure']}, d = {lo} / {hi}: the curves cross {where}; intervals disjoint at {sum(c['intervals_disjoint'])} of {len(rates)} rates")
-    path = a.out or os.path.join(ROOT, "profiles", f"threshold_sweep_{a.model.lower()}{'_closed' if a.final_round == 'perfect' else ''}.json")
+    path = a.out or os.path.join(ROOT, "profiles", f"threshold_sweep_{a.model.lower()}{'_closed' if a.final_round == 'perfect' else ''}{'_refereed' if a.referee else ''}.json")
     with open(path, "w") as f:
         json.dump(record, f, indent=1)
         f.write("\n")
