@@ -38,6 +38,21 @@ def check_method(method, who="method"):
     return method
 
 
+def is_int(x):
+    """An integer of Python or numpy that is not a boolean."""
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def check_positive(x, name):
+    if not is_int(x) or x < 1:
+        raise ValueError(f"{name} must be a positive integer, not {x!r}")
+    return int(x)
+
+
+def check_chunk(chunk):
+    return check_positive(chunk, "chunk")
+
+
 def action_layers(error_model, use_Y):
     """n_action_layers of Environments.py:55-65 (num_actions = layers d^2 + 1)."""
     if error_model == "X":
@@ -160,38 +175,66 @@ def check_eval_args(lattice, env, n_volumes, p_phys=None, p_meas=None, seed=None
     floats or per-volume float64 arrays (default: the environment's, p_meas=None with a given p_phys: the same as p_phys), block = volumes per
     block of counters (default: all in one)."""
     check_eval_lattice(lattice, env)
+    return check_volume_args(n_volumes, p_phys, p_meas, seed, env_id_base, block, own_rates(env))
+
+
+def own_rates(env):
+    """The (p_phys, p_meas, seed) an environment offers as the defaults of a scoring request, None where it has none."""
     v = getattr(env, "_v", env)
-    if isinstance(n_volumes, (bool, np.bool_)) or not isinstance(n_volumes, (int, np.integer)) or n_volumes < 1:
-        raise ValueError(f"n_volumes must be a positive integer, not {n_volumes!r}")
-    n_volumes = int(n_volumes)
-    if n_volumes >= 1 << 31:
-        raise ValueError("n_volumes must be below 2^31")
+    return getattr(v, "p_phys", None), getattr(v, "p_meas", None), getattr(v, "seed", None)
+
+
+def check_volume_args(n, p_phys, p_meas, seed, env_id_base, block, own, count="n_volumes", total="n_volumes"):
+    """"Which volumes, at which rates" of every scoring entry point, validated without touching the library.  own: the defaults (p_phys, p_meas, seed) of
+    the environment, or None when the lattice came as a tuple and has none; count / total: what the messages call n and the number of volumes in all.
+    Returns (n, p_phys, p_meas, seed, env_id_base, block): rates as floats or per-volume float64 arrays, block = volumes per block of counters
+    (default: all in one)."""
+    n = check_positive(n, count)
+    if n >= 1 << 31:
+        raise ValueError(f"{total} must be below 2^31")
+    own = (None, None, None) if own is None else own
     if p_phys is None:
         if p_meas is not None:
             raise ValueError("p_meas without p_phys: give both, p_phys alone (p_meas = p_phys), or neither (the environment's rates)")
-        p_phys, p_meas = v.p_phys, v.p_meas
+        if own[0] is None or own[1] is None:
+            raise ValueError("p_phys is required when the lattice is given as (d, error_model)")
+        p_phys, p_meas = own[0], own[1]
     elif p_meas is None:
         p_meas = p_phys
-    p_phys, p_meas = check_rates(p_phys, n_volumes, "p_phys"), check_rates(p_meas, n_volumes, "p_meas")
+    p_phys, p_meas = check_rates(p_phys, n, "p_phys"), check_rates(p_meas, n, "p_meas")
     if isinstance(p_phys, float) != isinstance(p_meas, float):      # one array: the scalar becomes one too
-        full = lambda x: np.full(n_volumes, x, dtype=np.float64) if isinstance(x, float) else x
+        full = lambda x: np.full(n, x, dtype=np.float64) if isinstance(x, float) else x
         p_phys, p_meas = full(p_phys), full(p_meas)
     if seed is None:
-        seed = v.seed
+        if own[2] is None:
+            raise ValueError("seed is required when the lattice is given as (d, error_model)")
+        seed = own[2]
     try:
-        ok = len(seed) == 2 and all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) and 0 <= x < 1 << 32 for x in seed)
-        seed = (int(seed[0]), int(seed[1])) if ok else seed
+        ok = len(seed) == 2 and all(is_int(x) and 0 <= x < 1 << 32 for x in seed)
     except (TypeError, IndexError):
         ok = False
     if not ok:
         raise ValueError(f"seed must be a pair of 32-bit words, not {seed!r}")
-    if isinstance(env_id_base, (bool, np.bool_)) or not isinstance(env_id_base, (int, np.integer)) or not 0 <= env_id_base < 1 << 32:
+    if not is_int(env_id_base) or not 0 <= env_id_base < 1 << 32:
         raise ValueError(f"env_id_base must be an integer in 0 .. 2^32 - 1, not {env_id_base!r}")
-    if block is None:
-        block = n_volumes
-    if isinstance(block, (bool, np.bool_)) or not isinstance(block, (int, np.integer)) or block < 1:
-        raise ValueError(f"block must be a positive integer, not {block!r}")
-    return n_volumes, p_phys, p_meas, seed, int(env_id_base), int(block)
+    return n, p_phys, p_meas, (int(seed[0]), int(seed[1])), int(env_id_base), n if block is None else check_positive(block, "block")
+
+
+def rate_blocks(n, rates, p_meas, who, count="n_volumes"):
+    """rates=[...] of the scoring entry points: n volumes at EACH physical rate, in one evaluation of K n volumes in blocks of n.  p_meas: None (the same
+    rates), a scalar, or one per rate.  Returns (total, p_phys, p_meas, block, keys) with per-volume float64 arrays; the rates themselves are for
+    check_volume_args to judge."""
+    n = check_positive(n, count)
+    keys = [float(r) for r in rates]
+    K = len(keys)
+    if K < 1:
+        raise ValueError(f"{who}: no error rates")
+    if len(set(keys)) != K:
+        raise ValueError(f"{who}: the error rates must be distinct (they key the result)")
+    meas = keys if p_meas is None else ([float(p_meas)] * K if np.ndim(p_meas) == 0 else [float(r) for r in p_meas])
+    if len(meas) != K:
+        raise ValueError(f"{who}: {len(meas)} measurement rates for {K} error rates")
+    return n * K, np.repeat(np.asarray(keys, dtype=np.float64), n), np.repeat(np.asarray(meas, dtype=np.float64), n), n, keys
 
 
 def check_codes(x, d, name, allow_none=False):
@@ -299,7 +342,16 @@ def _narrow_env(env):
     return v
 
 
-class Evaluator:
+class Counting:
+    """dq_decode_count on the library and the stream of a handle: what Evaluator and decoder_wide.WideEvaluator share."""
+
+    def count_into(self, verdict, trivial, status, n_corr, m, first, block, counters):
+        from . import _lib
+        _lib.check(self.L.dq_decode_count(_lib.ptr(verdict), _lib.ptr(trivial), _lib.ptr(status), _lib.ptr(n_corr), m, first, block,
+                                          counters.shape[0], _lib.ptr(counters), self._stream()))
+
+
+class Evaluator(Counting):
     """Owns a dq_decode_eval handle for chunks of at most `chunk` volumes of one lattice: the sampler, the verdict and the counters."""
 
     def __init__(self, d, error_model, use_Y, volume_depth, chunk=DEFAULT_CHUNK, device=None):
@@ -379,32 +431,27 @@ class Evaluator:
         from . import _lib
         _lib.check(self.L.dq_decode_verdict(self._h, venv._h, _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), self._stream()))
 
-    def count_into(self, verdict, trivial, status, n_corr, m, first, block, counters):
-        from . import _lib
-        _lib.check(self.L.dq_decode_count(_lib.ptr(verdict), _lib.ptr(trivial), _lib.ptr(status), _lib.ptr(n_corr), m, first, block,
-                                          counters.shape[0], _lib.ptr(counters), self._stream()))
 
-
-def score_chunks(ev, venv, dev, n, chunk, ph, pm, seed, base, blk, decode, decode_phase, keep=False, no_decoder=False, timings=None):
-    """The loop behind BatchDecoder.evaluate and score_matching: per chunk of at most `chunk` volumes sample -> decode -> verdict -> counts on the
-    device, so that two decoders scored with the same (n, rates, seed, base) see the same volumes whatever their chunk sizes.  decode(vol, m, o)
-    decodes the m volumes `vol` (rows o .. o + m of the caller's per-volume buffers) and returns (frame, status, n_corr, extra) device tensors,
-    `extra` an optional uint8 flag per volume summed per block; its wall time is reported as timings[decode_phase].  keep: the per-volume
-    tensors of all n volumes stay (else one chunk is resident).  Returns (counters, counters of frame = 0 or None, extra sums, tensors) with the
-    counters int64 [n_blocks, 9] on the host and tensors = dict(volumes, hidden, trivial, verdict)."""
+def score_chunks(ev, dev, n, ph, pm, blk, draw, rows, uncorrected=None, keep=False, decode=None, phases=("sample", "decode"), setup=None, timings=None):
+    """The one chunk loop of every scoring entry point -- BatchDecoder.evaluate and score_matching (through score_sampled), memory_experiment, and
+    decoder_wide's memory_experiment_wide and score_decode_wide: cuts n volumes into chunks of at most ev.chunk, and per chunk of m volumes, the first
+    being volume s, runs draw -> decode -> one verdict and one dq_decode_count per row, on the device; the host reads the counters once, at the end.
+    The caller owns the per-volume buffers and addresses them with the slice sl the loop hands out: rows s .. s + m with keep (all n volumes stay),
+    else rows 0 .. m (one chunk is resident).
+      draw(m, s, sl, p_phys, p_meas) fills the chunk's buffers; the rates are the chunk's share, scalars where it holds one rate pair.
+      decode(m, sl), optional, decodes what was drawn.
+      rows, and uncorrected where the frame = 0 counts are asked for: each row(m, sl) writes its verdict bytes and returns what count_into takes and
+      the loop sums per block of blk volumes -- (verdict, trivial, status or None, n_corr or None, uint8 flags or None: one per volume in their first m cells).
+    timings, where given, receives the wall seconds of the phases -- setup (where named: the wait for the previous chunk), phases[0] for draw,
+    phases[1] for decode, "verdict" for the rows -- each closed by a synchronisation; without it nothing synchronises before the final read.
+    Returns, per row of `rows`, one EvalResult per block, inexact = the row's flagged volumes, no_decoder = the uncorrected row's counts."""
     import time
     import torch
-    d, depth, each = ev.d, ev.volume_depth, not isinstance(ph, float)
-    rows = n if keep else min(chunk, n)
-    vol = torch.empty((rows, depth, d + 1, d + 1), dtype=torch.uint8, device=dev)
-    hid = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
-    triv = torch.empty(rows, dtype=torch.uint8, device=dev)
-    verd = torch.empty(rows, dtype=torch.uint8, device=dev)
-    verd0 = torch.empty(min(chunk, n), dtype=torch.uint8, device=dev) if no_decoder else None
+    each = not isinstance(ph, float)
+    every = list(rows) + ([uncorrected] if uncorrected is not None else [])
     n_blocks = -(-n // blk)
-    counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
-    counters0 = torch.zeros_like(counters) if no_decoder else None
-    extras = torch.zeros(n_blocks, dtype=torch.int64, device=dev)
+    counters = torch.zeros((len(every), n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
+    flagged = torch.zeros((len(every), n_blocks), dtype=torch.int64, device=dev)
 
     def phase(name, t0):
         if timings is None:
@@ -414,41 +461,91 @@ def score_chunks(ev, venv, dev, n, chunk, ph, pm, seed, base, blk, decode, decod
         timings[name] = timings.get(name, 0.0) + (t1 - t0)
         return t1
 
-    for s in range(0, n, chunk):
-        m = min(chunk, n - s)
+    for s in range(0, n, ev.chunk):
+        m = min(ev.chunk, n - s)
         o = s if keep else 0
         sl = slice(o, o + m)
-        t = phase("setup", time.perf_counter()) if timings is not None else 0.0
+        t = time.perf_counter()
+        if setup is not None:
+            t = phase(setup, t)
         a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
         if each and (a == a[0]).all() and (b == b[0]).all():   # one rate pair in this chunk: the scalar form (the same thresholds, no table upload)
             a, b = float(a[0]), float(b[0])
-        ev.sample_into(venv, m, base + s, seed, a, b, vol[sl], hid[sl], triv[sl])
-        t = phase("sample", t)
-        frame, status, ncorr, extra = decode(vol[sl], m, o)
-        t = phase(decode_phase, t)
-        ev.verdict_into(venv, hid[sl], frame, m, verd[sl])
-        ev.count_into(verd[sl], triv[sl], status, ncorr, m, s, blk, counters)
-        if extra is not None:
-            extras.index_add_(0, torch.div(torch.arange(s, s + m, device=dev), blk, rounding_mode="floor"), extra.to(torch.int64))
-        if no_decoder:
-            ev.verdict_into(venv, hid[sl], None, m, verd0[:m])
-            ev.count_into(verd0[:m], triv[sl], None, None, m, s, blk, counters0)
+        draw(m, s, sl, a, b)
+        t = phase(phases[0], t)
+        if decode is not None:
+            decode(m, sl)
+            t = phase(phases[1], t)
+        for k, row in enumerate(every):
+            verdict, trivial, status, n_corr, flags = row(m, sl)
+            ev.count_into(verdict, trivial, status, n_corr, m, s, blk, counters[k])
+            if flags is not None:                               # (dq_decode_count's block rule)
+                flagged[k].index_add_(0, torch.div(torch.arange(s, s + m, device=dev), blk, rounding_mode="floor"), flags[:m].to(torch.int64))
         t = phase("verdict", t)
-    return (counters.cpu().numpy(), counters0.cpu().numpy() if no_decoder else None, extras.cpu().numpy(),
-            dict(volumes=vol, hidden=hid, trivial=triv, verdict=verd))
+    host, sums = counters.cpu().numpy(), flagged.cpu().numpy()
+    host0, sums0 = (host[-1], sums[-1]) if uncorrected is not None else (None, None)
+    return [block_results(host[k], sums[k], host0, sums0, blk, ph, pm) for k in range(len(rows))]
 
 
-def block_results(host, host0, extras, n_blocks, blk, ph, pm):
-    """One EvalResult per block of counters (score_chunks' output)."""
+def block_results(host, flagged, host0, flagged0, blk, ph, pm):
+    """One EvalResult per block of a row's counters and flag sums (score_chunks' host read); host0 / flagged0: those of the uncorrected row, or None."""
     each = not isinstance(ph, float)
     results = []
-    for k in range(n_blocks):
+    for k in range(len(host)):
         lo = k * blk
-        r = EvalResult(host[k], ph[lo] if each else ph, pm[lo] if each else pm, inexact=extras[k])
+        r = EvalResult(host[k], ph[lo] if each else ph, pm[lo] if each else pm, inexact=flagged[k])
         if host0 is not None:
-            r.no_decoder = EvalResult(host0[k], r.p_phys, r.p_meas)
+            r.no_decoder = EvalResult(host0[k], r.p_phys, r.p_meas, inexact=flagged0[k])
         results.append(r)
     return results
+
+
+def keyed(results, keys):
+    """A scoring call's answer from its EvalResults per block: the one result, or {rate: result} for rates=[...]."""
+    return results[0] if keys is None else dict(zip(keys, results))
+
+
+def corrected_cells(frame):
+    """The non-zero cells of each frame [m, d, d] as int32 [m]: the corrections a baseline decoder's volume is counted with."""
+    import torch
+    return (frame != 0).reshape(frame.shape[0], -1).sum(dim=1, dtype=torch.int32)
+
+
+def score_sampled(ev, venv, dev, n, ph, pm, seed, base, blk, decode, decode_phase, keep=False, no_decoder=False, timings=None):
+    """What BatchDecoder.evaluate and score_matching hand to score_chunks: sample -> decode -> verdict -> counts, so that two decoders scored with the
+    same (n, rates, seed, base) see the same volumes whatever their chunk sizes.  decode(vol, m, o) decodes the m volumes `vol` (rows o .. o + m of the
+    caller's per-volume buffers) and returns (frame, status, n_corr, extra) device tensors, `extra` an optional uint8 flag per volume summed per
+    block; its wall time is reported as timings[decode_phase].  keep: the per-volume tensors of all n volumes stay (else one chunk is resident).
+    Returns (one EvalResult per block, tensors = dict(volumes, hidden, trivial, verdict))."""
+    import torch
+    d, depth = ev.d, ev.volume_depth
+    rows = n if keep else min(ev.chunk, n)
+    vol = torch.empty((rows, depth, d + 1, d + 1), dtype=torch.uint8, device=dev)
+    hid = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+    triv = torch.empty(rows, dtype=torch.uint8, device=dev)
+    verd = torch.empty(rows, dtype=torch.uint8, device=dev)
+    verd0 = torch.empty(min(ev.chunk, n), dtype=torch.uint8, device=dev) if no_decoder else None
+    decoded = None
+
+    def sample(m, s, sl, a, b):
+        ev.sample_into(venv, m, base + s, seed, a, b, vol[sl], hid[sl], triv[sl])
+
+    def decode_chunk(m, sl):
+        nonlocal decoded
+        decoded = decode(vol[sl], m, sl.start)
+
+    def corrected(m, sl):
+        frame, status, n_corr, extra = decoded
+        ev.verdict_into(venv, hid[sl], frame, m, verd[sl])
+        return verd[sl], triv[sl], status, n_corr, extra
+
+    def uncorrected(m, sl):
+        ev.verdict_into(venv, hid[sl], None, m, verd0[:m])
+        return verd0[:m], triv[sl], None, None, None
+
+    results, = score_chunks(ev, dev, n, ph, pm, blk, sample, [corrected], uncorrected if no_decoder else None, keep=keep, decode=decode_chunk,
+                            phases=("sample", decode_phase), setup="setup", timings=timings)
+    return results, dict(volumes=vol, hidden=hid, trivial=triv, verdict=verd)
 
 
 def sample_volumes(env, n_volumes, p_phys=None, p_meas=None, seed=None, env_id_base=0, chunk=DEFAULT_CHUNK, to_host=False):
@@ -526,8 +623,7 @@ class MatchResult:
 def check_match_args(env, volumes, chunk=DEFAULT_CHUNK):
     """Validates a matching_decode request without touching the library.  Returns (d, error_model, use_Y, volume_depth, n_volumes)."""
     d, model, use_Y, depth = check_eval_lattice(None, env)
-    if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
-        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
+    check_chunk(chunk)
     if not hasattr(volumes, "shape") or not hasattr(volumes, "dtype"):
         raise ValueError("volumes must be a numpy array or a torch tensor")
     if str(volumes.dtype).replace("torch.", "") != "uint8":
@@ -684,8 +780,7 @@ def check_match_policy_args(env, evaluator=None, chunk=DEFAULT_CHUNK):
     if not 1 <= depth <= 16:
         raise NotImplementedError(f"the matching policy covers volume_depth 1..16, not {depth}")
     check_decode_args(d, model, use_Y, depth, (depth, d + 1, d + 1))
-    if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
-        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
+    check_chunk(chunk)
     if evaluator is not None:
         theirs = (int(evaluator.d), str(evaluator.error_model), int(evaluator.volume_depth))
         if theirs != (d, model, depth) or (model != "X" and bool(evaluator.use_Y) != use_Y):
@@ -712,9 +807,7 @@ class MatchingAgent:
             if policy == "identity":
                 raise ValueError("policy='identity' plays no decoder: it takes no method")
         self.method = "matching" if method is None else method
-        if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
-            raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
-        self.evaluator, self.chunk, self.policy = evaluator, int(chunk), policy
+        self.evaluator, self.chunk, self.policy = evaluator, check_chunk(chunk), policy
         self.last_inexact_steps, self.last_inexact_by_rate, self.last_vector_steps = 0, {}, 0
 
     def evaluator_for(self, env):
@@ -737,7 +830,7 @@ class MatchingAgent:
         from .agent import DQNAgent, History
         self._check_env(env)
         v = getattr(env, "_v", env)
-        if isinstance(nb_episodes, (bool, np.bool_)) or not isinstance(nb_episodes, (int, np.integer)) or nb_episodes < 0:
+        if not is_int(nb_episodes) or nb_episodes < 0:
             raise ValueError(f"nb_episodes must be a non-negative integer, not {nb_episodes!r}")
         quota = episodes.share_quota(int(v.n_envs), int(nb_episodes))
         episodes.check_step_cap(nb_max_episode_steps, quota)
@@ -815,20 +908,19 @@ class MatchingAgent:
 def expand_rates(lattice, env, n_volumes, rates, p_meas, seed, env_id_base, who):
     """rates=[...] of decode_benchmark / score_matching: n_volumes at EACH physical rate in one evaluation of K n_volumes volumes in blocks of
     n_volumes.  Validates without touching the library; returns (total, p_phys, p_meas, block, keys)."""
-    keys = [float(r) for r in rates]
-    K = len(keys)
-    if K < 1:
-        raise ValueError(f"{who}: no error rates")
-    if len(set(keys)) != K:
-        raise ValueError(f"{who}: the error rates must be distinct (they key the result)")
-    meas = keys if p_meas is None else ([float(p_meas)] * K if np.ndim(p_meas) == 0 else [float(r) for r in p_meas])
-    if len(meas) != K:
-        raise ValueError(f"{who}: {len(meas)} measurement rates for {K} error rates")
-    check_eval_args(lattice, env, n_volumes, keys[0], meas[0], seed, env_id_base)
-    total, blk = int(n_volumes) * K, int(n_volumes)
-    ph, pm = np.repeat(np.asarray(keys, dtype=np.float64), blk), np.repeat(np.asarray(meas, dtype=np.float64), blk)
+    total, ph, pm, blk, keys = rate_blocks(n_volumes, rates, p_meas, who)
     check_eval_args(lattice, env, total, ph, pm, seed, env_id_base, blk)
     return total, ph, pm, blk, keys
+
+
+def check_rated_args(lattice, env, n, rates, p_phys, p_meas, seed, env_id_base, who):
+    """The volumes of score_matching / memory_experiment, with rates=[...] or without.  Returns check_eval_args' tuple and keys (the rates, or None)."""
+    block = keys = None
+    if rates is not None:
+        if p_phys is not None:
+            raise ValueError(f"{who}: rates=[...] are the physical rates; p_phys goes without them")
+        n, p_phys, p_meas, block, keys = rate_blocks(n, rates, p_meas, who)
+    return check_eval_args(lattice, env, n, p_phys, p_meas, seed, env_id_base, block) + (keys,)
 
 
 def score_matching(env, n_volumes, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, chunk=DEFAULT_CHUNK, no_decoder=False, timings=None,
@@ -844,16 +936,8 @@ def score_matching(env, n_volumes, rates=None, p_phys=None, p_meas=None, seed=No
     import torch
     check_method(method)
     lat = check_eval_lattice(None, env)
-    if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
-        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
-    if rates is None:
-        keys = None
-        n, ph, pm, seed, base, blk = check_eval_args(lat, env, n_volumes, p_phys, p_meas, seed, env_id_base)
-    else:
-        if p_phys is not None:
-            raise ValueError("score_matching: rates=[...] are the physical rates; p_phys goes without them")
-        total, ph, pm, block, keys = expand_rates(lat, env, n_volumes, rates, p_meas, seed, env_id_base, "score_matching")
-        n, ph, pm, seed, base, blk = check_eval_args(lat, env, total, ph, pm, seed, env_id_base, block)
+    check_chunk(chunk)
+    n, ph, pm, seed, base, blk, keys = check_rated_args(lat, env, n_volumes, rates, p_phys, p_meas, seed, env_id_base, "score_matching")
     if evaluator is not None and (evaluator.d, evaluator.error_model, evaluator.use_Y, evaluator.volume_depth) != lat:
         raise ValueError(f"the evaluator's lattice is not the environment's {lat}")
     venv = _narrow_env(env)
@@ -871,16 +955,14 @@ def score_matching(env, n_volumes, rates=None, p_phys=None, p_meas=None, seed=No
                 ev.uf_into(vol, m, frame[:m])
             else:
                 ev.match_into(vol, m, frame[:m], None, None, inexact[:m])
-            return frame[:m], status[:m], (frame[:m] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), inexact[:m]
+            return frame[:m], status[:m], corrected_cells(frame[:m]), inexact[:m]
 
         with torch.cuda.device(dev):
-            host, host0, extras, _ = score_chunks(ev, venv, dev, n, ev.chunk, ph, pm, seed, base, blk, decode, "match", no_decoder=no_decoder,
-                                                  timings=timings)
+            results, _ = score_sampled(ev, venv, dev, n, ph, pm, seed, base, blk, decode, "match", no_decoder=no_decoder, timings=timings)
     finally:
         if evaluator is None:
             ev.close()
-    results = block_results(host, host0, extras, -(-n // blk), blk, ph, pm)
-    return results[0] if keys is None else dict(zip(keys, results))
+    return keyed(results, keys)
 
 
 # ---- sliding-window union-find decoding of syndrome streams (include/deepq_hip.h dq_stream_decode_uf / dq_stream_run_uf) --------
@@ -930,7 +1012,6 @@ def closed_kw(final_round):
 
 def check_stream_schedule(d, rounds, window, commit):
     """(T, window, commit) with the defaults window = min(2 d, 16), commit = (window + 1) // 2; ValueError outside 1 <= commit <= window <= 16, 1 <= T <= 2^20."""
-    is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
     if window is None:
         window = min(2 * d, STREAM_MAX_WINDOW)
     if not is_int(window) or not 1 <= window <= STREAM_MAX_WINDOW:
@@ -956,8 +1037,7 @@ def check_stream_args(env, syndromes, window=None, commit=None, chunk=DEFAULT_CH
     """Validates a stream_decode request without touching the library.  Returns (d, error_model, use_Y, n_streams, single, T, window, commit)."""
     check_stream_method(method)
     d, model, use_Y, _ = check_eval_lattice(None, env)
-    if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
-        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
+    check_chunk(chunk)
     if not hasattr(syndromes, "shape") or not hasattr(syndromes, "dtype"):
         raise ValueError("syndromes must be a numpy array or a torch tensor")
     if str(syndromes.dtype).replace("torch.", "") != "uint8":
@@ -1004,6 +1084,39 @@ def stream_decode(syndromes, env, window=None, commit=None, chunk=DEFAULT_CHUNK,
     return StreamResult(*(tuple(x.cpu().numpy() for x in out) if to_host else out), stream_windows(T, window, commit))
 
 
+def score_streams(ev, dev, n, T, ph, pm, blk, run, verdict, uncorrected=None, flags=None, keep=False, setup=None, timings=None):
+    """What memory_experiment and decoder_wide.memory_experiment_wide hand to score_chunks: sample-and-decode in one launch -> verdict -> counts, every
+    stream counted as status identity with corrections = the frame's non-zero cells.  run(m, s, p_phys, p_meas, hidden, trivial, frame, syndromes)
+    draws and decodes streams s .. s + m of T rounds (syndromes: None unless kept); verdict(hidden, frame, m, out) writes the bytes of the corrected
+    residuals and uncorrected(hidden, m, out), where given, those of frame = 0; flags: the uint8 buffer of a chunk in which both leave a flag per
+    stream, or None.  keep: the streams of all n stay (else one chunk is resident).  Returns (one EvalResult per block, dict(syndromes, hidden,
+    frame, trivial))."""
+    import torch
+    d, step = ev.d, min(ev.chunk, n)
+    rows = n if keep else step
+    hid = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+    frame = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
+    triv = torch.empty(rows, dtype=torch.uint8, device=dev)
+    syn = torch.empty((n, T, d + 1, d + 1), dtype=torch.uint8, device=dev) if keep else None
+    verd = torch.empty(step, dtype=torch.uint8, device=dev)
+    status = torch.full((step,), STATUS_IDENTITY, dtype=torch.uint8, device=dev)
+
+    def draw(m, s, sl, a, b):
+        run(m, s, a, b, hid[sl], triv[sl], frame[sl], None if syn is None else syn[sl])
+
+    def corrected(m, sl):
+        verdict(hid[sl], frame[sl], m, verd[:m])
+        return verd[:m], triv[sl], status[:m], corrected_cells(frame[sl]), flags
+
+    def bare(m, sl):
+        uncorrected(hid[sl], m, verd[:m])
+        return verd[:m], triv[sl], None, None, flags
+
+    results, = score_chunks(ev, dev, n, ph, pm, blk, draw, [corrected], None if uncorrected is None else bare, keep=keep, phases=("run",), setup=setup,
+                            timings=timings)
+    return results, dict(syndromes=syn, hidden=hid, frame=frame, trivial=triv)
+
+
 def memory_experiment(env, n_runs, rounds, window=None, commit=None, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, chunk=DEFAULT_CHUNK,
                       no_decoder=False, timings=None, evaluator=None, return_streams=False, final_round="faulty"):
     """The logical failure of a memory experiment of `rounds` rounds, decoded by the sliding-window union-find decoder: n_runs streams, stream i the first
@@ -1016,73 +1129,31 @@ def memory_experiment(env, n_runs, rounds, window=None, commit=None, rates=None,
     device tensors; otherwise only the counters leave the device.  final_round="perfect": the last round is measured without error (its data errors
     land, its measurement flips are not applied; the same Philox words are drawn) and decoded as stream_decode decodes it; hidden and rounds
     0 .. rounds - 2 are those of the "faulty" run of the same seed and ids, and every residual is in the code space."""
-    import time
     import torch
     closed = closed_kw(final_round)
     lat = check_eval_lattice(None, env)
     d, model, use_Y, _ = lat
     T, window, commit = check_stream_schedule(d, rounds, window, commit)
-    if isinstance(chunk, (bool, np.bool_)) or not isinstance(chunk, (int, np.integer)) or chunk < 1:
-        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
-    if rates is None:
-        keys = None
-        n, ph, pm, seed, base, blk = check_eval_args(lat, env, n_runs, p_phys, p_meas, seed, env_id_base)
-    else:
-        if p_phys is not None:
-            raise ValueError("memory_experiment: rates=[...] are the physical rates; p_phys goes without them")
-        total, ph, pm, block, keys = expand_rates(lat, env, n_runs, rates, p_meas, seed, env_id_base, "memory_experiment")
-        n, ph, pm, seed, base, blk = check_eval_args(lat, env, total, ph, pm, seed, env_id_base, block)
+    check_chunk(chunk)
+    n, ph, pm, seed, base, blk, keys = check_rated_args(lat, env, n_runs, rates, p_phys, p_meas, seed, env_id_base, "memory_experiment")
     check_stream_evaluator(evaluator, d, model, use_Y, window)
     venv = _narrow_env(env)
     dev = venv.device
     ev = Evaluator(d, model, use_Y, window, chunk=min(int(chunk), n), device=dev) if evaluator is None else evaluator
-    each = not isinstance(ph, float)
     try:
-        step = min(ev.chunk, n)
-        rows = n if return_streams else step
-        hid = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
-        frame = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
-        triv = torch.empty(rows, dtype=torch.uint8, device=dev)
-        syn = torch.empty((n, T, d + 1, d + 1), dtype=torch.uint8, device=dev) if return_streams else None
-        verd = torch.empty(step, dtype=torch.uint8, device=dev)
-        status = torch.full((step,), STATUS_IDENTITY, dtype=torch.uint8, device=dev)
-        n_blocks = -(-n // blk)
-        counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
-        counters0 = torch.zeros_like(counters) if no_decoder else None
+        def run(m, s, a, b, hid, triv, frame, syn):
+            ev.stream_run_into(venv, m, T, commit, base + s, seed, a, b, hid, triv, frame, syndromes=syn, **closed)
 
-        def phase(name, t0):
-            if timings is None:
-                return t0
-            torch.cuda.current_stream(dev).synchronize()
-            t1 = time.perf_counter()
-            timings[name] = timings.get(name, 0.0) + (t1 - t0)
-            return t1
+        def verdict(hid, frame, m, out):
+            ev.verdict_into(venv, hid, frame, m, out)
 
         with torch.cuda.device(dev):
-            for s in range(0, n, step):
-                m = min(step, n - s)
-                o = s if return_streams else 0
-                sl = slice(o, o + m)
-                t = phase("setup", time.perf_counter()) if timings is not None else 0.0
-                a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
-                if each and (a == a[0]).all() and (b == b[0]).all():   # one rate pair in this chunk: the scalar form (the same thresholds, no table upload)
-                    a, b = float(a[0]), float(b[0])
-                ev.stream_run_into(venv, m, T, commit, base + s, seed, a, b, hid[sl], triv[sl], frame[sl], syndromes=None if syn is None else syn[s:s + m],
-                                   **closed)
-                t = phase("run", t)
-                ev.verdict_into(venv, hid[sl], frame[sl], m, verd[:m])
-                ev.count_into(verd[:m], triv[sl], status[:m], (frame[sl] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), m, s, blk, counters)
-                if no_decoder:
-                    ev.verdict_into(venv, hid[sl], None, m, verd[:m])
-                    ev.count_into(verd[:m], triv[sl], None, None, m, s, blk, counters0)
-                t = phase("verdict", t)
-            host, host0 = counters.cpu().numpy(), counters0.cpu().numpy() if no_decoder else None
+            results, streams = score_streams(ev, dev, n, T, ph, pm, blk, run, verdict, (lambda hid, m, out: verdict(hid, None, m, out)) if no_decoder else None,
+                                             keep=return_streams, setup="setup", timings=timings)
     finally:
         if evaluator is None:
             ev.close()
-    results = block_results(host, host0, np.zeros(n_blocks, dtype=np.int64), n_blocks, blk, ph, pm)
-    out = results[0] if keys is None else dict(zip(keys, results))
-    return (out, dict(syndromes=syn, hidden=hid, frame=frame, trivial=triv)) if return_streams else out
+    return (keyed(results, keys), streams) if return_streams else keyed(results, keys)
 
 
 class DecodeResult:
@@ -1238,9 +1309,8 @@ class BatchDecoder:
                 iters.append(self._decode_into(params, packed, vol, m, corr[sl], ncorr[sl], frame[sl], status[sl]))
                 return frame[sl], status[sl], ncorr[sl], None
 
-            host, host0, extras, kept = score_chunks(self._eval, venv, dev, n, self.chunk, ph, pm, seed, base, blk, decode, "decode",
-                                                     keep=return_volumes, no_decoder=no_decoder, timings=timings)
-        results = block_results(host, host0, extras, -(-n // blk), blk, ph, pm)
+            results, kept = score_sampled(self._eval, venv, dev, n, ph, pm, seed, base, blk, decode, "decode", keep=return_volumes, no_decoder=no_decoder,
+                                          timings=timings)
         if return_volumes:
             r = results[0]
             r.volumes, r.hidden, r.trivial, r.verdict = kept["volumes"], kept["hidden"], kept["trivial"], kept["verdict"]

@@ -15,20 +15,17 @@ import ctypes
 
 import numpy as np
 
-from .decoder import (COUNTER_NAMES, DEFAULT_CHUNK, MODELS, STATUS_IDENTITY, STREAM_MAX_ROUNDS, MatchingAgent, StreamResult, action_layers, block_results,
-                      check_binary, check_codes, check_final_round, check_rates, closed_kw, lattice_of, rate_threshold, stream_windows)
+from .decoder import (DEFAULT_CHUNK, MODELS, STATUS_IDENTITY, STREAM_MAX_ROUNDS, Counting, MatchingAgent, StreamResult, action_layers, check_binary,
+                      check_chunk, check_codes, check_final_round, check_volume_args, closed_kw, corrected_cells, is_int, keyed, lattice_of, own_rates,
+                      rate_blocks, rate_threshold, score_chunks, score_streams, stream_windows)
 
 WIDE_MAX_D = 15
 WIDE_MAX_WINDOW = 32
 
 
-def _is_int(x):
-    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
-
-
 def check_wide_lattice(d, error_model):
     """Odd d in 3 .. 15 and a known error model, else ValueError.  Returns (d, error_model)."""
-    if not _is_int(d) or d < 3 or d > WIDE_MAX_D or d % 2 == 0:
+    if not is_int(d) or d < 3 or d > WIDE_MAX_D or d % 2 == 0:
         raise ValueError(f"d = {d!r}: the wide union-find decoder covers odd d in 3..{WIDE_MAX_D}")
     if error_model not in MODELS:
         raise ValueError(f"error model {error_model!r} is not one of X, DP, IIDXZ")
@@ -40,13 +37,13 @@ def check_wide_schedule(d, rounds, window, commit):
     1 <= T <= 2^20."""
     if window is None:
         window = min(2 * d, WIDE_MAX_WINDOW)
-    if not _is_int(window) or not 1 <= window <= WIDE_MAX_WINDOW:
+    if not is_int(window) or not 1 <= window <= WIDE_MAX_WINDOW:
         raise ValueError(f"window must be an integer in 1..{WIDE_MAX_WINDOW}, not {window!r}")
     if commit is None:
         commit = (int(window) + 1) // 2
-    if not _is_int(commit) or not 1 <= commit <= window:
+    if not is_int(commit) or not 1 <= commit <= window:
         raise ValueError(f"commit must be an integer in 1..window = {window}, not {commit!r}")
-    if not _is_int(rounds) or not 1 <= rounds <= STREAM_MAX_ROUNDS:
+    if not is_int(rounds) or not 1 <= rounds <= STREAM_MAX_ROUNDS:
         raise ValueError(f"a stream has 1..{STREAM_MAX_ROUNDS} rounds, not {rounds!r}")
     return int(rounds), int(window), int(commit)
 
@@ -57,12 +54,6 @@ def check_referee(referee):
     if referee is not None and not (isinstance(referee, str) and referee == "matching"):
         raise ValueError(f"referee must be None or 'matching', not {referee!r}")
     return referee is not None
-
-
-def check_chunk(chunk):
-    if not _is_int(chunk) or chunk < 1:
-        raise ValueError(f"chunk must be a positive integer, not {chunk!r}")
-    return int(chunk)
 
 
 def check_wide_evaluator(evaluator, d, error_model, window):
@@ -84,7 +75,7 @@ def lattice_of_wide(lattice):
     if v is None or not hasattr(v, "d") or not hasattr(v, "error_model"):
         raise ValueError(f"lattice must be (d, error_model) or an environment, not {lattice!r}")
     d, model = check_wide_lattice(int(v.d), str(v.error_model))
-    return d, model, (getattr(v, "p_phys", None), getattr(v, "p_meas", None), getattr(v, "seed", None))
+    return d, model, own_rates(v)
 
 
 def check_wide_stream_args(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHUNK, evaluator=None, error_model="DP"):
@@ -113,56 +104,17 @@ def check_wide_experiment_args(lattice, n_runs, rounds, window=None, commit=None
     d, model, own = lattice_of_wide(lattice)
     T, window, commit = check_wide_schedule(d, rounds, window, commit)
     chunk = check_chunk(chunk)
-    if not _is_int(n_runs) or n_runs < 1:
-        raise ValueError(f"n_runs must be a positive integer, not {n_runs!r}")
-    keys = None
-    n = blk = int(n_runs)
+    n, blk, keys = n_runs, None, None
     if rates is not None:
         if p_phys is not None:
             raise ValueError("memory_experiment_wide: rates=[...] are the physical rates; p_phys goes without them")
-        keys = [float(r) for r in rates]
-        K = len(keys)
-        if K < 1:
-            raise ValueError("memory_experiment_wide: no error rates")
-        if len(set(keys)) != K:
-            raise ValueError("memory_experiment_wide: the error rates must be distinct (they key the result)")
-        meas = keys if p_meas is None else ([float(p_meas)] * K if np.ndim(p_meas) == 0 else [float(r) for r in p_meas])
-        if len(meas) != K:
-            raise ValueError(f"memory_experiment_wide: {len(meas)} measurement rates for {K} error rates")
-        n = blk * K
-        p_phys, p_meas = np.repeat(np.asarray(keys, dtype=np.float64), blk), np.repeat(np.asarray(meas, dtype=np.float64), blk)
-    if n >= 1 << 31:
-        raise ValueError("the number of streams must be below 2^31")
-    if p_phys is None:
-        if p_meas is not None:
-            raise ValueError("p_meas without p_phys: give both, p_phys alone (p_meas = p_phys), or neither (the environment's rates)")
-        if own is None or own[0] is None or own[1] is None:
-            raise ValueError("p_phys is required when the lattice is given as (d, error_model)")
-        p_phys, p_meas = own[0], own[1]
-    elif p_meas is None:
-        p_meas = p_phys
-    p_phys, p_meas = check_rates(p_phys, n, "p_phys"), check_rates(p_meas, n, "p_meas")
-    if isinstance(p_phys, float) != isinstance(p_meas, float):       # one array: the scalar becomes one too
-        full = lambda x: np.full(n, x, dtype=np.float64) if isinstance(x, float) else x
-        p_phys, p_meas = full(p_phys), full(p_meas)
-    if seed is None:
-        if own is None or own[2] is None:
-            raise ValueError("seed is required when the lattice is given as (d, error_model)")
-        seed = own[2]
-    try:
-        ok = len(seed) == 2 and all(_is_int(x) and 0 <= x < 1 << 32 for x in seed)
-    except (TypeError, IndexError):
-        ok = False
-    if not ok:
-        raise ValueError(f"seed must be a pair of 32-bit words, not {seed!r}")
-    seed = (int(seed[0]), int(seed[1]))
-    if not _is_int(env_id_base) or not 0 <= env_id_base < 1 << 32:
-        raise ValueError(f"env_id_base must be an integer in 0 .. 2^32 - 1, not {env_id_base!r}")
+        n, p_phys, p_meas, blk, keys = rate_blocks(n_runs, rates, p_meas, "memory_experiment_wide", "n_runs")
+    n, p_phys, p_meas, seed, base, blk = check_volume_args(n, p_phys, p_meas, seed, env_id_base, blk, own, "n_runs", "the number of streams")
     check_wide_evaluator(evaluator, d, model, window)
-    return d, model, T, window, commit, n, p_phys, p_meas, seed, int(env_id_base), blk, keys, chunk
+    return d, model, T, window, commit, n, p_phys, p_meas, seed, base, blk, keys, chunk
 
 
-class WideEvaluator:
+class WideEvaluator(Counting):
     """Owns a dq_wide_uf handle for chunks of at most `chunk` streams of one lattice and one window: decode, sample-and-decode, verdict, counters.  One host
     thread and one stream at a time."""
 
@@ -243,11 +195,6 @@ class WideEvaluator:
             return
         _lib.check(self.L.dq_wide_uf_verdict_refereed(self._h, self._referee(), _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), _lib.ptr(inexact),
                                                       self._stream()))
-
-    def count_into(self, verdict, trivial, status, n_corr, m, first, block, counters):
-        from . import _lib
-        _lib.check(self.L.dq_decode_count(_lib.ptr(verdict), _lib.ptr(trivial), _lib.ptr(status), _lib.ptr(n_corr), m, first, block,
-                                          counters.shape[0], _lib.ptr(counters), self._stream()))
 
 
 def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None, final_round="faulty"):
@@ -340,17 +287,13 @@ def refereed_uncorrected_into(ev, hidden, m, out, flags):
         ev.verdict_into(hidden[s:s + k], None, k, out[s:s + k], referee="matching", inexact=flags[s:s + k])
 
 
-def add_flags(extras, flags, m, first, blk):
-    """extras int64 [n_blocks] += the flags uint8 [m] of volumes first .. first + m - 1, per block of blk volumes (dq_decode_count's block rule)."""
-    import torch
-    idx = torch.div(torch.arange(first, first + m, dtype=torch.int64, device=extras.device), blk, rounding_mode="floor")
-    extras.index_add_(0, idx, flags[:m].to(torch.int64))
-
-
-def set_no_decoder_inexact(results, extras0):
-    for r, x in zip(results, extras0):
-        if r.no_decoder is not None:
-            r.no_decoder.inexact = int(x)
+def uncorrected_into(ev, hidden, m, out, flags=None):
+    """The verdict of m volumes with no correction, as a scoring call's no_decoder row asks for it: unrefereed, or with `flags` (uint8 [m]) the refereed
+    one in its measured launches."""
+    if flags is None:
+        ev.verdict_into(hidden, None, m, out)
+    else:
+        refereed_uncorrected_into(ev, hidden, m, out, flags)
 
 
 def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0,
@@ -369,7 +312,6 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
     timings: a dict that receives the wall seconds of the phases run / verdict.  evaluator: a WideEvaluator of this lattice and window.  return_streams:
     also returns dict(syndromes uint8 [N, rounds, d+1, d+1], hidden, frame uint8 [N, d, d], trivial uint8 [N]) of device tensors.  final_round="perfect":
     decoder.memory_experiment's closed form."""
-    import time
     import torch
     closed = closed_kw(final_round)
     refereed = check_referee(referee)
@@ -377,65 +319,21 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
         lattice, n_runs, rounds, window, commit, rates, p_phys, p_meas, seed, env_id_base, chunk, evaluator)
     ev = WideEvaluator(d, model, window, chunk=min(chunk, n)) if evaluator is None else evaluator
     dev = ev.device
-    each = not isinstance(ph, float)
     try:
-        step = min(ev.chunk, n)
-        rows = n if return_streams else step
-        hid = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
-        frame = torch.empty((rows, d, d), dtype=torch.uint8, device=dev)
-        triv = torch.empty(rows, dtype=torch.uint8, device=dev)
-        syn = torch.empty((n, T, d + 1, d + 1), dtype=torch.uint8, device=dev) if return_streams else None
-        verd = torch.empty(step, dtype=torch.uint8, device=dev)
-        status = torch.full((step,), STATUS_IDENTITY, dtype=torch.uint8, device=dev)
-        n_blocks = -(-n // blk)
-        counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
-        counters0 = torch.zeros_like(counters) if no_decoder else None
-        flags = torch.empty(step, dtype=torch.uint8, device=dev) if refereed else None
+        flags = torch.empty(min(ev.chunk, n), dtype=torch.uint8, device=dev) if refereed else None
         ref_kw = dict(referee=referee, inexact=flags) if refereed else {}     # (no referee: the call of before, argument for argument)
-        extras = torch.zeros(n_blocks, dtype=torch.int64, device=dev)
-        extras0 = torch.zeros_like(extras)
 
-        def phase(name, t0):
-            if timings is None:
-                return t0
-            torch.cuda.current_stream(dev).synchronize()
-            t1 = time.perf_counter()
-            timings[name] = timings.get(name, 0.0) + (t1 - t0)
-            return t1
+        def run(m, s, a, b, hid, triv, frame, syn):
+            ev.run_into(m, T, commit, base + s, seed, a, b, hid, triv, frame, syndromes=syn, **closed)
 
         with torch.cuda.device(dev):
-            for s in range(0, n, step):
-                m = min(step, n - s)
-                o = s if return_streams else 0
-                sl = slice(o, o + m)
-                t = time.perf_counter()                                  # (the previous chunk's verdict phase ended on a synchronisation)
-                a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
-                if each and (a == a[0]).all() and (b == b[0]).all():   # one rate pair in this chunk: the scalar form (the same thresholds, no table upload)
-                    a, b = float(a[0]), float(b[0])
-                ev.run_into(m, T, commit, base + s, seed, a, b, hid[sl], triv[sl], frame[sl], syndromes=None if syn is None else syn[s:s + m], **closed)
-                t = phase("run", t)
-                ev.verdict_into(hid[sl], frame[sl], m, verd[:m], **ref_kw)
-                ev.count_into(verd[:m], triv[sl], status[:m], (frame[sl] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), m, s, blk, counters)
-                if refereed:
-                    add_flags(extras, flags, m, s, blk)
-                if no_decoder:
-                    if refereed:
-                        refereed_uncorrected_into(ev, hid[sl], m, verd[:m], flags)
-                    else:
-                        ev.verdict_into(hid[sl], None, m, verd[:m])
-                    ev.count_into(verd[:m], triv[sl], None, None, m, s, blk, counters0)
-                    if refereed:
-                        add_flags(extras0, flags, m, s, blk)
-                t = phase("verdict", t)
-            host, host0 = counters.cpu().numpy(), counters0.cpu().numpy() if no_decoder else None
-            extras, extras0 = extras.cpu().numpy(), extras0.cpu().numpy()
+            results, streams = score_streams(ev, dev, n, T, ph, pm, blk, run, lambda hid, frame, m, out: ev.verdict_into(hid, frame, m, out, **ref_kw),
+                                             (lambda hid, m, out: uncorrected_into(ev, hid, m, out, flags)) if no_decoder else None, flags=flags,
+                                             keep=return_streams, timings=timings)
     finally:
         if evaluator is None:
             ev.close()
-    results = block_results(host, host0, extras, n_blocks, blk, ph, pm)
-    set_no_decoder_inexact(results, extras0)
-    out = results[0] if keys is None else dict(zip(keys, results))
-    return (out, dict(syndromes=syn, hidden=hid, frame=frame, trivial=triv)) if return_streams else out
+    return (keyed(results, keys), streams) if return_streams else keyed(results, keys)
 
 
 # ---- the union-find decoder as a policy and a teacher of the wide environment (include/deepq_hip.h dq_envb_uf_select, dq_envb_guided_select_uf;
@@ -584,13 +482,13 @@ def check_decode_wide_args(d, error_model, use_Y, volume_depth, shape, max_actio
     syndromes [N, depth, d+1, d+1] or one volume [depth, d+1, d+1] (else ValueError).  Returns (n_volumes, single, num_actions, max_actions)."""
     d, error_model = check_wide_lattice(d, error_model)
     layers = action_layers(error_model, use_Y)
-    if not _is_int(volume_depth) or not 1 <= volume_depth <= WIDE_MAX_DEPTH:
+    if not is_int(volume_depth) or not 1 <= volume_depth <= WIDE_MAX_DEPTH:
         raise ValueError(f"decode_wide covers volume_depth 1..{WIDE_MAX_DEPTH}, not {volume_depth!r}")
     volume_depth = int(volume_depth)
     num_actions = layers * d * d + 1
     if max_actions is None:
         max_actions = num_actions - 1
-    if not _is_int(max_actions) or not 1 <= max_actions <= num_actions - 1:
+    if not is_int(max_actions) or not 1 <= max_actions <= num_actions - 1:
         raise ValueError(f"max_actions must be an integer in 1..{num_actions - 1}, not {max_actions!r}")
     shape = tuple(int(x) for x in shape)
     grid = (volume_depth, d + 1, d + 1)
@@ -814,14 +712,12 @@ def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=No
     and dq_decode_count with the agent's status and correction count.  referee=None: no referee is consulted, alive := success; referee="matching":
     the verdicts of all three rows (the agent's, the union-find baseline's, no_decoder's) go through dq_wide_uf_verdict_refereed and each row's
     EvalResult.inexact counts its flagged volumes."""
-    import time
     import torch
     from .decoder import DecodeResult
     refereed = check_referee(referee)
     d, depth, dev = dec.d, dec.volume_depth, dec.device
     step = min(dec.chunk, n)
     ev = WideEvaluator(d, dec.error_model, depth, chunk=step, device=dev)
-    each = not isinstance(ph, float)
     closed = closed_kw(final_round)
     try:
         rows = n if return_volumes else step
@@ -833,72 +729,37 @@ def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=No
         verd2 = torch.empty(step, dtype=torch.uint8, device=dev)
         corr, ncorr, frame, status = dec.outputs(rows)
         uf_status = torch.full((step,), STATUS_IDENTITY, dtype=torch.uint8, device=dev)
-        n_blocks = -(-n // blk)
-        counters = torch.zeros((n_blocks, len(COUNTER_NAMES)), dtype=torch.int64, device=dev)
-        counters_uf = torch.zeros_like(counters) if baseline else None
-        counters0 = torch.zeros_like(counters) if no_decoder else None
         flags = torch.empty(step, dtype=torch.uint8, device=dev) if refereed else None
         ref_kw = dict(referee=referee, inexact=flags) if refereed else {}     # (no referee: the call of before, argument for argument)
-        extras = torch.zeros(n_blocks, dtype=torch.int64, device=dev)
-        extras_uf, extras0 = torch.zeros_like(extras), torch.zeros_like(extras)
         iters = []
 
-        def phase(name, t0):
-            if timings is None:
-                return t0
-            torch.cuda.current_stream(dev).synchronize()
-            t1 = time.perf_counter()
-            timings[name] = timings.get(name, 0.0) + (t1 - t0)
-            return t1
+        def run(m, s, sl, a, b):
+            ev.run_into(m, depth, depth, base + s, seed, a, b, hid[sl], triv[sl], uf_frame[sl], syndromes=syn[sl], **closed)
+
+        def decode(m, sl):
+            iters.append(dec.decode_into(params, packed, syn[sl], m, corr[sl], ncorr[sl], frame[sl], status[sl]))
+
+        def agent(m, sl):
+            ev.verdict_into(hid[sl], frame[sl], m, verd[sl], **ref_kw)
+            return verd[sl], triv[sl], status[sl], ncorr[sl], flags
+
+        def union_find(m, sl):
+            ev.verdict_into(hid[sl], uf_frame[sl], m, verd2[:m], **ref_kw)
+            return verd2[:m], triv[sl], uf_status[:m], corrected_cells(uf_frame[sl]), flags
+
+        def uncorrected(m, sl):
+            uncorrected_into(ev, hid[sl], m, verd2[:m], flags)
+            return verd2[:m], triv[sl], None, None, flags
 
         with torch.cuda.device(dev):
             packed = dec.net.pack(params)
-            for s in range(0, n, step):
-                m = min(step, n - s)
-                o = s if return_volumes else 0
-                sl = slice(o, o + m)
-                t = time.perf_counter()
-                a, b = (ph[s:s + m], pm[s:s + m]) if each else (ph, pm)
-                if each and (a == a[0]).all() and (b == b[0]).all():
-                    a, b = float(a[0]), float(b[0])
-                ev.run_into(m, depth, depth, base + s, seed, a, b, hid[sl], triv[sl], uf_frame[sl], syndromes=syn[sl], **closed)
-                t = phase("run", t)
-                iters.append(dec.decode_into(params, packed, syn[sl], m, corr[sl], ncorr[sl], frame[sl], status[sl]))
-                t = phase("decode", t)
-                ev.verdict_into(hid[sl], frame[sl], m, verd[sl], **ref_kw)
-                ev.count_into(verd[sl], triv[sl], status[sl], ncorr[sl], m, s, blk, counters)
-                if refereed:
-                    add_flags(extras, flags, m, s, blk)
-                if baseline:
-                    ev.verdict_into(hid[sl], uf_frame[sl], m, verd2[:m], **ref_kw)
-                    ev.count_into(verd2[:m], triv[sl], uf_status[:m], (uf_frame[sl] != 0).reshape(m, -1).sum(dim=1, dtype=torch.int32), m, s, blk,
-                                  counters_uf)
-                    if refereed:
-                        add_flags(extras_uf, flags, m, s, blk)
-                if no_decoder:
-                    if refereed:
-                        refereed_uncorrected_into(ev, hid[sl], m, verd2[:m], flags)
-                    else:
-                        ev.verdict_into(hid[sl], None, m, verd2[:m])
-                    ev.count_into(verd2[:m], triv[sl], None, None, m, s, blk, counters0)
-                    if refereed:
-                        add_flags(extras0, flags, m, s, blk)
-                t = phase("verdict", t)
-            host = counters.cpu().numpy()
-            host_uf = counters_uf.cpu().numpy() if baseline else None
-            host0 = counters0.cpu().numpy() if no_decoder else None
-            extras, extras_uf, extras0 = extras.cpu().numpy(), extras_uf.cpu().numpy(), extras0.cpu().numpy()
+            results = score_chunks(ev, dev, n, ph, pm, blk, run, [agent, union_find] if baseline else [agent], uncorrected if no_decoder else None,
+                                   keep=return_volumes, decode=decode, phases=("run", "decode"), timings=timings)
     finally:
         ev.close()
-    results = block_results(host, host0, extras, n_blocks, blk, ph, pm)
-    set_no_decoder_inexact(results, extras0)
     if return_volumes:
-        r = results[0]
+        r = results[0][0]
         r.volumes, r.hidden, r.trivial, r.verdict = syn, hid, triv, verd
         r.decode = DecodeResult(corr, ncorr, frame, status, iterations=iters)
-    out = results[0] if keys is None else dict(zip(keys, results))
-    if not baseline:
-        return out
-    rows_uf = block_results(host_uf, host0, extras_uf, n_blocks, blk, ph, pm)
-    set_no_decoder_inexact(rows_uf, extras0)
-    return out, (rows_uf[0] if keys is None else dict(zip(keys, rows_uf)))
+    out = tuple(keyed(x, keys) for x in results)
+    return out if baseline else out[0]

@@ -161,3 +161,131 @@ def test_the_restatement_runs_at_676_actions_under_supplied_q_rows():
         assert set(corr[v]) <= legal
         assert int((frames[v] != 0).sum()) <= len(corr[v])
     assert corr[0] == [] and status[0] == 1                          # the empty volume's legal set is the identity alone
+
+
+# ---- plumbing with stubs: score_decode_wide's three rows through the shared chunk loop ----------------------------------------------------------------
+class _FakeWideEvaluator:
+    """Stands for a WideEvaluator on CPU tensors.  The run writes the lattice id into the first cell of each volume, id & 3 into the hidden state and
+    (id >> 2) & 1 into the union-find frame; the verdict calls a zero residual a success, and with a referee a residual other than 3 alive and a residual
+    of 2 flagged.  Every call is recorded on the shared list."""
+    calls = None
+
+    def __init__(self, d, error_model, window, chunk, device):
+        self.d, self.error_model, self.window, self.chunk, self.device = d, error_model, window, chunk, device
+        self.calls.append(("open", d, error_model, window, chunk))
+
+    def close(self):
+        self.calls.append(("close",))
+
+    def run_into(self, m, T, commit, lattice_id, seed, p_phys, p_meas, hidden, trivial, frame, weight=None, n_defects=None, rounds=None, syndromes=None):
+        import torch
+        self.calls.append(("run", m, T, commit, lattice_id, seed, p_phys if isinstance(p_phys, float) else tuple(p_phys)))
+        ids = torch.arange(lattice_id, lattice_id + m)
+        for x in (hidden, frame, syndromes):
+            x.zero_()
+        syndromes.reshape(m, -1)[:, 0] = ids.to(torch.uint8)
+        hidden.reshape(m, -1)[:, 0] = (ids & 3).to(torch.uint8)
+        frame.reshape(m, -1)[:, 0] = ((ids >> 2) & 1).to(torch.uint8)
+        trivial.copy_((ids % 5 == 0).to(torch.uint8))
+
+    def verdict_into(self, hidden, frame, m, out, **kw):
+        import torch
+        self.calls.append(("verdict", m, None if frame is None else frame.reshape(m, -1)[:, 0].tolist(), sorted(kw)))
+        res = hidden.reshape(m, -1)[:, 0] ^ (frame.reshape(m, -1)[:, 0] if frame is not None else 0)
+        ok = res == 0
+        out.copy_(ok.to(torch.uint8) * 8 + ((res != 3) if kw else ok).to(torch.uint8) * 16)
+        if kw:
+            assert kw["referee"] == "matching"
+            kw["inexact"][:m] = (res == 2).to(torch.uint8)
+
+    def count_into(self, verdict, trivial, status, n_corr, m, first, block, counters):
+        self.calls.append(("count", m, first, block, None if status is None else status.tolist()))
+        for i in range(m):
+            c = counters[(first + i) // block]
+            c[0] += 1
+            c[1] += int(trivial[i])
+            c[3] += (int(verdict[i]) >> 3) & 1
+            c[4] += (int(verdict[i]) >> 4) & 1
+            if status is not None:
+                c[4 + int(status[i])] += 1
+            c[8] += int(n_corr[i]) if n_corr is not None else 0
+
+
+class _FakeWideDecoder:
+    """Stands for a WideBatchDecoder: the decode puts (id >> 3) & 3 into the frame, 1 + id % 3 into the status and id % 4 into the correction count."""
+
+    def __init__(self, calls, d, depth, chunk):
+        self.d, self.error_model, self.volume_depth, self.chunk, self.device, self.calls = d, "DP", depth, chunk, "cpu", calls
+        self.net = types.SimpleNamespace(pack=lambda params: "packed")
+
+    def outputs(self, n):
+        import torch
+        return (torch.empty((n, 4), dtype=torch.int32), torch.empty(n, dtype=torch.int32), torch.empty((n, self.d, self.d), dtype=torch.uint8),
+                torch.empty(n, dtype=torch.uint8))
+
+    def decode_into(self, params, packed, syn, m, corr, ncorr, frame, status):
+        import torch
+        self.calls.append(("decode", params, packed, m))
+        ids = syn.reshape(m, -1)[:, 0]
+        corr.fill_(-1)
+        frame.zero_()
+        frame.reshape(m, -1)[:, 0] = (ids >> 3) & 3
+        status.copy_(1 + ids % 3)
+        ncorr.copy_((ids % 4).to(torch.int32))
+        return 100 + m
+
+
+@pytest.mark.parametrize("referee", ["matching", None])
+def test_score_decode_wide_rows_blocks_flags_and_volumes(dq, monkeypatch, referee):
+    import contextlib
+    import torch
+    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda dev=None: types.SimpleNamespace(synchronize=lambda: None))
+    DW = dq.decoder_wide
+    calls = []
+    monkeypatch.setattr(_FakeWideEvaluator, "calls", calls)
+    monkeypatch.setattr(DW, "WideEvaluator", _FakeWideEvaluator)
+    monkeypatch.setattr(DW, "UNCORRECTED_REFEREE_SLICE", 3)
+    dec = _FakeWideDecoder(calls, 13, 3, 7)
+    _, _, _, _, _, n, ph, pm, seed, base, blk, keys, _ = DW.check_decode_benchmark_wide_args(
+        (13, "DP", False, 3), 10, rates=[0.01, 0.03], seed=(3, 4), env_id_base=40, baseline="union_find", referee=referee)
+    assert (n, blk, keys) == (20, 10, [0.01, 0.03])
+    timings = {}
+    out, out_uf = DW.score_decode_wide(dec, "params", n, ph, pm, seed, base, blk, keys, baseline="union_find", no_decoder=True, return_volumes=True,
+                                       timings=timings, referee=referee)
+    ids = np.arange(40, 60)
+    hidden, uf, agent, status = ids & 3, (ids >> 2) & 1, (ids >> 3) & 3, 1 + ids % 3
+    kw = ["inexact", "referee"] if referee else []
+    # per chunk: run, decode, the agent's verdict and count, union-find's, then the uncorrected verdict (sliced at d = 13 under a referee) and its count
+    want = [("open", 13, "DP", 3, 7)]
+    for m, first, rate in ((7, 0, 0.01), (7, 7, (0.01,) * 3 + (0.03,) * 4), (6, 14, 0.03)):
+        sl = slice(first, first + m)
+        want += [("run", m, 3, 3, 40 + first, (3, 4), rate), ("decode", "params", "packed", m),
+                 ("verdict", m, agent[sl].tolist(), kw), ("count", m, first, 10, status[sl].tolist()),
+                 ("verdict", m, uf[sl].tolist(), kw), ("count", m, first, 10, [1] * m)]
+        want += [("verdict", k, None, kw) for k in ([3] * (m // 3) + [m % 3] * (m % 3 > 0) if referee else [m])]
+        want += [("count", m, first, 10, None)]
+    assert calls == want + [("close",)]
+    assert set(timings) == {"run", "decode", "verdict"} and list(out) == list(out_uf) == [0.01, 0.03]
+    for k, rate in enumerate((0.01, 0.03)):
+        sl = slice(10 * k, 10 * k + 10)
+        for r, frame, st, ncorr in ((out[rate], agent[sl], status[sl], ids[sl] % 4), (out_uf[rate], uf[sl], np.ones(10, int), uf[sl] != 0)):
+            res, res0 = hidden[sl] ^ frame, hidden[sl]
+            alive = lambda x: int(((x != 3) if referee else (x == 0)).sum())
+            want_counters = dict(volumes=10, trivial=int((ids[sl] % 5 == 0).sum()), in_codespace=0, success=int((res == 0).sum()), alive=alive(res),
+                                 identity=int((st == 1).sum()), repeat=int((st == 2).sum()), stopped=int((st == 3).sum()), corrections=int(ncorr.sum()))
+            assert r.counters == want_counters and r.inexact == (int((res == 2).sum()) if referee else 0) and (r.p_phys, r.p_meas) == (rate, rate)
+            z = r.no_decoder
+            assert z.counters == dict(want_counters, success=int((res0 == 0).sum()), alive=alive(res0), identity=0, repeat=0, stopped=0, corrections=0)
+            assert z.inexact == (int((res0 == 2).sum()) if referee else 0)
+    # return_volumes: all 20 rows ride on the first result, in order
+    r = out[0.01]
+    assert tuple(r.volumes.shape) == (20, 3, 14, 14) and np.array_equal(r.volumes.reshape(20, -1)[:, 0].numpy(), ids)
+    assert tuple(r.hidden.shape) == (20, 13, 13) and np.array_equal(r.hidden.reshape(20, -1)[:, 0].numpy(), hidden)
+    assert np.array_equal(r.trivial.numpy(), (ids % 5 == 0).astype(np.uint8))
+    res = hidden ^ agent
+    assert r.verdict.dtype == torch.uint8 and np.array_equal(r.verdict.numpy(), (res == 0) * 8 + ((res != 3) if referee else (res == 0)) * 16)
+    assert isinstance(r.decode, dq.decoder.DecodeResult) and r.decode.iterations == [107, 107, 106] and tuple(r.decode.corrections.shape) == (20, 4)
+    assert np.array_equal(r.decode.frame.reshape(20, -1)[:, 0].numpy(), agent) and np.array_equal(r.decode.status.numpy(), status)
+    assert np.array_equal(r.decode.n_corrections.numpy(), ids % 4) and r.decode.n_corrections.dtype == torch.int32
+    assert out[0.03].volumes is None and out_uf[0.01].volumes is None and out_uf[0.01].verdict is None

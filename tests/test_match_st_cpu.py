@@ -123,3 +123,86 @@ def test_matching_abi_is_declared_and_bound(dq):
     assert "dq_decode_match" in L.SIGNATURES and hasattr(lib, "dq_decode_match")
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "deepq_hip.h")).read()
     assert "dq_status dq_decode_match(dq_decode_eval* ev, const uint8_t* volumes_dev, int n, uint8_t* frame_dev" in header
+
+
+# ---- plumbing with stubs: score_matching through the shared chunk loop -----------------------------------------------------------------
+class _FakeEvaluator:
+    """Stands for an Evaluator on CPU tensors.  The sampler writes the lattice id into the first cell of each volume and id & 3 into the hidden state;
+    both decoders put (id >> 2) & 3 into the frame, the matching also flags ids that are multiples of 3; the verdict calls a zero residual a success."""
+
+    def __init__(self, d, depth, chunk):
+        self.d, self.error_model, self.use_Y, self.volume_depth, self.chunk = d, "DP", False, depth, chunk
+        self.calls = []
+
+    def sample_into(self, venv, m, lattice_id, seed, p_phys, p_meas, volumes, hidden, trivial):
+        import torch
+        form = lambda p: p if isinstance(p, float) else tuple(p)
+        self.calls.append(("sample", m, lattice_id, seed, form(p_phys), form(p_meas)))
+        ids = torch.arange(lattice_id, lattice_id + m)
+        volumes.zero_()
+        hidden.zero_()
+        volumes.reshape(m, -1)[:, 0] = ids.to(torch.uint8)
+        hidden.reshape(m, -1)[:, 0] = (ids & 3).to(torch.uint8)
+        trivial.copy_((ids % 5 == 0).to(torch.uint8))
+
+    def _decode(self, name, volumes, m, frame):
+        self.calls.append((name, m))
+        frame.zero_()
+        frame.reshape(m, -1)[:, 0] = (volumes.reshape(m, -1)[:, 0] >> 2) & 3
+
+    def match_into(self, volumes, m, frame, weight=None, n_defects=None, inexact=None):
+        import torch
+        self._decode("match", volumes, m, frame)
+        inexact.copy_((volumes.reshape(m, -1)[:, 0] % 3 == 0).to(torch.uint8))
+
+    def uf_into(self, volumes, m, frame, weight=None, n_defects=None, rounds=None):
+        self._decode("uf", volumes, m, frame)
+
+    def verdict_into(self, venv, hidden, frame, m, out):
+        import torch
+        self.calls.append(("verdict", m, frame is not None))
+        res = hidden.reshape(m, -1)[:, 0] ^ (frame.reshape(m, -1)[:, 0] if frame is not None else 0)
+        out.copy_((res == 0).to(torch.uint8) * 24)
+
+    def count_into(self, verdict, trivial, status, n_corr, m, first, block, counters):
+        self.calls.append(("count", m, first, block, status is not None))
+        for i in range(m):
+            b = (first + i) // block
+            counters[b, 0] += 1
+            counters[b, 1] += int(trivial[i])
+            counters[b, 3] += (int(verdict[i]) >> 3) & 1
+            counters[b, 4] += (int(verdict[i]) >> 4) & 1
+            counters[b, 5] += int(status[i] == 1) if status is not None else 0
+            counters[b, 8] += int(n_corr[i]) if n_corr is not None else 0
+
+
+@pytest.mark.parametrize("method", ["matching", "union_find"])
+def test_score_matching_chunks_blocks_flags_and_timings(dq, monkeypatch, method):
+    import contextlib
+    import torch
+    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda dev=None: types.SimpleNamespace(synchronize=lambda: None))
+    D = dq.decoder
+    ev = _FakeEvaluator(5, 5, 7)
+    timings = {}
+    out = D.score_matching(_env(_h=1, device="cpu"), 10, rates=[0.01, 0.03], p_meas=0.0, seed=(3, 4), env_id_base=100, evaluator=ev, no_decoder=True,
+                           timings=timings, method=method)
+    # per chunk: sample (the scalar form where the chunk holds one rate), decode, the decoder's verdict and count, the uncorrected verdict and count
+    mixed = (0.01,) * 3 + (0.03,) * 4
+    want = []
+    for m, first, ph, pm in ((7, 0, 0.01, 0.0), (7, 7, mixed, (0.0,) * 7), (6, 14, 0.03, 0.0)):
+        want += [("sample", m, 100 + first, (3, 4), ph, pm), ("match" if method == "matching" else "uf", m), ("verdict", m, True),
+                 ("count", m, first, 10, True), ("verdict", m, False), ("count", m, first, 10, False)]
+    assert ev.calls == want
+    assert list(out) == [0.01, 0.03] and set(timings) == {"setup", "sample", "match", "verdict"}      # (the key stays "match" for union-find)
+    for k, rate in enumerate((0.01, 0.03)):
+        ids = np.arange(100 + 10 * k, 110 + 10 * k)
+        hidden, frame = ids & 3, (ids >> 2) & 3
+        r = out[rate]
+        assert isinstance(r, D.EvalResult) and (r.p_phys, r.p_meas) == (rate, 0.0)
+        assert r.counters["volumes"] == 10 and r.counters["trivial"] == int((ids % 5 == 0).sum()) and r.counters["identity"] == 10
+        assert r.counters["success"] == r.counters["alive"] == int((hidden == frame).sum()) and r.counters["corrections"] == int((frame != 0).sum())
+        assert r.inexact == (int((ids % 3 == 0).sum()) if method == "matching" else 0)
+        z = r.no_decoder
+        assert z.counters["volumes"] == 10 and z.counters["success"] == int((hidden == 0).sum()) and z.counters["identity"] == 0
+        assert z.counters["corrections"] == 0 and z.inexact == 0 and (z.p_phys, z.p_meas) == (rate, 0.0)
