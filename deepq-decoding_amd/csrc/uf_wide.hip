@@ -5,6 +5,8 @@
 //                              q < n_stab, stabilizer q's measurement flip): the syndromes never reach memory unless a buffer for them is given
 //   verdict_wide_kernel        residual = hidden XOR frame: in code space, homology class, success; no referee is consulted
 // The two stream kernels are templates on Closed (dq_wide_uf_decode_closed / dq_wide_uf_run_closed), as uf_stream.hip's are.
+// and on Weighted (dq_wide_uf_decode_weighted / dq_wide_uf_run_weighted): the same two bodies around ufw_component<Closed, true>, an edge
+// of weight w full at g = 2 w, one (w_space, w_time) per stream; the Weighted = false instantiations are the unit-weight kernels, instruction for instruction.
 // The lattice tables come from LatticeHost inside the handle; no environment handle is needed.
 #include "uf_wide.h"
 #include "lattice_host.h"
@@ -28,11 +30,33 @@ struct WideArgs {
     int32_t *weight, *n_defects, *rounds;      // [n][2] or NULL
 };
 
+// The weights of a weighted launch: one pair for all streams, or a pair per stream.
+struct WideWeights {
+    const u8* each;             // != NULL: [2 i] / [2 i + 1] = (w_space, w_time) of stream i
+    int w_space, w_time;
+};
+
+// The arguments of a weighted launch are the unweighted ones with the weights behind them; the unweighted kernels take WideArgs itself.
+struct WideArgsWeighted : WideArgs {
+    WideWeights w;
+};
+template <bool Weighted>
+using WideArgsOf = std::conditional_t<Weighted, WideArgsWeighted, WideArgs>;
+
+// The workgroup's own pair, clamped to 1 .. UFW_MAX_WEIGHT: a bad byte of a per-stream array cannot overrun the growth byte.
+static __device__ __forceinline__ void wide_weights(const WideWeights& w, size_t i, int& w_space, int& w_time) {
+    w_space = w.w_space; w_time = w.w_time;
+    if (w.each != nullptr) { w_space = w.each[2 * i]; w_time = w.each[2 * i + 1]; }
+    w_space = min(max(w_space, 1), UFW_MAX_WEIGHT); w_time = min(max(w_time, 1), UFW_MAX_WEIGHT);
+    UFW_IN_VGPR(w_space); UFW_IN_VGPR(w_time);
+}
+
 // The schedule around a source of rounds: next(j, row0, row1) is called once for every j = 0 .. T - 1, in order, by every thread; it leaves round j's defect
 // rows of the two components in the given LDS words (all UFW_ROW_WORDS of each) and may use barriers; `last` says j = T - 1 (the last row of the final window).
 // Closed: the stream ends on a round of perfect measurements, so the final window has no time edges in its last round.
-template <bool Closed, class Next>
-static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem, const UfwLayout& L, int tid, Next next) {
+// Weighted: ufw_component<Closed, true> with the stream's (w_space, w_time); the schedule, the carry and the closed final window are the same.
+template <bool Closed, bool Weighted, class Next>
+static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem, const UfwLayout& L, int tid, Next next, int w_space = 1, int w_time = 1) {
     u32* s_frame = reinterpret_cast<u32*>(smem + L.o_frame);
     u32* s_carry = reinterpret_cast<u32*>(smem + L.o_carry);
     int* s_acc = reinterpret_cast<int*>(smem + L.o_acc);
@@ -66,8 +90,12 @@ static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem,
         G.depth = l; G.B = l * G.n; G.NN = G.B + 1; G.NE = l * G.per_round;
         for (int c = 0; c < 2; ++c) {
             G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
-            ufw_component<Closed>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c,
-                          s_acc + 4 + c);
+            if constexpr (Weighted)
+                ufw_component<Closed, true>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS,
+                                            s_acc + c, s_acc + 4 + c, w_space, w_time, s_acc + 6);
+            else
+                ufw_component<Closed>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c,
+                                      s_acc + 4 + c);
         }
         if (final) break;
         // the ring moves down by `commit` rows (2 window UFW_ROW_WORDS <= UFW_THREADS words)
@@ -118,12 +146,14 @@ static __device__ __forceinline__ void wide_store(const WidePtrs& P, u8* smem, c
     }
 }
 
-template <bool Closed>
-__global__ __launch_bounds__(UFW_THREADS) void stream_wide_uf_kernel(WideArgs p) {
+template <bool Closed, bool Weighted = false>
+__global__ __launch_bounds__(UFW_THREADS) void stream_wide_uf_kernel(WideArgsOf<Weighted> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
     if ((int)blockIdx.x >= p.n_streams) return;                     // workgroup-uniform
+    int w_space = 1, w_time = 1;
+    if constexpr (Weighted) wide_weights(p.w, i, w_space, w_time);
     UfwLayout L = ufw_layout(p.n, p.d2, p.window);
     ufw_layout_in_vgpr(L);
     const int my_cell = p.node_cell[tid];
@@ -132,19 +162,21 @@ __global__ __launch_bounds__(UFW_THREADS) void stream_wide_uf_kernel(WideArgs p)
     const WidePtrs P = wide_ptrs(p, i, tid);
     int prev = 0, nd = 0, G = p.G;
     UFW_IN_VGPR(vp); UFW_IN_VGPR(prev); UFW_IN_VGPR(nd); UFW_IN_VGPR(G);
-    wide_windows<Closed>(p, smem, L, tid, [&](int j, bool, u32* row0, u32* row1) {
+    wide_windows<Closed, Weighted>(p, smem, L, tid, [&](int j, bool, u32* row0, u32* row1) {
         const int cur = vp[(size_t)j * G] != 0;                    // (a thread without a node reads cell 0 of its own stream and masks it)
         wide_rows(mine ? cur : 0, prev, tid, row0, row1, nd);
-    });
+    }, w_space, w_time);
     wide_store(P, smem, L, tid, nd);
 }
 
-template <bool Closed>
-__global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArgs p) {
+template <bool Closed, bool Weighted = false>
+__global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArgsOf<Weighted> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
     if ((int)blockIdx.x >= p.n_streams) return;                     // workgroup-uniform
+    int w_space = 1, w_time = 1;
+    if constexpr (Weighted) wide_weights(p.w, i, w_space, w_time);
     UfwLayout L = ufw_layout(p.n, p.d2, p.window);
     ufw_layout_in_vgpr(L);
     u8* s_ex = smem + L.o_ex;
@@ -172,7 +204,7 @@ __global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArg
     int x = 0, z = 0, prev = 0, seen = 0, nd = 0;
     UFW_IN_VGPR(has_q); UFW_IN_VGPR(has_s); UFW_IN_VGPR(isx); UFW_IN_VGPR(x); UFW_IN_VGPR(z); UFW_IN_VGPR(prev); UFW_IN_VGPR(seen); UFW_IN_VGPR(nd);
     UFW_IN_VGPR(hid); UFW_IN_VGPR(triv); UFW_IN_VGPR(syn);
-    wide_windows<Closed>(p, smem, L, tid, [&](int j, bool last, u32* row0, u32* row1) {
+    wide_windows<Closed, Weighted>(p, smem, L, tid, [&](int j, bool last, u32* row0, u32* row1) {
         u32 w[4];                                                  // sample_volumes' round, round counter j
         philox4x32_10((u32)j, 0u, id, (u32)tid, seed0, seed1, w);
         const bool hit = has_q && (u64)w[0] < T_phys;
@@ -195,7 +227,7 @@ __global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArg
         if (syn) syn[(size_t)j * G] = cs < 255 ? s_v[cs] : (u8)0;
         const int cur = my_stab < 255 && s_v[my_stab] != 0;
         wide_rows(cur, prev, tid, row0, row1, nd);
-    });
+    }, w_space, w_time);
     const int any_seen = __syncthreads_or(seen);
     if (has_q) *hid = (u8)(x ? (z ? 2 : 1) : (z ? 3 : 0));
     if (tid == 0) *triv = (u8)(any_seen == 0);
@@ -258,16 +290,30 @@ void wide_args(const dq_wide_uf* H, int n, int T, int commit, WideArgs* a) {
 }
 
 
-// The open and the closed entry points: one body, `who` names the caller in the messages.
+// What the weighted forms check on top: closed is a flag, the uniform pair lies in 1 .. UFW_MAX_WEIGHT (a per-stream array is the caller's to check; the kernel
+// clamps it).
+dq_status wide_check_weighted(int closed, int w_space, int w_time, const char* who) {
+    DQ_REQUIRE(closed == 0 || closed == 1, DQ_ERR_INVALID, "%s: closed = %d is not 0 or 1", who, closed);
+    DQ_REQUIRE(w_space >= 1 && w_space <= UFW_MAX_WEIGHT && w_time >= 1 && w_time <= UFW_MAX_WEIGHT, DQ_ERR_INVALID,
+               "%s: weights (%d, %d) outside 1..%d", who, w_space, w_time, UFW_MAX_WEIGHT);
+    return DQ_OK;
+}
+
+// The open and the closed entry points: one body, `who` names the caller in the messages.  ww: the weights of a weighted launch, NULL for the unit-weight kernels.
 dq_status wide_decode(bool closed, const char* who, dq_wide_uf* H, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
-                      int32_t* n_defects_dev, int32_t* rounds_dev, void* stream) {
+                      int32_t* n_defects_dev, int32_t* rounds_dev, void* stream, const WideWeights* ww = nullptr) {
     DQ_REQUIRE(H && syndromes_dev && frame_dev, DQ_ERR_INVALID, "%s: null argument", who);
     const dq_status rc = wide_check(H, n, T, commit, weight_dev, n_defects_dev, rounds_dev, who);
     if (rc != DQ_OK) return rc;
     WideArgs a;
     wide_args(H, n, T, commit, &a);
     a.syn_in = syndromes_dev; a.frame = frame_dev; a.weight = weight_dev; a.n_defects = n_defects_dev; a.rounds = rounds_dev;
-    if (closed) stream_wide_uf_kernel<true><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(a);
+    if (ww) {
+        WideArgsWeighted aw;
+        static_cast<WideArgs&>(aw) = a; aw.w = *ww;
+        if (closed) stream_wide_uf_kernel<true, true><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(aw);
+        else stream_wide_uf_kernel<false, true><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(aw);
+    } else if (closed) stream_wide_uf_kernel<true><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(a);
     else stream_wide_uf_kernel<false><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(a);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
@@ -275,7 +321,7 @@ dq_status wide_decode(bool closed, const char* who, dq_wide_uf* H, const uint8_t
 
 dq_status wide_run(bool closed, const char* who, dq_wide_uf* H, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
                    const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev,
-                   int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
+                   int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream, const WideWeights* ww = nullptr) {
     DQ_REQUIRE(H && seed && hidden_dev && trivial_dev && frame_dev, DQ_ERR_INVALID, "%s: null argument", who);
     dq_status rc = wide_check(H, n, T, commit, weight_dev, n_defects_dev, rounds_dev, who);
     if (rc != DQ_OK) return rc;
@@ -294,7 +340,12 @@ dq_status wide_run(bool closed, const char* who, dq_wide_uf* H, int n, int T, in
     a.env_id_base = env_id_base; a.seed0 = seed[0]; a.seed1 = seed[1];
     a.hidden = hidden_dev; a.trivial = trivial_dev; a.frame = frame_dev; a.weight = weight_dev; a.n_defects = n_defects_dev; a.rounds = rounds_dev;
     a.syn_out = syndromes_dev;
-    if (closed) stream_run_wide_uf_kernel<true><<<n, UFW_THREADS, H->lds, st>>>(a);
+    if (ww) {
+        WideArgsWeighted aw;
+        static_cast<WideArgs&>(aw) = a; aw.w = *ww;
+        if (closed) stream_run_wide_uf_kernel<true, true><<<n, UFW_THREADS, H->lds, st>>>(aw);
+        else stream_run_wide_uf_kernel<false, true><<<n, UFW_THREADS, H->lds, st>>>(aw);
+    } else if (closed) stream_run_wide_uf_kernel<true><<<n, UFW_THREADS, H->lds, st>>>(a);
     else stream_run_wide_uf_kernel<false><<<n, UFW_THREADS, H->lds, st>>>(a);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
@@ -342,10 +393,14 @@ dq_status dq_wide_uf_create(int d, int error_model, int window, int max_streams,
     const unsigned long long dev_bit = dq_device_bit();
     if (!(attr_devs & dev_bit)) {
         const int lds_max = ufw_layout((UFW_MAX_D * UFW_MAX_D - 1) / 2, UFW_MAX_D * UFW_MAX_D, UFW_MAX_WINDOW).bytes;
-        const void* kernels[4] = {reinterpret_cast<const void*>(stream_wide_uf_kernel<false>), reinterpret_cast<const void*>(stream_run_wide_uf_kernel<false>),
-                                  reinterpret_cast<const void*>(stream_wide_uf_kernel<true>), reinterpret_cast<const void*>(stream_run_wide_uf_kernel<true>)};
+        const void* kernels[8] = {reinterpret_cast<const void*>(stream_wide_uf_kernel<false>), reinterpret_cast<const void*>(stream_run_wide_uf_kernel<false>),
+                                  reinterpret_cast<const void*>(stream_wide_uf_kernel<true>), reinterpret_cast<const void*>(stream_run_wide_uf_kernel<true>),
+                                  reinterpret_cast<const void*>(stream_wide_uf_kernel<false, true>),
+                                  reinterpret_cast<const void*>(stream_run_wide_uf_kernel<false, true>),
+                                  reinterpret_cast<const void*>(stream_wide_uf_kernel<true, true>),
+                                  reinterpret_cast<const void*>(stream_run_wide_uf_kernel<true, true>)};
         hipError_t ea = hipSuccess;
-        for (int k = 0; k < 4 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        for (int k = 0; k < 8 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
         if (ea != hipSuccess) {
             (void)hipGetLastError();
             dq_set_error("dq_wide_uf_create: the device refuses %d bytes of LDS per workgroup: %s", lds_max, hipGetErrorString(ea));
@@ -403,6 +458,26 @@ dq_status dq_wide_uf_run_closed(dq_wide_uf* H, int n, int T, int commit, uint32_
                                 int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
     return wide_run(true, "dq_wide_uf_run_closed", H, n, T, commit, env_id_base, seed, p_phys, p_meas, p_phys_each, p_meas_each, hidden_dev, trivial_dev, frame_dev,
                     weight_dev, n_defects_dev, rounds_dev, syndromes_dev, stream);
+}
+
+dq_status dq_wide_uf_decode_weighted(dq_wide_uf* H, const uint8_t* syndromes_dev, int n, int T, int commit, int closed, int w_space, int w_time,
+                                     const uint8_t* weights_each_dev, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev,
+                                     void* stream) {
+    const dq_status rc = wide_check_weighted(closed, w_space, w_time, "dq_wide_uf_decode_weighted");
+    if (rc != DQ_OK) return rc;
+    const WideWeights ww = {weights_each_dev, w_space, w_time};
+    return wide_decode(closed != 0, "dq_wide_uf_decode_weighted", H, syndromes_dev, n, T, commit, frame_dev, weight_dev, n_defects_dev, rounds_dev, stream, &ww);
+}
+
+dq_status dq_wide_uf_run_weighted(dq_wide_uf* H, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
+                                  const double* p_phys_each, const double* p_meas_each, int closed, int w_space, int w_time, const uint8_t* weights_each_dev,
+                                  uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev,
+                                  int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
+    const dq_status rc = wide_check_weighted(closed, w_space, w_time, "dq_wide_uf_run_weighted");
+    if (rc != DQ_OK) return rc;
+    const WideWeights ww = {weights_each_dev, w_space, w_time};
+    return wide_run(closed != 0, "dq_wide_uf_run_weighted", H, n, T, commit, env_id_base, seed, p_phys, p_meas, p_phys_each, p_meas_each, hidden_dev, trivial_dev,
+                    frame_dev, weight_dev, n_defects_dev, rounds_dev, syndromes_dev, stream, &ww);
 }
 
 dq_status dq_wide_uf_verdict(dq_wide_uf* H, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev, void* stream) {

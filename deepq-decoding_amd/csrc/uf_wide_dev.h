@@ -12,6 +12,11 @@
 //     accumulated with LDS atomics;
 //   * the LDS is dynamic and sized from the call's (d, window) by ufw_layout, the same function on the host and on the device.
 // Every loop bound is a constant of (d, window, T, commit), which the host validates.  No scratch pool, no lock, no loop that waits on another workgroup.
+//
+// Weighted growth (ufw_component<Closed, true>): an edge of weight w is full at g = 2 w, w = w_space for k < d^2 and w_time for
+// k >= d^2, both in 1 .. UFW_MAX_WEIGHT, one pair per stream.  The growth byte then holds g in bits 0 .. 4, the edge's increment of the running event in bits
+// 5 .. 6 and "full" in bit 7; the layout is the unweighted one.  Growth jumps from event to event: the workgroup reduces the number of unit steps until the
+// next edge fills (an LDS atomic minimum into a spare word of o_acc), every growing edge gains that many increments, and `rounds` counts the unit steps.
 #pragma once
 #include "common.h"
 
@@ -22,6 +27,11 @@
 #define UFW_FRAME_WORDS 8                                        // 32-bit words of a component's frame: d^2 <= 225
 #define UFW_NONE 0xffffffffu
 #define UFW_NOLEVEL 0xffffu
+#define UFW_MAX_WEIGHT 15                                        // 2 w <= 30 fits the five growth bits
+#define UFW_G_MASK 0x1fu
+#define UFW_INC_SHIFT 5
+#define UFW_FULL 0x80u
+#define UFW_NO_EVENT 0x7fffffff
 
 struct UfwComp {
     const u8* eu;           // [d^2] qubit -> its first plaquette of the component (node index)
@@ -39,7 +49,7 @@ static __host__ __device__ inline UfwLayout ufw_layout(int n, int d2, int window
     int o = 0;
     L.o_frame = o; o += 2 * UFW_FRAME_WORDS * 4;                 // u32 [2][8] committed space edges per component
     L.o_carry = o; o += 2 * UFW_ROW_WORDS * 4;                   // u32 [2][4] the carry into the next window
-    L.o_acc = o; o += 8 * 4;                                     // int [2] weight, [2] defects, [2] growth rounds, [2] spare
+    L.o_acc = o; o += 8 * 4;                                     // int [2] weight, [2] defects, [2] growth rounds, [1] steps to the next event (weighted), [1] spare
     L.o_ring = o; o += 2 * window * UFW_ROW_WORDS * 4;           // u32 [2][window][4] defect rows of the window
     L.o_label = o; o += 4 * NN;                                  // u32 [NN] cluster label
     L.o_par = o; o += 4 * NN;                                    // u32 [NN] defect parity per label; then subtree parity per node
@@ -85,9 +95,12 @@ static __device__ __forceinline__ void ufw_ends(const UfwGraph& G, int e, int& a
 // Closed (a stream that ends on a round of perfect measurements): in a `final` window the time edges of the last round do not exist.
 // They are the last n edge ids, and the growth loop stops in front of them: never grown, they are never full, so no label crosses them, no level reaches
 // across them and they are never in the correction.
-template <bool Closed = false>
+// Weighted: w_space / w_time in 1 .. UFW_MAX_WEIGHT (the caller clamps), s_event the LDS word of the event reduction; a committed edge adds its weight to
+// *s_weight, *s_rounds counts unit growth steps.  With Weighted = false the three arguments are not read and the code is the unit-weight one.
+template <bool Closed = false, bool Weighted = false>
 static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u32* dw, u8* __restrict__ s, const UfwLayout& L, int tid, int commit, bool final,
-                                                     u32* s_frame, u32* s_carry, int* s_weight, int* s_rounds) {
+                                                     u32* s_frame, u32* s_carry, int* s_weight, int* s_rounds, int w_space = 1, int w_time = 1,
+                                                     int* s_event = nullptr) {
     u32* s_label = reinterpret_cast<u32*>(s + L.o_label);
     u32* s_par = reinterpret_cast<u32*>(s + L.o_par);
     u32* s_parent = reinterpret_cast<u32*>(s + L.o_parent);
@@ -111,43 +124,104 @@ static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u3
     __syncthreads();
     // ---- growth ---------------------------------------------------------------------------------------------------------------------------------
     int rounds = 0;
-    const int round_bound = 2 * NE;
-    for (int r = 0; r <= round_bound; ++r) {
-        for (int x = tid; x < NN; x += UFW_THREADS) v_par[x] = 0;
-        __syncthreads();
-        for (int x = tid; x < B; x += UFW_THREADS)
-            if (defect(x)) __hip_atomic_fetch_xor(s_par + v_label[x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __syncthreads();
-        bool any = false;
-        for (int x = tid; x < B; x += UFW_THREADS) { const u32 l = v_label[x]; any |= l != 0 && (v_par[l] & 1u); }
-        if (!__syncthreads_or(any) || r == round_bound) break;    // workgroup-uniform
-        ++rounds;
-        bool fresh = false;
-        for (int e = tid; e < NE_grown; e += UFW_THREADS) {
-            const int g0 = s_g[e];
-            if (g0 == 2) continue;
-            int a, b, t, k;
-            ufw_ends(G, e, a, b, t, k);
-            const u32 la = v_label[a], lb = v_label[b];
-            const int inc = (int)(la != 0 && (v_par[la] & 1u)) + (int)(lb != 0 && (v_par[lb] & 1u));
-            const int g1 = min(2, g0 + inc);
-            if (g1 != g0) { s_g[e] = (u8)g1; fresh |= g1 == 2; }
-        }
-        if (!__syncthreads_or(fresh)) continue;                   // workgroup-uniform: no new full edge, the clusters stand
-        for (int pass = 0; pass < NN; ++pass) {                   // (a label travels at least one edge per pass)
-            bool changed = false;
-            for (int e = tid; e < NE; e += UFW_THREADS) {
-                if (s_g[e] != 2) continue;
+    if constexpr (!Weighted) {
+        const int round_bound = 2 * NE;
+        for (int r = 0; r <= round_bound; ++r) {
+            for (int x = tid; x < NN; x += UFW_THREADS) v_par[x] = 0;
+            __syncthreads();
+            for (int x = tid; x < B; x += UFW_THREADS)
+                if (defect(x)) __hip_atomic_fetch_xor(s_par + v_label[x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __syncthreads();
+            bool any = false;
+            for (int x = tid; x < B; x += UFW_THREADS) { const u32 l = v_label[x]; any |= l != 0 && (v_par[l] & 1u); }
+            if (!__syncthreads_or(any) || r == round_bound) break;    // workgroup-uniform
+            ++rounds;
+            bool fresh = false;
+            for (int e = tid; e < NE_grown; e += UFW_THREADS) {
+                const int g0 = s_g[e];
+                if (g0 == 2) continue;
                 int a, b, t, k;
                 ufw_ends(G, e, a, b, t, k);
                 const u32 la = v_label[a], lb = v_label[b];
-                if (la != lb) {
-                    const u32 m = la < lb ? la : lb;
-                    __hip_atomic_fetch_min(s_label + (la < lb ? b : a), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    changed = true;
-                }
+                const int inc = (int)(la != 0 && (v_par[la] & 1u)) + (int)(lb != 0 && (v_par[lb] & 1u));
+                const int g1 = min(2, g0 + inc);
+                if (g1 != g0) { s_g[e] = (u8)g1; fresh |= g1 == 2; }
             }
-            if (!__syncthreads_or(changed)) break;                // workgroup-uniform
+            if (!__syncthreads_or(fresh)) continue;               // workgroup-uniform: no new full edge, the clusters stand
+            for (int pass = 0; pass < NN; ++pass) {               // (a label travels at least one edge per pass)
+                bool changed = false;
+                for (int e = tid; e < NE; e += UFW_THREADS) {
+                    if (s_g[e] != 2) continue;
+                    int a, b, t, k;
+                    ufw_ends(G, e, a, b, t, k);
+                    const u32 la = v_label[a], lb = v_label[b];
+                    if (la != lb) {
+                        const u32 m = la < lb ? la : lb;
+                        __hip_atomic_fetch_min(s_label + (la < lb ? b : a), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        changed = true;
+                    }
+                }
+                if (!__syncthreads_or(changed)) break;            // workgroup-uniform
+            }
+        }
+    } else {
+        // One event per pass: the steps until the next edge fills are reduced over the workgroup, every growing edge gains that many increments, and at
+        // least one edge fills.  So NE_grown + 1 passes cover any growth, a constant of the window's shape.
+        volatile int* v_event = s_event;
+        int events_left = NE_grown + 1;
+        asm volatile("" : "+v"(events_left));                 // (uf_wide.h UFW_IN_VGPR: the scalar registers are the scarce ones)
+        for (;; --events_left) {
+            if (tid == 0) *v_event = UFW_NO_EVENT;                // (the previous pass read it in front of its last barriers)
+            for (int x = tid; x < NN; x += UFW_THREADS) v_par[x] = 0;
+            __syncthreads();
+            for (int x = tid; x < B; x += UFW_THREADS)
+                if (defect(x)) __hip_atomic_fetch_xor(s_par + v_label[x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __syncthreads();
+            bool any = false;
+            for (int x = tid; x < B; x += UFW_THREADS) { const u32 l = v_label[x]; any |= l != 0 && (v_par[l] & 1u); }
+            if (!__syncthreads_or(any) || events_left == 0) break;    // workgroup-uniform
+            int steps = UFW_NO_EVENT;
+            for (int e = tid; e < NE_grown; e += UFW_THREADS) {
+                const u32 g0 = s_g[e];
+                if (g0 & UFW_FULL) continue;
+                int a, b, t, k;
+                ufw_ends(G, e, a, b, t, k);
+                const u32 la = v_label[a], lb = v_label[b];
+                const int inc = (int)(la != 0 && (v_par[la] & 1u)) + (int)(lb != 0 && (v_par[lb] & 1u));
+                if (!inc) continue;
+                const int left = 2 * (k < G.d2 ? w_space : w_time) - (int)g0;  // > 0: the edge is not full
+                steps = min(steps, (left + inc - 1) >> (inc - 1));             // ceil(left / inc), inc in {1, 2}
+                s_g[e] = (u8)(g0 | ((u32)inc << UFW_INC_SHIFT));
+            }
+            if (steps != UFW_NO_EVENT) __hip_atomic_fetch_min(s_event, steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __syncthreads();
+            const int jump = *v_event;                            // one word, written in front of the barrier: workgroup-uniform
+            if (jump == UFW_NO_EVENT) break;                      // (an odd cluster without B always has a growing edge; were there none, nothing could change)
+            rounds += jump;
+            for (int e = tid; e < NE_grown; e += UFW_THREADS) {   // (thread and edge as above: an increment is read by the thread that wrote it)
+                const u32 g0 = s_g[e];
+                const int inc = (int)((g0 >> UFW_INC_SHIFT) & 3u);
+                if (!inc) continue;
+                const int t = ufw_div(e, G.mag_pr), k = e - t * G.per_round, cap = 2 * (k < G.d2 ? w_space : w_time);
+                const int g1 = min(cap, (int)(g0 & UFW_G_MASK) + inc * jump);
+                s_g[e] = (u8)(g1 == cap ? (u32)g1 | UFW_FULL : (u32)g1);
+            }
+            __syncthreads();
+            for (int pass = 0; pass < NN; ++pass) {               // (a label travels at least one edge per pass)
+                bool changed = false;
+                for (int e = tid; e < NE; e += UFW_THREADS) {
+                    if (!(s_g[e] & UFW_FULL)) continue;
+                    int a, b, t, k;
+                    ufw_ends(G, e, a, b, t, k);
+                    const u32 la = v_label[a], lb = v_label[b];
+                    if (la != lb) {
+                        const u32 m = la < lb ? la : lb;
+                        __hip_atomic_fetch_min(s_label + (la < lb ? b : a), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        changed = true;
+                    }
+                }
+                if (!__syncthreads_or(changed)) break;            // workgroup-uniform
+            }
         }
     }
     // ---- peeling: levels and parent edges ---------------------------------------------------------------------------------------------------------
@@ -160,7 +234,7 @@ static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u3
     int deepest = 0;
     for (int lev = 1; lev < NN; ++lev) {
         for (int e = tid; e < NE; e += UFW_THREADS) {
-            if (s_g[e] != 2) continue;
+            if (Weighted ? !(s_g[e] & UFW_FULL) : s_g[e] != 2) continue;
             int a, b, t, k;
             ufw_ends(G, e, a, b, t, k);
             const u32 va = s_level[a], vb = s_level[b];
@@ -190,7 +264,7 @@ static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u3
                     __hip_atomic_fetch_or(s_carry + (u >> 5), 1u << (u & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
-            ++w;
+            w += Weighted ? (k < G.d2 ? w_space : w_time) : 1;
             if (k < G.d2) __hip_atomic_fetch_xor(s_frame + (k >> 5), 1u << (k & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         __syncthreads();

@@ -7,11 +7,16 @@ The algorithm and the window schedule are section 17's; for d <= 7 and window <=
 (verdict_wide, memory_experiment_wide, DQNAgent.decode_benchmark_wide) sends the residual's true syndrome through the matching referee,
 as the wide environment's step does: death_rate is then the share of volumes on which the environment would have ended the episode.
 
+weights= (stream_decode_wide, memory_experiment_wide) decodes on a weighted graph: an edge of weight w is full at growth 2 w, w_space
+for the space edges and w_time for the time edges, so that a misread stabilizer and a flipped qubit cost what their rates say (uf_weights).  None is the
+unit-weight launch of before, untouched.
+
 Further down: the union-find decoder as a policy and a teacher of the wide environment (section 19), and batched decoding by a trained agent at these
 sizes -- WideBatchDecoder, the wide form of decoder.BatchDecoder, and the scorer behind DQNAgent.decode_benchmark_wide (include/deepq_hip.h
 dq_decode_wide_*; csrc/decode_wide.hip).
 """
 import ctypes
+import math
 
 import numpy as np
 
@@ -21,6 +26,7 @@ from .decoder import (DEFAULT_CHUNK, MODELS, STATUS_IDENTITY, STREAM_MAX_ROUNDS,
 
 WIDE_MAX_D = 15
 WIDE_MAX_WINDOW = 32
+WIDE_MAX_WEIGHT = 15
 
 
 def check_wide_lattice(d, error_model):
@@ -54,6 +60,80 @@ def check_referee(referee):
     if referee is not None and not (isinstance(referee, str) and referee == "matching"):
         raise ValueError(f"referee must be None or 'matching', not {referee!r}")
     return referee is not None
+
+
+def uf_weights(p_phys, p_meas, error_model, max_weight=8):
+    """The coprime pair (w_space, w_time) in 1 .. max_weight whose ratio is closest, in the logarithm, to L(q_space) / L(q_time), L(q) = ln((1 - q) / q):
+    q_space the chance that a qubit flips in one component per round (p_phys for X and IIDXZ, 2 p_phys / 3 for DP), q_time = p_meas, both clamped to
+    [1e-12, 0.5 - 1e-12].  Ties go to the smaller sum; equal rates under X give (1, 1)."""
+    if error_model not in MODELS:
+        raise ValueError(f"error model {error_model!r} is not one of X, DP, IIDXZ")
+    if not is_int(max_weight) or not 1 <= max_weight <= WIDE_MAX_WEIGHT:
+        raise ValueError(f"max_weight must be an integer in 1..{WIDE_MAX_WEIGHT}, not {max_weight!r}")
+    for name, p in (("p_phys", p_phys), ("p_meas", p_meas)):
+        if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(p) <= 1.0:
+            raise ValueError(f"{name} must be a rate in [0, 1], not {p!r}")
+    clamp = lambda q: min(max(float(q), 1e-12), 0.5 - 1e-12)
+    L = lambda q: math.log((1.0 - q) / q)
+    q_space, q_time = clamp(float(p_phys) * (2.0 / 3.0 if error_model == "DP" else 1.0)), clamp(p_meas)
+    target = math.log(L(q_space) / L(q_time))
+    best = None
+    for ws in range(1, int(max_weight) + 1):
+        for wt in range(1, int(max_weight) + 1):
+            if math.gcd(ws, wt) != 1:
+                continue
+            err = abs(math.log(ws / wt) - target)
+            if best is None or err < best[0] - 1e-12 or (abs(err - best[0]) <= 1e-12 and ws + wt < best[1] + best[2]):
+                best = (err, ws, wt)
+    return best[1], best[2]
+
+
+def check_weights(weights, n=None, rates=False):
+    """weights= of the wide entry points, validated without touching the library: None; a pair (w_space, w_time) of integers in 1 .. 15, returned as a tuple;
+    with n, an integer array [n, 2] of such pairs, returned as uint8 [n, 2]; with rates, the string "rates", returned as it is.  Else ValueError."""
+    if weights is None:
+        return None
+    what = "a pair (w_space, w_time)" + (" or 'rates'" if rates else "") + (f" or an integer array [{n}, 2]" if n is not None else "")
+    if isinstance(weights, str):
+        if rates and weights == "rates":
+            return weights
+        raise ValueError(f"weights must be None, {what}, not {weights!r}")
+    if hasattr(weights, "detach"):                                    # a torch tensor
+        weights = weights.detach().cpu().numpy()
+    if isinstance(weights, (tuple, list)) and len(weights) == 2 and all(is_int(x) for x in weights):
+        a = np.asarray(weights, dtype=np.int64)
+    elif isinstance(weights, (tuple, list)) and all(isinstance(r, (tuple, list)) and all(is_int(x) for x in r) for r in weights):
+        a = np.asarray([list(r) for r in weights] or [[]], dtype=np.int64)
+    elif isinstance(weights, np.ndarray) and weights.dtype.kind in "iu":
+        a = weights
+    else:
+        raise ValueError(f"weights must be None, {what}, of integers in 1..{WIDE_MAX_WEIGHT}, not {weights!r}")
+    if a.shape != (2,) and (n is None or a.shape != (n, 2)):
+        raise ValueError(f"weights must be None, {what}, not shape {a.shape}")
+    if int(a.min()) < 1 or int(a.max()) > WIDE_MAX_WEIGHT:
+        raise ValueError(f"weights must lie in 1..{WIDE_MAX_WEIGHT}, not {weights!r}")
+    return (int(a[0]), int(a[1])) if a.ndim == 1 else np.ascontiguousarray(a.astype(np.uint8))
+
+
+def rate_weights(p_phys, p_meas, error_model, n):
+    """weights="rates": uf_weights of every stream's own (p_phys, p_meas).  Returns one pair where the rates are scalars, else uint8 [n, 2]."""
+    if isinstance(p_phys, float):
+        return uf_weights(p_phys, p_meas, error_model)
+    out = np.empty((n, 2), dtype=np.uint8)
+    pairs = {}
+    for i, key in enumerate(zip(p_phys.tolist(), p_meas.tolist())):
+        if key not in pairs:
+            pairs[key] = uf_weights(key[0], key[1], error_model)
+        out[i] = pairs[key]
+    return out
+
+
+def weights_kw(weights, dev, s=0, m=None):
+    """What decode_into / run_into take as weights= for streams s .. s + m: nothing for None (the unweighted call, argument for argument), the pair, or
+    the streams' rows of a uint8 device tensor [N, 2]."""
+    if weights is None:
+        return {}
+    return dict(weights=weights if isinstance(weights, tuple) else weights[s:s + m])
 
 
 def check_wide_evaluator(evaluator, d, error_model, window):
@@ -165,21 +245,36 @@ class WideEvaluator(Counting):
             self._m = m
         return self._m
 
-    def decode_into(self, syndromes, m, T, commit, frame, weight=None, n_defects=None, rounds=None, final_round="faulty"):
+    def decode_into(self, syndromes, m, T, commit, frame, weight=None, n_defects=None, rounds=None, final_round="faulty", weights=None):
         """The sliding-window decode (dq_wide_uf_decode) of m <= chunk streams of T rounds already on the device.  final_round="perfect":
-        dq_wide_uf_decode_closed."""
+        dq_wide_uf_decode_closed.  weights: a pair (w_space, w_time) or a uint8 device tensor [m, 2], both validated by the caller (check_weights):
+        dq_wide_uf_decode_weighted."""
         from . import _lib
+        if weights is not None:
+            pair, each = (weights, None) if isinstance(weights, tuple) else ((1, 1), weights)
+            _lib.check(self.L.dq_wide_uf_decode_weighted(self._h, _lib.ptr(syndromes), m, T, commit, int(check_final_round(final_round)), pair[0], pair[1],
+                                                         _lib.ptr(each), _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
+                                                         self._stream()))
+            return
         fn = self.L.dq_wide_uf_decode_closed if check_final_round(final_round) else self.L.dq_wide_uf_decode
         _lib.check(fn(self._h, _lib.ptr(syndromes), m, T, commit, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), self._stream()))
 
     def run_into(self, m, T, commit, lattice_id, seed, p_phys, p_meas, hidden, trivial, frame, weight=None, n_defects=None, rounds=None, syndromes=None,
-                 final_round="faulty"):
+                 final_round="faulty", weights=None):
         """m <= chunk streams of T rounds of lattices lattice_id .. lattice_id + m - 1 (mod 2^32), sampled and decoded in one kernel (dq_wide_uf_run).
-        final_round="perfect": dq_wide_uf_run_closed."""
+        final_round="perfect": dq_wide_uf_run_closed.  weights: as decode_into's: dq_wide_uf_run_weighted."""
         from . import _lib
-        fn = self.L.dq_wide_uf_run_closed if check_final_round(final_round) else self.L.dq_wide_uf_run
         arr = (ctypes.c_uint32 * 2)(*seed)
         each = not isinstance(p_phys, float)
+        if weights is not None:
+            pair, w_each = (weights, None) if isinstance(weights, tuple) else ((1, 1), weights)
+            _lib.check(self.L.dq_wide_uf_run_weighted(self._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
+                                                      p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None,
+                                                      int(check_final_round(final_round)), pair[0], pair[1], _lib.ptr(w_each), _lib.ptr(hidden),
+                                                      _lib.ptr(trivial), _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
+                                                      _lib.ptr(syndromes), self._stream()))
+            return
+        fn = self.L.dq_wide_uf_run_closed if check_final_round(final_round) else self.L.dq_wide_uf_run
         _lib.check(fn(self._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
                       p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, _lib.ptr(hidden), _lib.ptr(trivial),
                       _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), _lib.ptr(syndromes), self._stream()))
@@ -197,15 +292,18 @@ class WideEvaluator(Counting):
                                                       self._stream()))
 
 
-def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None, final_round="faulty"):
+def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None, final_round="faulty", weights=None):
     """decoder.stream_decode for any odd d in 3 .. 15 and a window of up to 32 rounds.  syndromes: uint8 [N, T, d+1, d+1] with 0/1 cells, or one stream
     [T, d+1, d+1], numpy or torch; window defaults to min(2 d, 32), commit to (window + 1) // 2.  Returns a decoder.StreamResult of device tensors (numpy
     arrays with to_host); the result of a stream does not depend on the batch around it or on `chunk`.  evaluator: a WideEvaluator of this d and window to
     run on (its chunk is used and it stays open); default: one for this call.  final_round="perfect": decoder.stream_decode's closed form (DESIGN.md
-    section 20)."""
+    section 20).  weights: None (unit weights: the launch of before), a pair (w_space, w_time) of integers in 1 .. 15 for every stream, or an integer
+    array [N, 2] with one pair per stream: an edge of weight w is full at growth 2 w, StreamResult.weight is the weighted cost
+    of the committed edges and StreamResult.rounds counts unit growth rounds."""
     import torch
     closed = closed_kw(final_round)
     d, n, single, T, window, commit, chunk = check_wide_stream_args(syndromes, d, window, commit, chunk, evaluator)
+    weights = check_weights(weights, n)
     ev = WideEvaluator(d, "DP", window, chunk=min(chunk, n)) if evaluator is None else evaluator
     dev = ev.device
     try:
@@ -213,10 +311,13 @@ def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHU
         syn = syn.reshape(n, T, d + 1, d + 1).contiguous()
         frame = torch.empty((n, d, d), dtype=torch.uint8, device=dev)
         weight, ndef, rounds = (torch.empty((n, 2), dtype=torch.int32, device=dev) for _ in range(3))
+        if isinstance(weights, np.ndarray):
+            weights = torch.from_numpy(weights).to(device=dev)
         with torch.cuda.device(dev):
             for s in range(0, n, ev.chunk):
                 m = min(ev.chunk, n - s)
-                ev.decode_into(syn[s:s + m], m, T, commit, frame[s:s + m], weight[s:s + m], ndef[s:s + m], rounds[s:s + m], **closed)
+                ev.decode_into(syn[s:s + m], m, T, commit, frame[s:s + m], weight[s:s + m], ndef[s:s + m], rounds[s:s + m], **closed,
+                               **weights_kw(weights, dev, s, m))
             torch.cuda.current_stream(dev).synchronize()
     finally:
         if evaluator is None:
@@ -297,7 +398,8 @@ def uncorrected_into(ev, hidden, m, out, flags=None):
 
 
 def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0,
-                           chunk=DEFAULT_CHUNK, no_decoder=False, timings=None, evaluator=None, return_streams=False, final_round="faulty", referee=None):
+                           chunk=DEFAULT_CHUNK, no_decoder=False, timings=None, evaluator=None, return_streams=False, final_round="faulty", referee=None,
+                           weights=None):
     """decoder.memory_experiment for any odd d in 3 .. 15 and a window of up to 32 rounds: n_runs streams, stream i the first `rounds` rounds of lattice
     env_id_base + i under sample_volumes' convention, sampled and decoded in ONE kernel per chunk (dq_wide_uf_run), then verdict -> counts on the device.
     lattice: (d, error_model), or an environment of either backend, of which only d, error_model, the rates and the seed are read (the defaults of p_phys /
@@ -311,20 +413,30 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
     n_runs modest there.
     timings: a dict that receives the wall seconds of the phases run / verdict.  evaluator: a WideEvaluator of this lattice and window.  return_streams:
     also returns dict(syndromes uint8 [N, rounds, d+1, d+1], hidden, frame uint8 [N, d, d], trivial uint8 [N]) of device tensors.  final_round="perfect":
-    decoder.memory_experiment's closed form."""
+    decoder.memory_experiment's closed form.  weights: None (unit weights: the launches of before), a pair (w_space, w_time) of
+    integers in 1 .. 15, or "rates": uf_weights of each stream's own (p_phys, p_meas) under the lattice's error model -- with rates=[...] every rate
+    block gets its own pair, in the same launches.  Every EvalResult of the answer then has .weights, the pair its streams were
+    decoded with (None without weights); it combines with final_round= and referee= without restriction."""
     import torch
     closed = closed_kw(final_round)
     refereed = check_referee(referee)
+    weights = check_weights(weights, rates=True)
     d, model, T, window, commit, n, ph, pm, seed, base, blk, keys, chunk = check_wide_experiment_args(
         lattice, n_runs, rounds, window, commit, rates, p_phys, p_meas, seed, env_id_base, chunk, evaluator)
+    if weights == "rates":
+        weights = rate_weights(ph, pm, model, n)
+    used = weights                                                    # None, the pair, or uint8 [n, 2] on the host
     ev = WideEvaluator(d, model, window, chunk=min(chunk, n)) if evaluator is None else evaluator
     dev = ev.device
     try:
         flags = torch.empty(min(ev.chunk, n), dtype=torch.uint8, device=dev) if refereed else None
         ref_kw = dict(referee=referee, inexact=flags) if refereed else {}     # (no referee: the call of before, argument for argument)
 
+        if isinstance(weights, np.ndarray):
+            weights = torch.from_numpy(weights).to(device=dev)
+
         def run(m, s, a, b, hid, triv, frame, syn):
-            ev.run_into(m, T, commit, base + s, seed, a, b, hid, triv, frame, syndromes=syn, **closed)
+            ev.run_into(m, T, commit, base + s, seed, a, b, hid, triv, frame, syndromes=syn, **closed, **weights_kw(weights, dev, s, m))
 
         with torch.cuda.device(dev):
             results, streams = score_streams(ev, dev, n, T, ph, pm, blk, run, lambda hid, frame, m, out: ev.verdict_into(hid, frame, m, out, **ref_kw),
@@ -333,6 +445,14 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
     finally:
         if evaluator is None:
             ev.close()
+    for k, r in enumerate(results):                                   # (a block of rates=[...] holds one rate pair, so one pair of weights)
+        if used is None or isinstance(used, tuple):
+            r.weights = used
+        else:
+            pairs = [(int(a), int(b)) for a, b in np.unique(used[k * blk:(k + 1) * blk], axis=0)]
+            r.weights = pairs[0] if len(pairs) == 1 else pairs
+        if r.no_decoder is not None:
+            r.no_decoder.weights = None
     return (keyed(results, keys), streams) if return_streams else keyed(results, keys)
 
 

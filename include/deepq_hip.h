@@ -910,6 +910,25 @@ dq_status dq_wide_uf_decode_closed(dq_wide_uf* h, const uint8_t* syndromes_dev, 
 dq_status dq_wide_uf_run_closed(dq_wide_uf* h, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
                                 const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev,
                                 int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
+/* Weighted union-find.  dq_version() stays 8: the capability is the presence of these two symbols.  The algorithm, the window schedule,
+ * the carry and the closed final window are dq_wide_uf_decode's / dq_wide_uf_run's with one change: an edge has an integer weight w and is full when its
+ * growth reaches 2 w instead of 2 -- w_space for the space edges (those to the boundary included), w_time for the time edges (the last round's edges to the
+ * boundary included).  In a growth round an edge gains 1 per end in an active cluster; rounds_dev counts these unit rounds (the kernel jumps from one filling
+ * edge to the next, which changes no result), weight_dev is the sum of the weights of the committed edges.  With (1, 1) every field equals the unweighted
+ * forms'; (k w_space, k w_time) gives the frame of (w_space, w_time), k times its rounds and k times its weight.  One pair holds for a whole stream, every
+ * window and both components.
+ * closed: 0 = dq_wide_uf_decode / dq_wide_uf_run, 1 = their _closed forms.  w_space, w_time: the pair of every stream, each in 1 .. 15.
+ * weights_each_dev (nullable): uint8 [n][2] on the device, (w_space, w_time) of stream i; it replaces the uniform pair, which must still be valid.  The
+ * caller keeps its bytes in 1 .. 15; the kernel clamps them to that range, so a bad byte changes a result but cannot overrun the growth byte.
+ * Every other argument, the validation and the error codes are those of the unweighted forms; closed outside {0, 1} or a uniform weight outside 1 .. 15 is
+ * DQ_ERR_INVALID before any device work.  The environment policies (dq_envb_uf_select, dq_envb_guided_select_uf) keep unit weights. */
+dq_status dq_wide_uf_decode_weighted(dq_wide_uf* h, const uint8_t* syndromes_dev, int n, int T, int commit, int closed, int w_space, int w_time,
+                                     const uint8_t* weights_each_dev, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev,
+                                     void* stream);
+dq_status dq_wide_uf_run_weighted(dq_wide_uf* h, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
+                                  const double* p_phys_each, const double* p_meas_each, int closed, int w_space, int w_time, const uint8_t* weights_each_dev,
+                                  uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev,
+                                  int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
 
 /* The union-find decoder as a policy and as a teacher of the wide environment, any odd d in 3 .. 15 (csrc/env_wide_uf.hip).
  * dq_version() stays 8: the capability is the presence of these two symbols.  The rules are dq_env_uf_select's and dq_env_guided_select_uf's on the wide
