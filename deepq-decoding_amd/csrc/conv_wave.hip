@@ -178,6 +178,7 @@ __global__ __launch_bounds__(CW_THREADS) void conv_wave_kernel(ConvWaveArgs a) {
 
 #ifndef CW_BITS_LIVE
 #define CW_BITS_LIVE 1                                              // 1: the four expanded bytes stay in 16 registers over the quarters; 0: re-read from the table per quarter
+                                                                    // (state 0 is UNMEASURED: no record of a run of it exists, so the switch stays until one does)
 #endif
         u32 la[2][T1];                                              // the bytes' table entries
 #pragma unroll

@@ -28,43 +28,9 @@
 
 DQ_STAMP_READER(dq_dbg_read_fwd)
 
-// Build-time switches of the one-box A/B comparisons (tools/build_ab.sh; DESIGN.md section 4 records what each measured):
-//   CONV_PIN / DENSE_PIN   sched_barrier pins that keep the weight-ring requests a whole block of MFMAs ahead of their use (+1 %: on)
-//   CONV_APIPE             conv2 / conv3: the A pieces of K block b + 1 are read before block b's MFMAs (+0.4 us: on)
-//   DENSE_XPIPE            the same for the dense forward's input pieces (neutral: on)
-//   DQ_EXP_NODROP / DQ_EXP_NOSTORE   TIMING EXPERIMENTS ONLY -- the training forward without its dropout arithmetic / without its saved
-//                          activations: WRONG RESULTS, used to price those parts of the training workgroups (never set in a product build)
-#ifndef CONV_PIN
-#define CONV_PIN 1
-#endif
-#ifndef DENSE_PIN
-#define DENSE_PIN 1
-#endif
-#ifndef CONV_APIPE
-#define CONV_APIPE 1
-#endif
-#ifndef DENSE_XPIPE
-#define DENSE_XPIPE 1
-#endif
-#ifndef CONV_SWZ
-#define CONV_SWZ 0                 // 1: a1 planes unpadded with their 16-byte chunks XOR-swizzled by pixel column (conv2's A reads conflict-free at d = 5): LDS bank
-                                   // conflicts -59 %, LDS-active cycles -24 %, VALU +12 %, kernel +1.7 us -- off; 0: rows padded by 8 halves
-#endif
-#define A1_PS (CONV_SWZ ? 64 : 72)  // halves per a1 pixel row in LDS
-#ifndef CONV1_PIPE
-#define CONV1_PIPE 0               // persistent conv forward, EXPERIMENT (measured neutral): 1 = the first convolution software-pipelined across tiles (tile
-                                   // t + 4's MFMAs in one basic block with tile t's epilogue; a1 planes hold whole tiles, rows past the end are stored too), 2 = the same
-                                   // with sched_group_barrier interleaving (one MFMA, six VALU, one LDS read, ...)
-#endif
-#ifndef DQ_EXP_NODROP
-#define DQ_EXP_NODROP 0
-#endif
-#ifndef DQ_EXP_NOSTORE
-#define DQ_EXP_NOSTORE 0
-#endif
-#if DQ_EXP_NODROP || DQ_EXP_NOSTORE
-#warning "timing-experiment build: the training forward's results are wrong"
-#endif
+// Build-time switch (a tunable number): DENSE_PR, below.  The A/B experiments this file once carried behind switches are settled; DESIGN.md section 4
+// records what each measured and the last commit that holds its code.
+#define A1_PS 72                   // halves per a1 pixel row in LDS: 64 channels padded by 8 (the persistent kernel and the patch-word input use unpadded rows of 64)
 #define CONV_THREADS 256
 #define CONV_WAVES 4
 #define CONV_LDS_2PER_CU (80 * 1024)
@@ -84,7 +50,6 @@ struct ConvChainArgs {
     const int* rowtab0;                // the first convolution's table: rowtab, or with patch-word input qnet.h PT_FWD
     int slot;                          // bytes per sample slot in LDS (multiple of 16, >= C*H*W + 30)
     int off_mis, off_t1, off_a1, off_a2;   // LDS byte offsets (observations at 0; a2 overlays observations + tables)
-    int off_fx;                        // CONV_SWZ: byte per first-convolution output row = its chunk swizzle in halves (8 * f, f = 2 (ox & 3))
     int total_groups, off_obs1, off_a2b;   // persistent kernel: groups of S samples over all jobs; second observation buffer; a2 when the group's observations are in it
     // patch-word input (the kernels' KG1 == 0 instances; qnet.h PT_*, c1c, b1p): observation rows are `slot` bytes of u32 words, 16-byte aligned
     int off_lut;                       // LDS: byte -> its eight bits as f16 0 / 1 (256 x 16 bytes), built by the workgroup
@@ -132,20 +97,15 @@ __device__ __forceinline__ void conv_w_prefetch(F16x2 (&ring)[R][NT], const u32x
     for (int b = 0; b < R; ++b) conv_w_load<NT>(ring[b], pk, b, lane);
 }
 
-// SWZ (the second convolution with CONV_SWZ): the input planes' rows are CIN halves, unpadded, and pixel (y, x)'s 16-byte chunk c sits at chunk
-// c ^ f(x), f(x) = 2 (x & 3).  With the lane groups ds_read_b128 is served in (MI355X_MICROARCH.md LDS table: rows 0-3, 12-15 of chunk kb together
-// with rows 4-11 of chunk kb + 1) the padded rows put two or three rows on the same banks in every group at d = 5 (12 LDS cycles per read against
-// 4; tools/probe/lds_swizzle.py enumerates it); the swizzle makes every group's 16 chunks hit 16 different bank quadruples for all four taps.
-// The row table then carries ox & 3 in bits 24+ and the lane keeps one address per (row tile, kx, channel half).
-template <int CIN, int COUT, int KS, int RR, int NTT, bool SWZ = false, int PADI = 8>
+// PADI: padding of the input planes' rows in halves (0: the unpadded a1 rows of the persistent kernel and of the patch-word input).
+template <int CIN, int COUT, int KS, int RR, int NTT, int PADI = 8>
 __device__ __forceinline__ void conv_from_lds(const unsigned short* __restrict__ in, int lo_in, int ih, int iw, int oh, int ow, int M,
                                               F16x2 (&ring)[RR][NTT], const u32x4* __restrict__ pk, const float* __restrict__ bias,
                                               unsigned short* __restrict__ out_lds, int lo_out, float* __restrict__ out_g, int wave, int lane,
                                               const int* __restrict__ rowtab, int pre0, int pre1, range_mask& rbad) {
     using SH = ConvShape<CIN, COUT, KS>;
-    constexpr int NT = SH::NT, PSI = SWZ ? CIN : CIN + PADI, PSO = COUT + 8, CB = SH::CB, NB = SH::NB, R = SH::R;
+    constexpr int NT = SH::NT, PSI = CIN + PADI, PSO = COUT + 8, CB = SH::CB, NB = SH::NB, R = SH::R;
     static_assert(NT == 2 && CIN % 32 == 0 && RR == R && NTT == NT, "written for 32 output channels, CIN a multiple of 32");
-    static_assert(!SWZ || (CIN == 64 && KS == 2), "the swizzle is laid out for 64 input channels (8 chunks per row) and 2 x 2 taps");
     const int j = lane & 15, kb = lane >> 4;
     const f32x2 bias2 = *reinterpret_cast<const f32x2*>(bias + 2 * j);
     const int tiles = (M + 15) >> 4;
@@ -162,18 +122,6 @@ __device__ __forceinline__ void conv_from_lds(const unsigned short* __restrict__
             for (int u = 0; u < 2; ++u) ent[u] = rowtab[min((t0 + u) * 16 + j, M - 1)];
         }
         int abase[2] = {ent[0] + 8 * kb, ent[1] + 8 * kb};
-        int sa[2][2][2];                                            // SWZ: [row tile][kx][channel half]: halves to this lane's chunk of tap (0, kx)
-        if (SWZ) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int kx = 0; kx < 2; ++kx) {
-                    const int f8 = (((ent[u] >> 24) + kx) & 3) << 4;                  // 8 f(x + kx) halves: 0, 16, 32, 48
-                    const int low = (ent[u] & 0xffffff) + kx * PSI + ((8 * kb) ^ (f8 & 16));
-                    sa[u][kx][0] = low + (f8 & 32);
-                    sa[u][kx][1] = low + (32 ^ (f8 & 32));
-                }
-        }
         f32x4 acc[2][NT][2];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
@@ -181,32 +129,30 @@ __device__ __forceinline__ void conv_from_lds(const unsigned short* __restrict__
             for (int t = 0; t < NT; ++t) { acc[u][t][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[u][t][1] = acc[u][t][0]; }
         // the weights stream through a ring of R blocks: block blk + R is requested as soon as block blk's MFMAs are issued, so the
         // L1/L2 weight traffic (every wave reads the whole layer) overlaps the matrix pipe instead of alternating with it
-        // ... and the A pieces of block blk + 1 are read from LDS BEFORE block blk's MFMAs are issued (CONV_APIPE): read next to their use,
-        // every block waited out two LDS latencies (one per row tile) with the matrix pipe idle
+        // ... and the A pieces of block blk + 1 are read from LDS BEFORE block blk's MFMAs are issued (measured +0.4 us against reading them next to
+        // their use, where every block waited out two LDS latencies -- one per row tile -- with the matrix pipe idle)
         auto a_read = [&](int blk, F16x2 (&av)[2]) {
             const int tap = blk / CB, c32 = blk - tap * CB, ky = tap / KS, kx = tap - ky * KS;
             const int off = (ky * iw + kx) * PSI + 32 * c32;
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                const unsigned short* ap = SWZ ? in + sa[u][kx & 1][c32 & 1] + ky * iw * PSI : in + abase[u] + off;
+                const unsigned short* ap = in + abase[u] + off;
                 av[u].h = *reinterpret_cast<const u32x4*>(ap);
                 av[u].l = *reinterpret_cast<const u32x4*>(ap + lo_in);
             }
         };
         F16x2 avr[2][2];
-        if (CONV_APIPE) a_read(0, avr[0]);
+        a_read(0, avr[0]);
 #pragma unroll
         for (int blk = 0; blk < NB; ++blk) {
-            if (CONV_APIPE) {
-                if (blk + 1 < NB) { a_read(blk + 1, avr[(blk + 1) & 1]); __builtin_amdgcn_sched_barrier(0); }
-            } else a_read(blk, avr[blk & 1]);
+            if (blk + 1 < NB) { a_read(blk + 1, avr[(blk + 1) & 1]); __builtin_amdgcn_sched_barrier(0); }
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int t = 0; t < NT; ++t) mma_f16x3(avr[blk & 1][u], ring[blk % R][t], acc[u][t][0], acc[u][t][1]);
             if (blk + R < NB) conv_w_load<NT>(ring[blk % R], pk, blk + R, lane);
             else if (more) conv_w_load<NT>(ring[blk % R], pk, blk + R - NB, lane);
-            if (CONV_PIN) __builtin_amdgcn_sched_barrier(0);        // the requests stay R blocks ahead of their use
+            __builtin_amdgcn_sched_barrier(0);                      // the requests stay R blocks ahead of their use (measured +1 %)
         }
         // C/D layout of 16x16x32: col = lane & 15, row = (lane >> 4) * 4 + reg; this lane owns columns 2j, 2j+1
 #pragma unroll
@@ -247,35 +193,35 @@ __device__ __forceinline__ void conv_from_lds(const unsigned short* __restrict__
 //   wb      [piece][column tile] the compact kernel's pieces (qnet.h c1c);  b1p  [r1][64] f32
 // Output: a1 piece planes, rows of 64 halves (l plane lo1 halves further), rows < M1 only.
 #define PATCH_BT 4
-#ifndef PATCH_SPLIT
-#define PATCH_SPLIT 0                   // 1: the odd last tile (13 tiles on 4 waves at 8 samples of d = 5) shared by waves 0 and 1, two column tiles each (below).
-                                        // Measured (one box, twice each, tools/ab_run.sh): conv forward 43.5-43.7 us with it against 42.0 without -- the critical wave
-                                        // does half a tile less, the kernel is 1.6 us SLOWER (four more live registers per lane, two more code paths in the unrolled
-                                        // tile loop): off; same bits either way (tests/test_compact_gpu.py passes with both)
-#endif
-// ent(m): table entry of row m (any source); this lane's rows 4kq .. 4kq+3 of its wave's first PATCH_BT tiles, and (bpx) of the group's LAST tile
+// ent(m): table entry of row m (any source); this lane's rows 4kq .. 4kq+3 of its wave's first PATCH_BT tiles
 template <typename EntFn>
-__device__ __forceinline__ void conv1_patch_bias(f32x4 (&bp)[PATCH_BT][4], f32x4 (&bpx)[4], const float* __restrict__ b1p, int slot, int wfirst, int last_tile,
-                                                 int j, int kq, EntFn ent) {
+__device__ __forceinline__ void conv1_patch_bias(f32x4 (&bp)[PATCH_BT][4], const float* __restrict__ b1p, int slot, int wfirst, int j, int kq, EntFn ent) {
 #pragma unroll
     for (int u = 0; u < PATCH_BT; ++u)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             bp[u][r] = *reinterpret_cast<const f32x4*>(b1p + ((ent((wfirst + CONV_WAVES * u) * 16 + 4 * kq + r) & (slot - 1)) << 4) + 4 * j);     // 4 p -> p * 64 floats
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bpx[r] = *reinterpret_cast<const f32x4*>(b1p + ((ent(last_tile * 16 + 4 * kq + r) & (slot - 1)) << 4) + 4 * j);
 }
 
-// Tile balance: M1 rows are ceil(M1 / 16) tiles on CONV_WAVES waves, tile t to wave t mod 4 -- 13 tiles at 8 samples of d = 5 (and at 4 of d = 7): wave 0
-// has four, the others three, and the barrier behind the phase waits for wave 0 (phase stamps: 6.6K cycles against 4.7K).  When the count is
-// 4 n + 1 the LAST tile is shared: wave 0 computes its column tiles 0, 1 (this lane's channels 4j, 4j + 1), wave 1 its column tiles 2, 3 -- half the MFMAs
-// and half the epilogue each: 3.5 tile times instead of 4 on the critical wave.
+// The tail of the first convolution's epilogue for output pixel mo (all three forms of conv1): v = this lane's four consecutive channels 4j .. 4j + 3 behind
+// bias and ReLU; the range guard and the split on write into the a1 piece planes -- rows of `ps` halves, the l plane lo1 halves further.
+__device__ __forceinline__ void conv1_store_a1(f32x4 v, unsigned short* s_a1, int ps, int lo1, int mo, int j, range_mask& rbad) {
+    range_track4(rbad, v);
+    u32 hp[2], lp[2];
+    split_f16x2_pair(v[0], v[1], hp[0], lp[0]);
+    split_f16x2_pair(v[2], v[3], hp[1], lp[1]);
+    unsigned short* dst = s_a1 + mo * ps + 4 * j;
+    *reinterpret_cast<uint2*>(dst) = uint2{hp[0], hp[1]};
+    *reinterpret_cast<uint2*>(dst + lo1) = uint2{lp[0], lp[1]};
+}
+
+// Tile balance: tile t goes to wave t mod 4, so with 13 tiles (8 samples of d = 5) wave 0 has one more than the others; sharing that last tile between two
+// waves was measured 1.6 us slower and is gone.
 __device__ __forceinline__ void conv1_patch_words(const u8* __restrict__ s_in, const int* __restrict__ s_t1, const u32x4* __restrict__ s_lut,
-                                                  const u32x4 (&wb)[2][1][4], const f32x4 (&bpr)[PATCH_BT][4], const f32x4 (&bpx)[4], const float* __restrict__ b1p,
-                                                  int slot, unsigned short* __restrict__ s_a1, int lo1, int M1, int wfirst, int j, int kq, int bpx_tile, range_mask& rbad) {
+                                                  const u32x4 (&wb)[2][1][4], const f32x4 (&bpr)[PATCH_BT][4], const float* __restrict__ b1p,
+                                                  int slot, unsigned short* __restrict__ s_a1, int lo1, int M1, int wfirst, int j, int kq, range_mask& rbad) {
     const int tiles = (M1 + 15) >> 4;
     if (wfirst >= tiles) return;                                    // wave-uniform
-    const bool split = PATCH_SPLIT && (tiles & (CONV_WAVES - 1)) == 1 && tiles > CONV_WAVES;     // wave-uniform: the last tile belongs to wave 0 and is shared with wave 1
     auto byte_of = [&](int tile) -> u32 { return s_in[(s_t1[min(tile * 16 + j, M1 - 1)] & 0x1ffff) + kq]; };      // (tiles past the end reread the last row)
     auto tile_out = [&](int tile, u32 byte, const f32x4 (&bp)[4]) {
         const u32x4 av = s_lut[byte];
@@ -296,63 +242,17 @@ __device__ __forceinline__ void conv1_patch_words(const u8* __restrict__ s_in, c
             f32x4 v;
 #pragma unroll
             for (int t = 0; t < 4; ++t) v[t] = relu1(vs[t][r] + bp[r][t]);
-            range_track4(rbad, v);
-            u32 hp[2], lp[2];                                       // split on write: this lane's 4 consecutive channels of pixel mo
-            split_f16x2_pair(v[0], v[1], hp[0], lp[0]);
-            split_f16x2_pair(v[2], v[3], hp[1], lp[1]);
-            unsigned short* dst = s_a1 + mo * 64 + 4 * j;
-            *reinterpret_cast<uint2*>(dst) = uint2{hp[0], hp[1]};
-            *reinterpret_cast<uint2*>(dst + lo1) = uint2{lp[0], lp[1]};
-        }
-    };
-    // half of the shared last tile: column tiles 2 HALF, 2 HALF + 1 = this lane's channels 4j + 2 HALF, + 1 (one dword per plane and row)
-    auto tile_half = [&](int tile, u32 byte, const f32x4 (&bp)[4], auto half_c) {
-        constexpr int HALF = decltype(half_c)::value;
-        const u32x4 av = s_lut[byte];
-        f32x4 acc[2], accl[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) { acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; accl[t] = acc[t]; }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) acc[t] = MFMA_F16(av, wb[0][0][2 * HALF + t], acc[t]);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) accl[t] = MFMA_F16(av, wb[1][0][2 * HALF + t], accl[t]);
-        f32x4 vs[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) vs[t] = f16x2_sum(acc[t], accl[t]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int mo = tile * 16 + 4 * kq + r;
-            if (mo >= M1) continue;
-            u32 hp, lp;
-            const float r0 = relu1(vs[0][r] + bp[r][2 * HALF]), r1 = relu1(vs[1][r] + bp[r][2 * HALF + 1]);
-            range_track(rbad, r0, r1);
-            split_f16x2_pair(r0, r1, hp, lp);
-            unsigned short* dst = s_a1 + mo * 64 + 4 * j + 2 * HALF;
-            *reinterpret_cast<u32*>(dst) = hp;
-            *reinterpret_cast<u32*>(dst + lo1) = lp;
+            conv1_store_a1(v, s_a1, 64, lo1, mo, j, rbad);
         }
     };
     u32 by[PATCH_BT + 1];
     by[0] = byte_of(wfirst);
-    const u32 byx = byte_of(tiles - 1);                             // (the shared tile's byte: waves 0 and 1 use it when `split`)
 #pragma unroll
     for (int u = 0; u < PATCH_BT; ++u) {                            // (bytes one tile ahead)
         const int tile = wfirst + CONV_WAVES * u;
         if (tile >= tiles) break;                                   // wave-uniform
         by[u + 1] = byte_of(tile + CONV_WAVES);
-        if (split && tile == tiles - 1) tile_half(tile, by[u], bpr[u], std::integral_constant<int, 0>());      // (wave 0's last)
-        else tile_out(tile, by[u], bpr[u]);
-    }
-    if (split && wfirst == 1) {                                     // wave 1: the other half of wave 0's last tile
-        if (tiles - 1 == bpx_tile) tile_half(tiles - 1, byx, bpx, std::integral_constant<int, 1>());
-        else {                                                      // (a ragged group of the persistent kernel: bpx holds a full group's last tile -- this tile's bias through L1)
-            const int4 e4 = *reinterpret_cast<const int4*>(s_t1 + (tiles - 1) * 16 + 4 * kq);
-            const int ent[4] = {e4.x, e4.y, e4.z, e4.w};
-            f32x4 bp[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) bp[r] = *reinterpret_cast<const f32x4*>(b1p + ((ent[r] & (slot - 1)) << 4) + 4 * j);
-            tile_half(tiles - 1, byx, bp, std::integral_constant<int, 1>());
-        }
+        tile_out(tile, by[u], bpr[u]);
     }
     u32 bA = by[PATCH_BT];
     for (int tile = wfirst + CONV_WAVES * PATCH_BT; tile < tiles; tile += CONV_WAVES) {     // larger groups: the bias through L1, per tile
@@ -362,8 +262,7 @@ __device__ __forceinline__ void conv1_patch_words(const u8* __restrict__ s_in, c
         f32x4 bp[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) bp[r] = *reinterpret_cast<const f32x4*>(b1p + ((ent[r] & (slot - 1)) << 4) + 4 * j);
-        if (split && tile == tiles - 1) tile_half(tile, bA, bp, std::integral_constant<int, 0>());
-        else tile_out(tile, bA, bp);
+        tile_out(tile, bA, bp);
         bA = bB;
     }
 }
@@ -374,7 +273,6 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_kernel(ConvChainAr
     u8* s_in = smem;
     int* s_mis = reinterpret_cast<int*>(smem + a.off_mis);
     unsigned short* s_a1 = reinterpret_cast<unsigned short*>(smem + a.off_a1);      // f16 piece planes [2][S*r1][A1_PS]
-    u8* s_fx = smem + a.off_fx;                                                     // CONV_SWZ: chunk swizzle of every a1 row, in halves
     unsigned short* s_a2 = reinterpret_cast<unsigned short*>(smem + a.off_a2);      // [2][S*r2][40]; overlays the observations (dead after conv1)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), j = lane & 15, kq = lane >> 4;
     range_mask rbad = 0;                                            // the forward's range guard (qnet.h range_track)
@@ -427,11 +325,10 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_kernel(ConvChainAr
         tab3[u] = a.rowtab[2 * CONV_ROWTAB + min((2 * wave + u) * 16 + j, M3 - 1)];
     }
     u32x4* s_lut = reinterpret_cast<u32x4*>(smem + a.off_lut);
-    f32x4 bp1[PATCH_BT][4], bpx[4];                                 // CP: per-pixel bias of this lane's rows (conv1_patch_words); bpx: of the group's last tile
+    f32x4 bp1[PATCH_BT][4];                                         // CP: per-pixel bias of this lane's rows (conv1_patch_words)
     if constexpr (CP) {
         conv_build_bit_lut(s_lut, tid, CONV_THREADS);
-        conv1_patch_bias(bp1, bpx, reinterpret_cast<const float*>(J.packed + a.pk_b1p), a.slot, wave, (M1 + 15) / 16 - 1, j, kq,
-                         [&](int m) { return a.rowtab0[min(m, CONV_ROWTAB - 1)]; });
+        conv1_patch_bias(bp1, reinterpret_cast<const float*>(J.packed + a.pk_b1p), a.slot, wave, j, kq, [&](int m) { return a.rowtab0[min(m, CONV_ROWTAB - 1)]; });
     }
 
     DQ_STAMP(DQ_TAG_CONV_FWD, 1);
@@ -470,10 +367,9 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_kernel(ConvChainAr
     // byte offset of output pixel m's patch origin inside the staged observations
     const int lo1 = a.S * r1 * A1S, lo2 = a.S * a.oh2 * a.ow2 * 40;     // halves from an h plane to its l plane
     int* s_t1 = reinterpret_cast<int*>(smem + a.off_t1);
-    for (int m = tid; m < (CP ? (M1 + 15) & ~15 : M1); m += CONV_THREADS) {     // table entry: sample << 20 | swizzle f << 17 | offset of the patch inside the observation
+    for (int m = tid; m < (CP ? (M1 + 15) & ~15 : M1); m += CONV_THREADS) {     // table entry: sample << 20 | offset of the patch inside the observation
         const int e = m == tid && m < M1 ? tab1 : a.rowtab0[min(m, M1 - 1)], s = e >> 20;      // (patch words: padded to whole tiles with the last row)
         s_t1[m] = s * a.slot + s_mis[s] + (e & 0x1ffff);
-        if (CONV_SWZ) s_fx[m] = (u8)(((e >> 17) & 7) << 3);         // 8 f halves
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // this wave's DMA pieces have landed
     __syncthreads();
@@ -482,7 +378,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_kernel(ConvChainAr
     // ---- convolution 1: A gathered byte-wise from the uint8 image; the bytes of this wave's next tile are requested before the
     //      MFMAs of the current one ----------------------------------------------------------------------------------------------
     if constexpr (CP) {
-        conv1_patch_words(s_in, s_t1, s_lut, wb, bp1, bpx, reinterpret_cast<const float*>(J.packed + a.pk_b1p), a.slot, s_a1, lo1, M1, wave, j, kq, (M1 + 15) / 16 - 1, rbad);
+        conv1_patch_words(s_in, s_t1, s_lut, wb, bp1, reinterpret_cast<const float*>(J.packed + a.pk_b1p), a.slot, s_a1, lo1, M1, wave, j, kq, rbad);
     } else {
         const int tiles = (M1 + 15) >> 4;
         auto origin = [&](int tile) { return s_t1[min(tile * 16 + j, M1 - 1)]; };     // rows past the end (and whole tiles past it) reread the last row
@@ -494,11 +390,6 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_kernel(ConvChainAr
                 for (int e = 0; e < 8; ++e) ab[h][e] = ap[ko[h][e]];        // 0 or 1
         };
         auto tile_out = [&](int tile, const u32 (&ab)[NH1][8]) {
-            u32 fxh[4];                                             // CONV_SWZ: swizzles of this lane's four output rows (bytes past M1 belong to rows that are not stored)
-            if (CONV_SWZ) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) fxh[r] = s_fx[tile * 16 + 4 * kq + r];
-            }
             f32x4 acc[4], accl[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) { acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; accl[t] = acc[t]; }
@@ -522,14 +413,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_kernel(ConvChainAr
                 f32x4 v;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) v[t] = relu1(vs[t][r]);
-                range_track4(rbad, v);
-                u32 hp[2], lp[2];                                   // split on write: this lane's 4 consecutive channels of pixel mo
-                split_f16x2_pair(v[0], v[1], hp[0], lp[0]);
-                split_f16x2_pair(v[2], v[3], hp[1], lp[1]);
-                // this lane's 4 channels 4j .. 4j+3 = half (j & 1) of chunk j >> 1
-                unsigned short* dst = CONV_SWZ ? s_a1 + mo * 64 + (((j >> 1) << 3) ^ (int)fxh[r]) + ((j & 1) << 2) : s_a1 + mo * 72 + 4 * j;
-                *reinterpret_cast<uint2*>(dst) = uint2{hp[0], hp[1]};
-                *reinterpret_cast<uint2*>(dst + lo1) = uint2{lp[0], lp[1]};
+                conv1_store_a1(v, s_a1, A1_PS, lo1, mo, j, rbad);
             }
         };
         u32 abA[NH1][8], abB[NH1][8];
@@ -550,11 +434,11 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_kernel(ConvChainAr
     __syncthreads();
     DQ_STAMP(DQ_TAG_CONV_FWD, 4);
     if constexpr (CP) {
-        conv_from_lds<64, 32, 2, 4, 2, false, 0>(s_a1, lo1, a.oh1, a.ow1, a.oh2, a.ow2, M2, ring, J.packed + PK_CONV2_FWD, J.params + a.b_off[1], s_a2, lo2,
-                                                 nullptr, wave, lane, a.rowtab + 3 * CONV_ROWTAB, tab2[0], tab2[1], rbad);
+        conv_from_lds<64, 32, 2, 4, 2, 0>(s_a1, lo1, a.oh1, a.ow1, a.oh2, a.ow2, M2, ring, J.packed + PK_CONV2_FWD, J.params + a.b_off[1], s_a2, lo2,
+                                          nullptr, wave, lane, a.rowtab + 3 * CONV_ROWTAB, tab2[0], tab2[1], rbad);
     } else {
-        conv_from_lds<64, 32, 2, 4, 2, CONV_SWZ != 0>(s_a1, lo1, a.oh1, a.ow1, a.oh2, a.ow2, M2, ring, J.packed + PK_CONV2_FWD, J.params + a.b_off[1], s_a2, lo2,
-                                                      nullptr, wave, lane, a.rowtab + CONV_ROWTAB, tab2[0], tab2[1], rbad);
+        conv_from_lds<64, 32, 2, 4, 2>(s_a1, lo1, a.oh1, a.ow1, a.oh2, a.ow2, M2, ring, J.packed + PK_CONV2_FWD, J.params + a.b_off[1], s_a2, lo2,
+                                       nullptr, wave, lane, a.rowtab + CONV_ROWTAB, tab2[0], tab2[1], rbad);
     }
     DQ_STAMP(DQ_TAG_CONV_FWD, 5);
     conv_w_prefetch(ring, J.packed + PK_CONV3_FWD, lane);
@@ -571,10 +455,10 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_kernel(ConvChainAr
     if (J.write_all) {                                              // block-uniform; a1 is dead but intact since conv2, a2 since conv3
         __syncthreads();
         const int r2 = a.oh2 * a.ow2;
-        // a1: LDS rows of A1_PS halves (chunks swizzled with CONV_SWZ) -> global rows of 64 (8 slots of 16 B per row and plane); a2: rows of 40 -> 32 (4 slots)
+        // a1: LDS rows of A1S halves -> global rows of 64 (8 slots of 16 B per row and plane); a2: rows of 40 -> 32 (4 slots)
         for (int i = tid; i < 2 * M1 * 8; i += CONV_THREADS) {
             const int piece = i >= M1 * 8 ? 1 : 0, q = i - piece * M1 * 8, row = q >> 3, part = q & 7;
-            const int src = CP ? row * 64 + 8 * part : CONV_SWZ ? row * 64 + ((8 * part) ^ (int)s_fx[row]) : row * 72 + 8 * part;
+            const int src = row * A1S + 8 * part;
             *reinterpret_cast<u32x4*>(J.a1_pl + piece * J.a1_lo + ((size_t)b0 * r1 + row) * 64 + 8 * part) =
                 *reinterpret_cast<const u32x4*>(s_a1 + piece * lo1 + src);
         }
@@ -616,7 +500,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_pkernel(ConvChainA
     const int in_bytes = CP ? a.slot : a.C * a.H * a.W;
     constexpr int NH1 = CP ? 1 : (KG1 + 1) / 2;                     // first convolution's K in halves of 32
     const int r1 = a.oh1 * a.ow1, r2 = a.oh2 * a.ow2, r3 = a.oh3 * a.ow3;
-    const int lo1 = (CONV1_PIPE ? (a.S * r1 + 15) & ~15 : a.S * r1) * 64, lo2 = a.S * r2 * 40;      // halves from an h plane to its l plane (CONV1_PIPE: whole 16-row tiles)
+    const int lo1 = a.S * r1 * 64, lo2 = a.S * r2 * 40;             // halves from an h plane to its l plane
     const int total = a.total_groups, gstride = (int)gridDim.x;
     auto job_of = [&](int g) { return (g >= a.wg_first[1]) + (g >= a.wg_first[2]) + (g >= a.wg_first[3]); };     // block-uniform
 
@@ -638,9 +522,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_pkernel(ConvChainA
     // first-layer weight pieces (PK_CONV1, zero past K1) and bias of a job
     u32x4 wb[2][NH1][4];                                            // [piece][k-half of 32][column tile]: 8 f16 each
     f32x4 bias1;
-    f32x4 bp1[PATCH_BT][4], bpx[4];                                 // CP: per-pixel bias of this lane's rows (conv1_patch_words), reloaded with the pieces; bpx: of a
-                                                                    // FULL group's last tile (a ragged last group: its own last tile's rows are a prefix of the same pixels
-                                                                    // only when it ends on the same tile -- see the use)
+    f32x4 bp1[PATCH_BT][4];                                         // CP: per-pixel bias of this lane's rows (conv1_patch_words), reloaded with the pieces
     auto load_w1 = [&](const ConvJob& Jn) {
         const u32x4* pk1 = opaque_global(Jn.packed + (CP ? a.pk_c1c : PK_CONV1)) + lane;
 #pragma unroll
@@ -651,7 +533,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_pkernel(ConvChainA
                 for (int piece = 0; piece < 2; ++piece) wb[piece][h][t] = pk1[(h * 4 + t) * PK_BLOCK + PK_LO * piece];
         if constexpr (CP) {
             const int* tc = reinterpret_cast<const int*>(smem + a.off_t1);      // (the constant table: row m -> sample, 4 p; padded to whole tiles)
-            conv1_patch_bias(bp1, bpx, reinterpret_cast<const float*>(opaque_global(Jn.packed + a.pk_b1p)), a.slot, wave, (MF1 + 15) / 16 - 1, j, kq,
+            conv1_patch_bias(bp1, reinterpret_cast<const float*>(opaque_global(Jn.packed + a.pk_b1p)), a.slot, wave, j, kq,
                              [&](int m) { return tc[min(m, ((MF1 + 15) & ~15) - 1)]; });
         } else {
             bias1 = *reinterpret_cast<const f32x4*>(Jn.params + a.b_off[0] + 4 * j);
@@ -754,7 +636,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_pkernel(ConvChainA
         DQ_STAMP(DQ_TAG_CONV_FWD, 8 * gk + 2);
         // ---- convolution 1 (conv_chain_kernel's, on rows of 64 halves) ------------------------------------------------------------
         if constexpr (CP) {
-            conv1_patch_words(s_in, s_t1, s_lut, wb, bp1, bpx, reinterpret_cast<const float*>(J.packed + a.pk_b1p), a.slot, s_a1, lo1, M1, wv, j, kq, (MF1 + 15) / 16 - 1, rbad);
+            conv1_patch_words(s_in, s_t1, s_lut, wb, bp1, reinterpret_cast<const float*>(J.packed + a.pk_b1p), a.slot, s_a1, lo1, M1, wv, j, kq, rbad);
         } else {
             const int tiles = (M1 + 15) >> 4;
             auto origin = [&](int tile) {                           // (constant table entry + the sample's alignment offset of THIS group)
@@ -792,84 +674,11 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_pkernel(ConvChainA
                     f32x4 v;
 #pragma unroll
                     for (int t = 0; t < 4; ++t) v[t] = relu1(vs[t][r]);
-                    range_track4(rbad, v);
-                    u32 hp[2], lp[2];                               // split on write: this lane's 4 consecutive channels of pixel mo
-                    split_f16x2_pair(v[0], v[1], hp[0], lp[0]);
-                    split_f16x2_pair(v[2], v[3], hp[1], lp[1]);
-                    unsigned short* dst = s_a1 + mo * 64 + 4 * j;
-                    *reinterpret_cast<uint2*>(dst) = uint2{hp[0], hp[1]};
-                    *reinterpret_cast<uint2*>(dst + lo1) = uint2{lp[0], lp[1]};
+                    conv1_store_a1(v, s_a1, 64, lo1, mo, j, rbad);
                 }
             };
             u32 abA[NH1][8], abB[NH1][8];
             const int w1 = wv;                                      // (tiles to the waves in reverse order -- the odd 13th tile to the wave the last convolution leaves idle -- measured: +0.4 us)
-#if CONV1_PIPE
-            // software pipeline across the wave's tiles: bytes two tiles ahead, MFMAs one tile ahead, epilogue of the current tile -- the MFMAs of tile
-            // t + 4 and the epilogue of tile t are independent and sit in ONE basic block (no row guards: the planes hold whole tiles)
-            auto mma = [&](const u32 (&ab)[NH1][8], f32x4 (&acc)[4], f32x4 (&accl)[4]) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; accl[t] = acc[t]; }
-#pragma unroll
-                for (int h = 0; h < NH1; ++h) {
-                    u32x4 av;
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) av[e >> 1] = __umul24(ab[h][e] | (ab[h][e + 1] << 16), 0x3c00u);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) acc[t] = MFMA_F16(av, wb[0][h][t], acc[t]);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) accl[t] = MFMA_F16(av, wb[1][h][t], accl[t]);
-                }
-            };
-            auto epi = [&](int tile, const f32x4 (&acc)[4], const f32x4 (&accl)[4]) {
-                f32x4 vs[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) vs[t] = f16x2_sum(acc[t], accl[t]) + f32x4{bias1[t], bias1[t], bias1[t], bias1[t]};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int mo = tile * 16 + 4 * kq + r;
-                    f32x4 v;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) v[t] = relu1(vs[t][r]);
-                    range_track4(rbad, v);
-                    u32 hp[2], lp[2];
-                    split_f16x2_pair(v[0], v[1], hp[0], lp[0]);
-                    split_f16x2_pair(v[2], v[3], hp[1], lp[1]);
-                    unsigned short* dst = s_a1 + mo * 64 + 4 * j;
-                    *reinterpret_cast<uint2*>(dst) = uint2{hp[0], hp[1]};
-                    *reinterpret_cast<uint2*>(dst + lo1) = uint2{lp[0], lp[1]};
-                }
-            };
-            auto interleave = [&]() {
-#if CONV1_PIPE == 2
-                // 16 MFMAs, ~110 VALU, 17 LDS reads, 8 LDS writes in the block: one MFMA, then what fits into its shadow
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);      // VALU
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // DS read
-                    if (i & 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);      // DS write
-                }
-#endif
-            };
-            if (w1 < tiles) {
-                f32x4 accA[4], acclA[4], accB[4], acclB[4];
-                int tile = w1;
-                rd(origin(tile), abA);
-                rd(origin(tile + CONV_WAVES), abB);
-                int orgN = origin(tile + 2 * CONV_WAVES);
-                mma(abA, accA, acclA);
-                for (;;) {
-                    if (tile + CONV_WAVES >= tiles) { epi(tile, accA, acclA); break; }
-                    rd(orgN, abA); orgN = origin(tile + 3 * CONV_WAVES);
-                    mma(abB, accB, acclB); epi(tile, accA, acclA); interleave();
-                    tile += CONV_WAVES;
-                    if (tile + CONV_WAVES >= tiles) { epi(tile, accB, acclB); break; }
-                    rd(orgN, abB); orgN = origin(tile + 3 * CONV_WAVES);
-                    mma(abA, accA, acclA); epi(tile, accB, acclB); interleave();
-                    tile += CONV_WAVES;
-                }
-            }
-#else
             if (w1 < tiles) {
                 int orgB = origin(w1 + CONV_WAVES), orgA;
                 rd(origin(w1), abA);
@@ -878,7 +687,6 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_pkernel(ConvChainA
                     rd(orgA, abA); orgB = origin(tile + 2 * CONV_WAVES); tile_out(tile, abB); tile += CONV_WAVES; if (tile >= tiles) break;
                 }
             }
-#endif
         }
         DQ_STAMP(DQ_TAG_CONV_FWD, 8 * gk + 3);
         // ---- convolutions 2 and 3 ----------------------------------------------------------------------------------------------------
@@ -886,8 +694,8 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_chain_pkernel(ConvChainA
         conv_w_prefetch(ring, J.packed + PK_CONV2_FWD, ln);
         __syncthreads();
         DQ_STAMP(DQ_TAG_CONV_FWD, 8 * gk + 4);
-        conv_from_lds<64, 32, 2, 4, 2, false, 0>(s_a1, lo1, a.oh1, a.ow1, a.oh2, a.ow2, M2, ring, J.packed + PK_CONV2_FWD, J.params + a.b_off[1], s_a2, lo2,
-                                                 nullptr, wv, ln, rowtab + 3 * CONV_ROWTAB, tab2[0], tab2[1], rbad);
+        conv_from_lds<64, 32, 2, 4, 2, 0>(s_a1, lo1, a.oh1, a.ow1, a.oh2, a.ow2, M2, ring, J.packed + PK_CONV2_FWD, J.params + a.b_off[1], s_a2, lo2,
+                                          nullptr, wv, ln, rowtab + 3 * CONV_ROWTAB, tab2[0], tab2[1], rbad);
         DQ_STAMP(DQ_TAG_CONV_FWD, 8 * gk + 5);
         conv_w_prefetch(ring, J.packed + PK_CONV3_FWD, ln);
         __syncthreads();
@@ -1027,7 +835,7 @@ __global__ __launch_bounds__(DENSE_THREADS, LEAN ? 4 : 2) void dense_chain_kerne
             kbw[u] = *reinterpret_cast<const uint2*>(J.keep_bits + (size_t)min(b0 + 16 * u + j, J.batch - 1) * 16 + 2 * wave);
     }
     auto draw_keep_bits = [&]() {
-        if (!(J.keep_scale > 0.f) || DQ_EXP_NODROP) return;         // block-uniform
+        if (!(J.keep_scale > 0.f)) return;                          // block-uniform
         if (kb_ahead) {                                             // word 2 wave + b: units 64 wave + 32 b .. + 31; this lane's eight: byte kq
 #pragma unroll
             for (int u = 0; u < RT; ++u) keepb[u] = ((kbw[u].x >> (8 * kq)) & 0xffu) | (((kbw[u].y >> (8 * kq)) & 0xffu) << 8);
@@ -1089,7 +897,7 @@ __global__ __launch_bounds__(DENSE_THREADS, LEAN ? 4 : 2) void dense_chain_kerne
                 unsigned short* d = s_pl + r * LDP + c8;
                 *reinterpret_cast<u32x4*>(d) = o.h;
                 *reinterpret_cast<u32x4*>(d + ROWS * LDP) = o.l;
-                if (J.x_pl && r < ns && !DQ_EXP_NOSTORE) {                             // the same pieces feed the weight gradient of this layer (fused_bwd.hip)
+                if (J.x_pl && r < ns) {                             // the same pieces feed the weight gradient of this layer (fused_bwd.hip)
                     unsigned short* gp = J.x_pl + (size_t)(b0 + r) * K1 + c8;
                     *reinterpret_cast<u32x4*>(gp) = o.h;
                     *reinterpret_cast<u32x4*>(gp + (size_t)J.plane_rows * K1) = o.l;
@@ -1114,25 +922,23 @@ __global__ __launch_bounds__(DENSE_THREADS, LEAN ? 4 : 2) void dense_chain_kerne
         xv.h = *reinterpret_cast<const u32x4*>(xp);
         xv.l = *reinterpret_cast<const u32x4*>(xp + ROWS * LDP);
     };
-    // the input pieces of step (b, u) + 1 are read from LDS BEFORE step (b, u)'s MFMAs are issued (DENSE_XPIPE; xq[parity of the step]):
+    // the input pieces of step (b, u) + 1 are read from LDS BEFORE step (b, u)'s MFMAs are issued (xq[parity of the step]; measured neutral):
     // read next to their use, every row tile of every block waited out one LDS latency with the matrix pipe idle
     F16x2 xq[2];
-    if (DENSE_XPIPE && !LEAN) x_read(0, 0, xq[0]);
+    if (!LEAN) x_read(0, 0, xq[0]);
     auto do_block = [&](int b, F16x2 (&cur)[4], F16x2 (&nxt)[4], auto ptag) {
         constexpr int P0 = decltype(ptag)::value;                   // parity of step (b, 0)
         const u32x4* pn = pkw + (size_t)min(b + 1, KB - 1) * 32 * PK_BLOCK;      // next block: unconditional, clamped prefetch
 #pragma unroll
         for (int t = 0; t < 4; ++t) { nxt[t].h = pn[t * PK_BLOCK]; nxt[t].l = pn[t * PK_BLOCK + PK_LO]; }
-        if (DENSE_PIN) __builtin_amdgcn_sched_barrier(0);           // the requests stay HERE, a whole block of MFMAs ahead of their use (hipcc otherwise sinks
-                                                                    // each next to its use -- a few MFMAs ahead -- and the wave waits out one L2 latency per pair)
+        __builtin_amdgcn_sched_barrier(0);                          // the requests stay HERE, a whole block of MFMAs ahead of their use (hipcc otherwise sinks
+                                                                    // each next to its use -- a few MFMAs ahead -- and the wave waits out one L2 latency per pair; +1 %)
 #pragma unroll
         for (int u = 0; u < RT; ++u) {
             const int pp = (P0 + u) & 1;
-            if (DENSE_XPIPE) {
-                if (u + 1 < RT) x_read(b, u + 1, xq[pp ^ 1]);
-                else x_read(min(b + 1, KB - 1), 0, xq[pp ^ 1]);     // (past the last block: re-reads it, unused)
-                __builtin_amdgcn_sched_barrier(0);
-            } else x_read(b, u, xq[pp]);
+            if (u + 1 < RT) x_read(b, u + 1, xq[pp ^ 1]);
+            else x_read(min(b + 1, KB - 1), 0, xq[pp ^ 1]);         // (past the last block: re-reads it, unused)
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int t = 0; t < 4; ++t) mma_f16x3(cur[t], xq[pp], acc[u][t][0], acc[u][t][1]);
         }
@@ -1237,7 +1043,7 @@ __global__ __launch_bounds__(DENSE_THREADS, LEAN ? 4 : 2) void dense_chain_kerne
                 hb[b].h[2 * s] = hp[0]; hb[b].h[2 * s + 1] = hp[1];
                 hb[b].l[2 * s] = lp[0]; hb[b].l[2 * s + 1] = lp[1];
             }
-            if (J.h1_pl && row < ns && !DQ_EXP_NOSTORE) {           // (training: the hidden output as piece planes, see below)
+            if (J.h1_pl && row < ns) {                              // (training: the hidden output as piece planes, see below)
                 unsigned short* gp = J.h1_pl + (size_t)(b0 + row) * DENSE_HID + 64 * wave + 32 * b + 8 * kq;
                 *reinterpret_cast<u32x4*>(gp) = hb[b].h;
                 *reinterpret_cast<u32x4*>(gp + (size_t)J.plane_rows * DENSE_HID) = hb[b].l;
@@ -1321,7 +1127,7 @@ __global__ __launch_bounds__(DENSE_THREADS, LEAN ? 4 : 2) void dense_chain_kerne
                 // training: the hidden output is kept as its piece planes ONLY (the weight gradients' operand; the backward takes its ReLU /
                 // dropout mask from them too: an f32 copy beside them made the 64 training workgroups' stores the dense forward's critical
                 // path, +7 us) -- one 16-byte store per piece for the lane's eight units
-                if (J.h1_pl && row < ns && !DQ_EXP_NOSTORE) {
+                if (J.h1_pl && row < ns) {
                     unsigned short* gp = J.h1_pl + (size_t)(b0 + row) * DENSE_HID + 64 * wave + 32 * b + 8 * kq;
                     *reinterpret_cast<u32x4*>(gp) = hb[b].h;
                     *reinterpret_cast<u32x4*>(gp + (size_t)J.plane_rows * DENSE_HID) = hb[b].l;
@@ -1803,7 +1609,7 @@ dq_status fused_pack_weights(const dq_qnet* Q, const float* params_dev, void* pa
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct ConvPlan { int S, slot, off_mis, off_t1, off_a1, off_a2, off_fx, off_lut, KG1; size_t lds; };
+struct ConvPlan { int S, slot, off_mis, off_t1, off_a1, off_a2, off_lut, KG1; size_t lds; };
 
 // patch: the observations are patch words (dq_qnet_set_patch_input): rows of 4 * patch_stride bytes, a1 rows unpadded, a byte -> bits table behind a1
 static bool plan_conv(const dq_qnet* Q, ConvPlan* P, bool patch = false) {
@@ -1816,7 +1622,7 @@ static bool plan_conv(const dq_qnet* Q, ConvPlan* P, bool patch = false) {
     P->KG1 = (L1.K + 15) / 16;
     if (P->KG1 < 3) P->KG1 = 3;
     const int in_bytes = Q->cfg.in_c * Q->cfg.in_h * Q->cfg.in_w;
-    if (in_bytes >= (1 << 17)) return false;                        // (first row table: sample << 20 | swizzle << 17 | offset inside the observation)
+    if (in_bytes >= (1 << 17)) return false;                        // (first row table: sample << 20 | offset inside the observation, 17 bits)
     P->slot = patch ? 4 * Q->patch_stride : (in_bytes + 15 + 15 + 15) & ~15;      // the 16-byte-aligned window around an arbitrarily aligned row
     const int a1ps = patch ? 64 : A1_PS;
     for (int pass = 0; pass < 2; ++pass) {                          // prefer two workgroups per CU; else the largest S that fits
@@ -1830,10 +1636,9 @@ static bool plan_conv(const dq_qnet* Q, ConvPlan* P, bool patch = false) {
             const size_t a2_bytes = up16((size_t)2 * S * L2.rows * 40 * 2);
             if (off < a2_bytes) off = a2_bytes;
             const size_t a1 = off; off += up16((size_t)2 * S * L1.rows * a1ps * 2);
-            const size_t fx = off; off += CONV_SWZ ? up16((size_t)S * L1.rows + 16) : 0;      // (+ 16: the last tile's rows past the end are read, not used)
             const size_t lut = off; off += patch ? 4096 : 0;
             if (off <= budget && S * L1.rows <= CONV_ROWTAB) {      // (rows per workgroup: the row tables' capacity)
-                P->S = S; P->off_mis = (int)mis; P->off_t1 = (int)t1; P->off_a1 = (int)a1; P->off_a2 = 0; P->off_fx = (int)fx; P->off_lut = (int)lut; P->lds = off;
+                P->S = S; P->off_mis = (int)mis; P->off_t1 = (int)t1; P->off_a1 = (int)a1; P->off_a2 = 0; P->off_lut = (int)lut; P->lds = off;
                 return true;
             }
         }
@@ -1855,7 +1660,7 @@ static bool plan_conv_persist(const dq_qnet* Q, ConvPlanP* P, bool patch = false
             size_t core = a2b > obs ? a2b - obs : 0;
             if (core < t1b) core = t1b;
             size_t off = 2 * obs + core;
-            const size_t a1 = off; off += up16((size_t)2 * (CONV1_PIPE ? (S * L1.rows + 15) & ~15 : S * L1.rows) * 64 * 2);
+            const size_t a1 = off; off += up16((size_t)2 * S * L1.rows * 64 * 2);
             const size_t mis = off; off += 2 * 16 * 4;
             const size_t t1c = off; off += t1b;                     // the patch-origin table, constant over the groups: a place of its own (a2 overlays the core)
             const size_t lut = off; off += patch ? 4096 : 0;
@@ -1870,10 +1675,8 @@ static bool plan_conv_persist(const dq_qnet* Q, ConvPlanP* P, bool patch = false
 }
 
 // Row tables of the fused conv forward for this network (CONV_ROWTAB ints each; qnet.hip uploads them behind kofftab at creation):
-//   [0] first convolution, row m = s * r1 + oy * ow1 + ox of a workgroup's S samples:  s << 20 | f << 17 | (oy * stride * W + ox * stride), f = 2 (ox & 3)
-//       the chunk swizzle of the row's a1 planes (CONV_SWZ)
-//   [1] / [2] second / third convolution: halves from the input image's start to row m's patch, ((s * ih + oy) * iw + ox) * row stride (a1: A1_PS, and
-//       with CONV_SWZ ox & 3 in bits 24+; a2: 40)
+//   [0] first convolution, row m = s * r1 + oy * ow1 + ox of a workgroup's S samples:  s << 20 | (oy * stride * W + ox * stride)
+//   [1] / [2] second / third convolution: halves from the input image's start to row m's patch, ((s * ih + oy) * iw + ox) * row stride (a1: A1_PS; a2: 40)
 //   [3] the second convolution's over a1 rows of 64 halves (conv_chain_pkernel)
 bool fused_conv_row_tables(const dq_qnet* Q, int* tab) {
     ConvPlan P;
@@ -1889,14 +1692,13 @@ bool fused_conv_row_tables(const dq_qnet* Q, int* tab) {
     }
     for (int m = 0; m < rows_of(L1); ++m) {
         const int s = m / L1.rows, pix = m % L1.rows, oy = pix / L1.ow, ox = pix % L1.ow;
-        tab[m] = s << 20 | (CONV_SWZ ? (2 * (ox & 3)) << 17 : 0) | (oy * L1.s * L1.iw + ox * L1.s);
+        tab[m] = s << 20 | (oy * L1.s * L1.iw + ox * L1.s);
     }
     const Layer* Ls[2] = {&L2, &L3};
     for (int l = 0; l < 2; ++l)
         for (int m = 0; m < rows_of(*Ls[l]); ++m) {
             const int s = m / Ls[l]->rows, pix = m % Ls[l]->rows, oy = pix / Ls[l]->ow, ox = pix % Ls[l]->ow;
-            tab[(1 + l) * CONV_ROWTAB + m] = l == 0 ? ((s * L2.ih + oy) * L2.iw + ox) * A1_PS | (CONV_SWZ ? (ox & 3) << 24 : 0)
-                                                    : ((s * L3.ih + oy) * L3.iw + ox) * (L3.cin + 8);
+            tab[(1 + l) * CONV_ROWTAB + m] = l == 0 ? ((s * L2.ih + oy) * L2.iw + ox) * A1_PS : ((s * L3.ih + oy) * L3.iw + ox) * (L3.cin + 8);
         }
     return true;
 }
@@ -1991,6 +1793,11 @@ bool fused_forward_supported(const dq_qnet* Q) {
 typedef void (*conv_kernel_t)(ConvChainArgs);
 typedef void (*dense_kernel_t)(DenseChainArgs);
 
+// The instances of the two conv kernels: [0] patch-word input, [KG1 - 2] uint8 images with the first convolution's K padded to 16 KG1 (plan_conv: 3 <= KG1 <= 6)
+static const conv_kernel_t conv_chain_kernels[5] = {conv_chain_kernel<0>, conv_chain_kernel<3>, conv_chain_kernel<4>, conv_chain_kernel<5>, conv_chain_kernel<6>};
+static const conv_kernel_t conv_chain_pkernels[5] = {conv_chain_pkernel<0>, conv_chain_pkernel<3>, conv_chain_pkernel<4>, conv_chain_pkernel<5>, conv_chain_pkernel<6>};
+static int conv_instance(bool patch, int KG1) { return patch ? 0 : KG1 - 2; }
+
 dq_status fused_forward_multi(dq_qnet* Q, int n_jobs, const dq_qnet_job* jobs, hipStream_t st) {
     ConvPlan cp;
     DensePlan dp;
@@ -2001,7 +1808,8 @@ dq_status fused_forward_multi(dq_qnet* Q, int n_jobs, const dq_qnet_job* jobs, h
         DQ_REQUIRE(((jobs[i].reserved & 1u) != 0) == patch, DQ_ERR_INVALID, "dq_qnet_forward_multi: the jobs of one launch must all read uint8 images or all read patch words");
     DQ_REQUIRE(!patch || Q->patch_depth, DQ_ERR_STATE, "dq_qnet_forward_multi: patch-word input without dq_qnet_set_patch_input");
     DQ_REQUIRE(plan_conv(Q, &cp, patch) && plan_dense(Q, &dp), DQ_ERR_UNSUPPORTED, "fused_forward: configuration not covered");
-    conv_kernel_t ck = patch ? conv_chain_kernel<0> : cp.KG1 == 3 ? conv_chain_kernel<3> : cp.KG1 == 4 ? conv_chain_kernel<4> : cp.KG1 == 5 ? conv_chain_kernel<5> : conv_chain_kernel<6>;
+    DQ_REQUIRE(cp.KG1 >= 3 && cp.KG1 <= 6, DQ_ERR_UNSUPPORTED, "fused_forward: no conv kernel instance for a first convolution of K = 16 x %d", cp.KG1);
+    const conv_kernel_t ck = conv_chain_kernels[conv_instance(patch, cp.KG1)], pk = conv_chain_pkernels[conv_instance(patch, cp.KG1)];
     // the persistent form (DQ_CONV_PERSIST=0 selects the one-group-per-workgroup kernel: A/B runs) when the launch has more groups than resident workgroups
     // (read per call: tests flip it.  0: never; 1 / unset: when the launch has more groups than resident workgroups; 2: always, with DQ_CONV_PERSIST_GRID
     // workgroups if that is set -- a small grid makes every workgroup walk many groups)
@@ -2011,16 +1819,13 @@ dq_status fused_forward_multi(dq_qnet* Q, int n_jobs, const dq_qnet_job* jobs, h
     const char* pg = getenv("DQ_CONV_PERSIST_GRID");
     const int persist_grid = persist_env == 2 && pg ? atoi(pg) : 0;
     const bool can_persist = persist_env != 0 && plan_conv_persist(Q, &pp, patch) && pp.S == cp.S;
-    const conv_kernel_t pk = patch ? conv_chain_pkernel<0> : cp.KG1 == 3 ? conv_chain_pkernel<3> : cp.KG1 == 4 ? conv_chain_pkernel<4> : cp.KG1 == 5 ? conv_chain_pkernel<5> : conv_chain_pkernel<6>;
     static unsigned long long attr_devs = 0;                          // per device (common.h dq_device_bit)
     const unsigned long long dev_bit = dq_device_bit();
     if (!(attr_devs & dev_bit)) {
-        const conv_kernel_t cks[5] = {conv_chain_kernel<3>, conv_chain_kernel<4>, conv_chain_kernel<5>, conv_chain_kernel<6>, conv_chain_kernel<0>};
-        for (int i = 0; i < 5; ++i)
-            DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cks[i]), hipFuncAttributeMaxDynamicSharedMemorySize, CONV_LDS_MAX));
-        const conv_kernel_t pks[5] = {conv_chain_pkernel<3>, conv_chain_pkernel<4>, conv_chain_pkernel<5>, conv_chain_pkernel<6>, conv_chain_pkernel<0>};
-        for (int i = 0; i < 5; ++i)
-            DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pks[i]), hipFuncAttributeMaxDynamicSharedMemorySize, CONV_LDS_MAX));
+        for (int i = 0; i < 5; ++i) {
+            DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_chain_kernels[i]), hipFuncAttributeMaxDynamicSharedMemorySize, CONV_LDS_MAX));
+            DQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_chain_pkernels[i]), hipFuncAttributeMaxDynamicSharedMemorySize, CONV_LDS_MAX));
+        }
         const dense_kernel_t dks[6] = {dense_chain_kernel<4, 4, 1>, dense_chain_kernel<8, 8, 1>, dense_chain_kernel<4, 4, 2>, dense_chain_kernel<4, 4, 4>,
                                        dense_chain_kernel<8, 8, 2>, dense_chain_kernel<4, 4, 2, true>};
         for (int i = 0; i < 6; ++i)
@@ -2039,7 +1844,7 @@ dq_status fused_forward_multi(dq_qnet* Q, int n_jobs, const dq_qnet_job* jobs, h
     ca.oh1 = L1.oh; ca.ow1 = L1.ow; ca.oh2 = L2.oh; ca.ow2 = L2.ow; ca.oh3 = L3.oh; ca.ow3 = L3.ow;
     for (int l = 0; l < 3; ++l) { ca.w_off[l] = (int)Q->L[l].w_off; ca.b_off[l] = (int)Q->L[l].b_off; }
     ca.kofftab = Q->kofftab; ca.rowtab = Q->kofftab + 96; ca.rowtab0 = patch ? Q->ptab + PT_FWD : ca.rowtab;
-    ca.slot = cp.slot; ca.off_mis = cp.off_mis; ca.off_t1 = cp.off_t1; ca.off_a1 = cp.off_a1; ca.off_a2 = cp.off_a2; ca.off_fx = cp.off_fx; ca.off_lut = cp.off_lut;
+    ca.slot = cp.slot; ca.off_mis = cp.off_mis; ca.off_t1 = cp.off_t1; ca.off_a1 = cp.off_a1; ca.off_a2 = cp.off_a2; ca.off_lut = cp.off_lut;
     const PackLayout PL = fused_pack_layout(Q);
     ca.pk_c1c = (int)PL.c1c; ca.pk_b1p = (int)PL.b1p;
     da.K1 = D1.nin; da.perm_hw = Q->flat_hw; da.perm_c = Q->flat_c; da.pk_dense1 = (int)PL.dense1; da.pk_dense2 = (int)PL.dense2; da.pk_w3q = (int)PL.w3q;

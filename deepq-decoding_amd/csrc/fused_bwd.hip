@@ -16,16 +16,13 @@
 #include "conv_bwd.h"
 #include "env_dev.h"
 
-// Build-time switches of one-box A/B comparisons (tools/build_ab.sh): GX_PIN = a sched_barrier pin of the gX weight ring, GX_RING = its
-// depth in K blocks.  (Round 2: ring 3 unpinned -- the ISA showed hipcc sinking every load next to its use, one or two in flight per wave, the
+// Build-time numbers of one-box A/B comparisons (tools/build_ab.sh): GX_RING = the depth in K blocks of the gX weight ring, whose requests a
+// sched_barrier pins ahead of their use.  (Round 2: ring 3 unpinned -- the ISA showed hipcc sinking every load next to its use, one or two in flight per wave, the
 // phase a chain of L2 latencies (20K cycles); ring 3 pinned = 139 VGPRs = three waves per SIMD = no room for the riding environment
 // workgroup beside the dense one.  Round 3: ring 2 PINNED = 117 VGPRs: next block's six loads issued before this block's MFMAs: gX 20K -> 11-14K
 // cycles, dense workgroups end 3.5 us earlier in the loop); WG_ROWS (below) = batch rows per iteration of the dense weight gradients; CB_PRIO / DB_PRIO = static
 // issue priority for the second-dispatched half of an 8-wave workgroup's waves (conv backward -0.55 us, dense backward -0.2 us: on; the same in the
 // dense forward measured nothing).
-#ifndef GX_PIN
-#define GX_PIN 1
-#endif
 #ifndef GX_RING
 #define GX_RING 2
 #endif
@@ -186,7 +183,7 @@ __device__ __forceinline__ void gx_pass(const DenseBwdArgs& a, const unsigned sh
     static_assert((NB - 1) % RING == 0 || NB % RING == 0, "the block loop is unrolled in whole rings (plus one)");
     auto block = [&](int blk, int u) {
         load(min(blk + RING - 1, NB - 1), bw[(u + RING - 1) % RING]);      // unconditional (clamped): static s_waitcnt counts
-        if (GX_PIN) __builtin_amdgcn_sched_barrier(0);              // the requests stay RING - 1 blocks ahead of their use (hipcc sinks them next to it)
+        __builtin_amdgcn_sched_barrier(0);                          // the requests stay RING - 1 blocks ahead of their use (hipcc sinks them next to it: gX 20K -> 11-14K cycles)
         F16x2 av;
         av.h = *reinterpret_cast<const u32x4*>(arow + 32 * blk);
         av.l = *reinterpret_cast<const u32x4*>(arow + 32 * blk + DENSE_ROWS * LDH);
@@ -222,21 +219,13 @@ __device__ __forceinline__ void gx_pass(const DenseBwdArgs& a, const unsigned sh
 // gH1 = (gY2 W2^T) * [h1 > 0] * scale on the f16 pipe: K = N2 padded to KB2 blocks of 32 (a compile-time count: a register ring indexed by a
 // run-time block number would live in scratch memory); wave w owns columns 64w + 4j + t.  The result is split on write into the piece
 // planes gX and the weight gradients read.
-// What gh1_phase needs that does NOT depend on the gradient -- its first K block of W2^T pieces and the mask operand (the saved hidden
-// output's pieces) -- is requested at the top of the kernel, under the TD step's own load latencies (round 3: in the loop the phase
-// spent most of its 7-10K cycles waiting for exactly these loads).
-#ifndef GH1_PRE_W
-#define GH1_PRE_W 0                     // 1: the first weight block too (+32 registers across the TD step: 155 VGPRs, three waves per SIMD -- off); 2: behind the TD step, before gY2
-#endif
-struct Gh1Pre { F16x2 bw0[4]; uint2 hvh[4], hvl[4]; };
+// The mask operand (the saved hidden output's pieces) does NOT depend on the gradient: it is requested at the top of the kernel, under the TD
+// step's own load latencies (round 3: in the loop the phase spent most of its 7-10K cycles waiting for exactly these loads).  The first K block of
+// W2^T pieces stays in the phase: preloaded too it cost 32 registers across the TD step (155 VGPRs, three waves per SIMD).
+struct Gh1Pre { uint2 hvh[4], hvl[4]; };
 __device__ __forceinline__ void gh1_preload(const DenseBwdArgs& a, int b0, int wave, int lane, Gh1Pre& P) {
     const int j = lane & 15, kq = lane >> 4;
     const int c0 = 64 * wave + 4 * j;
-    const u32x4* pk = a.packed + a.pk_dense2t + (size_t)(4 * wave) * PK_BLOCK + lane;
-    if (GH1_PRE_W == 1) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { P.bw0[t].h = pk[t * PK_BLOCK]; P.bw0[t].l = pk[t * PK_BLOCK + PK_LO]; }
-    }
     // the mask operand: the saved hidden output's pieces (h > 0 or, for values below f16's range, l > 0  <=>  the f32 value was > 0)
     // (rows past the batch are read unclamped -- two base addresses + immediate offsets; eight clamped addresses cost 16 registers and
     // with them the fourth wave per SIMD, i.e. the co-residence of the riding environment workgroups -- and ignored: they lie inside the
@@ -259,10 +248,7 @@ __device__ __forceinline__ void gh1_phase(const DenseBwdArgs& a, const unsigned 
     const u32x4* pk = a.packed + a.pk_dense2t + (size_t)(4 * wave) * PK_BLOCK + lane;
     F16x2 bw[2][4];                                                 // two blocks in flight (the loop below is fully unrolled: static indices)
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        if (GH1_PRE_W) bw[0][t] = P.bw0[t];
-        else { bw[0][t].h = pk[t * PK_BLOCK]; bw[0][t].l = pk[t * PK_BLOCK + PK_LO]; }
-    }
+    for (int t = 0; t < 4; ++t) { bw[0][t].h = pk[t * PK_BLOCK]; bw[0][t].l = pk[t * PK_BLOCK + PK_LO]; }
     const uint2 (&hvh)[4] = P.hvh;
     const uint2 (&hvl)[4] = P.hvl;
     f32x4 acc[4][2];
@@ -304,9 +290,6 @@ __device__ __forceinline__ void gh1_phase(const DenseBwdArgs& a, const unsigned 
     }
 }
 
-#ifndef DB_SHORT_LEAN
-#define DB_SHORT_LEAN 0                 // 1: the shortcut without the LDS copy of W3'^T (its row from L2), without clearing gY2's image and without the first barrier
-#endif
 template <int NT2, bool TD, bool DUEL = true>      // N2 <= 16*NT2 and N3 <= 16*NT2; TD: the TD step in the prologue (a compile-time switch: around loads a run-time one
                                         // is a branch whose merge hipcc guards with s_waitcnt vmcnt(0) -- every preload below was waited for at once); DUEL: a dueling layer
                                         // whose tables pack_weights_kernel built (with TD: the shortcut SHORT below)
@@ -369,13 +352,13 @@ __global__ __launch_bounds__(DENSE_THREADS, 2) void dense_bwd_chain_kernel(Dense
             }
         }
     }
-    // ---- requested now, used two / three phases later: the folded dueling layer for gY2, gH1's first weight block and mask operand --------
+    // ---- requested now, used two / three phases later: the folded dueling layer for gY2 and gH1's mask operand -----------------------------
     // The dueling layer's backward and gY2 = g3 W3^T are ONE linear map of dq: gY2 = dq W3'^T, W3' the forward's folded matrix (qnet.h w3q).  With the
     // TD step fused in, dq has one non-zero per row -- gY2[b] = dq[b][a_b] * W3'^T[a_b] --: a row of the 16 KB table, copied into LDS at the top, times
     // a scalar; no dq image, no matrix phase, no barrier in between (SHORT: tables up to 64 x 64; round 3: that phase and its barrier were 3K of a
     // workgroup's 34K cycles).  A caller's dense dq goes through the matrix pipe as before, K = |A|: the same bits where dq has one non-zero per row.
     constexpr bool SHORT = TD && DUEL;
-    constexpr bool W3LDS = SHORT && NT2 == 4 && !DB_SHORT_LEAN;                       // W3'^T (64 x 64) copied into LDS; wider tables (|A| > 64): its row read from the L2-resident table
+    constexpr bool W3LDS = SHORT && NT2 == 4;                       // W3'^T (64 x 64) copied into LDS; wider tables (|A| > 64): its row read from the L2-resident table
     constexpr int PW3 = 16 * NT2;
     float w3b[NT2][4];
     f32x4 wt3[2];
@@ -431,10 +414,7 @@ __global__ __launch_bounds__(DENSE_THREADS, 2) void dense_bwd_chain_kernel(Dense
     } else if constexpr (!SHORT) {
         for (int i = tid; i < DENSE_ROWS * ldg; i += DENSE_THREADS) s_g3[i] = 0.f;
     }
-    // (SHORT writes whole rows of both gradient images, each wave its own: rows past the batch stay undefined -- they only reach MFMA output rows that
-    // are never stored --, so DB_SHORT_LEAN drops the clearing and the barrier behind it)
-    if (!(SHORT && DB_SHORT_LEAN))
-        for (int i = tid; i < DENSE_ROWS * LDY; i += DENSE_THREADS) reinterpret_cast<u32*>(s_gy2p)[i] = 0u;      // both planes (2 x 16 x LDY halves)
+    for (int i = tid; i < DENSE_ROWS * LDY; i += DENSE_THREADS) reinterpret_cast<u32*>(s_gy2p)[i] = 0u;      // both planes (2 x 16 x LDY halves)
     if constexpr (TD) {                                             // the replay rows' fields: in flight across the barrier
 #pragma unroll
         for (int u = 0; u < RPW; ++u) {
@@ -444,7 +424,7 @@ __global__ __launch_bounds__(DENSE_THREADS, 2) void dense_bwd_chain_kernel(Dense
             a_b[u] = a.td.action[rr];
         }
     }
-    if (!(SHORT && DB_SHORT_LEAN)) __syncthreads();
+    __syncthreads();
     DQ_STAMP(DQ_TAG_DENSE_BWD, 6);
     f32x4 wcr[RPW][2];                                              // SHORT: this wave's rows of Wc, in flight under the TD arithmetic below
     if constexpr (SHORT) {
@@ -618,12 +598,6 @@ __global__ __launch_bounds__(DENSE_THREADS, 2) void dense_bwd_chain_kernel(Dense
         }
     }
     DQ_STAMP(DQ_TAG_DENSE_BWD, 1);
-    if (GH1_PRE_W == 2) {                                           // gH1's first weight block: in flight under gY2
-        const u32x4* pk = a.packed + a.pk_dense2t + (size_t)(4 * wave) * PK_BLOCK + lane;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { gh1_pre.bw0[t].h = pk[t * PK_BLOCK]; gh1_pre.bw0[t].l = pk[t * PK_BLOCK + PK_LO]; }
-        __builtin_amdgcn_sched_barrier(0);
-    }
     // ---- gY2 = dq W3'^T  (K = |A|, one column tile per wave; SHORT: done above, row by row) ---------------------------------------
     if (!SHORT && N3 > 0) {
         if (wave < NT2) {

@@ -576,3 +576,39 @@ def test_bench_dump_outputs_sample_a_large_step_under_64_mb(tmp_path):
     assert np.array_equal(got["actions"], c.action_ring[0].numpy()[rows]) and np.array_equal(got["done"], c.terminal_ring[0].numpy()[rows])
     assert np.array_equal(got["observations"], c.obs_ring[1].numpy()[rows]) and np.array_equal(got["q_values"], c.q_act.numpy()[rows])
     assert np.array_equal(got["params"], c.params.numpy())
+
+
+def test_kernel_asm_compare_keeps_integer_template_instances_apart(tmp_path, monkeypatch, capsys):
+    """tools/kernel_asm_compare.py on two synthetic listings of one kernel with two integer-template instances whose bodies differ between the
+    instances but not between the files (only the numbering of the basic-block labels does): every instance is matched with ITSELF by its mangled
+    symbol -- "identical" twice, exit status 0.  One changed instruction in one instance, or one changed register count in its descriptor: exit status 1,
+    the other instance still identical."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("kernel_asm_compare", os.path.join(ROOT, "tools", "kernel_asm_compare.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+
+    def listing(first_function, add3="v_add_u32_e32 v0, 3, v0", vgpr4=9):
+        out = ["\t.text"]
+        for n, (kg, body, vgpr) in enumerate(((3, add3, 8), (4, "v_add_u32_e32 v0, 4, v0\n\tv_mul_u32_u24_e32 v0, v0, v0", vgpr4))):
+            sym, f = f"_Z17conv_chain_kernelILi{kg}EEv13ConvChainArgs", first_function + n
+            out += [f"{sym}:                ; @{sym}", "; %bb.0:", "\ts_load_dword s2, s[0:1], 0x10", f".LBB{f}_1:                  ; =>This Inner Loop", f"\t{body}",
+                    f"\ts_cbranch_scc1 .LBB{f}_1", "\ts_endpgm", f".Lfunc_end{f}:", "\t.section\t.rodata,\"a\",@progbits", f"\t.amdhsa_kernel {sym}",
+                    "\t\t.amdhsa_group_segment_fixed_size 0", "\t\t.amdhsa_private_segment_fixed_size 0", f"\t\t.amdhsa_next_free_vgpr {vgpr}",
+                    "\t\t.amdhsa_next_free_sgpr 6", "\t.end_amdhsa_kernel", "\t.text"]
+        return "\n".join(out) + "\n"
+
+    def run(new_text):
+        (tmp_path / "old.s").write_text(listing(0))
+        (tmp_path / "new.s").write_text(new_text)
+        monkeypatch.setattr(sys, "argv", ["kernel_asm_compare.py", str(tmp_path / "old.s"), str(tmp_path / "new.s")])
+        status = tool.main()
+        return status, capsys.readouterr().out.splitlines()
+
+    status, lines = run(listing(5))
+    assert status == 0 and len(lines) == 2, lines
+    assert lines[0].startswith("conv_chain_kernel<3>") and lines[0].endswith("identical") and lines[1].startswith("conv_chain_kernel<4>") and lines[1].endswith("identical")
+    status, lines = run(listing(5, add3="v_add_u32_e32 v0, 5, v0"))
+    assert status == 1 and "DIFFERENT" in lines[0] and lines[1].endswith("identical"), lines
+    status, lines = run(listing(5, vgpr4=10))
+    assert status == 1 and lines[0].endswith("identical") and lines[1].endswith("identical") and "next_free_vgpr: 9 -> 10" in lines[2], lines
