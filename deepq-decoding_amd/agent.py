@@ -541,7 +541,7 @@ class DQNAgent:
 
     def decode_benchmark_wide(self, lattice, n_volumes, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, masked_greedy=None,
                               max_actions=None, chunk=None, baseline=None, no_decoder=False, final_round="faulty", return_volumes=False, timings=None,
-                              referee=None):
+                              referee=None, weights=None):
         """Scores decode_wide() on the device for any odd d in 3 .. 15 under decoder_wide.memory_experiment_wide's conventions:
         volume i is the first volume_depth rounds of lattice env_id_base + i.  lattice: an environment of either backend (the defaults of the rates and
         the seed; the agent is bound to a VectorEnv or drop-in environment given here), or (d, error_model, use_Y, volume_depth) with explicit rates and
@@ -555,8 +555,13 @@ class DQNAgent:
         22): alive is what the wide environment's step would decide on the residual, and EvalResult.inexact counts the volumes on which the referee's
         flagged fallback fired.  Anything else is a ValueError.  With no_decoder the refereed verdict of the uncorrected errors is the slow part at
         d >= 13 (decoder_wide.refereed_uncorrected_into: launches of at most 2048 volumes, 0.24 s each at d = 15, depth 5, p = 0.006): keep n_volumes
-        modest there."""
+        modest there.  weights (with baseline="union_find" only, else ValueError): None, a pair (w_space, w_time) of integers in
+        1 .. 15, or "rates" -- the union-find row is decoded on the weighted graph exactly as memory_experiment_wide(weights=...) decodes it, with
+        rates=[...] one pair per rate block in the same launches, and its EvalResult reports .weights; the agent's row keeps its bits."""
         from . import decoder as D, decoder_wide as W
+        weights = W.check_weights(weights, rates=True)
+        if weights is not None and baseline != "union_find":
+            raise ValueError("decode_benchmark_wide: weights= weights the union-find baseline's row: give baseline='union_find'")
         d, model, use_Y, depth, max_actions, n, ph, pm, seed, base, blk, keys, _ = W.check_decode_benchmark_wide_args(
             lattice, n_volumes, rates, p_phys, p_meas, seed, env_id_base, max_actions, chunk, baseline, final_round, referee)
         layers = D.action_layers(model, use_Y)
@@ -568,7 +573,8 @@ class DQNAgent:
             self._bind(lattice)
         dec = self._wide_decoder_for(d, model, use_Y, depth, masked_greedy, max_actions, chunk)
         return W.score_decode_wide(dec, self._core.params, n, ph, pm, seed, base, blk, keys, baseline=baseline, no_decoder=no_decoder,
-                                   final_round=final_round, return_volumes=return_volumes, timings=timings, referee=referee)
+                                   final_round=final_round, return_volumes=return_volumes, timings=timings, referee=referee,
+                                   **({} if weights is None else dict(weights=weights)))
 
     def compute_q_values(self, observation):
         obs = torch.as_tensor(np.asarray(observation), dtype=torch.uint8, device=self._core.device).reshape((1,) + tuple(self.model.input_shape)).contiguous()
@@ -603,6 +609,17 @@ class DQNAgent:
             self._core.update_target_hard()
             self._last_target_sync = self.step
 
+    @staticmethod
+    def _guided_step(guide, core, venv):
+        """The vector step fit() takes with the policy's teacher `guide`: DQNCore.guided_act_and_step with the teacher's method on the narrow environment;
+        on the wide one (decoder_wide.WideUnionFindAgent) guided_act_and_step_wide -- with the teacher's weights where it has some
+        (WideUnionFindAgent(weights=...)), resolved once for the run; without them the call of before, argument for argument."""
+        if not core._wide:
+            return functools.partial(core.guided_act_and_step, method=getattr(guide, "method", "matching"))
+        if getattr(guide, "weights", None) is None:
+            return core.guided_act_and_step_wide
+        return functools.partial(core.guided_act_and_step_wide, weights=guide.weights_for(venv))
+
     def fit(self, env, nb_steps, action_repetition=1, callbacks=None, verbose=1, visualize=False, nb_max_start_steps=0,
             start_step_policy=None, log_interval=10000, nb_max_episode_steps=None, episode_averaging_length=10,
             success_threshold=None, stopping_patience=None, min_nb_steps=500, single_cycle=True, sync_interval=None):
@@ -621,10 +638,8 @@ class DQNAgent:
             if core.world_size > 1:
                 raise NotImplementedError("fit() with a guide runs on one GPU: several ranks are not supported")
             guide_ev, guide_opened = guide.evaluator_for(venv)
-            guide_method = getattr(guide, "method", "matching")
             core.guide_counts.zero_()
-            # the wide environment's teacher (decoder_wide.WideUnionFindAgent) has a step of its own
-            guided_step = core.guided_act_and_step_wide if core._wide else functools.partial(core.guided_act_and_step, method=guide_method)
+            guided_step = self._guided_step(guide, core, venv)
         self.last_guided_steps = self.last_inexact_steps = 0
         self.training = True
         # Several ranks (one per GPU): every step-counted hyper-parameter -- nb_steps, nb_steps_warmup, the epsilon schedule, min_nb_steps,

@@ -247,14 +247,18 @@ class DQNCore:
         r.advance()
         self.vector_steps += 1
 
-    def guided_act_and_step_wide(self, evaluator, eps, guide_share, masked_greedy=False, record_stats=True):
+    def guided_act_and_step_wide(self, evaluator, eps, guide_share, masked_greedy=False, record_stats=True, weights=None):
         """guided_act_and_step() for the wide environment with the union-find teacher: Q forward on the current observations,
         VectorEnv.guided_select_wide into the ring's action slot, then dq_envb_step with auto-reset writing the ring's reward / done slots and the successor
         observation; the referee's inexact flags are accumulated as _launch_env does it, the lattice-steps that followed the teacher are added to
         self.guide_counts[0].  Nothing rides on a wide launch: the update draws its own minibatch.  evaluator: a decoder_wide.WideEvaluator of the
-        environment's d and error model, window >= volume_depth.  One GPU, the wide environment."""
+        environment's d and error model, window >= volume_depth.  weights: VectorEnv.guided_select_wide's -- the teacher decodes
+        on the weighted graph; None is the call of before, argument for argument.  One GPU, the wide environment."""
         if not self._wide or self.world_size > 1:
             raise NotImplementedError("guided_act_and_step_wide: one GPU and the wide environment (the narrow one: guided_act_and_step)")
+        if weights is not None:
+            weights = self.env._wide_uf_weights(weights, "guided_act_and_step_wide")      # ValueError before the acting forward is launched
+        kw = {} if weights is None else dict(weights=weights)
         self._flush_stats()
         r, env = self.ring, self.env
         cur, nxt = r.cur, r.next_slot()
@@ -263,7 +267,7 @@ class DQNCore:
             self._guide_flags = torch.zeros((2, self.N), dtype=torch.uint8, device=self.device)
         flags = self._guide_flags
         env.guided_select_wide(evaluator, self.vector_steps, q=q, eps=eps, guide_share=guide_share, masked_greedy=masked_greedy, out=r.action[cur],
-                               out_guided=flags[0])
+                               out_guided=flags[0], **kw)
         self.guide_counts[0] += flags[0].sum()
         r.presampled = None
         check(self.L.dq_envb_step(env._h, ptr(r.action[cur]), 1, ptr(r.store[nxt]), ptr(r.reward[cur]), ptr(r.terminal[cur]), ptr(env.legal), ptr(env.lifetime),

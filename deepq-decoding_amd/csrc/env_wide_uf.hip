@@ -8,6 +8,11 @@
 // component c out of round t's words, D_t = S_t xor S_(t-1) goes into the LDS ring as stream_wide_uf_kernel stores it, and the whole volume is decoded as one
 // last window (final, commit = depth): union_find_ref on the volume.  Every exit in front of or between barriers is decided by a kernel argument, the record's
 // meta word or the Philox words every thread draws alike.  No scratch pool, no lock, no loop that waits on another workgroup.
+// The action body and the two kernels are templates on Weighted (dq_envb_uf_select_weighted, dq_envb_guided_select_uf_weighted): the same
+// volume, still one last open window, decoded by ufw_component<false, true> with the lattice's own (w_space, w_time) -- the launch's pair or the lattice's two
+// bytes of a uint8 [n_envs][2] array, clamped to 1 .. UFW_MAX_WEIGHT --, so the last round's time edges to B cost w_time.  The Weighted = false instantiations
+// are the unit-weight kernels, instruction for instruction.
+#include <type_traits>
 #include "uf_wide.h"
 #include "env_big_view.h"
 
@@ -30,8 +35,32 @@ struct EnvUfArgs {
     u8* guided;                 // [n_envs] or NULL
 };
 
-// The select body for the lattice whose record is `rec`, by the whole workgroup; returns the action to every thread.
-static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, const u64* __restrict__ rec, u8* smem, int tid) {
+// The weights of a weighted launch: one pair for all lattices, or a pair per lattice.
+struct EnvUfWeights {
+    const u8* each;             // != NULL: [2 i] / [2 i + 1] = (w_space, w_time) of lattice i
+    int w_space, w_time;
+};
+
+// The arguments of a weighted launch are the unweighted ones with the weights behind them; the unweighted kernels take EnvUfArgs itself.
+struct EnvUfArgsWeighted : EnvUfArgs {
+    EnvUfWeights w;
+};
+template <bool Weighted>
+using EnvUfArgsOf = std::conditional_t<Weighted, EnvUfArgsWeighted, EnvUfArgs>;
+
+// The workgroup's own pair, read once and clamped to 1 .. UFW_MAX_WEIGHT: a bad byte of a per-lattice array cannot overrun the growth byte.  Every thread reads
+// the same two bytes, so the pair is workgroup-uniform; it lives across the decode in vector registers, as the stream kernels hold theirs.
+static __device__ __forceinline__ void env_wide_uf_weights(const EnvUfWeights& w, size_t i, int& w_space, int& w_time) {
+    w_space = w.w_space; w_time = w.w_time;
+    if (w.each != nullptr) { w_space = w.each[2 * i]; w_time = w.each[2 * i + 1]; }
+    w_space = min(max(w_space, 1), UFW_MAX_WEIGHT); w_time = min(max(w_time, 1), UFW_MAX_WEIGHT);
+    UFW_IN_VGPR(w_space); UFW_IN_VGPR(w_time);
+}
+
+// The select body for the lattice whose record is `rec`, by the whole workgroup; returns the action to every thread.  Weighted: the lattice's pair, clamped by
+// the caller; the growth's event reduction takes the spare word s_acc[7], since s_acc[6] is this body's own (below).
+template <bool Weighted>
+static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, const u64* __restrict__ rec, u8* smem, int tid, int w_space = 1, int w_time = 1) {
     int W = p.W, depth = p.depth, identity = p.identity;
     const int O_META = 3 * W + 1;
     int o_comp = 3 * W + 2;
@@ -53,7 +82,7 @@ static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, con
     UFW_IN_VGPR(use_Y);
     if (tid < 2 * UFW_FRAME_WORDS) s_frame[tid] = 0;
     if (tid < 2 * UFW_ROW_WORDS) s_carry[tid] = 0;
-    if (tid < 8) s_acc[tid] = tid == 6 ? EWU_NONE : 0;             // [6]: the lowest wanted action that is not completed
+    if (tid < 8) s_acc[tid] = tid == 6 ? EWU_NONE : 0;             // [6]: the lowest wanted action that is not completed; [7]: the weighted growth's s_event
     int prev = 0, nd = 0;
     for (int t = 0; t < depth; ++t) {
         const int cur = (int)((vp[(size_t)t * W] >> my_bit) & 1);
@@ -70,7 +99,11 @@ static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, con
     const int n_comp = model == DQ_MODEL_X ? 1 : 2;                 // the X model has no action layer for component 1: its frame is not asked for
     for (int c = 0; c < n_comp; ++c) {
         G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
-        ufw_component(G, s_ring + c * row_stride, smem, L, tid, depth, true, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c, s_acc + 4 + c);
+        if constexpr (Weighted)
+            ufw_component<false, true>(G, s_ring + c * row_stride, smem, L, tid, depth, true, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c,
+                                       s_acc + 4 + c, w_space, w_time, s_acc + 7);
+        else
+            ufw_component(G, s_ring + c * row_stride, smem, L, tid, depth, true, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c, s_acc + 4 + c);
     }
     // decoder.frame_to_actions' rule; thread q < d^2 holds qubit q's cell of the two frames (the component's last barrier is behind every thread, or its
     // frame words still hold the zeros stored in front of the first one)
@@ -91,18 +124,25 @@ static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, con
     return a == EWU_NONE ? identity : a;
 }
 
-__global__ __launch_bounds__(UFW_THREADS) void env_wide_uf_kernel(EnvUfArgs p) {
+template <bool Weighted = false>
+__global__ __launch_bounds__(UFW_THREADS) void env_wide_uf_kernel(EnvUfArgsOf<Weighted> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
     if ((int)blockIdx.x >= p.n_envs) return;                        // workgroup-uniform
     int32_t* out = p.action + i;
     UFW_IN_VGPR(out);
-    const int a = env_wide_uf_action(p, p.state + i * p.sw, smem, tid);
+    int a;
+    if constexpr (Weighted) {
+        int w_space, w_time;
+        env_wide_uf_weights(p.w, i, w_space, w_time);
+        a = env_wide_uf_action<true>(p, p.state + i * p.sw, smem, tid, w_space, w_time);
+    } else a = env_wide_uf_action<false>(p, p.state + i * p.sw, smem, tid);
     if (tid == 0) *out = a;
 }
 
-__global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfArgs p) {
+template <bool Weighted = false>
+__global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfArgsOf<Weighted> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
@@ -119,7 +159,11 @@ __global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfAr
     int a;
     if (follow) {                                                   // workgroup-uniform: the only branch with barriers, the only one that touches LDS
         UFW_IN_VGPR(out); UFW_IN_VGPR(flag);
-        a = env_wide_uf_action(p, rec, smem, tid);
+        if constexpr (Weighted) {
+            int w_space, w_time;
+            env_wide_uf_weights(p.w, i, w_space, w_time);
+            a = env_wide_uf_action<true>(p, rec, smem, tid, w_space, w_time);
+        } else a = env_wide_uf_action<false>(p, rec, smem, tid);
     } else {
         if (tid >= 64) return;                                      // one wave suffices, and no barrier follows
         const u64* lg = rec + 3 * p.W + 2 + p.LW;                   // the record's legal set: what the last reset / step also wrote to its legal_dev
@@ -173,8 +217,10 @@ dq_status env_wide_uf_prepare(const dq_envb* E, const dq_wide_uf* H, const int32
     const unsigned long long dev_bit = dq_device_bit();
     if (!(attr_devs & dev_bit)) {
         const int lds_max = ufw_layout((UFW_MAX_D * UFW_MAX_D - 1) / 2, UFW_MAX_D * UFW_MAX_D, EWU_MAX_DEPTH).bytes;
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(env_wide_uf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        if (ea == hipSuccess) ea = hipFuncSetAttribute(reinterpret_cast<const void*>(env_wide_guided_uf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        const void* kernels[4] = {reinterpret_cast<const void*>(env_wide_uf_kernel<false>), reinterpret_cast<const void*>(env_wide_guided_uf_kernel<false>),
+                                  reinterpret_cast<const void*>(env_wide_uf_kernel<true>), reinterpret_cast<const void*>(env_wide_guided_uf_kernel<true>)};
+        hipError_t ea = hipSuccess;
+        for (int k = 0; k < 4 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
         if (ea != hipSuccess) {
             (void)hipGetLastError();
             dq_set_error("%s: the device refuses %d bytes of LDS per workgroup: %s", who, lds_max, hipGetErrorString(ea));
@@ -192,34 +238,75 @@ dq_status env_wide_uf_prepare(const dq_envb* E, const dq_wide_uf* H, const int32
     return DQ_OK;
 }
 
+// What the weighted forms check on top, before anything else: without a per-lattice array the uniform pair lies in 1 .. UFW_MAX_WEIGHT (an array is the caller's to
+// check; the kernel clamps it and does not read the uniform pair).
+dq_status env_wide_uf_check_weights(int w_space, int w_time, const uint8_t* weights_each_dev, const char* who) {
+    DQ_REQUIRE(weights_each_dev != nullptr || (w_space >= 1 && w_space <= UFW_MAX_WEIGHT && w_time >= 1 && w_time <= UFW_MAX_WEIGHT), DQ_ERR_INVALID,
+               "%s: weights (%d, %d) outside 1..%d", who, w_space, w_time, UFW_MAX_WEIGHT);
+    return DQ_OK;
+}
+
+// The select entry points: one body, `who` names the caller in the messages.  ww: the weights of a weighted launch, NULL for the unit-weight kernel.
+dq_status env_wide_uf_select(const char* who, dq_envb* env, dq_wide_uf* H, int32_t* action_dev, void* stream, const EnvUfWeights* ww = nullptr) {
+    EnvUfArgsWeighted a;
+    int lds = 0;
+    const dq_status rc = env_wide_uf_prepare(env, H, action_dev, nullptr, &a, &lds, who);
+    if (rc != DQ_OK) return rc;
+    if (ww) {
+        a.w = *ww;
+        env_wide_uf_kernel<true><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(a);
+    } else env_wide_uf_kernel<false><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(static_cast<const EnvUfArgs&>(a));
+    DQ_LAUNCH_CHECK();
+    return DQ_OK;
+}
+
+dq_status env_wide_uf_guided_select(const char* who, dq_envb* env, dq_wide_uf* H, const float* q_dev, double eps, double guide_share, int masked_greedy,
+                                    const uint32_t seed[2], uint64_t t, int32_t* action_dev, uint8_t* guided_dev, void* stream, const EnvUfWeights* ww = nullptr) {
+    DQ_REQUIRE(seed, DQ_ERR_INVALID, "%s: null argument", who);
+    DQ_REQUIRE(eps >= 0.0 && eps <= 1.0, DQ_ERR_INVALID, "%s: eps must be in [0,1]", who);                                    // (NaN fails both compares)
+    DQ_REQUIRE(guide_share >= 0.0 && guide_share <= 1.0, DQ_ERR_INVALID, "%s: guide_share must be in [0,1]", who);
+    EnvUfArgsWeighted a;
+    int lds = 0;
+    const dq_status rc = env_wide_uf_prepare(env, H, action_dev, q_dev, &a, &lds, who);
+    if (rc != DQ_OK) return rc;
+    a.q = q_dev; a.T_eps = dq_rate_threshold(eps); a.T_share = dq_rate_threshold(guide_share); a.t = t; a.masked_greedy = masked_greedy;
+    a.seed0 = seed[0]; a.seed1 = seed[1]; a.guided = guided_dev;
+    if (ww) {
+        a.w = *ww;
+        env_wide_guided_uf_kernel<true><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(a);
+    } else env_wide_guided_uf_kernel<false><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(static_cast<const EnvUfArgs&>(a));
+    DQ_LAUNCH_CHECK();
+    return DQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 dq_status dq_envb_uf_select(dq_envb* env, dq_wide_uf* H, int32_t* action_dev, void* stream) {
-    EnvUfArgs a;
-    int lds = 0;
-    const dq_status rc = env_wide_uf_prepare(env, H, action_dev, nullptr, &a, &lds, "dq_envb_uf_select");
+    return env_wide_uf_select("dq_envb_uf_select", env, H, action_dev, stream);
+}
+
+dq_status dq_envb_uf_select_weighted(dq_envb* env, dq_wide_uf* H, int w_space, int w_time, const uint8_t* weights_each_dev, int32_t* action_dev, void* stream) {
+    const dq_status rc = env_wide_uf_check_weights(w_space, w_time, weights_each_dev, "dq_envb_uf_select_weighted");
     if (rc != DQ_OK) return rc;
-    env_wide_uf_kernel<<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(a);
-    DQ_LAUNCH_CHECK();
-    return DQ_OK;
+    const EnvUfWeights ww = {weights_each_dev, w_space, w_time};
+    return env_wide_uf_select("dq_envb_uf_select_weighted", env, H, action_dev, stream, &ww);
 }
 
 dq_status dq_envb_guided_select_uf(dq_envb* env, dq_wide_uf* H, const float* q_dev, double eps, double guide_share, int masked_greedy, const uint32_t seed[2],
                                    uint64_t t, int32_t* action_dev, uint8_t* guided_dev, void* stream) {
-    DQ_REQUIRE(seed, DQ_ERR_INVALID, "dq_envb_guided_select_uf: null argument");
-    DQ_REQUIRE(eps >= 0.0 && eps <= 1.0, DQ_ERR_INVALID, "dq_envb_guided_select_uf: eps must be in [0,1]");                  // (NaN fails both compares)
-    DQ_REQUIRE(guide_share >= 0.0 && guide_share <= 1.0, DQ_ERR_INVALID, "dq_envb_guided_select_uf: guide_share must be in [0,1]");
-    EnvUfArgs a;
-    int lds = 0;
-    const dq_status rc = env_wide_uf_prepare(env, H, action_dev, q_dev, &a, &lds, "dq_envb_guided_select_uf");
+    return env_wide_uf_guided_select("dq_envb_guided_select_uf", env, H, q_dev, eps, guide_share, masked_greedy, seed, t, action_dev, guided_dev, stream);
+}
+
+dq_status dq_envb_guided_select_uf_weighted(dq_envb* env, dq_wide_uf* H, const float* q_dev, double eps, double guide_share, int masked_greedy,
+                                            const uint32_t seed[2], uint64_t t, int w_space, int w_time, const uint8_t* weights_each_dev, int32_t* action_dev,
+                                            uint8_t* guided_dev, void* stream) {
+    const dq_status rc = env_wide_uf_check_weights(w_space, w_time, weights_each_dev, "dq_envb_guided_select_uf_weighted");
     if (rc != DQ_OK) return rc;
-    a.q = q_dev; a.T_eps = dq_rate_threshold(eps); a.T_share = dq_rate_threshold(guide_share); a.t = t; a.masked_greedy = masked_greedy;
-    a.seed0 = seed[0]; a.seed1 = seed[1]; a.guided = guided_dev;
-    env_wide_guided_uf_kernel<<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(a);
-    DQ_LAUNCH_CHECK();
-    return DQ_OK;
+    const EnvUfWeights ww = {weights_each_dev, w_space, w_time};
+    return env_wide_uf_guided_select("dq_envb_guided_select_uf_weighted", env, H, q_dev, eps, guide_share, masked_greedy, seed, t, action_dev, guided_dev, stream,
+                                     &ww);
 }
 
 }  // extern "C"

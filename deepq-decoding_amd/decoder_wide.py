@@ -9,7 +9,8 @@ as the wide environment's step does: death_rate is then the share of volumes on 
 
 weights= (stream_decode_wide, memory_experiment_wide) decodes on a weighted graph: an edge of weight w is full at growth 2 w, w_space
 for the space edges and w_time for the time edges, so that a misread stabilizer and a flipped qubit cost what their rates say (uf_weights).  None is the
-unit-weight launch of before, untouched.
+unit-weight launch of before, untouched.  The policy and teacher of the wide environment and decode_benchmark_wide's union-find row take it too (DESIGN.md
+section 24): WideUnionFindAgent(weights=...), VectorEnv.uf_select_wide / guided_select_wide(weights=...).
 
 Further down: the union-find decoder as a policy and a teacher of the wide environment (section 19), and batched decoding by a trained agent at these
 sizes -- WideBatchDecoder, the wide form of decoder.BatchDecoder, and the scorer behind DQNAgent.decode_benchmark_wide (include/deepq_hip.h
@@ -126,6 +127,44 @@ def rate_weights(p_phys, p_meas, error_model, n):
             pairs[key] = uf_weights(key[0], key[1], error_model)
         out[i] = pairs[key]
     return out
+
+
+def check_policy_weights(weights, n=None):
+    """weights= of the wide environment's policy and teacher (WideUnionFindAgent, VectorEnv.uf_select_wide's values), validated without touching the
+    library: None, a pair, "rates", or one pair per lattice -- an integer array [n, 2], or a uint8 device tensor [n, 2], which is returned as it is.
+    n=None (the lattices are not known yet): any number of rows.  Else ValueError."""
+    if weights is None:
+        return None
+    if getattr(weights, "is_cuda", False):
+        shape = tuple(int(x) for x in weights.shape)
+        if str(weights.dtype) != "torch.uint8" or len(shape) != 2 or shape[1] != 2 or (n is not None and shape[0] != n):
+            raise ValueError(f"a device tensor of weights is uint8 [{'n_envs' if n is None else n}, 2], not {weights.dtype} {shape}")
+        return weights
+    rows = n
+    if rows is None and not isinstance(weights, (str, dict)):
+        try:
+            shape = np.shape(weights)
+        except ValueError:                                            # ragged nesting
+            shape = ()
+        rows = shape[0] if len(shape) == 2 else None
+    return check_weights(weights, rows, rates=True)
+
+
+def weight_pairs(weights, rates=None, error_model=None, n=None):
+    """What a validated weights= amounts to, for a report: None, the pair, or the sorted list of the distinct pairs of the lattices (one pair where all
+    agree).  rates: the lattices' (p_phys, p_meas), read for "rates"."""
+    if weights is None or isinstance(weights, tuple):
+        return weights
+    if isinstance(weights, str):
+        ph, pm = rates
+        pm = ph if pm is None else pm
+        if np.ndim(ph) == 0 and np.ndim(pm) == 0:
+            return uf_weights(float(ph), float(pm), error_model)
+        weights = rate_weights(*(np.broadcast_to(np.asarray(x, dtype=np.float64), (n,)) for x in (ph, pm)), error_model, n)
+    if hasattr(weights, "detach"):
+        weights = weights.detach().cpu().numpy()
+    pairs = sorted({(int(a), int(b)) for a, b in np.unique(np.asarray(weights).reshape(-1, 2), axis=0)})
+    return pairs[0] if len(pairs) == 1 else pairs
 
 
 def weights_kw(weights, dev, s=0, m=None):
@@ -546,19 +585,39 @@ class WideUnionFindAgent(MatchingAgent):
     MatchingAgent's return -- the same keys, quotas, block layout, record order and step cap, through episodes.py.  policy="identity": only ever the identity,
     the "no decoder" row on the same handle.  evaluator: a WideEvaluator of the environment's d and error model with window >= volume_depth (it stays
     open); default: one per call.  The decoder has no fallback, so last_inexact_steps is 0.  As a subclass it is accepted by EpsGreedyQPolicy(guide=...):
-    DQNAgent.fit then runs DQNCore.guided_act_and_step_wide."""
+    DQNAgent.fit then runs DQNCore.guided_act_and_step_wide.  weights: VectorEnv.uf_select_wide's -- None (unit weights, the
+    calls of before), a pair, one pair per lattice, or "rates": every select of test / test_error_rates and, as a guide, every guided step of fit
+    decodes on the weighted graph; with "rates" test_error_rates gives every rate block its own pair in the same launches.  After a call last_weights
+    holds what was used: None, a pair, or the sorted list of the lattices' distinct pairs.  The identity row takes no weights."""
 
-    def __init__(self, evaluator=None, chunk=DEFAULT_CHUNK, policy="matching"):
+    def __init__(self, evaluator=None, chunk=DEFAULT_CHUNK, policy="matching", weights=None):
         super().__init__(evaluator=evaluator, chunk=chunk, policy=policy)
         self.method = "union_find"
+        self.weights = check_policy_weights(weights)
+        if self.weights is not None and policy == "identity":
+            raise ValueError("policy='identity' plays no decoder: it takes no weights")
+        self.last_weights = None
 
     def _check_env(self, env):
         check_wide_policy_args(env, self.evaluator, self.chunk)
+        check_policy_weights(self.weights, int(getattr(env, "_v", env).n_envs))
+
+    def weights_for(self, env):
+        """The agent's weights as VectorEnv.uf_select_wide / guided_select_wide take them on env, for a caller that makes many calls (DQNAgent.fit): None, the
+        pair, "rates" (the environment keeps the uploaded array and follows set_rates), or the per-lattice pairs as ONE uint8 device tensor.  Validates the
+        rows against env.n_envs (ValueError) before any library call."""
+        v = getattr(env, "_v", env)
+        w = check_policy_weights(self.weights, int(v.n_envs))
+        if isinstance(w, np.ndarray):
+            import torch
+            w = torch.from_numpy(w).to(v.device)
+        return w
 
     def evaluator_for(self, env):
         """(a WideEvaluator(d, error_model, window=volume_depth) of env's lattice, whether it was opened here and is the caller's to close): the agent's own
         where it was given one.  Validates like test(), before any library call."""
         d, model, _, depth = check_wide_policy_args(env, self.evaluator, self.chunk)
+        check_policy_weights(self.weights, int(getattr(env, "_v", env).n_envs))
         if self.evaluator is not None:
             return self.evaluator, False
         v = getattr(env, "_v", env)
@@ -575,10 +634,13 @@ class WideUnionFindAgent(MatchingAgent):
             with torch.cuda.device(dev):
                 action = torch.full((N,), int(venv.identity_index), dtype=torch.int32, device=dev)
                 steps = [0]
+                weights = self.weights_for(venv) if decode else None
+                kw = {} if weights is None else dict(weights=weights)         # (no weights: the call of before, argument for argument)
+                self.last_weights = weight_pairs(weights, venv.rates, venv.error_model, N) if weights is not None else None
 
                 def step(k):
                     if decode:
-                        venv.uf_select_wide(ev, out=action)
+                        venv.uf_select_wide(ev, out=action, **kw)
                     venv.step(action, auto_reset=True, write_obs=False)
                     steps[0] = k + 1
                     return venv.done, venv.was_reset, venv.reward, venv.lifetime
@@ -826,16 +888,23 @@ def check_decode_benchmark_wide_args(lattice, n_volumes, rates=None, p_phys=None
 
 
 def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=None, no_decoder=False, final_round="faulty", return_volumes=False,
-                      timings=None, referee=None):
+                      timings=None, referee=None, weights=None):
     """The loop behind DQNAgent.decode_benchmark_wide for a validated request: per chunk ONE dq_wide_uf_run (T = window = commit = volume_depth, with
     syndromes) yields the agent's input, the hidden state and the union-find frame of the same volumes; then dq_decode_wide_run, dq_wide_uf_verdict
     and dq_decode_count with the agent's status and correction count.  referee=None: no referee is consulted, alive := success; referee="matching":
     the verdicts of all three rows (the agent's, the union-find baseline's, no_decoder's) go through dq_wide_uf_verdict_refereed and each row's
-    EvalResult.inexact counts its flagged volumes."""
+    EvalResult.inexact counts its flagged volumes.  weights (validated: None, a pair or "rates"): the sampling launch is
+    dq_wide_uf_run_weighted, as memory_experiment_wide's -- the volumes and the hidden state do not depend on the weights, only the union-find frame does, so
+    the agent's row keeps its bits; the baseline's EvalResult of every block reports .weights."""
     import torch
     from .decoder import DecodeResult
     refereed = check_referee(referee)
     d, depth, dev = dec.d, dec.volume_depth, dec.device
+    if isinstance(weights, str):                                      # "rates"
+        weights = rate_weights(ph, pm, dec.error_model, n)
+    used = weights                                                    # None, the pair, or uint8 [n, 2] on the host
+    if isinstance(weights, np.ndarray):
+        weights = torch.from_numpy(weights).to(device=dev)
     step = min(dec.chunk, n)
     ev = WideEvaluator(d, dec.error_model, depth, chunk=step, device=dev)
     closed = closed_kw(final_round)
@@ -854,7 +923,7 @@ def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=No
         iters = []
 
         def run(m, s, sl, a, b):
-            ev.run_into(m, depth, depth, base + s, seed, a, b, hid[sl], triv[sl], uf_frame[sl], syndromes=syn[sl], **closed)
+            ev.run_into(m, depth, depth, base + s, seed, a, b, hid[sl], triv[sl], uf_frame[sl], syndromes=syn[sl], **closed, **weights_kw(weights, dev, s, m))
 
         def decode(m, sl):
             iters.append(dec.decode_into(params, packed, syn[sl], m, corr[sl], ncorr[sl], frame[sl], status[sl]))
@@ -881,5 +950,8 @@ def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=No
         r = results[0][0]
         r.volumes, r.hidden, r.trivial, r.verdict = syn, hid, triv, verd
         r.decode = DecodeResult(corr, ncorr, frame, status, iterations=iters)
+    if baseline:
+        for k, r in enumerate(results[1]):                            # (a block of rates=[...] holds one rate pair, so one pair of weights)
+            r.weights = weight_pairs(used if used is None or isinstance(used, tuple) else used[k * blk:(k + 1) * blk])
     out = tuple(keyed(x, keys) for x in results)
     return out if baseline else out[0]

@@ -921,7 +921,8 @@ dq_status dq_wide_uf_run_closed(dq_wide_uf* h, int n, int T, int commit, uint32_
  * weights_each_dev (nullable): uint8 [n][2] on the device, (w_space, w_time) of stream i; it replaces the uniform pair, which must still be valid.  The
  * caller keeps its bytes in 1 .. 15; the kernel clamps them to that range, so a bad byte changes a result but cannot overrun the growth byte.
  * Every other argument, the validation and the error codes are those of the unweighted forms; closed outside {0, 1} or a uniform weight outside 1 .. 15 is
- * DQ_ERR_INVALID before any device work.  The environment policies (dq_envb_uf_select, dq_envb_guided_select_uf) keep unit weights. */
+ * DQ_ERR_INVALID before any device work.  The environment policies (dq_envb_uf_select, dq_envb_guided_select_uf) keep unit weights; their weighted forms are
+ * dq_envb_uf_select_weighted and dq_envb_guided_select_uf_weighted. */
 dq_status dq_wide_uf_decode_weighted(dq_wide_uf* h, const uint8_t* syndromes_dev, int n, int T, int commit, int closed, int w_space, int w_time,
                                      const uint8_t* weights_each_dev, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev,
                                      void* stream);
@@ -949,6 +950,19 @@ dq_status dq_wide_uf_run_weighted(dq_wide_uf* h, int n, int T, int commit, uint3
 dq_status dq_envb_uf_select(dq_envb* env, dq_wide_uf* h, int32_t* action_dev, void* stream);
 dq_status dq_envb_guided_select_uf(dq_envb* env, dq_wide_uf* h, const float* q_dev, double eps, double guide_share, int masked_greedy,
                                    const uint32_t seed[2], uint64_t t, int32_t* action_dev, uint8_t* guided_dev, void* stream);
+/* The weighted forms.  dq_version() stays 8: the capability is the presence of these two symbols.  dq_envb_uf_select's and
+ * dq_envb_guided_select_uf's rules, arguments, validation and error codes with one change: the lattice's volume is decoded on dq_wide_uf_decode_weighted's
+ * graph -- still one last open window, so the last round's time edges to the boundary cost w_time.  w_space, w_time: the pair of every lattice, each in
+ * 1 .. 15.  weights_each_dev (nullable): uint8 [n_envs][2] on the device, (w_space, w_time) of lattice i; it replaces the uniform pair, which is then not
+ * read.  The caller keeps its bytes in 1 .. 15; the kernel clamps them to that range (0 decodes as 1, 200 as 15), so a bad byte changes an action but cannot
+ * overrun the growth byte.  Without an array a uniform weight outside 1 .. 15 is DQ_ERR_INVALID before any device work.  With (1, 1) every action equals the
+ * unweighted forms'; a lattice whose done flag is set gets the identity; in the guided form only the guided lattices run the decoder and every other
+ * lattice's action and flag are dq_envb_guided_select_uf's.  The records are read in place and never written. */
+dq_status dq_envb_uf_select_weighted(dq_envb* env, dq_wide_uf* h, int w_space, int w_time, const uint8_t* weights_each_dev, int32_t* action_dev,
+                                     void* stream);
+dq_status dq_envb_guided_select_uf_weighted(dq_envb* env, dq_wide_uf* h, const float* q_dev, double eps, double guide_share, int masked_greedy,
+                                            const uint32_t seed[2], uint64_t t, int w_space, int w_time, const uint8_t* weights_each_dev,
+                                            int32_t* action_dev, uint8_t* guided_dev, void* stream);
 
 /* Batched agent decoding for any odd d in 3 .. 15 (csrc/decode_wide.hip).  dq_version() stays 8: the capability is the presence of
  * these symbols.  The semantics are dq_decode_run's, statement for statement, with DQ_DECODE_PLANES_ENV and DQ_DECODE_OBS_UINT8 (patch words and the README

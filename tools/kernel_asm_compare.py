@@ -5,7 +5,7 @@
 
 Kernels are matched by their full mangled symbol where both files have it (every instance of a template is a kernel of its own).  A symbol that only one file
 has is matched by its name and its boolean template arguments, a kernel with fewer arguments in one file as if the missing ones were false (a template argument
-added with the default false).  Compared are the instructions and their operands -- comments, directives and the numbering of the basic-block labels (which
+added with the default false; a kernel that was no template at all as the instance with every argument false).  Compared are the instructions and their operands -- comments, directives and the numbering of the basic-block labels (which
 counts the functions in front) are not -- and the kernel descriptor's register, LDS and scratch sizes.  One line per kernel of new.s, the sizes where they
 differ, with --diff the differing lines; exit status 1 if a matched kernel differs."""
 import difflib
@@ -48,7 +48,7 @@ def kernels(path):
 def key(symbol, n_flags):
     m = re.search(r"\d+([a-z0-9_]+kernel)(?:I((?:Lb[01]E)+)E)?", symbol)
     flags = re.findall(r"Lb([01])E", m.group(2) or "") if m else []
-    return (m.group(1) if m else symbol, tuple(flags + ["0"] * (n_flags - len(flags))) if flags else ())
+    return (m.group(1) if m else symbol, tuple(flags + ["0"] * (n_flags - len(flags))))      # (a kernel that was no template before: all false)
 
 
 def shown(symbol):

@@ -1,11 +1,14 @@
-"""Launch times of the wide environment's union-find selection: recorded, not gated.
+"""Launch times of the wide environment's union-find selection (DESIGN.md sections 19 and 24): recorded, not gated.
 
-    python tools/wide_env_uf_timing.py [--lattices 4096] [--p 0.006] [--rounds 5] [--play 8] [--out FILE]
+    python tools/wide_env_uf_timing.py [--lattices 4096] [--p 0.006] [--rounds 5] [--play 8] [--meas-ratio R] [--weights rates|WS,WT] [--out FILE]
 
 Per configuration (d = 9 / volume_depth 9 and d = 15 / volume_depth 5, DP) on --lattices mid-episode lattices (--play agent steps of the union-find policy
 from a reset): the select launch (env_wide_uf_kernel), dq_envb_step, dq_wide_uf_decode on the same volumes exported as grids with window = commit =
 volume_depth (stream_wide_uf_kernel), and the guided launch (env_wide_guided_uf_kernel) at guided fractions 0, 0.1 and 1 (eps = 1, guide_share = the
-fraction).  Device events around single launches; the configurations alternate within each of --rounds rounds, and every round ends with one untimed agent
+fraction).  --meas-ratio R plays at p_meas = R p.  --weights adds, on the same records in the same process, the weighted select launch
+(env_wide_uf_kernel<true>) under (1, 1), under (2, 1) and under the given pair -- "rates": decoder_wide.uf_weights of (p, p_meas) --, and the weighted guided
+launch under that pair at the three fractions; each is reported over the UNWEIGHTED select / guided launch, which is the yardstick; the lattices are still
+played by the unweighted policy, and the record goes to profiles/wide_env_uf_weighted_timing.json.  Device events around single launches; the configurations alternate within each of --rounds rounds, and every round ends with one untimed agent
 step and a fresh export, so that all launches of a round see the same volumes.  Median, min and max.  Writes profiles/wide_env_uf_timing.json."""
 import argparse
 import importlib
@@ -34,10 +37,12 @@ def timed_us(fn):
 
 
 class Config:
-    def __init__(self, d, depth, n, p):
+    def __init__(self, d, depth, n, p, p_meas=None, weights=None):
         from oracle import lattice
         self.d, self.depth, self.n = d, depth, n
-        self.env = dq.VectorEnv(n_envs=n, seed=SEED, d=d, error_model="DP", use_Y=False, volume_depth=depth, p_phys=p, p_meas=p, backend="wide")
+        p_meas = p if p_meas is None else p_meas
+        self.pair = None if weights is None else dq.uf_weights(p, p_meas, "DP") if weights == "rates" else weights
+        self.env = dq.VectorEnv(n_envs=n, seed=SEED, d=d, error_model="DP", use_Y=False, volume_depth=depth, p_phys=p, p_meas=p_meas, backend="wide")
         self.ev = dq.WideEvaluator(d, "DP", window=depth, chunk=n, device=self.env.device)
         dev = self.env.device
         self.action, self.other = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
@@ -70,6 +75,12 @@ class Config:
                "decode": lambda: ev.decode_into(self.grids, n, self.depth, self.depth, self.frame)}
         for share in (0.0, 0.1, 1.0):
             out[f"guided_{share:g}"] = lambda share=share: e.guided_select_wide(ev, self.t, q=self.q, eps=1.0, guide_share=share, out=self.other, out_guided=self.flag)
+        if self.pair is not None:                                                        # (into `other`: the step below plays the unweighted action)
+            for name, w in (("select_w_1_1", (1, 1)), ("select_w_2_1", (2, 1)), ("select_w_pair", self.pair)):
+                out[name] = lambda w=w: e.uf_select_wide(ev, out=self.other, weights=w)
+            for share in (0.0, 0.1, 1.0):
+                out[f"guided_w_pair_{share:g}"] = lambda share=share: e.guided_select_wide(ev, self.t, q=self.q, eps=1.0, guide_share=share, out=self.other,
+                                                                                          out_guided=self.flag, weights=self.pair)
         out["step"] = lambda: e.step(self.action, auto_reset=True, write_obs=False)      # last: it moves the lattices on
         return out
 
@@ -80,9 +91,13 @@ def main():
     ap.add_argument("--p", type=float, default=0.006)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--play", type=int, default=8)
+    ap.add_argument("--meas-ratio", type=float, default=1.0)
+    ap.add_argument("--weights", default=None)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    cfgs = {f"d{d}_depth{depth}": Config(d, depth, a.lattices, a.p) for d, depth in SHAPES}
+    weights = None if a.weights is None else a.weights if a.weights == "rates" else tuple(int(x) for x in a.weights.split(","))
+    p_meas = min(1.0, a.meas_ratio * a.p)
+    cfgs = {f"d{d}_depth{depth}": Config(d, depth, a.lattices, a.p, p_meas, weights) for d, depth in SHAPES}
     for c in cfgs.values():
         for _ in range(a.play):
             c.play()
@@ -101,7 +116,8 @@ def main():
             live[k].append(float((c.action != c.env.identity_index).float().mean()))
             c.t += 1
             c.export()
-    record = dict(device=torch.cuda.get_device_name(0), lattices=a.lattices, p=a.p, model="DP", played_steps=a.play, timing_rounds=a.rounds, configurations={})
+    record = dict(device=torch.cuda.get_device_name(0), lattices=a.lattices, p=a.p, p_meas=p_meas, weights=a.weights, model="DP", played_steps=a.play,
+                  timing_rounds=a.rounds, configurations={})
     for k, c in cfgs.items():
         rows = {name: dict(median_us=float(np.median(v)), min_us=float(np.min(v)), max_us=float(np.max(v))) for name, v in t[k].items()}
         ratio = rows["select"]["median_us"] / rows["decode"]["median_us"]
@@ -109,7 +125,12 @@ def main():
         for name, r in rows.items():
             print(f"{k:12s} {name:12s} median {r['median_us']:10.1f} us  [{r['min_us']:10.1f}, {r['max_us']:10.1f}]")
         print(f"{k:12s} select / decode = {ratio:.3f}")
-    path = a.out or os.path.join(ROOT, "profiles", "wide_env_uf_timing.json")
+        if c.pair is not None:                                                           # the weighted launches over the unweighted ones of the same records
+            over = {name: r["median_us"] / rows["select" if name.startswith("select") else "guided_" + name.rsplit("_", 1)[1]]["median_us"]
+                    for name, r in rows.items() if "_w_" in name}
+            record["configurations"][k].update(pair=list(c.pair), weighted_over_unweighted=over)
+            print(f"{k:12s} pair {c.pair}: " + "  ".join(f"{name} x {v:.3f}" for name, v in over.items()))
+    path = a.out or os.path.join(ROOT, "profiles", "wide_env_uf_weighted_timing.json" if weights else "wide_env_uf_timing.json")
     with open(path, "w") as f:
         json.dump(record, f, indent=1)
         f.write("\n")

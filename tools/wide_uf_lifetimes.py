@@ -1,11 +1,15 @@
-"""Episode lifetimes of the wide environment under the union-find policy against the identity: recorded, not gated.
+"""Episode lifetimes of the wide environment under the union-find policy against the identity (DESIGN.md sections 19 and 24): recorded, not gated.
 
-    python tools/wide_uf_lifetimes.py [--d 9 11 13 15] [--rates 0.016 ... 0.002] [--lattices 64] [--episodes 64] [--max-steps 40000] [--out FILE]
+    python tools/wide_uf_lifetimes.py [--d 9 11 13 15] [--rates 0.016 ... 0.002] [--lattices 64] [--episodes 64] [--max-steps 40000]
+                                      [--meas-ratio R] [--weights rates|WS,WT] [--out FILE]
 
-DP, volume_depth 5, p_meas = p_phys.  Per d one environment of --lattices lattices (one seed, ids 0 ..), and per rate one
-WideUnionFindAgent.test_error_rates(env, [rate]) for the union-find row and one for the identity row: the same seed and ids for both.  The rates are taken
-from the highest down; a rate whose union-find episodes do not end within --max-steps vector steps is recorded as censored and the lower ones, which last
-longer still, are not run.  Mean lifetime with a 95 % normal interval of the mean.  Writes profiles/wide_uf_lifetimes_dp.json."""
+DP, volume_depth 5, p_meas = p_phys (--meas-ratio R: p_meas = R p).  Per d one environment of --lattices lattices (one seed, ids 0 ..), and per rate one
+WideUnionFindAgent.test_error_rates(env, [rate]) for the union-find row and one for the identity row: the same seed and ids for both.  --weights adds a third
+row on the same seed and ids, the policy on the weighted graph: "rates" takes decoder_wide.uf_weights of the row's own (p, p_meas),
+WS,WT one pair for every row; the row records the pair it played with and the ratio of its mean lifetime to the unit row's, with both episode counts and
+whether the two 95 % intervals overlap (where they do the ratio resolves nothing).  The rates are taken from the highest down; a rate whose union-find
+episodes do not end within --max-steps vector steps is recorded as censored and the lower ones, which last longer still, are not run.  Mean lifetime with a
+95 % normal interval of the mean.  Writes profiles/wide_uf_lifetimes_dp.json (with --weights: profiles/wide_uf_lifetimes_weighted.json)."""
 import argparse
 import importlib
 import json
@@ -29,6 +33,19 @@ def summary(hist):
                 max_lifetime=float(life.max()))
 
 
+def played(agent, env, rate, pm, a):
+    """One row: the agent's episodes at (rate, pm) from a reset, or the censoring."""
+    try:
+        h = agent.test_error_rates(env, [rate], nb_episodes=a.episodes, p_meas=pm, verbose=0, nb_max_episode_steps=a.max_steps)[rate]
+        return dict(summary(h), vector_steps=agent.last_vector_steps)
+    except RuntimeError as e:
+        return dict(censored=True, reason=str(e)[:160])
+
+
+def shown(u):
+    return "censored" if u.get("censored") else f"{u['mean_lifetime']:9.1f} [{u['interval95'][0]:.1f}, {u['interval95'][1]:.1f}] in {u['vector_steps']} steps"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--d", type=int, nargs="+", default=[9, 11, 13, 15])
@@ -36,32 +53,40 @@ def main():
     ap.add_argument("--lattices", type=int, default=64)
     ap.add_argument("--episodes", type=int, default=64)
     ap.add_argument("--max-steps", type=int, default=40000)
+    ap.add_argument("--meas-ratio", type=float, default=1.0)
+    ap.add_argument("--weights", default=None)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    weights = None if a.weights is None else a.weights if a.weights == "rates" else tuple(int(x) for x in a.weights.split(","))
     record = dict(device=torch.cuda.get_device_name(0), model="DP", volume_depth=5, lattices=a.lattices, episodes=a.episodes, max_vector_steps=a.max_steps,
-                  seed=list(SEED), rows={})
-    path = a.out or os.path.join(ROOT, "profiles", "wide_uf_lifetimes_dp.json")
+                  seed=list(SEED), p_meas="= p" if a.meas_ratio == 1.0 else f"= {a.meas_ratio:g} p", weights=a.weights, rows={})
+    path = a.out or os.path.join(ROOT, "profiles", "wide_uf_lifetimes_weighted.json" if weights else "wide_uf_lifetimes_dp.json")
     for d in a.d:
         env = dq.VectorEnv(n_envs=a.lattices, seed=SEED, d=d, error_model="DP", use_Y=False, volume_depth=5, p_phys=0.01, p_meas=0.01, backend="wide")
         ev = dq.WideEvaluator(d, "DP", window=5, chunk=a.lattices, device=env.device)
         uf, ident = dq.WideUnionFindAgent(evaluator=ev), dq.WideUnionFindAgent(policy="identity")
+        weighted = dq.WideUnionFindAgent(evaluator=ev, weights=weights) if weights else None
         rows = record["rows"][f"d{d}"] = {}
         for rate in sorted(a.rates, reverse=True):
-            row = dict(identity=summary(ident.test_error_rates(env, [rate], nb_episodes=a.episodes, verbose=0, nb_max_episode_steps=a.max_steps)[rate]))
-            try:
-                row["union_find"] = dict(summary(uf.test_error_rates(env, [rate], nb_episodes=a.episodes, verbose=0, nb_max_episode_steps=a.max_steps)[rate]),
-                                         vector_steps=uf.last_vector_steps)
-            except RuntimeError as e:
-                row["union_find"] = dict(censored=True, reason=str(e)[:160])
+            pm = min(1.0, a.meas_ratio * rate)
+            row = dict(p_meas=pm, identity=summary(ident.test_error_rates(env, [rate], nb_episodes=a.episodes, p_meas=pm, verbose=0,
+                                                                          nb_max_episode_steps=a.max_steps)[rate]))
+            u = row["union_find"] = played(uf, env, rate, pm, a)
+            print(f"d = {d:2d} p = {rate:.3f}: identity {row['identity']['mean_lifetime']:9.1f}   union-find " + shown(u), flush=True)
+            if weighted is not None:
+                w = row["union_find_weighted"] = played(weighted, env, rate, pm, a)
+                w["weights"] = weighted.last_weights
+                if not u.get("censored") and not w.get("censored"):
+                    apart = w["interval95"][0] > u["interval95"][1] or u["interval95"][0] > w["interval95"][1]
+                    w.update(lifetime_over_unit=w["mean_lifetime"] / u["mean_lifetime"], episodes_unit=u["episodes"], intervals_overlap=not apart)
+                print(f"                    weighted {w['weights']} " + shown(w)
+                      + ("" if "lifetime_over_unit" not in w else f"   x {w['lifetime_over_unit']:.2f} of unit"
+                         + (" (intervals overlap)" if w["intervals_overlap"] else "")), flush=True)
             rows[f"{rate:g}"] = row
-            u = row["union_find"]
-            print(f"d = {d:2d} p = {rate:.3f}: identity {row['identity']['mean_lifetime']:9.1f}   union-find "
-                  + ("censored" if u.get("censored") else f"{u['mean_lifetime']:9.1f} [{u['interval95'][0]:.1f}, {u['interval95'][1]:.1f}] in {u['vector_steps']} steps"),
-                  flush=True)
             with open(path, "w") as f:                                                   # after every row: a time limit loses the row in progress only
                 json.dump(record, f, indent=1)
                 f.write("\n")
-            if u.get("censored"):
+            if u.get("censored") or (weighted is not None and row["union_find_weighted"].get("censored")):
                 break
         ev.close()
         env.close()
