@@ -27,7 +27,7 @@ def __getattr__(name):
         from . import agent
         return getattr(agent, name)
     if name in ("WideEvaluator", "stream_decode_wide", "memory_experiment_wide", "WideUnionFindAgent", "guided_actions_wide",
-                "completed_from_state", "WideBatchDecoder", "verdict_wide", "uf_weights"):
+                "completed_from_state", "WideBatchDecoder", "verdict_wide", "uf_weights", "uf_weights_correlated"):
         from . import decoder_wide
         return getattr(decoder_wide, name)
     if name in ("dist", "hdf5_reader", "weights_io", "function_library", "runner", "decoder", "decoder_wide"):

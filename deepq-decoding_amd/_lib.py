@@ -217,6 +217,8 @@ SIGNATURES = {
     "dq_wide_uf_run_closed": (_i, [_vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_decode_weighted": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_run_weighted": (_i, [_vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dq_wide_uf_decode_correlated": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dq_wide_uf_run_correlated": (_i, [_vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_envb_uf_select": (_i, [_vp, _vp, _vp, _vp]),
     "dq_envb_guided_select_uf": (_i, [_vp, _vp, _vp, _dbl, _dbl, _i, _seedp, _u64, _vp, _vp, _vp]),
     "dq_envb_uf_select_weighted": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),

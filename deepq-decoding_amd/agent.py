@@ -541,7 +541,7 @@ class DQNAgent:
 
     def decode_benchmark_wide(self, lattice, n_volumes, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0, masked_greedy=None,
                               max_actions=None, chunk=None, baseline=None, no_decoder=False, final_round="faulty", return_volumes=False, timings=None,
-                              referee=None, weights=None):
+                              referee=None, weights=None, correlated=None):
         """Scores decode_wide() on the device for any odd d in 3 .. 15 under decoder_wide.memory_experiment_wide's conventions:
         volume i is the first volume_depth rounds of lattice env_id_base + i.  lattice: an environment of either backend (the defaults of the rates and
         the seed; the agent is bound to a VectorEnv or drop-in environment given here), or (d, error_model, use_Y, volume_depth) with explicit rates and
@@ -557,11 +557,14 @@ class DQNAgent:
         d >= 13 (decoder_wide.refereed_uncorrected_into: launches of at most 2048 volumes, 0.24 s each at d = 15, depth 5, p = 0.006): keep n_volumes
         modest there.  weights (with baseline="union_find" only, else ValueError): None, a pair (w_space, w_time) of integers in
         1 .. 15, or "rates" -- the union-find row is decoded on the weighted graph exactly as memory_experiment_wide(weights=...) decodes it, with
-        rates=[...] one pair per rate block in the same launches, and its EvalResult reports .weights; the agent's row keeps its bits."""
+        rates=[...] one pair per rate block in the same launches, and its EvalResult reports .weights; the agent's row keeps its bits.  correlated
+        (with baseline="union_find" only): memory_experiment_wide's -- None, an integer w_corr beside an explicit pair, or "rates"
+        beside weights None or "rates" -- the union-find row is the correlated three-pass decode and reports the triple."""
         from . import decoder as D, decoder_wide as W
         weights = W.check_weights(weights, rates=True)
-        if weights is not None and baseline != "union_find":
-            raise ValueError("decode_benchmark_wide: weights= weights the union-find baseline's row: give baseline='union_find'")
+        correlated = W.check_correlated(correlated, weights, rates=True)
+        if (weights is not None or correlated is not None) and baseline != "union_find":
+            raise ValueError("decode_benchmark_wide: weights= and correlated= weight the union-find baseline's row: give baseline='union_find'")
         d, model, use_Y, depth, max_actions, n, ph, pm, seed, base, blk, keys, _ = W.check_decode_benchmark_wide_args(
             lattice, n_volumes, rates, p_phys, p_meas, seed, env_id_base, max_actions, chunk, baseline, final_round, referee)
         layers = D.action_layers(model, use_Y)
@@ -574,7 +577,8 @@ class DQNAgent:
         dec = self._wide_decoder_for(d, model, use_Y, depth, masked_greedy, max_actions, chunk)
         return W.score_decode_wide(dec, self._core.params, n, ph, pm, seed, base, blk, keys, baseline=baseline, no_decoder=no_decoder,
                                    final_round=final_round, return_volumes=return_volumes, timings=timings, referee=referee,
-                                   **({} if weights is None else dict(weights=weights)))
+                                   **({} if weights is None else dict(weights=weights)),
+                                   **({} if correlated is None else dict(correlated=correlated)))
 
     def compute_q_values(self, observation):
         obs = torch.as_tensor(np.asarray(observation), dtype=torch.uint8, device=self._core.device).reshape((1,) + tuple(self.model.input_shape)).contiguous()

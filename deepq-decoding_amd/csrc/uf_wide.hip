@@ -7,6 +7,8 @@
 // The two stream kernels are templates on Closed (dq_wide_uf_decode_closed / dq_wide_uf_run_closed), as uf_stream.hip's are.
 // and on Weighted (dq_wide_uf_decode_weighted / dq_wide_uf_run_weighted): the same two bodies around ufw_component<Closed, true>, an edge
 // of weight w full at g = 2 w, one (w_space, w_time) per stream; the Weighted = false instantiations are the unit-weight kernels, instruction for instruction.
+// And on Corr (dq_wide_uf_decode_correlated / dq_wide_uf_run_correlated): three component decodes per window, 0 dry, 1, 0, each one's
+// space edges cheap (w_corr) where the one before put its correction; one (w_space, w_time, w_corr) per stream, two masks behind the layout's bytes.
 // The lattice tables come from LatticeHost inside the handle; no environment handle is needed.
 #include "uf_wide.h"
 #include "lattice_host.h"
@@ -40,8 +42,17 @@ struct WideWeights {
 struct WideArgsWeighted : WideArgs {
     WideWeights w;
 };
-template <bool Weighted>
-using WideArgsOf = std::conditional_t<Weighted, WideArgsWeighted, WideArgs>;
+// The weights of a correlated launch: one triple for all streams, or a triple per stream.
+struct WideWeightsCorr {
+    const u8* each;             // != NULL: [3 i] .. [3 i + 2] = (w_space, w_time, w_corr) of stream i
+    int w_space, w_time, w_corr;
+};
+
+struct WideArgsCorrelated : WideArgs {
+    WideWeightsCorr w;
+};
+template <bool Weighted, bool Corr = false>
+using WideArgsOf = std::conditional_t<Corr, WideArgsCorrelated, std::conditional_t<Weighted, WideArgsWeighted, WideArgs>>;
 
 // The workgroup's own pair, clamped to 1 .. UFW_MAX_WEIGHT: a bad byte of a per-stream array cannot overrun the growth byte.
 static __device__ __forceinline__ void wide_weights(const WideWeights& w, size_t i, int& w_space, int& w_time) {
@@ -51,12 +62,23 @@ static __device__ __forceinline__ void wide_weights(const WideWeights& w, size_t
     UFW_IN_VGPR(w_space); UFW_IN_VGPR(w_time);
 }
 
+// The workgroup's own triple: the pair clamped as above, w_corr to 1 .. w_space.
+static __device__ __forceinline__ void wide_weights(const WideWeightsCorr& w, size_t i, int& w_space, int& w_time, int& w_corr) {
+    w_space = w.w_space; w_time = w.w_time; w_corr = w.w_corr;
+    if (w.each != nullptr) { w_space = w.each[3 * i]; w_time = w.each[3 * i + 1]; w_corr = w.each[3 * i + 2]; }
+    w_space = min(max(w_space, 1), UFW_MAX_WEIGHT); w_time = min(max(w_time, 1), UFW_MAX_WEIGHT); w_corr = min(max(w_corr, 1), w_space);
+    UFW_IN_VGPR(w_space); UFW_IN_VGPR(w_time); UFW_IN_VGPR(w_corr);
+}
+
 // The schedule around a source of rounds: next(j, row0, row1) is called once for every j = 0 .. T - 1, in order, by every thread; it leaves round j's defect
 // rows of the two components in the given LDS words (all UFW_ROW_WORDS of each) and may use barriers; `last` says j = T - 1 (the last row of the final window).
 // Closed: the stream ends on a round of perfect measurements, so the final window has no time edges in its last round.
 // Weighted: ufw_component<Closed, true> with the stream's (w_space, w_time); the schedule, the carry and the closed final window are the same.
-template <bool Closed, bool Weighted, class Next>
-static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem, const UfwLayout& L, int tid, Next next, int w_space = 1, int w_time = 1) {
+// Corr: per window three component decodes instead of two -- component 0 dry, which only leaves mask A of its correction's space
+// edges; component 1 with w_corr on A, committed, leaving mask B; component 0 again with w_corr on B, committed.  o_mask: the byte offset of the two masks.
+template <bool Closed, bool Weighted, bool Corr = false, class Next>
+static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem, const UfwLayout& L, int tid, Next next, int w_space = 1, int w_time = 1,
+                                                    int w_corr = 1, int o_mask = 0) {
     u32* s_frame = reinterpret_cast<u32*>(smem + L.o_frame);
     u32* s_carry = reinterpret_cast<u32*>(smem + L.o_carry);
     int* s_acc = reinterpret_cast<int*>(smem + L.o_acc);
@@ -88,14 +110,32 @@ static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem,
         }
         __syncthreads();
         G.depth = l; G.B = l * G.n; G.NN = G.B + 1; G.NE = l * G.per_round;
-        for (int c = 0; c < 2; ++c) {
-            G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
-            if constexpr (Weighted)
-                ufw_component<Closed, true>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS,
-                                            s_acc + c, s_acc + 4 + c, w_space, w_time, s_acc + 6);
-            else
-                ufw_component<Closed>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c,
-                                      s_acc + 4 + c);
+        if constexpr (Corr) {
+            u32* s_mask = reinterpret_cast<u32*>(smem + o_mask);   // u32 [2][window][8]: A, B
+            int mask_stride = window * UFW_FRAME_WORDS;
+            // without a defect of component 1 in the window nobody reads A: the dry pass is left out (workgroup-uniform)
+            int pass = __syncthreads_or(tid < l * UFW_ROW_WORDS && s_ring[row_stride + tid] != 0) ? 0 : 1;
+            UFW_IN_VGPR(mask_stride); UFW_IN_VGPR(pass);
+            for (; pass < 3; ++pass) {                             // components 0, 1, 0
+                const int c = pass & 1;
+                int dry = pass == 0;
+                UFW_IN_VGPR(dry);
+                G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
+                // pass 0 reads B, which nobody has written for this window, under w_corr = w_space: every space edge weighs w_space
+                ufw_component<Closed, true, true>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS,
+                                                  s_carry + c * UFW_ROW_WORDS, s_acc + c, s_acc + 4 + c, w_space, w_time, s_acc + 6, pass ? w_corr : w_space,
+                                                  s_mask + (c ? 0 : mask_stride), s_mask + (c ? mask_stride : 0), dry);
+            }
+        } else {
+            for (int c = 0; c < 2; ++c) {
+                G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
+                if constexpr (Weighted)
+                    ufw_component<Closed, true>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS,
+                                                s_acc + c, s_acc + 4 + c, w_space, w_time, s_acc + 6);
+                else
+                    ufw_component<Closed>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c,
+                                          s_acc + 4 + c);
+            }
         }
         if (final) break;
         // the ring moves down by `commit` rows (2 window UFW_ROW_WORDS <= UFW_THREADS words)
@@ -146,15 +186,17 @@ static __device__ __forceinline__ void wide_store(const WidePtrs& P, u8* smem, c
     }
 }
 
-template <bool Closed, bool Weighted = false>
-__global__ __launch_bounds__(UFW_THREADS) void stream_wide_uf_kernel(WideArgsOf<Weighted> p) {
+template <bool Closed, bool Weighted = false, bool Corr = false>
+__global__ __launch_bounds__(UFW_THREADS) void stream_wide_uf_kernel(WideArgsOf<Weighted, Corr> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
     if ((int)blockIdx.x >= p.n_streams) return;                     // workgroup-uniform
-    int w_space = 1, w_time = 1;
-    if constexpr (Weighted) wide_weights(p.w, i, w_space, w_time);
+    int w_space = 1, w_time = 1, w_corr = 1, o_mask = 0;
+    if constexpr (Corr) wide_weights(p.w, i, w_space, w_time, w_corr);
+    else if constexpr (Weighted) wide_weights(p.w, i, w_space, w_time);
     UfwLayout L = ufw_layout(p.n, p.d2, p.window);
+    if constexpr (Corr) { o_mask = L.bytes; UFW_IN_VGPR(o_mask); }  // the two masks: a tail behind the layout of before
     ufw_layout_in_vgpr(L);
     const int my_cell = p.node_cell[tid];
     const bool mine = (tid & (UFW_NODE_SLOTS - 1)) < p.n;            // (255 is a cell of the d = 15 grid: the table's padding does not tell)
@@ -162,22 +204,24 @@ __global__ __launch_bounds__(UFW_THREADS) void stream_wide_uf_kernel(WideArgsOf<
     const WidePtrs P = wide_ptrs(p, i, tid);
     int prev = 0, nd = 0, G = p.G;
     UFW_IN_VGPR(vp); UFW_IN_VGPR(prev); UFW_IN_VGPR(nd); UFW_IN_VGPR(G);
-    wide_windows<Closed, Weighted>(p, smem, L, tid, [&](int j, bool, u32* row0, u32* row1) {
+    wide_windows<Closed, Weighted, Corr>(p, smem, L, tid, [&](int j, bool, u32* row0, u32* row1) {
         const int cur = vp[(size_t)j * G] != 0;                    // (a thread without a node reads cell 0 of its own stream and masks it)
         wide_rows(mine ? cur : 0, prev, tid, row0, row1, nd);
-    }, w_space, w_time);
+    }, w_space, w_time, w_corr, o_mask);
     wide_store(P, smem, L, tid, nd);
 }
 
-template <bool Closed, bool Weighted = false>
-__global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArgsOf<Weighted> p) {
+template <bool Closed, bool Weighted = false, bool Corr = false>
+__global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArgsOf<Weighted, Corr> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
     if ((int)blockIdx.x >= p.n_streams) return;                     // workgroup-uniform
-    int w_space = 1, w_time = 1;
-    if constexpr (Weighted) wide_weights(p.w, i, w_space, w_time);
+    int w_space = 1, w_time = 1, w_corr = 1, o_mask = 0;
+    if constexpr (Corr) wide_weights(p.w, i, w_space, w_time, w_corr);
+    else if constexpr (Weighted) wide_weights(p.w, i, w_space, w_time);
     UfwLayout L = ufw_layout(p.n, p.d2, p.window);
+    if constexpr (Corr) { o_mask = L.bytes; UFW_IN_VGPR(o_mask); }  // the two masks: a tail behind the layout of before
     ufw_layout_in_vgpr(L);
     u8* s_ex = smem + L.o_ex;
     u8* s_ez = smem + L.o_ez;
@@ -204,7 +248,7 @@ __global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArg
     int x = 0, z = 0, prev = 0, seen = 0, nd = 0;
     UFW_IN_VGPR(has_q); UFW_IN_VGPR(has_s); UFW_IN_VGPR(isx); UFW_IN_VGPR(x); UFW_IN_VGPR(z); UFW_IN_VGPR(prev); UFW_IN_VGPR(seen); UFW_IN_VGPR(nd);
     UFW_IN_VGPR(hid); UFW_IN_VGPR(triv); UFW_IN_VGPR(syn);
-    wide_windows<Closed, Weighted>(p, smem, L, tid, [&](int j, bool last, u32* row0, u32* row1) {
+    wide_windows<Closed, Weighted, Corr>(p, smem, L, tid, [&](int j, bool last, u32* row0, u32* row1) {
         u32 w[4];                                                  // sample_volumes' round, round counter j
         philox4x32_10((u32)j, 0u, id, (u32)tid, seed0, seed1, w);
         const bool hit = has_q && (u64)w[0] < T_phys;
@@ -227,7 +271,7 @@ __global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArg
         if (syn) syn[(size_t)j * G] = cs < 255 ? s_v[cs] : (u8)0;
         const int cur = my_stab < 255 && s_v[my_stab] != 0;
         wide_rows(cur, prev, tid, row0, row1, nd);
-    }, w_space, w_time);
+    }, w_space, w_time, w_corr, o_mask);
     const int any_seen = __syncthreads_or(seen);
     if (has_q) *hid = (u8)(x ? (z ? 2 : 1) : (z ? 3 : 0));
     if (tid == 0) *triv = (u8)(any_seen == 0);
@@ -299,16 +343,31 @@ dq_status wide_check_weighted(int closed, int w_space, int w_time, const char* w
     return DQ_OK;
 }
 
-// The open and the closed entry points: one body, `who` names the caller in the messages.  ww: the weights of a weighted launch, NULL for the unit-weight kernels.
+// ... and the correlated forms on top of that: w_corr in 1 .. w_space.
+dq_status wide_check_correlated(int closed, int w_space, int w_time, int w_corr, const char* who) {
+    const dq_status rc = wide_check_weighted(closed, w_space, w_time, who);
+    if (rc != DQ_OK) return rc;
+    DQ_REQUIRE(w_corr >= 1 && w_corr <= w_space, DQ_ERR_INVALID, "%s: w_corr = %d outside 1..w_space = %d", who, w_corr, w_space);
+    return DQ_OK;
+}
+
+// The open and the closed entry points: one body, `who` names the caller in the messages.  ww: the weights of a weighted launch, wc: of a correlated one, both
+// NULL for the unit-weight kernels.
 dq_status wide_decode(bool closed, const char* who, dq_wide_uf* H, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
-                      int32_t* n_defects_dev, int32_t* rounds_dev, void* stream, const WideWeights* ww = nullptr) {
+                      int32_t* n_defects_dev, int32_t* rounds_dev, void* stream, const WideWeights* ww = nullptr, const WideWeightsCorr* wc = nullptr) {
     DQ_REQUIRE(H && syndromes_dev && frame_dev, DQ_ERR_INVALID, "%s: null argument", who);
     const dq_status rc = wide_check(H, n, T, commit, weight_dev, n_defects_dev, rounds_dev, who);
     if (rc != DQ_OK) return rc;
     WideArgs a;
     wide_args(H, n, T, commit, &a);
     a.syn_in = syndromes_dev; a.frame = frame_dev; a.weight = weight_dev; a.n_defects = n_defects_dev; a.rounds = rounds_dev;
-    if (ww) {
+    if (wc) {
+        WideArgsCorrelated ac;
+        static_cast<WideArgs&>(ac) = a; ac.w = *wc;
+        const int lds = H->lds + ufw_mask_bytes(H->window);
+        if (closed) stream_wide_uf_kernel<true, true, true><<<n, UFW_THREADS, lds, (hipStream_t)stream>>>(ac);
+        else stream_wide_uf_kernel<false, true, true><<<n, UFW_THREADS, lds, (hipStream_t)stream>>>(ac);
+    } else if (ww) {
         WideArgsWeighted aw;
         static_cast<WideArgs&>(aw) = a; aw.w = *ww;
         if (closed) stream_wide_uf_kernel<true, true><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(aw);
@@ -321,7 +380,8 @@ dq_status wide_decode(bool closed, const char* who, dq_wide_uf* H, const uint8_t
 
 dq_status wide_run(bool closed, const char* who, dq_wide_uf* H, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
                    const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev,
-                   int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream, const WideWeights* ww = nullptr) {
+                   int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream, const WideWeights* ww = nullptr,
+                   const WideWeightsCorr* wc = nullptr) {
     DQ_REQUIRE(H && seed && hidden_dev && trivial_dev && frame_dev, DQ_ERR_INVALID, "%s: null argument", who);
     dq_status rc = wide_check(H, n, T, commit, weight_dev, n_defects_dev, rounds_dev, who);
     if (rc != DQ_OK) return rc;
@@ -340,7 +400,13 @@ dq_status wide_run(bool closed, const char* who, dq_wide_uf* H, int n, int T, in
     a.env_id_base = env_id_base; a.seed0 = seed[0]; a.seed1 = seed[1];
     a.hidden = hidden_dev; a.trivial = trivial_dev; a.frame = frame_dev; a.weight = weight_dev; a.n_defects = n_defects_dev; a.rounds = rounds_dev;
     a.syn_out = syndromes_dev;
-    if (ww) {
+    if (wc) {
+        WideArgsCorrelated ac;
+        static_cast<WideArgs&>(ac) = a; ac.w = *wc;
+        const int lds = H->lds + ufw_mask_bytes(H->window);
+        if (closed) stream_run_wide_uf_kernel<true, true, true><<<n, UFW_THREADS, lds, st>>>(ac);
+        else stream_run_wide_uf_kernel<false, true, true><<<n, UFW_THREADS, lds, st>>>(ac);
+    } else if (ww) {
         WideArgsWeighted aw;
         static_cast<WideArgs&>(aw) = a; aw.w = *ww;
         if (closed) stream_run_wide_uf_kernel<true, true><<<n, UFW_THREADS, H->lds, st>>>(aw);
@@ -399,11 +465,18 @@ dq_status dq_wide_uf_create(int d, int error_model, int window, int max_streams,
                                   reinterpret_cast<const void*>(stream_run_wide_uf_kernel<false, true>),
                                   reinterpret_cast<const void*>(stream_wide_uf_kernel<true, true>),
                                   reinterpret_cast<const void*>(stream_run_wide_uf_kernel<true, true>)};
+        // the correlated kernels carry their two masks behind that
+        const int lds_max_corr = lds_max + ufw_mask_bytes(UFW_MAX_WINDOW);
+        const void* correlated[4] = {reinterpret_cast<const void*>(stream_wide_uf_kernel<false, true, true>),
+                                     reinterpret_cast<const void*>(stream_run_wide_uf_kernel<false, true, true>),
+                                     reinterpret_cast<const void*>(stream_wide_uf_kernel<true, true, true>),
+                                     reinterpret_cast<const void*>(stream_run_wide_uf_kernel<true, true, true>)};
         hipError_t ea = hipSuccess;
         for (int k = 0; k < 8 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        for (int k = 0; k < 4 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(correlated[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max_corr);
         if (ea != hipSuccess) {
             (void)hipGetLastError();
-            dq_set_error("dq_wide_uf_create: the device refuses %d bytes of LDS per workgroup: %s", lds_max, hipGetErrorString(ea));
+            dq_set_error("dq_wide_uf_create: the device refuses %d bytes of LDS per workgroup: %s", lds_max_corr, hipGetErrorString(ea));
             return DQ_ERR_UNSUPPORTED;
         }
         attr_devs |= dev_bit;
@@ -478,6 +551,27 @@ dq_status dq_wide_uf_run_weighted(dq_wide_uf* H, int n, int T, int commit, uint3
     const WideWeights ww = {weights_each_dev, w_space, w_time};
     return wide_run(closed != 0, "dq_wide_uf_run_weighted", H, n, T, commit, env_id_base, seed, p_phys, p_meas, p_phys_each, p_meas_each, hidden_dev, trivial_dev,
                     frame_dev, weight_dev, n_defects_dev, rounds_dev, syndromes_dev, stream, &ww);
+}
+
+dq_status dq_wide_uf_decode_correlated(dq_wide_uf* H, const uint8_t* syndromes_dev, int n, int T, int commit, int closed, int w_space, int w_time, int w_corr,
+                                       const uint8_t* weights_each_dev, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev,
+                                       void* stream) {
+    const dq_status rc = wide_check_correlated(closed, w_space, w_time, w_corr, "dq_wide_uf_decode_correlated");
+    if (rc != DQ_OK) return rc;
+    const WideWeightsCorr wc = {weights_each_dev, w_space, w_time, w_corr};
+    return wide_decode(closed != 0, "dq_wide_uf_decode_correlated", H, syndromes_dev, n, T, commit, frame_dev, weight_dev, n_defects_dev, rounds_dev, stream, nullptr,
+                       &wc);
+}
+
+dq_status dq_wide_uf_run_correlated(dq_wide_uf* H, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
+                                    const double* p_phys_each, const double* p_meas_each, int closed, int w_space, int w_time, int w_corr,
+                                    const uint8_t* weights_each_dev, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev,
+                                    int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
+    const dq_status rc = wide_check_correlated(closed, w_space, w_time, w_corr, "dq_wide_uf_run_correlated");
+    if (rc != DQ_OK) return rc;
+    const WideWeightsCorr wc = {weights_each_dev, w_space, w_time, w_corr};
+    return wide_run(closed != 0, "dq_wide_uf_run_correlated", H, n, T, commit, env_id_base, seed, p_phys, p_meas, p_phys_each, p_meas_each, hidden_dev, trivial_dev,
+                    frame_dev, weight_dev, n_defects_dev, rounds_dev, syndromes_dev, stream, nullptr, &wc);
 }
 
 dq_status dq_wide_uf_verdict(dq_wide_uf* H, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev, void* stream) {

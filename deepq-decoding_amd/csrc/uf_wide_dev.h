@@ -17,6 +17,10 @@
 // k >= d^2, both in 1 .. UFW_MAX_WEIGHT, one pair per stream.  The growth byte then holds g in bits 0 .. 4, the edge's increment of the running event in bits
 // 5 .. 6 and "full" in bit 7; the layout is the unweighted one.  Growth jumps from event to event: the workgroup reduces the number of unit steps until the
 // next edge fills (an LDS atomic minimum into a spare word of o_acc), every growing edge gains that many increments, and `rounds` counts the unit steps.
+//
+// Correlated decode (ufw_component<Closed, true, true>): the weight of a space edge is per edge -- w_corr where the edge's bit of a mask
+// u32 [depth][UFW_FRAME_WORDS] is set, else w_space -- and the peeling sets the bit of every space edge of the correction, committed or not, in a second
+// mask.  The two masks are a tail of 2 x window x UFW_FRAME_WORDS words behind ufw_layout's bytes (ufw_mask_bytes), for the correlated kernels only.
 #pragma once
 #include "common.h"
 
@@ -63,6 +67,9 @@ static __host__ __device__ inline UfwLayout ufw_layout(int n, int d2, int window
     return L;
 }
 
+// The correlated kernels' tail behind ufw_layout(...).bytes: two masks u32 [window][UFW_FRAME_WORDS], one read while the other is written.
+static __host__ __device__ inline int ufw_mask_bytes(int window) { return 2 * window * UFW_FRAME_WORDS * 4; }
+
 #ifdef __HIPCC__
 
 // x / p for x < 2^32 / p by one multiply: m = floor(2^32 / p) + 1
@@ -89,6 +96,17 @@ static __device__ __forceinline__ void ufw_ends(const UfwGraph& G, int e, int& a
     }
 }
 
+// The weight of edge (t, k): w_time for a time edge, w_space for a space edge -- with Corr, w_corr where the mask u32 [depth][UFW_FRAME_WORDS] has the edge's bit.
+template <bool Corr>
+static __device__ __forceinline__ int ufw_weight(int t, int k, int d2, int w_space, int w_time, int w_corr, volatile const u32* mask) {
+    if constexpr (Corr) {
+        if (k >= d2) return w_time;
+        return (mask[t * UFW_FRAME_WORDS + (k >> 5)] >> (k & 31)) & 1u ? w_corr : w_space;
+    } else {
+        return k < d2 ? w_space : w_time;
+    }
+}
+
 // One component of one window by the whole workgroup; every thread calls it with the same arguments.  dw: the component's rows u32 [depth][4] in LDS.
 // Unless `final`, only the edges of rounds t < commit count; a committed space edge XORs its qubit into s_frame [8], a committed edge adds 1 to *s_weight, the
 // time edges of round commit - 1 set their bit of s_carry [4] (zero on entry).  The growth rounds made are added to *s_rounds.
@@ -97,10 +115,15 @@ static __device__ __forceinline__ void ufw_ends(const UfwGraph& G, int e, int& a
 // across them and they are never in the correction.
 // Weighted: w_space / w_time in 1 .. UFW_MAX_WEIGHT (the caller clamps), s_event the LDS word of the event reduction; a committed edge adds its weight to
 // *s_weight, *s_rounds counts unit growth steps.  With Weighted = false the three arguments are not read and the code is the unit-weight one.
-template <bool Closed = false, bool Weighted = false>
+// Corr (with Weighted): the space edge (t, k) weighs w_corr where bit k of mask_r [t][8] is set; mask_w [depth][8] is zeroed on entry, in front of the early
+// return, and receives the bit of every space edge of the correction, whatever its round.  dry (workgroup-uniform): nothing is committed -- frame, carry, weight
+// and rounds stay as they are.  With Corr = false the four arguments are not read and the code is the one of before.
+template <bool Closed = false, bool Weighted = false, bool Corr = false>
 static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u32* dw, u8* __restrict__ s, const UfwLayout& L, int tid, int commit, bool final,
                                                      u32* s_frame, u32* s_carry, int* s_weight, int* s_rounds, int w_space = 1, int w_time = 1,
-                                                     int* s_event = nullptr) {
+                                                     int* s_event = nullptr, int w_corr = 1, const u32* mask_r = nullptr, u32* mask_w = nullptr,
+                                                     int dry = 0) {
+    static_assert(Weighted || !Corr, "the correlated decode is a weighted one");
     u32* s_label = reinterpret_cast<u32*>(s + L.o_label);
     u32* s_par = reinterpret_cast<u32*>(s + L.o_par);
     u32* s_parent = reinterpret_cast<u32*>(s + L.o_parent);
@@ -112,6 +135,12 @@ static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u3
     volatile const u32* v_dw = dw;
     const int n = G.n, B = G.B, NN = G.NN, NE = G.NE;
     const int NE_grown = Closed && final ? NE - n : NE;
+    const int d2 = G.d2;
+    volatile const u32* v_mask = mask_r;
+#define UFW_WEIGHT_OF(t, k) ufw_weight<Corr>(t, k, d2, w_space, w_time, w_corr, v_mask)
+    if constexpr (Corr) {                                         // (depth <= UFW_MAX_WINDOW: one word per thread; the barrier below publishes it)
+        if (tid < G.depth * UFW_FRAME_WORDS) mask_w[tid] = 0;
+    }
     // nothing to correct: workgroup-uniform, the graph arrays untouched
     if (!__syncthreads_or(tid < G.depth * UFW_ROW_WORDS && v_dw[tid] != 0)) return;
     auto defect = [&](int x) -> u32 {
@@ -189,7 +218,7 @@ static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u3
                 const u32 la = v_label[a], lb = v_label[b];
                 const int inc = (int)(la != 0 && (v_par[la] & 1u)) + (int)(lb != 0 && (v_par[lb] & 1u));
                 if (!inc) continue;
-                const int left = 2 * (k < G.d2 ? w_space : w_time) - (int)g0;  // > 0: the edge is not full
+                const int left = 2 * UFW_WEIGHT_OF(t, k) - (int)g0;             // > 0: the edge is not full
                 steps = min(steps, (left + inc - 1) >> (inc - 1));             // ceil(left / inc), inc in {1, 2}
                 s_g[e] = (u8)(g0 | ((u32)inc << UFW_INC_SHIFT));
             }
@@ -202,7 +231,7 @@ static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u3
                 const u32 g0 = s_g[e];
                 const int inc = (int)((g0 >> UFW_INC_SHIFT) & 3u);
                 if (!inc) continue;
-                const int t = ufw_div(e, G.mag_pr), k = e - t * G.per_round, cap = 2 * (k < G.d2 ? w_space : w_time);
+                const int t = ufw_div(e, G.mag_pr), k = e - t * G.per_round, cap = 2 * UFW_WEIGHT_OF(t, k);
                 const int g1 = min(cap, (int)(g0 & UFW_G_MASK) + inc * jump);
                 s_g[e] = (u8)(g1 == cap ? (u32)g1 | UFW_FULL : (u32)g1);
             }
@@ -257,6 +286,10 @@ static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u3
             int a, b, t, k;
             ufw_ends(G, e, a, b, t, k);
             __hip_atomic_fetch_xor(s_par + (a == x ? b : a), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if constexpr (Corr) {
+                if (k < G.d2) __hip_atomic_fetch_or(mask_w + t * UFW_FRAME_WORDS + (k >> 5), 1u << (k & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (dry) continue;
+            }
             if (!final) {                                         // (an edge is in the correction once: its lower end has one parent edge)
                 if (t >= commit) continue;
                 if (k >= G.d2 && t == commit - 1) {
@@ -264,14 +297,15 @@ static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u3
                     __hip_atomic_fetch_or(s_carry + (u >> 5), 1u << (u & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
-            w += Weighted ? (k < G.d2 ? w_space : w_time) : 1;
+            w += Weighted ? UFW_WEIGHT_OF(t, k) : 1;
             if (k < G.d2) __hip_atomic_fetch_xor(s_frame + (k >> 5), 1u << (k & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         __syncthreads();
     }
     if (w) __hip_atomic_fetch_add(s_weight, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (tid == 0) *s_rounds += rounds;
+    if (tid == 0 && !(Corr && dry)) *s_rounds += rounds;
     __syncthreads();                                              // every thread is through with the graph arrays before the next component reuses them
+#undef UFW_WEIGHT_OF
 }
 
 #endif  // __HIPCC__

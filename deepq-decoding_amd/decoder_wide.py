@@ -12,6 +12,11 @@ for the space edges and w_time for the time edges, so that a misread stabilizer 
 unit-weight launch of before, untouched.  The policy and teacher of the wide environment and decode_benchmark_wide's union-find row take it too (DESIGN.md
 section 24): WideUnionFindAgent(weights=...), VectorEnv.uf_select_wide / guided_select_wide(weights=...).
 
+correlated= (stream_decode_wide, memory_experiment_wide, DQNAgent.decode_benchmark_wide) stops decoding the two Pauli components
+independently: per window component 0 is decoded dry, component 1 with weight w_corr on the space edges of that correction, component 0 again with
+w_corr on the space edges of component 1's (uf_weights_correlated: w_corr = 1 under DP, where a Y error flips one qubit in both).  None is the launch
+of before, untouched.
+
 Further down: the union-find decoder as a policy and a teacher of the wide environment (section 19), and batched decoding by a trained agent at these
 sizes -- WideBatchDecoder, the wide form of decoder.BatchDecoder, and the scorer behind DQNAgent.decode_benchmark_wide (include/deepq_hip.h
 dq_decode_wide_*; csrc/decode_wide.hip).
@@ -89,6 +94,75 @@ def uf_weights(p_phys, p_meas, error_model, max_weight=8):
     return best[1], best[2]
 
 
+CORRELATED_MIN_SPACE = 4
+
+
+def uf_weights_correlated(p_phys, p_meas, error_model, max_weight=8):
+    """uf_weights' pair with w_corr behind it: the weight of a space edge of one component where the other component's correction
+    has the same qubit in the same round.  X and IIDXZ: the components are independent, w_corr = w_space (the weighted decode, unchanged).  DP: given a
+    flip in one component the other one has flipped too with chance 1/2, a log-likelihood weight of 0, and the smallest weight the growth bits hold is 1:
+    w_corr = 1.  So that 1 is well below w_space, a DP pair with w_space < 4 is multiplied by ceil(4 / w_space) -- by less where the product would pass
+    15, the largest weight (with the default max_weight that happens for w_time = 8 alone: (1, 8) stays and w_corr = w_space = 1 changes nothing)."""
+    w_space, w_time = uf_weights(p_phys, p_meas, error_model, max_weight)
+    if error_model != "DP":
+        return w_space, w_time, w_space
+    k = max(1, min(-(-CORRELATED_MIN_SPACE // w_space), WIDE_MAX_WEIGHT // max(w_space, w_time)))
+    return k * w_space, k * w_time, 1
+
+
+def check_correlated(correlated, weights, rates=False):
+    """correlated= of the wide entry points beside an already validated weights= (check_weights), without touching the library.  None: nothing changes.
+    An integer w_corr in 1 .. 15: weights must be an explicit pair or an array of pairs with w_corr <= w_space in each.  With rates, "rates": weights
+    must be None or "rates" (uf_weights_correlated of every stream's own rates).  Else ValueError.  Returns None, the integer, or "rates"."""
+    if correlated is None:
+        return None
+    if isinstance(correlated, str):
+        if not (rates and correlated == "rates"):
+            raise ValueError("correlated must be None" + (", 'rates'" if rates else "") + f" or an integer w_corr in 1..{WIDE_MAX_WEIGHT}, not {correlated!r}")
+        if weights is not None and not (isinstance(weights, str) and weights == "rates"):
+            raise ValueError(f"correlated='rates' takes its weights from the rates: weights must be None or 'rates', not {weights!r}")
+        return correlated
+    if not is_int(correlated) or not 1 <= correlated <= WIDE_MAX_WEIGHT:
+        raise ValueError("correlated must be None" + (", 'rates'" if rates else "") + f" or an integer w_corr in 1..{WIDE_MAX_WEIGHT}, not {correlated!r}")
+    if weights is None or isinstance(weights, str):
+        raise ValueError(f"correlated={correlated!r} needs explicit weights=(w_space, w_time) with w_corr <= w_space, not weights={weights!r}")
+    w_space = weights[0] if isinstance(weights, tuple) else int(weights[:, 0].min())
+    if correlated > w_space:
+        raise ValueError(f"correlated: w_corr = {correlated} exceeds w_space = {w_space}")
+    return int(correlated)
+
+
+def with_correlated(weights, correlated):
+    """The validated (weights, correlated) as one value for decode_into / run_into: the pair or the uint8 [n, 2] array with w_corr behind it (a triple,
+    uint8 [n, 3]); weights itself where correlated is None."""
+    if correlated is None:
+        return weights
+    if isinstance(weights, tuple):
+        return weights + (correlated,)
+    return np.ascontiguousarray(np.concatenate([weights, np.full((len(weights), 1), correlated, dtype=np.uint8)], axis=1))
+
+
+def rate_weights_correlated(p_phys, p_meas, error_model, n):
+    """correlated="rates": uf_weights_correlated of every stream's own (p_phys, p_meas).  Returns one triple where the rates are scalars, else uint8 [n, 3]."""
+    if isinstance(p_phys, float):
+        return uf_weights_correlated(p_phys, p_meas, error_model)
+    out = np.empty((n, 3), dtype=np.uint8)
+    triples = {}
+    for i, key in enumerate(zip(p_phys.tolist(), p_meas.tolist())):
+        if key not in triples:
+            triples[key] = uf_weights_correlated(key[0], key[1], error_model)
+        out[i] = triples[key]
+    return out
+
+
+def is_correlated(weights):
+    """Whether what decode_into / run_into got as weights= is a triple or an array of triples."""
+    if isinstance(weights, tuple):
+        return len(weights) == 3
+    shape = getattr(weights, "shape", None)
+    return shape is not None and len(shape) == 2 and int(shape[1]) == 3
+
+
 def check_weights(weights, n=None, rates=False):
     """weights= of the wide entry points, validated without touching the library: None; a pair (w_space, w_time) of integers in 1 .. 15, returned as a tuple;
     with n, an integer array [n, 2] of such pairs, returned as uint8 [n, 2]; with rates, the string "rates", returned as it is.  Else ValueError."""
@@ -163,7 +237,8 @@ def weight_pairs(weights, rates=None, error_model=None, n=None):
         weights = rate_weights(*(np.broadcast_to(np.asarray(x, dtype=np.float64), (n,)) for x in (ph, pm)), error_model, n)
     if hasattr(weights, "detach"):
         weights = weights.detach().cpu().numpy()
-    pairs = sorted({(int(a), int(b)) for a, b in np.unique(np.asarray(weights).reshape(-1, 2), axis=0)})
+    a = np.asarray(weights)
+    pairs = sorted({tuple(int(x) for x in row) for row in np.unique(a.reshape(-1, a.shape[-1]), axis=0)})       # (pairs, or triples with correlated=)
     return pairs[0] if len(pairs) == 1 else pairs
 
 
@@ -287,8 +362,14 @@ class WideEvaluator(Counting):
     def decode_into(self, syndromes, m, T, commit, frame, weight=None, n_defects=None, rounds=None, final_round="faulty", weights=None):
         """The sliding-window decode (dq_wide_uf_decode) of m <= chunk streams of T rounds already on the device.  final_round="perfect":
         dq_wide_uf_decode_closed.  weights: a pair (w_space, w_time) or a uint8 device tensor [m, 2], both validated by the caller (check_weights):
-        dq_wide_uf_decode_weighted."""
+        dq_wide_uf_decode_weighted.  A triple (w_space, w_time, w_corr) or a uint8 device tensor [m, 3] (with_correlated): dq_wide_uf_decode_correlated."""
         from . import _lib
+        if is_correlated(weights):
+            triple, each = (weights, None) if isinstance(weights, tuple) else ((1, 1, 1), weights)
+            _lib.check(self.L.dq_wide_uf_decode_correlated(self._h, _lib.ptr(syndromes), m, T, commit, int(check_final_round(final_round)), *triple,
+                                                           _lib.ptr(each), _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
+                                                           self._stream()))
+            return
         if weights is not None:
             pair, each = (weights, None) if isinstance(weights, tuple) else ((1, 1), weights)
             _lib.check(self.L.dq_wide_uf_decode_weighted(self._h, _lib.ptr(syndromes), m, T, commit, int(check_final_round(final_round)), pair[0], pair[1],
@@ -301,10 +382,18 @@ class WideEvaluator(Counting):
     def run_into(self, m, T, commit, lattice_id, seed, p_phys, p_meas, hidden, trivial, frame, weight=None, n_defects=None, rounds=None, syndromes=None,
                  final_round="faulty", weights=None):
         """m <= chunk streams of T rounds of lattices lattice_id .. lattice_id + m - 1 (mod 2^32), sampled and decoded in one kernel (dq_wide_uf_run).
-        final_round="perfect": dq_wide_uf_run_closed.  weights: as decode_into's: dq_wide_uf_run_weighted."""
+        final_round="perfect": dq_wide_uf_run_closed.  weights: as decode_into's: dq_wide_uf_run_weighted, dq_wide_uf_run_correlated."""
         from . import _lib
         arr = (ctypes.c_uint32 * 2)(*seed)
         each = not isinstance(p_phys, float)
+        if is_correlated(weights):
+            triple, w_each = (weights, None) if isinstance(weights, tuple) else ((1, 1, 1), weights)
+            _lib.check(self.L.dq_wide_uf_run_correlated(self._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
+                                                        p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None,
+                                                        int(check_final_round(final_round)), *triple, _lib.ptr(w_each), _lib.ptr(hidden),
+                                                        _lib.ptr(trivial), _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
+                                                        _lib.ptr(syndromes), self._stream()))
+            return
         if weights is not None:
             pair, w_each = (weights, None) if isinstance(weights, tuple) else ((1, 1), weights)
             _lib.check(self.L.dq_wide_uf_run_weighted(self._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
@@ -331,18 +420,22 @@ class WideEvaluator(Counting):
                                                       self._stream()))
 
 
-def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None, final_round="faulty", weights=None):
+def stream_decode_wide(syndromes, d, window=None, commit=None, chunk=DEFAULT_CHUNK, to_host=False, evaluator=None, final_round="faulty", weights=None,
+                       correlated=None):
     """decoder.stream_decode for any odd d in 3 .. 15 and a window of up to 32 rounds.  syndromes: uint8 [N, T, d+1, d+1] with 0/1 cells, or one stream
     [T, d+1, d+1], numpy or torch; window defaults to min(2 d, 32), commit to (window + 1) // 2.  Returns a decoder.StreamResult of device tensors (numpy
     arrays with to_host); the result of a stream does not depend on the batch around it or on `chunk`.  evaluator: a WideEvaluator of this d and window to
     run on (its chunk is used and it stays open); default: one for this call.  final_round="perfect": decoder.stream_decode's closed form (DESIGN.md
     section 20).  weights: None (unit weights: the launch of before), a pair (w_space, w_time) of integers in 1 .. 15 for every stream, or an integer
     array [N, 2] with one pair per stream: an edge of weight w is full at growth 2 w, StreamResult.weight is the weighted cost
-    of the committed edges and StreamResult.rounds counts unit growth rounds."""
+    of the committed edges and StreamResult.rounds counts unit growth rounds.  correlated: None (the launches of before), or an integer w_corr with
+    1 <= w_corr <= w_space beside explicit weights: per window component 0 is decoded dry, component 1 with w_corr on the space
+    edges of that correction, and component 0 again with w_corr on the space edges of component 1's; weight and rounds count the last two."""
     import torch
     closed = closed_kw(final_round)
     d, n, single, T, window, commit, chunk = check_wide_stream_args(syndromes, d, window, commit, chunk, evaluator)
     weights = check_weights(weights, n)
+    weights = with_correlated(weights, check_correlated(correlated, weights))
     ev = WideEvaluator(d, "DP", window, chunk=min(chunk, n)) if evaluator is None else evaluator
     dev = ev.device
     try:
@@ -438,7 +531,7 @@ def uncorrected_into(ev, hidden, m, out, flags=None):
 
 def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0,
                            chunk=DEFAULT_CHUNK, no_decoder=False, timings=None, evaluator=None, return_streams=False, final_round="faulty", referee=None,
-                           weights=None):
+                           weights=None, correlated=None):
     """decoder.memory_experiment for any odd d in 3 .. 15 and a window of up to 32 rounds: n_runs streams, stream i the first `rounds` rounds of lattice
     env_id_base + i under sample_volumes' convention, sampled and decoded in ONE kernel per chunk (dq_wide_uf_run), then verdict -> counts on the device.
     lattice: (d, error_model), or an environment of either backend, of which only d, error_model, the rates and the seed are read (the defaults of p_phys /
@@ -455,16 +548,24 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
     decoder.memory_experiment's closed form.  weights: None (unit weights: the launches of before), a pair (w_space, w_time) of
     integers in 1 .. 15, or "rates": uf_weights of each stream's own (p_phys, p_meas) under the lattice's error model -- with rates=[...] every rate
     block gets its own pair, in the same launches.  Every EvalResult of the answer then has .weights, the pair its streams were
-    decoded with (None without weights); it combines with final_round= and referee= without restriction."""
+    decoded with (None without weights); it combines with final_round= and referee= without restriction.  correlated: None (the
+    launches of before); an integer w_corr beside an explicit pair, as stream_decode_wide's; or "rates" beside weights None or "rates":
+    uf_weights_correlated of each stream's own rates, every rate block its own triple in the same launches.  .weights is then the triple
+    (w_space, w_time, w_corr)."""
     import torch
     closed = closed_kw(final_round)
     refereed = check_referee(referee)
     weights = check_weights(weights, rates=True)
+    correlated = check_correlated(correlated, weights, rates=True)
     d, model, T, window, commit, n, ph, pm, seed, base, blk, keys, chunk = check_wide_experiment_args(
         lattice, n_runs, rounds, window, commit, rates, p_phys, p_meas, seed, env_id_base, chunk, evaluator)
-    if weights == "rates":
+    if correlated == "rates":
+        weights = rate_weights_correlated(ph, pm, model, n)
+    elif weights == "rates":
         weights = rate_weights(ph, pm, model, n)
-    used = weights                                                    # None, the pair, or uint8 [n, 2] on the host
+    else:
+        weights = with_correlated(weights, correlated)
+    used = weights                                                    # None, the pair / triple, or uint8 [n, 2] / [n, 3] on the host
     ev = WideEvaluator(d, model, window, chunk=min(chunk, n)) if evaluator is None else evaluator
     dev = ev.device
     try:
@@ -488,8 +589,7 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
         if used is None or isinstance(used, tuple):
             r.weights = used
         else:
-            pairs = [(int(a), int(b)) for a, b in np.unique(used[k * blk:(k + 1) * blk], axis=0)]
-            r.weights = pairs[0] if len(pairs) == 1 else pairs
+            r.weights = weight_pairs(used[k * blk:(k + 1) * blk])
         if r.no_decoder is not None:
             r.no_decoder.weights = None
     return (keyed(results, keys), streams) if return_streams else keyed(results, keys)
@@ -888,21 +988,26 @@ def check_decode_benchmark_wide_args(lattice, n_volumes, rates=None, p_phys=None
 
 
 def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=None, no_decoder=False, final_round="faulty", return_volumes=False,
-                      timings=None, referee=None, weights=None):
+                      timings=None, referee=None, weights=None, correlated=None):
     """The loop behind DQNAgent.decode_benchmark_wide for a validated request: per chunk ONE dq_wide_uf_run (T = window = commit = volume_depth, with
     syndromes) yields the agent's input, the hidden state and the union-find frame of the same volumes; then dq_decode_wide_run, dq_wide_uf_verdict
     and dq_decode_count with the agent's status and correction count.  referee=None: no referee is consulted, alive := success; referee="matching":
     the verdicts of all three rows (the agent's, the union-find baseline's, no_decoder's) go through dq_wide_uf_verdict_refereed and each row's
     EvalResult.inexact counts its flagged volumes.  weights (validated: None, a pair or "rates"): the sampling launch is
     dq_wide_uf_run_weighted, as memory_experiment_wide's -- the volumes and the hidden state do not depend on the weights, only the union-find frame does, so
-    the agent's row keeps its bits; the baseline's EvalResult of every block reports .weights."""
+    the agent's row keeps its bits; the baseline's EvalResult of every block reports .weights.  correlated (validated: None, an integer or "rates";
+    DESIGN.md section 25): dq_wide_uf_run_correlated, and .weights is the triple."""
     import torch
     from .decoder import DecodeResult
     refereed = check_referee(referee)
     d, depth, dev = dec.d, dec.volume_depth, dec.device
-    if isinstance(weights, str):                                      # "rates"
+    if correlated == "rates":
+        weights = rate_weights_correlated(ph, pm, dec.error_model, n)
+    elif isinstance(weights, str):                                    # "rates"
         weights = rate_weights(ph, pm, dec.error_model, n)
-    used = weights                                                    # None, the pair, or uint8 [n, 2] on the host
+    else:
+        weights = with_correlated(weights, correlated)
+    used = weights                                                    # None, the pair / triple, or uint8 [n, 2] / [n, 3] on the host
     if isinstance(weights, np.ndarray):
         weights = torch.from_numpy(weights).to(device=dev)
     step = min(dec.chunk, n)

@@ -930,6 +930,26 @@ dq_status dq_wide_uf_run_weighted(dq_wide_uf* h, int n, int T, int commit, uint3
                                   const double* p_phys_each, const double* p_meas_each, int closed, int w_space, int w_time, const uint8_t* weights_each_dev,
                                   uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev,
                                   int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
+/* Correlated union-find.  dq_version() stays 8: the capability is the presence of these two symbols.  Under depolarising noise a Y
+ * error flips one qubit in both components, so a correction of one component says where the other one's errors are likely.  Per stream and per window, inside
+ * the weighted forms' schedule, carry and closed final window, three component decodes are made instead of two:
+ *   pass 0  component 0 with (w_space, w_time), dry: nothing is committed; mask A = the space edges (round, qubit) of its correction, in every round of the
+ *           window, committed or not
+ *   pass 1  component 1, a space edge weighing w_corr where A has it and w_space elsewhere; committed as in the weighted form (frame, carry, weight = the sum
+ *           of the weights used, rounds); mask B = the space edges of its whole correction
+ *   pass 2  component 0 on pass 0's rows with B in A's place, committed
+ * weight_dev and rounds_dev count passes 1 and 2.  A component without defects in the window leaves an empty mask; with w_corr = w_space every field equals the
+ * weighted forms'.  The result of a stream is a function of the stream alone.
+ * w_corr: in 1 .. w_space, else DQ_ERR_INVALID before any device work.  weights_each_dev (nullable): uint8 [n][3] on the device, (w_space, w_time, w_corr) of
+ * stream i; the kernel clamps the pair to 1 .. 15 and w_corr to 1 .. w_space.  Every other argument, the validation and the error codes are those of the
+ * weighted forms.  The kernels need 2 x window x 32 bytes of LDS more than the handle's other launches (65 200 bytes at d = 15, window 32). */
+dq_status dq_wide_uf_decode_correlated(dq_wide_uf* h, const uint8_t* syndromes_dev, int n, int T, int commit, int closed, int w_space, int w_time, int w_corr,
+                                       const uint8_t* weights_each_dev, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev,
+                                       void* stream);
+dq_status dq_wide_uf_run_correlated(dq_wide_uf* h, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
+                                    const double* p_phys_each, const double* p_meas_each, int closed, int w_space, int w_time, int w_corr,
+                                    const uint8_t* weights_each_dev, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev,
+                                    int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream);
 
 /* The union-find decoder as a policy and as a teacher of the wide environment, any odd d in 3 .. 15 (csrc/env_wide_uf.hip).
  * dq_version() stays 8: the capability is the presence of these two symbols.  The rules are dq_env_uf_select's and dq_env_guided_select_uf's on the wide

@@ -1,7 +1,7 @@
 """Logical failure of a memory experiment against the physical error rate for a family of distances: the threshold table.
 
     python tools/threshold_sweep.py [--distances 3,5,...,15] [--rates 0.005,...] [--rounds 60,120] [--streams 4096] [--model DP] [--final-round faulty|perfect] [--referee matching]
-                                      [--meas-ratio R] [--weights rates|WS,WT] [--out FILE]
+                                      [--meas-ratio R] [--weights rates|WS,WT] [--correlated rates|W] [--out FILE]
 
 Every cell (d, p) is memory_experiment_wide on --streams streams with p_meas = p, window min(2 d, 32), commit (window + 1) // 2, one seed and one range of
 lattice ids for every cell, at each of the one or two stream lengths of --rounds.  For d <= 7 the same streams also go through decoder.memory_experiment
@@ -19,7 +19,9 @@ would have ended the episode, the referee having completed the residual under pe
 inexact, the crossings are also read on death_rate, and the record goes to profiles/threshold_sweep_<model>_refereed.json.  --meas-ratio R sweeps with
 p_meas = R p instead of p_meas = p.  --weights decodes on the weighted graph: "rates" takes decoder_wide.uf_weights of every cell's
 own (p, p_meas), WS,WT one pair for every cell; each cell records the pair it was decoded with, the one-wavefront kernels (unit weights only) are then not
-compared, and the record's name ends in _weighted."""
+compared, and the record's name ends in _weighted.  --correlated decodes the three passes of DESIGN.md section 25: "rates" (with --weights rates or none)
+takes decoder_wide.uf_weights_correlated of every cell's rates, W an integer w_corr beside --weights WS,WT; each cell records its triple and the record's
+name ends in _correlated."""
 import argparse
 import importlib
 import json
@@ -71,21 +73,24 @@ def main():
     ap.add_argument("--referee", choices=("matching",), default=None)
     ap.add_argument("--meas-ratio", type=float, default=1.0)
     ap.add_argument("--weights", default=None)
+    ap.add_argument("--correlated", default=None)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     weights = None if a.weights is None else a.weights if a.weights == "rates" else tuple(int(x) for x in a.weights.split(","))
+    correlated = None if a.correlated is None else a.correlated if a.correlated == "rates" else int(a.correlated)
+    dq.decoder_wide.check_correlated(correlated, dq.decoder_wide.check_weights(weights, rates=True), rates=True)      # (a ValueError before any cell is run)
     distances = [int(x) for x in a.distances.split(",")]
     rates = [float(x) for x in a.rates.split(",")]
     lengths = sorted(int(x) for x in a.rounds.split(","))
     assert 1 <= len(lengths) <= 2 and len(set(lengths)) == len(lengths), "--rounds takes one or two distinct stream lengths"
     D, DW = dq.decoder, dq.decoder_wide
     record = dict(device=torch.cuda.get_device_name(0), model=a.model, rounds=lengths, streams_per_cell=a.streams, seed=list(SEED),
-                  env_id_base=a.env_id_base, p_meas="= p" if a.meas_ratio == 1.0 else f"= {a.meas_ratio:g} p", weights=a.weights, final_round=a.final_round, referee=a.referee, cells={}, narrow_checked=[])
+                  env_id_base=a.env_id_base, p_meas="= p" if a.meas_ratio == 1.0 else f"= {a.meas_ratio:g} p", weights=a.weights, correlated=a.correlated, final_round=a.final_round, referee=a.referee, cells={}, narrow_checked=[])
     table = {}
     for d in distances:
         _, window, commit = DW.check_wide_schedule(d, lengths[0], None, None)
         ev = DW.WideEvaluator(d, a.model, window, chunk=a.streams)
-        env = dq.VectorEnv(n_envs=1, p_phys=rates[0], p_meas=rates[0], seed=SEED, d=d, error_model=a.model, use_Y=False, volume_depth=5) if d <= 7 and weights is None else None
+        env = dq.VectorEnv(n_envs=1, p_phys=rates[0], p_meas=rates[0], seed=SEED, d=d, error_model=a.model, use_Y=False, volume_depth=5) if d <= 7 and weights is None and correlated is None else None
         table[d] = {}
         for p in rates:
             pm = min(1.0, a.meas_ratio * p)
@@ -93,7 +98,7 @@ def main():
             for T in lengths:
                 t0 = time.perf_counter()
                 r = DW.memory_experiment_wide((d, a.model), a.streams, T, p_phys=p, p_meas=pm, seed=SEED, env_id_base=a.env_id_base, evaluator=ev,
-                                              final_round=a.final_round, referee=a.referee, weights=weights)
+                                              final_round=a.final_round, referee=a.referee, weights=weights, correlated=correlated)
                 cell["weights"] = r.weights
                 torch.cuda.synchronize()
                 one = r.summary()
@@ -135,7 +140,7 @@ def main():
         where = (f"between p = {c['crossing_between'][0]} and {c['crossing_between'][1]}" if c["crossing_between"] else
                  "not inside the grid" + (" (the larger distance fails less at every rate)" if all(c["larger_distance_fails_less"]) else ""))
         print(f"{c['figure']}, d = {lo} / {hi}: the curves cross {where}; intervals disjoint at {sum(c['intervals_disjoint'])} of {len(rates)} rates")
-    path = a.out or os.path.join(ROOT, "profiles", f"threshold_sweep_{a.model.lower()}{'_closed' if a.final_round == 'perfect' else ''}{'_refereed' if a.referee else ''}{'_weighted' if weights else ''}.json")
+    path = a.out or os.path.join(ROOT, "profiles", f"threshold_sweep_{a.model.lower()}{'_closed' if a.final_round == 'perfect' else ''}{'_refereed' if a.referee else ''}{'_weighted' if weights else ''}{'_correlated' if correlated else ''}.json")
     with open(path, "w") as f:
         json.dump(record, f, indent=1)
         f.write("\n")
