@@ -223,6 +223,8 @@ SIGNATURES = {
     "dq_envb_guided_select_uf": (_i, [_vp, _vp, _vp, _dbl, _dbl, _i, _seedp, _u64, _vp, _vp, _vp]),
     "dq_envb_uf_select_weighted": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "dq_envb_guided_select_uf_weighted": (_i, [_vp, _vp, _vp, _dbl, _dbl, _i, _seedp, _u64, _i, _i, _vp, _vp, _vp, _vp]),
+    "dq_envb_uf_select_correlated": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "dq_envb_guided_select_uf_correlated": (_i, [_vp, _vp, _vp, _dbl, _dbl, _i, _seedp, _u64, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dq_decode_wide_create": (_i, [ctypes.POINTER(DecodeCfg), _i, ctypes.POINTER(_vp)]),
     "dq_decode_wide_destroy": (None, [_vp]),
     "dq_decode_wide_pack": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -620,8 +620,10 @@ class DQNAgent:
         (WideUnionFindAgent(weights=...)), resolved once for the run; without them the call of before, argument for argument."""
         if not core._wide:
             return functools.partial(core.guided_act_and_step, method=getattr(guide, "method", "matching"))
-        if getattr(guide, "weights", None) is None:
+        if getattr(guide, "weights", None) is None and getattr(guide, "correlated", None) is None:
             return core.guided_act_and_step_wide
+        if getattr(guide, "correlated", None) is not None:            # (DESIGN.md section 26)
+            return functools.partial(core.guided_act_and_step_wide, **guide.select_kw(venv))
         return functools.partial(core.guided_act_and_step_wide, weights=guide.weights_for(venv))
 
     def fit(self, env, nb_steps, action_repetition=1, callbacks=None, verbose=1, visualize=False, nb_max_start_steps=0,

@@ -247,18 +247,21 @@ class DQNCore:
         r.advance()
         self.vector_steps += 1
 
-    def guided_act_and_step_wide(self, evaluator, eps, guide_share, masked_greedy=False, record_stats=True, weights=None):
+    def guided_act_and_step_wide(self, evaluator, eps, guide_share, masked_greedy=False, record_stats=True, weights=None, correlated=None):
         """guided_act_and_step() for the wide environment with the union-find teacher: Q forward on the current observations,
         VectorEnv.guided_select_wide into the ring's action slot, then dq_envb_step with auto-reset writing the ring's reward / done slots and the successor
         observation; the referee's inexact flags are accumulated as _launch_env does it, the lattice-steps that followed the teacher are added to
         self.guide_counts[0].  Nothing rides on a wide launch: the update draws its own minibatch.  evaluator: a decoder_wide.WideEvaluator of the
         environment's d and error model, window >= volume_depth.  weights: VectorEnv.guided_select_wide's -- the teacher decodes
-        on the weighted graph; None is the call of before, argument for argument.  One GPU, the wide environment."""
+        on the weighted graph; None is the call of before, argument for argument.  correlated: VectorEnv.guided_select_wide's -- the
+        teacher decodes in the three correlated passes.  One GPU, the wide environment."""
         if not self._wide or self.world_size > 1:
             raise NotImplementedError("guided_act_and_step_wide: one GPU and the wide environment (the narrow one: guided_act_and_step)")
-        if weights is not None:
-            weights = self.env._wide_uf_weights(weights, "guided_act_and_step_wide")      # ValueError before the acting forward is launched
+        if weights is not None or correlated is not None:             # ValueError before the acting forward is launched
+            weights = self.env._wide_uf_weights(weights, "guided_act_and_step_wide", correlated)
         kw = {} if weights is None else dict(weights=weights)
+        if isinstance(weights, tuple) and len(weights) == 3:
+            kw = dict(weights=weights[:2], correlated=weights[2])
         self._flush_stats()
         r, env = self.ring, self.env
         cur, nxt = r.cur, r.next_slot()

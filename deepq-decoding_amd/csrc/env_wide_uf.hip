@@ -12,6 +12,10 @@
 // volume, still one last open window, decoded by ufw_component<false, true> with the lattice's own (w_space, w_time) -- the launch's pair or the lattice's two
 // bytes of a uint8 [n_envs][2] array, clamped to 1 .. UFW_MAX_WEIGHT --, so the last round's time edges to B cost w_time.  The Weighted = false instantiations
 // are the unit-weight kernels, instruction for instruction.
+// And on Corr (dq_envb_uf_select_correlated, dq_envb_guided_select_uf_correlated): section 25's three passes on that window -- component 0
+// dry, component 1 with w_corr on the space edges of that correction, component 0 again with w_corr on the space edges of component 1's -- around
+// ufw_component<false, true, true>, one (w_space, w_time, w_corr) per lattice (the launch's, or three bytes of a uint8 [n_envs][3] array).  The two masks are a
+// tail of ufw_mask_bytes(depth) bytes behind ufw_layout's, for these two instantiations only; the other four are the kernels of before, instruction for instruction.
 #include <type_traits>
 #include "uf_wide.h"
 #include "env_big_view.h"
@@ -45,8 +49,18 @@ struct EnvUfWeights {
 struct EnvUfArgsWeighted : EnvUfArgs {
     EnvUfWeights w;
 };
-template <bool Weighted>
-using EnvUfArgsOf = std::conditional_t<Weighted, EnvUfArgsWeighted, EnvUfArgs>;
+
+// The weights of a correlated launch: one triple for all lattices, or a triple per lattice.
+struct EnvUfWeightsCorr {
+    const u8* each;             // != NULL: [3 i] .. [3 i + 2] = (w_space, w_time, w_corr) of lattice i
+    int w_space, w_time, w_corr;
+};
+
+struct EnvUfArgsCorrelated : EnvUfArgs {
+    EnvUfWeightsCorr w;
+};
+template <bool Weighted, bool Corr = false>
+using EnvUfArgsOf = std::conditional_t<Corr, EnvUfArgsCorrelated, std::conditional_t<Weighted, EnvUfArgsWeighted, EnvUfArgs>>;
 
 // The workgroup's own pair, read once and clamped to 1 .. UFW_MAX_WEIGHT: a bad byte of a per-lattice array cannot overrun the growth byte.  Every thread reads
 // the same two bytes, so the pair is workgroup-uniform; it lives across the decode in vector registers, as the stream kernels hold theirs.
@@ -57,15 +71,27 @@ static __device__ __forceinline__ void env_wide_uf_weights(const EnvUfWeights& w
     UFW_IN_VGPR(w_space); UFW_IN_VGPR(w_time);
 }
 
+// The workgroup's own triple: the pair clamped as above, w_corr to 1 .. w_space.
+static __device__ __forceinline__ void env_wide_uf_weights(const EnvUfWeightsCorr& w, size_t i, int& w_space, int& w_time, int& w_corr) {
+    w_space = w.w_space; w_time = w.w_time; w_corr = w.w_corr;
+    if (w.each != nullptr) { w_space = w.each[3 * i]; w_time = w.each[3 * i + 1]; w_corr = w.each[3 * i + 2]; }
+    w_space = min(max(w_space, 1), UFW_MAX_WEIGHT); w_time = min(max(w_time, 1), UFW_MAX_WEIGHT); w_corr = min(max(w_corr, 1), w_space);
+    UFW_IN_VGPR(w_space); UFW_IN_VGPR(w_time); UFW_IN_VGPR(w_corr);
+}
+
 // The select body for the lattice whose record is `rec`, by the whole workgroup; returns the action to every thread.  Weighted: the lattice's pair, clamped by
 // the caller; the growth's event reduction takes the spare word s_acc[7], since s_acc[6] is this body's own (below).
-template <bool Weighted>
-static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, const u64* __restrict__ rec, u8* smem, int tid, int w_space = 1, int w_time = 1) {
+// Corr: the lattice's triple; the dynamic LDS then holds the two masks behind the layout's bytes, and the two components are decoded in three passes.
+template <bool Weighted, bool Corr = false>
+static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, const u64* __restrict__ rec, u8* smem, int tid, int w_space = 1, int w_time = 1,
+                                                         int w_corr = 1) {
     int W = p.W, depth = p.depth, identity = p.identity;
     const int O_META = 3 * W + 1;
     int o_comp = 3 * W + 2;
     if ((rec[O_META] >> 32) & 1) return identity;                   // done: workgroup-uniform, no barrier passed yet
     UfwLayout L = ufw_layout(p.n, p.d2, depth);
+    int o_mask = 0;
+    if constexpr (Corr) { o_mask = L.bytes; UFW_IN_VGPR(o_mask); }  // the two masks: a tail behind the layout of before
     ufw_layout_in_vgpr(L);
     u32* s_frame = reinterpret_cast<u32*>(smem + L.o_frame);
     u32* s_carry = reinterpret_cast<u32*>(smem + L.o_carry);
@@ -97,6 +123,26 @@ static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, con
     UFW_IN_VGPR(eu0); UFW_IN_VGPR(ev0); UFW_IN_VGPR(eu1); UFW_IN_VGPR(ev1);
     G.depth = depth; G.B = depth * G.n; G.NN = G.B + 1; G.NE = depth * G.per_round;
     const int n_comp = model == DQ_MODEL_X ? 1 : 2;                 // the X model has no action layer for component 1: its frame is not asked for
+    if constexpr (Corr) {
+        u32* s_mask = reinterpret_cast<u32*>(smem + o_mask);       // u32 [2][depth][8]: A, B
+        int mask_stride = depth * UFW_FRAME_WORDS;
+        // X model: component 1 is not decoded, so nobody writes B, and the last pass alone runs under w_corr = w_space, where no bit of B tells: the weighted
+        // decode.  Else, without a defect of component 1 in the volume nobody reads A and the dry pass is left out.  Both workgroup-uniform.
+        int pass = 2;
+        if (model == DQ_MODEL_X) w_corr = w_space;
+        else pass = __syncthreads_or(tid < depth * UFW_ROW_WORDS && s_ring[row_stride + tid] != 0) ? 0 : 1;
+        UFW_IN_VGPR(mask_stride); UFW_IN_VGPR(pass);
+        for (; pass < 3; ++pass) {                                 // components 0, 1, 0
+            const int c = pass & 1;
+            int dry = pass == 0;
+            UFW_IN_VGPR(dry);
+            G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
+            // pass 0 reads B, which nobody has written, under w_corr = w_space: every space edge weighs w_space
+            ufw_component<false, true, true>(G, s_ring + c * row_stride, smem, L, tid, depth, true, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS,
+                                             s_acc + c, s_acc + 4 + c, w_space, w_time, s_acc + 7, pass ? w_corr : w_space, s_mask + (c ? 0 : mask_stride),
+                                             s_mask + (c ? mask_stride : 0), dry);
+        }
+    } else
     for (int c = 0; c < n_comp; ++c) {
         G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
         if constexpr (Weighted)
@@ -124,8 +170,8 @@ static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, con
     return a == EWU_NONE ? identity : a;
 }
 
-template <bool Weighted = false>
-__global__ __launch_bounds__(UFW_THREADS) void env_wide_uf_kernel(EnvUfArgsOf<Weighted> p) {
+template <bool Weighted = false, bool Corr = false>
+__global__ __launch_bounds__(UFW_THREADS) void env_wide_uf_kernel(EnvUfArgsOf<Weighted, Corr> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
@@ -133,7 +179,11 @@ __global__ __launch_bounds__(UFW_THREADS) void env_wide_uf_kernel(EnvUfArgsOf<We
     int32_t* out = p.action + i;
     UFW_IN_VGPR(out);
     int a;
-    if constexpr (Weighted) {
+    if constexpr (Corr) {
+        int w_space, w_time, w_corr;
+        env_wide_uf_weights(p.w, i, w_space, w_time, w_corr);
+        a = env_wide_uf_action<true, true>(p, p.state + i * p.sw, smem, tid, w_space, w_time, w_corr);
+    } else if constexpr (Weighted) {
         int w_space, w_time;
         env_wide_uf_weights(p.w, i, w_space, w_time);
         a = env_wide_uf_action<true>(p, p.state + i * p.sw, smem, tid, w_space, w_time);
@@ -141,8 +191,8 @@ __global__ __launch_bounds__(UFW_THREADS) void env_wide_uf_kernel(EnvUfArgsOf<We
     if (tid == 0) *out = a;
 }
 
-template <bool Weighted = false>
-__global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfArgsOf<Weighted> p) {
+template <bool Weighted = false, bool Corr = false>
+__global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfArgsOf<Weighted, Corr> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
@@ -159,7 +209,11 @@ __global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfAr
     int a;
     if (follow) {                                                   // workgroup-uniform: the only branch with barriers, the only one that touches LDS
         UFW_IN_VGPR(out); UFW_IN_VGPR(flag);
-        if constexpr (Weighted) {
+        if constexpr (Corr) {
+            int w_space, w_time, w_corr;
+            env_wide_uf_weights(p.w, i, w_space, w_time, w_corr);
+            a = env_wide_uf_action<true, true>(p, rec, smem, tid, w_space, w_time, w_corr);
+        } else if constexpr (Weighted) {
             int w_space, w_time;
             env_wide_uf_weights(p.w, i, w_space, w_time);
             a = env_wide_uf_action<true>(p, rec, smem, tid, w_space, w_time);
@@ -219,11 +273,16 @@ dq_status env_wide_uf_prepare(const dq_envb* E, const dq_wide_uf* H, const int32
         const int lds_max = ufw_layout((UFW_MAX_D * UFW_MAX_D - 1) / 2, UFW_MAX_D * UFW_MAX_D, EWU_MAX_DEPTH).bytes;
         const void* kernels[4] = {reinterpret_cast<const void*>(env_wide_uf_kernel<false>), reinterpret_cast<const void*>(env_wide_guided_uf_kernel<false>),
                                   reinterpret_cast<const void*>(env_wide_uf_kernel<true>), reinterpret_cast<const void*>(env_wide_guided_uf_kernel<true>)};
+        // the correlated kernels carry their two masks behind that
+        const int lds_max_corr = lds_max + ufw_mask_bytes(EWU_MAX_DEPTH);
+        const void* correlated[2] = {reinterpret_cast<const void*>(env_wide_uf_kernel<true, true>),
+                                     reinterpret_cast<const void*>(env_wide_guided_uf_kernel<true, true>)};
         hipError_t ea = hipSuccess;
         for (int k = 0; k < 4 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        for (int k = 0; k < 2 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(correlated[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max_corr);
         if (ea != hipSuccess) {
             (void)hipGetLastError();
-            dq_set_error("%s: the device refuses %d bytes of LDS per workgroup: %s", who, lds_max, hipGetErrorString(ea));
+            dq_set_error("%s: the device refuses %d bytes of LDS per workgroup: %s", who, lds_max_corr, hipGetErrorString(ea));
             return DQ_ERR_UNSUPPORTED;
         }
         attr_devs |= dev_bit;
@@ -246,13 +305,27 @@ dq_status env_wide_uf_check_weights(int w_space, int w_time, const uint8_t* weig
     return DQ_OK;
 }
 
-// The select entry points: one body, `who` names the caller in the messages.  ww: the weights of a weighted launch, NULL for the unit-weight kernel.
-dq_status env_wide_uf_select(const char* who, dq_envb* env, dq_wide_uf* H, int32_t* action_dev, void* stream, const EnvUfWeights* ww = nullptr) {
+// ... and the correlated forms: the pair as above, the uniform w_corr in 1 .. w_space.
+dq_status env_wide_uf_check_correlated(int w_space, int w_time, int w_corr, const uint8_t* weights_each_dev, const char* who) {
+    const dq_status rc = env_wide_uf_check_weights(w_space, w_time, weights_each_dev, who);
+    if (rc != DQ_OK) return rc;
+    DQ_REQUIRE(weights_each_dev != nullptr || (w_corr >= 1 && w_corr <= w_space), DQ_ERR_INVALID, "%s: w_corr = %d outside 1..w_space = %d", who, w_corr, w_space);
+    return DQ_OK;
+}
+
+// The select entry points: one body, `who` names the caller in the messages.  ww: the weights of a weighted launch, wc: of a correlated one, both NULL for the
+// unit-weight kernel.
+dq_status env_wide_uf_select(const char* who, dq_envb* env, dq_wide_uf* H, int32_t* action_dev, void* stream, const EnvUfWeights* ww = nullptr,
+                             const EnvUfWeightsCorr* wc = nullptr) {
     EnvUfArgsWeighted a;
     int lds = 0;
     const dq_status rc = env_wide_uf_prepare(env, H, action_dev, nullptr, &a, &lds, who);
     if (rc != DQ_OK) return rc;
-    if (ww) {
+    if (wc) {
+        EnvUfArgsCorrelated ac;
+        static_cast<EnvUfArgs&>(ac) = a; ac.w = *wc;
+        env_wide_uf_kernel<true, true><<<a.n_envs, UFW_THREADS, lds + ufw_mask_bytes(a.depth), (hipStream_t)stream>>>(ac);
+    } else if (ww) {
         a.w = *ww;
         env_wide_uf_kernel<true><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(a);
     } else env_wide_uf_kernel<false><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(static_cast<const EnvUfArgs&>(a));
@@ -261,7 +334,8 @@ dq_status env_wide_uf_select(const char* who, dq_envb* env, dq_wide_uf* H, int32
 }
 
 dq_status env_wide_uf_guided_select(const char* who, dq_envb* env, dq_wide_uf* H, const float* q_dev, double eps, double guide_share, int masked_greedy,
-                                    const uint32_t seed[2], uint64_t t, int32_t* action_dev, uint8_t* guided_dev, void* stream, const EnvUfWeights* ww = nullptr) {
+                                    const uint32_t seed[2], uint64_t t, int32_t* action_dev, uint8_t* guided_dev, void* stream, const EnvUfWeights* ww = nullptr,
+                                    const EnvUfWeightsCorr* wc = nullptr) {
     DQ_REQUIRE(seed, DQ_ERR_INVALID, "%s: null argument", who);
     DQ_REQUIRE(eps >= 0.0 && eps <= 1.0, DQ_ERR_INVALID, "%s: eps must be in [0,1]", who);                                    // (NaN fails both compares)
     DQ_REQUIRE(guide_share >= 0.0 && guide_share <= 1.0, DQ_ERR_INVALID, "%s: guide_share must be in [0,1]", who);
@@ -271,7 +345,11 @@ dq_status env_wide_uf_guided_select(const char* who, dq_envb* env, dq_wide_uf* H
     if (rc != DQ_OK) return rc;
     a.q = q_dev; a.T_eps = dq_rate_threshold(eps); a.T_share = dq_rate_threshold(guide_share); a.t = t; a.masked_greedy = masked_greedy;
     a.seed0 = seed[0]; a.seed1 = seed[1]; a.guided = guided_dev;
-    if (ww) {
+    if (wc) {
+        EnvUfArgsCorrelated ac;
+        static_cast<EnvUfArgs&>(ac) = a; ac.w = *wc;
+        env_wide_guided_uf_kernel<true, true><<<a.n_envs, UFW_THREADS, lds + ufw_mask_bytes(a.depth), (hipStream_t)stream>>>(ac);
+    } else if (ww) {
         a.w = *ww;
         env_wide_guided_uf_kernel<true><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(a);
     } else env_wide_guided_uf_kernel<false><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(static_cast<const EnvUfArgs&>(a));
@@ -294,6 +372,14 @@ dq_status dq_envb_uf_select_weighted(dq_envb* env, dq_wide_uf* H, int w_space, i
     return env_wide_uf_select("dq_envb_uf_select_weighted", env, H, action_dev, stream, &ww);
 }
 
+dq_status dq_envb_uf_select_correlated(dq_envb* env, dq_wide_uf* H, int w_space, int w_time, int w_corr, const uint8_t* weights_each_dev, int32_t* action_dev,
+                                       void* stream) {
+    const dq_status rc = env_wide_uf_check_correlated(w_space, w_time, w_corr, weights_each_dev, "dq_envb_uf_select_correlated");
+    if (rc != DQ_OK) return rc;
+    const EnvUfWeightsCorr wc = {weights_each_dev, w_space, w_time, w_corr};
+    return env_wide_uf_select("dq_envb_uf_select_correlated", env, H, action_dev, stream, nullptr, &wc);
+}
+
 dq_status dq_envb_guided_select_uf(dq_envb* env, dq_wide_uf* H, const float* q_dev, double eps, double guide_share, int masked_greedy, const uint32_t seed[2],
                                    uint64_t t, int32_t* action_dev, uint8_t* guided_dev, void* stream) {
     return env_wide_uf_guided_select("dq_envb_guided_select_uf", env, H, q_dev, eps, guide_share, masked_greedy, seed, t, action_dev, guided_dev, stream);
@@ -307,6 +393,16 @@ dq_status dq_envb_guided_select_uf_weighted(dq_envb* env, dq_wide_uf* H, const f
     const EnvUfWeights ww = {weights_each_dev, w_space, w_time};
     return env_wide_uf_guided_select("dq_envb_guided_select_uf_weighted", env, H, q_dev, eps, guide_share, masked_greedy, seed, t, action_dev, guided_dev, stream,
                                      &ww);
+}
+
+dq_status dq_envb_guided_select_uf_correlated(dq_envb* env, dq_wide_uf* H, const float* q_dev, double eps, double guide_share, int masked_greedy,
+                                              const uint32_t seed[2], uint64_t t, int w_space, int w_time, int w_corr, const uint8_t* weights_each_dev,
+                                              int32_t* action_dev, uint8_t* guided_dev, void* stream) {
+    const dq_status rc = env_wide_uf_check_correlated(w_space, w_time, w_corr, weights_each_dev, "dq_envb_guided_select_uf_correlated");
+    if (rc != DQ_OK) return rc;
+    const EnvUfWeightsCorr wc = {weights_each_dev, w_space, w_time, w_corr};
+    return env_wide_uf_guided_select("dq_envb_guided_select_uf_correlated", env, H, q_dev, eps, guide_share, masked_greedy, seed, t, action_dev, guided_dev,
+                                     stream, nullptr, &wc);
 }
 
 }  // extern "C"

@@ -10,7 +10,8 @@ as the wide environment's step does: death_rate is then the share of volumes on 
 weights= (stream_decode_wide, memory_experiment_wide) decodes on a weighted graph: an edge of weight w is full at growth 2 w, w_space
 for the space edges and w_time for the time edges, so that a misread stabilizer and a flipped qubit cost what their rates say (uf_weights).  None is the
 unit-weight launch of before, untouched.  The policy and teacher of the wide environment and decode_benchmark_wide's union-find row take it too (DESIGN.md
-section 24): WideUnionFindAgent(weights=...), VectorEnv.uf_select_wide / guided_select_wide(weights=...).
+section 24): WideUnionFindAgent(weights=...), VectorEnv.uf_select_wide / guided_select_wide(weights=...).  So do they take correlated= (DESIGN.md
+section 26): the policy and the teacher decode the lattice's volume in the three correlated passes.
 
 correlated= (stream_decode_wide, memory_experiment_wide, DQNAgent.decode_benchmark_wide) stops decoding the two Pauli components
 independently: per window component 0 is decoded dry, component 1 with weight w_corr on the space edges of that correction, component 0 again with
@@ -205,14 +206,15 @@ def rate_weights(p_phys, p_meas, error_model, n):
 
 def check_policy_weights(weights, n=None):
     """weights= of the wide environment's policy and teacher (WideUnionFindAgent, VectorEnv.uf_select_wide's values), validated without touching the
-    library: None, a pair, "rates", or one pair per lattice -- an integer array [n, 2], or a uint8 device tensor [n, 2], which is returned as it is.
+    library: None, a pair, "rates", or one pair per lattice -- an integer array [n, 2], or a uint8 device tensor [n, 2], which is returned as it is; so
+    is a uint8 device tensor [n, 3] of triples (w_space, w_time, w_corr), which asks for the correlated decode.
     n=None (the lattices are not known yet): any number of rows.  Else ValueError."""
     if weights is None:
         return None
     if getattr(weights, "is_cuda", False):
         shape = tuple(int(x) for x in weights.shape)
-        if str(weights.dtype) != "torch.uint8" or len(shape) != 2 or shape[1] != 2 or (n is not None and shape[0] != n):
-            raise ValueError(f"a device tensor of weights is uint8 [{'n_envs' if n is None else n}, 2], not {weights.dtype} {shape}")
+        if str(weights.dtype) != "torch.uint8" or len(shape) != 2 or shape[1] not in (2, 3) or (n is not None and shape[0] != n):
+            raise ValueError(f"a device tensor of weights is uint8 [{'n_envs' if n is None else n}, 2 or 3], not {weights.dtype} {shape}")
         return weights
     rows = n
     if rows is None and not isinstance(weights, (str, dict)):
@@ -688,13 +690,19 @@ class WideUnionFindAgent(MatchingAgent):
     DQNAgent.fit then runs DQNCore.guided_act_and_step_wide.  weights: VectorEnv.uf_select_wide's -- None (unit weights, the
     calls of before), a pair, one pair per lattice, or "rates": every select of test / test_error_rates and, as a guide, every guided step of fit
     decodes on the weighted graph; with "rates" test_error_rates gives every rate block its own pair in the same launches.  After a call last_weights
-    holds what was used: None, a pair, or the sorted list of the lattices' distinct pairs.  The identity row takes no weights."""
+    holds what was used: None, a pair, or the sorted list of the lattices' distinct pairs.  The identity row takes no weights.  correlated (DESIGN.md
+    section 26): VectorEnv.uf_select_wide's -- None, an integer w_corr beside a pair or per-lattice pairs, or "rates" beside weights None or "rates":
+    every select and every guided step decodes in the three correlated passes; with "rates" test_error_rates gives every rate block its own triple
+    (uf_weights_correlated) in the same launches.  last_weights then holds the triple or the sorted list of the distinct triples."""
 
-    def __init__(self, evaluator=None, chunk=DEFAULT_CHUNK, policy="matching", weights=None):
+    def __init__(self, evaluator=None, chunk=DEFAULT_CHUNK, policy="matching", weights=None, correlated=None):
         super().__init__(evaluator=evaluator, chunk=chunk, policy=policy)
         self.method = "union_find"
         self.weights = check_policy_weights(weights)
-        if self.weights is not None and policy == "identity":
+        if correlated is not None and is_correlated(self.weights):
+            raise ValueError("weights are triples already: they take no correlated=")
+        self.correlated = check_correlated(correlated, self.weights, rates=True)
+        if (self.weights is not None or self.correlated is not None) and policy == "identity":
             raise ValueError("policy='identity' plays no decoder: it takes no weights")
         self.last_weights = None
 
@@ -712,6 +720,19 @@ class WideUnionFindAgent(MatchingAgent):
             import torch
             w = torch.from_numpy(w).to(v.device)
         return w
+
+    def select_kw(self, env):
+        """What VectorEnv.uf_select_wide / guided_select_wide take on env beside their own arguments, for a caller that makes many calls: nothing without
+        weights and correlated (the call of before, argument for argument), weights= alone as weights_for gives them, and with correlated= the pair with
+        the integer, "rates" as the string (the environment keeps the uploaded triples and follows set_rates), or per-lattice pairs with their w_corr as
+        ONE uint8 device tensor [n_envs, 3].  Validates before any library call (ValueError)."""
+        w = self.weights_for(env)
+        if self.correlated is None:
+            return {} if w is None else dict(weights=w)
+        if w is None or isinstance(w, (str, tuple)):
+            return dict(correlated=self.correlated, **({} if w is None else dict(weights=w)))
+        v = getattr(env, "_v", env)
+        return dict(weights=v._wide_uf_weights(w, "WideUnionFindAgent", self.correlated))
 
     def evaluator_for(self, env):
         """(a WideEvaluator(d, error_model, window=volume_depth) of env's lattice, whether it was opened here and is the caller's to close): the agent's own
@@ -734,8 +755,16 @@ class WideUnionFindAgent(MatchingAgent):
             with torch.cuda.device(dev):
                 action = torch.full((N,), int(venv.identity_index), dtype=torch.int32, device=dev)
                 steps = [0]
-                weights = self.weights_for(venv) if decode else None
-                kw = {} if weights is None else dict(weights=weights)         # (no weights: the call of before, argument for argument)
+                kw = self.select_kw(venv) if decode else {}                   # (no weights: the call of before, argument for argument)
+                weights = kw.get("weights")
+                if kw.get("correlated") == "rates":
+                    ph, pm = venv.rates
+                    pm = ph if pm is None else pm
+                    scalar = np.ndim(ph) == 0 and np.ndim(pm) == 0
+                    weights = rate_weights_correlated(*((float(ph), float(pm)) if scalar else
+                                                        (np.broadcast_to(np.asarray(x, dtype=np.float64), (N,)) for x in (ph, pm))), venv.error_model, N)
+                elif "correlated" in kw:
+                    weights = weights + (kw["correlated"],)
                 self.last_weights = weight_pairs(weights, venv.rates, venv.error_model, N) if weights is not None else None
 
                 def step(k):

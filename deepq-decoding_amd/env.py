@@ -192,6 +192,7 @@ class VectorEnv:
         check(getattr(self.L, self._pfx + "set_rates")(self._h, self._p_phys, self._p_meas))
         self._rates_arr = None          # set_rates with a sequence: the (p_phys, p_meas) arrays of the lattices; None: the scalar pair
         self._uf_rate_weights = None    # weights="rates" of uf_select_wide / guided_select_wide: the uploaded uint8 [n_envs, 2] of the rates as they stand
+        self._uf_rate_triples = None    # correlated="rates": the uploaded uint8 [n_envs, 3], a cache of its own
         dev, n = self.device, self.n_envs
         self.obs = torch.zeros((n,) + self.obs_shape, dtype=torch.uint8, device=dev)
         self.reward = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -244,7 +245,7 @@ class VectorEnv:
         rebuilt per lattice).  Validation (validate_rates) happens before any library call."""
         ph = validate_rates(p_phys, self.n_envs, "p_phys")
         pm = ph if p_meas is None else validate_rates(p_meas, self.n_envs, "p_meas")
-        self._uf_rate_weights = None
+        self._uf_rate_weights = self._uf_rate_triples = None
         if isinstance(ph, float) and isinstance(pm, float):
             check(getattr(self.L, self._pfx + "set_rates")(self._h, ph, pm))
             self._p_phys, self._p_meas, self._rates_arr = ph, pm, None
@@ -561,20 +562,45 @@ class VectorEnv:
         if int(window) < int(self.volume_depth):
             raise ValueError(f"{who}: the evaluator's window {window} is below the environment's volume_depth {self.volume_depth}")
 
-    def _wide_uf_weights(self, weights, who):
+    @staticmethod
+    def _is_triples(weights):
+        """Whether what _wide_uf_weights returned asks for the correlated launch: a triple, or a device tensor [n_envs, 3]."""
+        return len(weights) == 3 if isinstance(weights, tuple) else int(weights.shape[1]) == 3
+
+    def _wide_uf_weights(self, weights, who, correlated=None):
         """weights= of uf_select_wide / guided_select_wide, validated before any library call (decoder_wide.check_weights; ValueError): None; a pair
         (w_space, w_time) of integers in 1 .. 15, returned as a tuple; an integer array [n_envs, 2] of such pairs (numpy or nested lists: uploaded per
         call; a contiguous uint8 device tensor: used in place, its bytes are the caller's to keep in range and the kernel clamps them); "rates":
         decoder_wide.rate_weights of the lattices' rates as they stand, uploaded once and kept until set_rates.  Returns None, the pair, or the
-        uint8 device tensor [n_envs, 2]."""
+        uint8 device tensor [n_envs, 2].
+        correlated= beside it (decoder_wide.check_correlated): None -- the above, and a contiguous uint8 device tensor [n_envs, 3]
+        of triples (w_space, w_time, w_corr) is accepted as weights and used in place --; an integer w_corr beside a pair or per-lattice pairs with
+        w_corr <= w_space in every row; "rates" beside weights None or "rates": decoder_wide.uf_weights_correlated of the lattices' rates as they stand,
+        uploaded once and kept until set_rates, in a cache of its own.  Returns then the triple or the uint8 device tensor [n_envs, 3]."""
         from . import decoder_wide as W
-        if weights is None:
+        if weights is None and correlated is None:
             return None
         if isinstance(weights, torch.Tensor) and weights.is_cuda:
-            if not (weights.dtype == torch.uint8 and weights.is_contiguous() and tuple(weights.shape) == (self.n_envs, 2)):
-                raise ValueError(f"{who}: a device tensor of weights is contiguous uint8 [{self.n_envs}, 2], not {weights.dtype} {tuple(weights.shape)}")
-            return weights
+            cols = (2,) if correlated is not None else (2, 3)
+            if not (weights.dtype == torch.uint8 and weights.is_contiguous() and weights.dim() == 2 and tuple(weights.shape)[0] == self.n_envs
+                    and tuple(weights.shape)[1] in cols):
+                raise ValueError(f"{who}: a device tensor of weights is contiguous uint8 [{self.n_envs}, {' or '.join(str(c) for c in cols)}], "
+                                 f"not {weights.dtype} {tuple(weights.shape)}")
+            if correlated is None:
+                return weights
+            correlated = W.check_correlated(correlated, weights, rates=True)
+            return torch.cat([weights, torch.full((self.n_envs, 1), correlated, dtype=torch.uint8, device=weights.device)], dim=1).contiguous()
         weights = W.check_weights(weights, self.n_envs, rates=True)
+        correlated = W.check_correlated(correlated, weights, rates=True)
+        if isinstance(correlated, str):                               # "rates" beside weights None or "rates"
+            if not self.wide:
+                raise ValueError(f"{who}: correlated='rates' reads the per-lattice rates of the wide environment (backend='wide' / d >= 9)")
+            if getattr(self, "_uf_rate_triples", None) is None:
+                ph, pm = self.rates
+                self._uf_rate_triples = torch.from_numpy(W.rate_weights_correlated(ph, pm, self.error_model, self.n_envs)).to(self.device)
+            return self._uf_rate_triples
+        if correlated is not None:
+            weights = W.with_correlated(weights, correlated)
         if isinstance(weights, tuple):
             return weights
         if isinstance(weights, str):                                  # "rates"
@@ -586,7 +612,7 @@ class VectorEnv:
             return self._uf_rate_weights
         return torch.from_numpy(weights).to(self.device)
 
-    def uf_select_wide(self, evaluator, out=None, weights=None):
+    def uf_select_wide(self, evaluator, out=None, weights=None, correlated=None):
         """match_select(method="union_find") for the wide environment, any odd d in 3 .. 15 (include/deepq_hip.h dq_envb_uf_select):
         the lowest action index of the union-find decoder's Pauli frame for the lattice's current volume that is not in completed_actions, else the
         identity; the identity for a lattice whose done flag is set.  evaluator: a decoder_wide.WideEvaluator of this d and error model whose window is at
@@ -594,9 +620,13 @@ class VectorEnv:
         step(actions, auto_reset=True) is the agent step.  A narrow handle raises NotImplementedError.  weights (DESIGN.md section 24;
         dq_envb_uf_select_weighted): None -- unit weights, the call of before --, a pair (w_space, w_time) of integers in 1 .. 15 for every lattice, an
         integer array [n_envs, 2] with one pair per lattice (numpy, or a uint8 device tensor that is used in place), or "rates":
-        decoder_wide.uf_weights of every lattice's own (p_phys, p_meas) as set_rates left them.  Anything else is a ValueError."""
-        if weights is not None:
-            weights = self._wide_uf_weights(weights, "uf_select_wide")
+        decoder_wide.uf_weights of every lattice's own (p_phys, p_meas) as set_rates left them.  Anything else is a ValueError.  correlated (DESIGN.md
+        section 26; dq_envb_uf_select_correlated): None -- the calls above --, an integer w_corr beside a pair or per-lattice pairs (w_corr <= w_space in
+        every row), or "rates" beside weights None or "rates": decoder_wide.uf_weights_correlated of every lattice's own rates.  The volume is then
+        decoded in section 25's three passes -- component 0 dry, component 1 with w_corr on the space edges of that correction, component 0 again with
+        w_corr on the space edges of component 1's.  A uint8 device tensor [n_envs, 3] of triples as weights= (correlated=None) is used in place."""
+        if weights is not None or correlated is not None:
+            weights = self._wide_uf_weights(weights, "uf_select_wide", correlated)
         self._check_wide_uf(evaluator, "uf_select_wide")
         self._check_outputs("uf_select_wide", (out, torch.int32))
         if out is None:
@@ -604,20 +634,26 @@ class VectorEnv:
         if weights is None:
             check(self.L.dq_envb_uf_select(self._h, evaluator._h, ptr(out), self._stream()))
             return out
+        if self._is_triples(weights):
+            triple, each = (weights, None) if isinstance(weights, tuple) else ((1, 1, 1), weights)
+            check(self.L.dq_envb_uf_select_correlated(self._h, evaluator._h, triple[0], triple[1], triple[2], ptr(each), ptr(out), self._stream()))
+            return out
         pair, each = (weights, None) if isinstance(weights, tuple) else ((1, 1), weights)
         check(self.L.dq_envb_uf_select_weighted(self._h, evaluator._h, pair[0], pair[1], ptr(each), ptr(out), self._stream()))
         return out
 
-    def guided_select_wide(self, evaluator, t, q=None, eps=1.0, guide_share=1.0, masked_greedy=False, out=None, out_guided=None, weights=None):
+    def guided_select_wide(self, evaluator, t, q=None, eps=1.0, guide_share=1.0, masked_greedy=False, out=None, out_guided=None, weights=None,
+                           correlated=None):
         """guided_select(method="union_find") for the wide environment (include/deepq_hip.h dq_envb_guided_select_uf; the rule in
         numpy: decoder_wide.guided_actions_wide).  With select_actions' Philox words w of policy counter t: explore = q is None or w[1] < T(eps);
         guided = explore and w[2] < T(guide_share); a guided lattice gets uf_select_wide's action, another exploring one the k-th legal action, the rest the
         first maximum of their row of q (float32 [n_envs, num_actions]; over the legal set when masked_greedy).  guide_share = 0: select_actions' actions bit
         for bit; eps = 1 with guide_share = 1: uf_select_wide's.  The decoder runs for the guided lattices only.  out: int32 [n_envs]; out_guided: uint8
         [n_envs] or None (1 where the lattice followed the decoder).  Returns the actions.  A narrow handle raises NotImplementedError.  weights: as
-        uf_select_wide's -- the teacher decodes on the weighted graph (dq_envb_guided_select_uf_weighted); None is the call of before."""
-        if weights is not None:
-            weights = self._wide_uf_weights(weights, "guided_select_wide")
+        uf_select_wide's -- the teacher decodes on the weighted graph (dq_envb_guided_select_uf_weighted); None is the call of before.  correlated: as
+        uf_select_wide's -- the teacher decodes in the three correlated passes (dq_envb_guided_select_uf_correlated)."""
+        if weights is not None or correlated is not None:
+            weights = self._wide_uf_weights(weights, "guided_select_wide", correlated)
         self._check_wide_uf(evaluator, "guided_select_wide")
         for name, v in (("eps", eps), ("guide_share", guide_share)):
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
@@ -633,6 +669,11 @@ class VectorEnv:
         if weights is None:
             check(self.L.dq_envb_guided_select_uf(self._h, evaluator._h, ptr(q), float(eps), float(guide_share), int(masked_greedy), seed, int(t), ptr(out),
                                                   ptr(out_guided), self._stream()))
+            return out
+        if self._is_triples(weights):
+            triple, each = (weights, None) if isinstance(weights, tuple) else ((1, 1, 1), weights)
+            check(self.L.dq_envb_guided_select_uf_correlated(self._h, evaluator._h, ptr(q), float(eps), float(guide_share), int(masked_greedy), seed, int(t),
+                                                             triple[0], triple[1], triple[2], ptr(each), ptr(out), ptr(out_guided), self._stream()))
             return out
         pair, each = (weights, None) if isinstance(weights, tuple) else ((1, 1), weights)
         check(self.L.dq_envb_guided_select_uf_weighted(self._h, evaluator._h, ptr(q), float(eps), float(guide_share), int(masked_greedy), seed, int(t),

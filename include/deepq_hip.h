@@ -983,6 +983,20 @@ dq_status dq_envb_uf_select_weighted(dq_envb* env, dq_wide_uf* h, int w_space, i
 dq_status dq_envb_guided_select_uf_weighted(dq_envb* env, dq_wide_uf* h, const float* q_dev, double eps, double guide_share, int masked_greedy,
                                             const uint32_t seed[2], uint64_t t, int w_space, int w_time, const uint8_t* weights_each_dev,
                                             int32_t* action_dev, uint8_t* guided_dev, void* stream);
+/* The correlated forms.  dq_version() stays 8: the capability is the presence of these two symbols.  The weighted forms' rules,
+ * arguments, validation and error codes with one change: the lattice's volume -- still one last open window -- is decoded by dq_wide_uf_decode_correlated's
+ * three passes: component 0 dry under (w_space, w_time); component 1 with w_corr on the space edges (t, q) of that correction; component 0 again with w_corr
+ * on the space edges of component 1's correction.  The action is then the weighted forms'.  w_corr: in 1 .. w_space.  weights_each_dev (nullable): uint8
+ * [n_envs][3] on the device, (w_space, w_time, w_corr) of lattice i; it replaces the uniform triple, which is then not read; the kernel clamps the pair to
+ * 1 .. 15 and w_corr to 1 .. w_space.  Without an array a uniform pair outside 1 .. 15 or a w_corr outside 1 .. w_space is DQ_ERR_INVALID before any device
+ * work.  With w_corr = w_space every action equals the weighted forms'; under the X model component 1 is not decoded, there is no mask, and every action
+ * equals the weighted forms' whatever w_corr.  A lattice whose done flag is set gets the identity; in the guided form only the guided lattices run the
+ * decoder.  The records are read in place and never written. */
+dq_status dq_envb_uf_select_correlated(dq_envb* env, dq_wide_uf* h, int w_space, int w_time, int w_corr, const uint8_t* weights_each_dev,
+                                       int32_t* action_dev, void* stream);
+dq_status dq_envb_guided_select_uf_correlated(dq_envb* env, dq_wide_uf* h, const float* q_dev, double eps, double guide_share, int masked_greedy,
+                                              const uint32_t seed[2], uint64_t t, int w_space, int w_time, int w_corr,
+                                              const uint8_t* weights_each_dev, int32_t* action_dev, uint8_t* guided_dev, void* stream);
 
 /* Batched agent decoding for any odd d in 3 .. 15 (csrc/decode_wide.hip).  dq_version() stays 8: the capability is the presence of
  * these symbols.  The semantics are dq_decode_run's, statement for statement, with DQ_DECODE_PLANES_ENV and DQ_DECODE_OBS_UINT8 (patch words and the README

@@ -1,6 +1,6 @@
-"""Launch times of the wide environment's union-find selection (DESIGN.md sections 19 and 24): recorded, not gated.
+"""Launch times of the wide environment's union-find selection (DESIGN.md sections 19, 24 and 26): recorded, not gated.
 
-    python tools/wide_env_uf_timing.py [--lattices 4096] [--p 0.006] [--rounds 5] [--play 8] [--meas-ratio R] [--weights rates|WS,WT] [--out FILE]
+    python tools/wide_env_uf_timing.py [--lattices 4096] [--p 0.006] [--rounds 5] [--play 8] [--meas-ratio R] [--weights rates|WS,WT] [--correlated] [--out FILE]
 
 Per configuration (d = 9 / volume_depth 9 and d = 15 / volume_depth 5, DP) on --lattices mid-episode lattices (--play agent steps of the union-find policy
 from a reset): the select launch (env_wide_uf_kernel), dq_envb_step, dq_wide_uf_decode on the same volumes exported as grids with window = commit =
@@ -9,7 +9,10 @@ fraction).  --meas-ratio R plays at p_meas = R p.  --weights (DESIGN.md section 
 (env_wide_uf_kernel<true>) under (1, 1), under (2, 1) and under the given pair -- "rates": decoder_wide.uf_weights of (p, p_meas) --, and the weighted guided
 launch under that pair at the three fractions; each is reported over the UNWEIGHTED select / guided launch, which is the yardstick; the lattices are still
 played by the unweighted policy, and the record goes to profiles/wide_env_uf_weighted_timing.json.  Device events around single launches; the configurations alternate within each of --rounds rounds, and every round ends with one untimed agent
-step and a fresh export, so that all launches of a round see the same volumes.  Median, min and max.  Writes profiles/wide_env_uf_timing.json."""
+step and a fresh export, so that all launches of a round see the same volumes.  Median, min and max.  Writes profiles/wide_env_uf_timing.json.
+--correlated (with --weights) adds the correlated select launch (env_wide_uf_kernel<true, true>) and the correlated guided launch at
+the three fractions under the pair with w_corr = 1 and with w_corr = w_space -- with --weights rates the pair of decoder_wide.uf_weights_correlated, which the
+weighted launches then take too --, each reported over the WEIGHTED launch at the same pair; the record goes to profiles/wide_env_uf_correlated_timing.json."""
 import argparse
 import importlib
 import json
@@ -37,11 +40,14 @@ def timed_us(fn):
 
 
 class Config:
-    def __init__(self, d, depth, n, p, p_meas=None, weights=None):
+    def __init__(self, d, depth, n, p, p_meas=None, weights=None, correlated=False):
         from oracle import lattice
         self.d, self.depth, self.n = d, depth, n
         p_meas = p if p_meas is None else p_meas
         self.pair = None if weights is None else dq.uf_weights(p, p_meas, "DP") if weights == "rates" else weights
+        self.correlated = correlated
+        if correlated and weights == "rates":
+            self.pair = dq.uf_weights_correlated(p, p_meas, "DP")[:2]
         self.env = dq.VectorEnv(n_envs=n, seed=SEED, d=d, error_model="DP", use_Y=False, volume_depth=depth, p_phys=p, p_meas=p_meas, backend="wide")
         self.ev = dq.WideEvaluator(d, "DP", window=depth, chunk=n, device=self.env.device)
         dev = self.env.device
@@ -81,6 +87,12 @@ class Config:
             for share in (0.0, 0.1, 1.0):
                 out[f"guided_w_pair_{share:g}"] = lambda share=share: e.guided_select_wide(ev, self.t, q=self.q, eps=1.0, guide_share=share, out=self.other,
                                                                                           out_guided=self.flag, weights=self.pair)
+        if self.correlated:
+            for wc in dict.fromkeys((1, self.pair[0])):
+                out[f"select_c_{wc}"] = lambda wc=wc: e.uf_select_wide(ev, out=self.other, weights=self.pair, correlated=wc)
+                for share in (0.0, 0.1, 1.0):
+                    out[f"guided_c_{wc}_{share:g}"] = lambda wc=wc, share=share: e.guided_select_wide(
+                        ev, self.t, q=self.q, eps=1.0, guide_share=share, out=self.other, out_guided=self.flag, weights=self.pair, correlated=wc)
         out["step"] = lambda: e.step(self.action, auto_reset=True, write_obs=False)      # last: it moves the lattices on
         return out
 
@@ -93,11 +105,14 @@ def main():
     ap.add_argument("--play", type=int, default=8)
     ap.add_argument("--meas-ratio", type=float, default=1.0)
     ap.add_argument("--weights", default=None)
+    ap.add_argument("--correlated", action="store_true")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     weights = None if a.weights is None else a.weights if a.weights == "rates" else tuple(int(x) for x in a.weights.split(","))
+    if a.correlated and weights is None:
+        ap.error("--correlated times against the weighted launch: give --weights")
     p_meas = min(1.0, a.meas_ratio * a.p)
-    cfgs = {f"d{d}_depth{depth}": Config(d, depth, a.lattices, a.p, p_meas, weights) for d, depth in SHAPES}
+    cfgs = {f"d{d}_depth{depth}": Config(d, depth, a.lattices, a.p, p_meas, weights, a.correlated) for d, depth in SHAPES}
     for c in cfgs.values():
         for _ in range(a.play):
             c.play()
@@ -116,7 +131,8 @@ def main():
             live[k].append(float((c.action != c.env.identity_index).float().mean()))
             c.t += 1
             c.export()
-    record = dict(device=torch.cuda.get_device_name(0), lattices=a.lattices, p=a.p, p_meas=p_meas, weights=a.weights, model="DP", played_steps=a.play,
+    record = dict(device=torch.cuda.get_device_name(0), lattices=a.lattices, p=a.p, p_meas=p_meas, weights=a.weights, correlated=a.correlated, model="DP",
+                  played_steps=a.play,
                   timing_rounds=a.rounds, configurations={})
     for k, c in cfgs.items():
         rows = {name: dict(median_us=float(np.median(v)), min_us=float(np.min(v)), max_us=float(np.max(v))) for name, v in t[k].items()}
@@ -130,7 +146,13 @@ def main():
                     for name, r in rows.items() if "_w_" in name}
             record["configurations"][k].update(pair=list(c.pair), weighted_over_unweighted=over)
             print(f"{k:12s} pair {c.pair}: " + "  ".join(f"{name} x {v:.3f}" for name, v in over.items()))
-    path = a.out or os.path.join(ROOT, "profiles", "wide_env_uf_weighted_timing.json" if weights else "wide_env_uf_timing.json")
+        if c.correlated:                                                                # the correlated launches over the weighted ones at the same pair
+            over = {name: r["median_us"] / rows["select_w_pair" if name.startswith("select") else "guided_w_pair_" + name.rsplit("_", 1)[1]]["median_us"]
+                    for name, r in rows.items() if "_c_" in name}
+            record["configurations"][k].update(correlated_over_weighted=over)
+            print(f"{k:12s} pair {c.pair}: " + "  ".join(f"{name} x {v:.3f}" for name, v in over.items()))
+    path = a.out or os.path.join(ROOT, "profiles", "wide_env_uf_correlated_timing.json" if a.correlated else
+                                 "wide_env_uf_weighted_timing.json" if weights else "wide_env_uf_timing.json")
     with open(path, "w") as f:
         json.dump(record, f, indent=1)
         f.write("\n")

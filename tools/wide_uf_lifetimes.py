@@ -1,7 +1,7 @@
-"""Episode lifetimes of the wide environment under the union-find policy against the identity (DESIGN.md sections 19 and 24): recorded, not gated.
+"""Episode lifetimes of the wide environment under the union-find policy against the identity (DESIGN.md sections 19, 24 and 26): recorded, not gated.
 
     python tools/wide_uf_lifetimes.py [--d 9 11 13 15] [--rates 0.016 ... 0.002] [--lattices 64] [--episodes 64] [--max-steps 40000]
-                                      [--meas-ratio R] [--weights rates|WS,WT] [--out FILE]
+                                      [--meas-ratio R] [--weights rates|WS,WT] [--correlated rates|W] [--out FILE]
 
 DP, volume_depth 5, p_meas = p_phys (--meas-ratio R: p_meas = R p).  Per d one environment of --lattices lattices (one seed, ids 0 ..), and per rate one
 WideUnionFindAgent.test_error_rates(env, [rate]) for the union-find row and one for the identity row: the same seed and ids for both.  --weights adds a third
@@ -9,7 +9,11 @@ row on the same seed and ids, the policy on the weighted graph (DESIGN.md sectio
 WS,WT one pair for every row; the row records the pair it played with and the ratio of its mean lifetime to the unit row's, with both episode counts and
 whether the two 95 % intervals overlap (where they do the ratio resolves nothing).  The rates are taken from the highest down; a rate whose union-find
 episodes do not end within --max-steps vector steps is recorded as censored and the lower ones, which last longer still, are not run.  Mean lifetime with a
-95 % normal interval of the mean.  Writes profiles/wide_uf_lifetimes_dp.json (with --weights: profiles/wide_uf_lifetimes_weighted.json)."""
+95 % normal interval of the mean.  --correlated (with --weights) adds a fourth row on the same seed and ids, the policy in the three
+correlated passes: "rates" (beside --weights rates) takes decoder_wide.uf_weights_correlated of the row's own rates, W one w_corr beside the pair WS,WT; the
+row records the triple it played with and the ratio of its mean lifetime to the WEIGHTED row's, with both episode counts and whether the two 95 % intervals
+overlap -- where they are apart the row says which policy lives longer.  Writes profiles/wide_uf_lifetimes_dp.json (with --weights:
+profiles/wide_uf_lifetimes_weighted.json, with --correlated: profiles/wide_uf_lifetimes_correlated.json)."""
 import argparse
 import importlib
 import json
@@ -55,17 +59,23 @@ def main():
     ap.add_argument("--max-steps", type=int, default=40000)
     ap.add_argument("--meas-ratio", type=float, default=1.0)
     ap.add_argument("--weights", default=None)
+    ap.add_argument("--correlated", default=None)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     weights = None if a.weights is None else a.weights if a.weights == "rates" else tuple(int(x) for x in a.weights.split(","))
+    correlated = None if a.correlated is None else a.correlated if a.correlated == "rates" else int(a.correlated)
+    if correlated is not None and weights is None:
+        ap.error("--correlated compares against the weighted row: give --weights")
     record = dict(device=torch.cuda.get_device_name(0), model="DP", volume_depth=5, lattices=a.lattices, episodes=a.episodes, max_vector_steps=a.max_steps,
-                  seed=list(SEED), p_meas="= p" if a.meas_ratio == 1.0 else f"= {a.meas_ratio:g} p", weights=a.weights, rows={})
-    path = a.out or os.path.join(ROOT, "profiles", "wide_uf_lifetimes_weighted.json" if weights else "wide_uf_lifetimes_dp.json")
+                  seed=list(SEED), p_meas="= p" if a.meas_ratio == 1.0 else f"= {a.meas_ratio:g} p", weights=a.weights, correlated=a.correlated, rows={})
+    path = a.out or os.path.join(ROOT, "profiles", "wide_uf_lifetimes_correlated.json" if correlated is not None else
+                                 "wide_uf_lifetimes_weighted.json" if weights else "wide_uf_lifetimes_dp.json")
     for d in a.d:
         env = dq.VectorEnv(n_envs=a.lattices, seed=SEED, d=d, error_model="DP", use_Y=False, volume_depth=5, p_phys=0.01, p_meas=0.01, backend="wide")
         ev = dq.WideEvaluator(d, "DP", window=5, chunk=a.lattices, device=env.device)
         uf, ident = dq.WideUnionFindAgent(evaluator=ev), dq.WideUnionFindAgent(policy="identity")
         weighted = dq.WideUnionFindAgent(evaluator=ev, weights=weights) if weights else None
+        corr = dq.WideUnionFindAgent(evaluator=ev, weights=weights, correlated=correlated) if correlated is not None else None
         rows = record["rows"][f"d{d}"] = {}
         for rate in sorted(a.rates, reverse=True):
             pm = min(1.0, a.meas_ratio * rate)
@@ -82,11 +92,22 @@ def main():
                 print(f"                    weighted {w['weights']} " + shown(w)
                       + ("" if "lifetime_over_unit" not in w else f"   x {w['lifetime_over_unit']:.2f} of unit"
                          + (" (intervals overlap)" if w["intervals_overlap"] else "")), flush=True)
+            if corr is not None:
+                c = row["union_find_correlated"] = played(corr, env, rate, pm, a)
+                c["weights"] = corr.last_weights
+                if not w.get("censored") and not c.get("censored"):
+                    longer = "correlated" if c["interval95"][0] > w["interval95"][1] else "weighted" if w["interval95"][0] > c["interval95"][1] else None
+                    c.update(lifetime_over_weighted=c["mean_lifetime"] / w["mean_lifetime"], episodes_weighted=w["episodes"], intervals_overlap=longer is None,
+                             resolved_longer=longer)
+                print(f"                    correlated {c['weights']} " + shown(c)
+                      + ("" if "lifetime_over_weighted" not in c else f"   x {c['lifetime_over_weighted']:.2f} of weighted"
+                         + (" (intervals overlap)" if c["intervals_overlap"] else f" ({c['resolved_longer']} lives longer, resolved)")), flush=True)
             rows[f"{rate:g}"] = row
             with open(path, "w") as f:                                                   # after every row: a time limit loses the row in progress only
                 json.dump(record, f, indent=1)
                 f.write("\n")
-            if u.get("censored") or (weighted is not None and row["union_find_weighted"].get("censored")):
+            if u.get("censored") or (weighted is not None and row["union_find_weighted"].get("censored")) or (
+                    corr is not None and row["union_find_correlated"].get("censored")):
                 break
         ev.close()
         env.close()
