@@ -8,15 +8,14 @@
 // component c out of round t's words, D_t = S_t xor S_(t-1) goes into the LDS ring as stream_wide_uf_kernel stores it, and the whole volume is decoded as one
 // last window (final, commit = depth): union_find_ref on the volume.  Every exit in front of or between barriers is decided by a kernel argument, the record's
 // meta word or the Philox words every thread draws alike.  No scratch pool, no lock, no loop that waits on another workgroup.
-// The action body and the two kernels are templates on Weighted (dq_envb_uf_select_weighted, dq_envb_guided_select_uf_weighted): the same
-// volume, still one last open window, decoded by ufw_component<false, true> with the lattice's own (w_space, w_time) -- the launch's pair or the lattice's two
-// bytes of a uint8 [n_envs][2] array, clamped to 1 .. UFW_MAX_WEIGHT --, so the last round's time edges to B cost w_time.  The Weighted = false instantiations
-// are the unit-weight kernels, instruction for instruction.
-// And on Corr (dq_envb_uf_select_correlated, dq_envb_guided_select_uf_correlated): section 25's three passes on that window -- component 0
-// dry, component 1 with w_corr on the space edges of that correction, component 0 again with w_corr on the space edges of component 1's -- around
-// ufw_component<false, true, true>, one (w_space, w_time, w_corr) per lattice (the launch's, or three bytes of a uint8 [n_envs][3] array).  The two masks are a
-// tail of ufw_mask_bytes(depth) bytes behind ufw_layout's, for these two instantiations only; the other four are the kernels of before, instruction for instruction.
-#include <type_traits>
+// The action body and the two kernels are templates on (Weighted, Corr), three variants of each kernel, and differ only in what uf_wide.h's ufw_setup and
+// ufw_window do for the flags:
+//   <false, false>  unit weights (dq_envb_uf_select, dq_envb_guided_select_uf)
+//   <true, false>   DESIGN.md section 24 (dq_envb_*_weighted): the lattice's own (w_space, w_time) -- the launch's pair or the lattice's two bytes of a uint8
+//                   [n_envs][2] array --, so the last round's time edges to B cost w_time
+//   <true, true>    DESIGN.md section 26 (dq_envb_*_correlated): section 25's three passes on that window with the lattice's own (w_space, w_time, w_corr), the
+//                   launch's triple or three bytes of a uint8 [n_envs][3] array; the dynamic LDS holds the two masks behind ufw_layout's bytes
+// The flags are compile-time: the unit-weight kernels carry no code of the other two.  env_wide_uf_kernel_of is the one map from (guided, mode) to a kernel.
 #include "uf_wide.h"
 #include "env_big_view.h"
 
@@ -39,64 +38,26 @@ struct EnvUfArgs {
     u8* guided;                 // [n_envs] or NULL
 };
 
-// The weights of a weighted launch: one pair for all lattices, or a pair per lattice.
-struct EnvUfWeights {
-    const u8* each;             // != NULL: [2 i] / [2 i + 1] = (w_space, w_time) of lattice i
-    int w_space, w_time;
-};
-
-// The arguments of a weighted launch are the unweighted ones with the weights behind them; the unweighted kernels take EnvUfArgs itself.
+// The arguments of a weighted or a correlated launch are the unweighted ones with the weights behind them; the unit-weight kernels take EnvUfArgs itself.
 struct EnvUfArgsWeighted : EnvUfArgs {
-    EnvUfWeights w;
+    UfwWeights w;
 };
+template <bool Weighted>
+using EnvUfArgsOf = std::conditional_t<Weighted, EnvUfArgsWeighted, EnvUfArgs>;
 
-// The weights of a correlated launch: one triple for all lattices, or a triple per lattice.
-struct EnvUfWeightsCorr {
-    const u8* each;             // != NULL: [3 i] .. [3 i + 2] = (w_space, w_time, w_corr) of lattice i
-    int w_space, w_time, w_corr;
-};
-
-struct EnvUfArgsCorrelated : EnvUfArgs {
-    EnvUfWeightsCorr w;
-};
-template <bool Weighted, bool Corr = false>
-using EnvUfArgsOf = std::conditional_t<Corr, EnvUfArgsCorrelated, std::conditional_t<Weighted, EnvUfArgsWeighted, EnvUfArgs>>;
-
-// The workgroup's own pair, read once and clamped to 1 .. UFW_MAX_WEIGHT: a bad byte of a per-lattice array cannot overrun the growth byte.  Every thread reads
-// the same two bytes, so the pair is workgroup-uniform; it lives across the decode in vector registers, as the stream kernels hold theirs.
-static __device__ __forceinline__ void env_wide_uf_weights(const EnvUfWeights& w, size_t i, int& w_space, int& w_time) {
-    w_space = w.w_space; w_time = w.w_time;
-    if (w.each != nullptr) { w_space = w.each[2 * i]; w_time = w.each[2 * i + 1]; }
-    w_space = min(max(w_space, 1), UFW_MAX_WEIGHT); w_time = min(max(w_time, 1), UFW_MAX_WEIGHT);
-    UFW_IN_VGPR(w_space); UFW_IN_VGPR(w_time);
-}
-
-// The workgroup's own triple: the pair clamped as above, w_corr to 1 .. w_space.
-static __device__ __forceinline__ void env_wide_uf_weights(const EnvUfWeightsCorr& w, size_t i, int& w_space, int& w_time, int& w_corr) {
-    w_space = w.w_space; w_time = w.w_time; w_corr = w.w_corr;
-    if (w.each != nullptr) { w_space = w.each[3 * i]; w_time = w.each[3 * i + 1]; w_corr = w.each[3 * i + 2]; }
-    w_space = min(max(w_space, 1), UFW_MAX_WEIGHT); w_time = min(max(w_time, 1), UFW_MAX_WEIGHT); w_corr = min(max(w_corr, 1), w_space);
-    UFW_IN_VGPR(w_space); UFW_IN_VGPR(w_time); UFW_IN_VGPR(w_corr);
-}
-
-// The select body for the lattice whose record is `rec`, by the whole workgroup; returns the action to every thread.  Weighted: the lattice's pair, clamped by
-// the caller; the growth's event reduction takes the spare word s_acc[7], since s_acc[6] is this body's own (below).
-// Corr: the lattice's triple; the dynamic LDS then holds the two masks behind the layout's bytes, and the two components are decoded in three passes.
-template <bool Weighted, bool Corr = false>
-static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, const u64* __restrict__ rec, u8* smem, int tid, int w_space = 1, int w_time = 1,
-                                                         int w_corr = 1) {
+// The select body for lattice i, whose record is `rec`, by the whole workgroup; returns the action to every thread.  Weighted, Corr: the lattice's own pair or
+// triple (uf_wide.h ufw_setup); the dynamic LDS of a correlated launch holds the two masks behind the layout's bytes.  The growth's event reduction takes the
+// spare word s_acc[7], since s_acc[6] is this body's own (below).
+template <bool Weighted, bool Corr>
+static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgsOf<Weighted>& p, size_t i, const u64* __restrict__ rec, u8* smem, int tid) {
     int W = p.W, depth = p.depth, identity = p.identity;
     const int O_META = 3 * W + 1;
     int o_comp = 3 * W + 2;
     if ((rec[O_META] >> 32) & 1) return identity;                   // done: workgroup-uniform, no barrier passed yet
-    UfwLayout L = ufw_layout(p.n, p.d2, depth);
-    int o_mask = 0;
-    if constexpr (Corr) { o_mask = L.bytes; UFW_IN_VGPR(o_mask); }  // the two masks: a tail behind the layout of before
-    ufw_layout_in_vgpr(L);
-    u32* s_frame = reinterpret_cast<u32*>(smem + L.o_frame);
-    u32* s_carry = reinterpret_cast<u32*>(smem + L.o_carry);
-    int* s_acc = reinterpret_cast<int*>(smem + L.o_acc);
-    u32* s_ring = reinterpret_cast<u32*>(smem + L.o_ring);
+    const UfwSetup S = ufw_setup<Weighted, Corr>(p, i, p.n, p.d2, depth);
+    const UfwHead H = ufw_head(smem, S.L);
+    u32 *s_frame = H.s_frame, *s_carry = H.s_carry, *s_ring = H.s_ring;
+    int* s_acc = H.s_acc;
     int row_stride = depth * UFW_ROW_WORDS;
     const int my_stab = (tid & (UFW_NODE_SLOTS - 1)) < p.n ? p.node_stab[tid] : 255;
     const bool mine = my_stab < 255;
@@ -115,42 +76,11 @@ static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, con
         wide_rows(mine ? cur : 0, prev, tid, s_ring + t * UFW_ROW_WORDS, s_ring + row_stride + t * UFW_ROW_WORDS, nd);
     }
     __syncthreads();
-    UfwGraph G;
-    G.n = p.n; G.d2 = p.d2; G.per_round = p.d2 + p.n;
-    G.mag_n = ufw_magic(G.n); G.mag_pr = ufw_magic(G.per_round);
-    UFW_IN_VGPR(G.n); UFW_IN_VGPR(G.d2); UFW_IN_VGPR(G.per_round); UFW_IN_VGPR(G.mag_n); UFW_IN_VGPR(G.mag_pr);
-    const u8 *eu0 = p.c0.eu, *ev0 = p.c0.ev, *eu1 = p.c1.eu, *ev1 = p.c1.ev;
-    UFW_IN_VGPR(eu0); UFW_IN_VGPR(ev0); UFW_IN_VGPR(eu1); UFW_IN_VGPR(ev1);
+    UfwGraph G = ufw_graph_in_vgpr(p.n, p.d2);
+    const UfwEnds E = ufw_ends_in_vgpr(p.c0, p.c1);
     G.depth = depth; G.B = depth * G.n; G.NN = G.B + 1; G.NE = depth * G.per_round;
-    const int n_comp = model == DQ_MODEL_X ? 1 : 2;                 // the X model has no action layer for component 1: its frame is not asked for
-    if constexpr (Corr) {
-        u32* s_mask = reinterpret_cast<u32*>(smem + o_mask);       // u32 [2][depth][8]: A, B
-        int mask_stride = depth * UFW_FRAME_WORDS;
-        // X model: component 1 is not decoded, so nobody writes B, and the last pass alone runs under w_corr = w_space, where no bit of B tells: the weighted
-        // decode.  Else, without a defect of component 1 in the volume nobody reads A and the dry pass is left out.  Both workgroup-uniform.
-        int pass = 2;
-        if (model == DQ_MODEL_X) w_corr = w_space;
-        else pass = __syncthreads_or(tid < depth * UFW_ROW_WORDS && s_ring[row_stride + tid] != 0) ? 0 : 1;
-        UFW_IN_VGPR(mask_stride); UFW_IN_VGPR(pass);
-        for (; pass < 3; ++pass) {                                 // components 0, 1, 0
-            const int c = pass & 1;
-            int dry = pass == 0;
-            UFW_IN_VGPR(dry);
-            G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
-            // pass 0 reads B, which nobody has written, under w_corr = w_space: every space edge weighs w_space
-            ufw_component<false, true, true>(G, s_ring + c * row_stride, smem, L, tid, depth, true, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS,
-                                             s_acc + c, s_acc + 4 + c, w_space, w_time, s_acc + 7, pass ? w_corr : w_space, s_mask + (c ? 0 : mask_stride),
-                                             s_mask + (c ? mask_stride : 0), dry);
-        }
-    } else
-    for (int c = 0; c < n_comp; ++c) {
-        G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
-        if constexpr (Weighted)
-            ufw_component<false, true>(G, s_ring + c * row_stride, smem, L, tid, depth, true, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c,
-                                       s_acc + 4 + c, w_space, w_time, s_acc + 7);
-        else
-            ufw_component(G, s_ring + c * row_stride, smem, L, tid, depth, true, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c, s_acc + 4 + c);
-    }
+    // the whole volume as one last open window; the X model has no action layer for component 1: its frame is not asked for
+    ufw_window<false, Weighted, Corr>(G, E, smem, S, H, tid, row_stride, depth, true, model == DQ_MODEL_X ? 1 : 2, s_acc + 7);
     // decoder.frame_to_actions' rule; thread q < d^2 holds qubit q's cell of the two frames (the component's last barrier is behind every thread, or its
     // frame words still hold the zeros stored in front of the first one)
     int best = EWU_NONE;
@@ -171,28 +101,19 @@ static __device__ __forceinline__ int env_wide_uf_action(const EnvUfArgs& p, con
 }
 
 template <bool Weighted = false, bool Corr = false>
-__global__ __launch_bounds__(UFW_THREADS) void env_wide_uf_kernel(EnvUfArgsOf<Weighted, Corr> p) {
+__global__ __launch_bounds__(UFW_THREADS) void env_wide_uf_kernel(EnvUfArgsOf<Weighted> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
     if ((int)blockIdx.x >= p.n_envs) return;                        // workgroup-uniform
     int32_t* out = p.action + i;
     UFW_IN_VGPR(out);
-    int a;
-    if constexpr (Corr) {
-        int w_space, w_time, w_corr;
-        env_wide_uf_weights(p.w, i, w_space, w_time, w_corr);
-        a = env_wide_uf_action<true, true>(p, p.state + i * p.sw, smem, tid, w_space, w_time, w_corr);
-    } else if constexpr (Weighted) {
-        int w_space, w_time;
-        env_wide_uf_weights(p.w, i, w_space, w_time);
-        a = env_wide_uf_action<true>(p, p.state + i * p.sw, smem, tid, w_space, w_time);
-    } else a = env_wide_uf_action<false>(p, p.state + i * p.sw, smem, tid);
+    const int a = env_wide_uf_action<Weighted, Corr>(p, i, p.state + i * p.sw, smem, tid);
     if (tid == 0) *out = a;
 }
 
 template <bool Weighted = false, bool Corr = false>
-__global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfArgsOf<Weighted, Corr> p) {
+__global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfArgsOf<Weighted> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
@@ -209,15 +130,7 @@ __global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfAr
     int a;
     if (follow) {                                                   // workgroup-uniform: the only branch with barriers, the only one that touches LDS
         UFW_IN_VGPR(out); UFW_IN_VGPR(flag);
-        if constexpr (Corr) {
-            int w_space, w_time, w_corr;
-            env_wide_uf_weights(p.w, i, w_space, w_time, w_corr);
-            a = env_wide_uf_action<true, true>(p, rec, smem, tid, w_space, w_time, w_corr);
-        } else if constexpr (Weighted) {
-            int w_space, w_time;
-            env_wide_uf_weights(p.w, i, w_space, w_time);
-            a = env_wide_uf_action<true>(p, rec, smem, tid, w_space, w_time);
-        } else a = env_wide_uf_action<false>(p, rec, smem, tid);
+        a = env_wide_uf_action<Weighted, Corr>(p, i, rec, smem, tid);
     } else {
         if (tid >= 64) return;                                      // one wave suffices, and no barrier follows
         const u64* lg = rec + 3 * p.W + 2 + p.LW;                   // the record's legal set: what the last reset / step also wrote to its legal_dev
@@ -253,9 +166,20 @@ __global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfAr
     }
 }
 
+// The one place that maps (guided, mode) to a kernel instantiation: f(kernel) gets the __global__ function, whose argument is EnvUfArgs for the unit weights
+// and EnvUfArgsWeighted otherwise.  The launches (env_wide_uf_launch) and env_wide_uf_prepare's LDS limits both go through it.
+template <class F>
+void env_wide_uf_kernel_of(bool guided, UfwMode mode, F&& f) {
+    ufw_with_mode(mode, [&](auto weighted, auto corr) {
+        constexpr bool W = decltype(weighted)::value, K = decltype(corr)::value;
+        guided ? f(env_wide_guided_uf_kernel<W, K>) : f(env_wide_uf_kernel<W, K>);
+    });
+}
+
 // What both entry points check alike, before any device work: the handles, the decoder's lattice and window (DQ_ERR_INVALID); then the kernels' LDS limit, once per
 // device (DQ_ERR_UNSUPPORTED).
-dq_status env_wide_uf_prepare(const dq_envb* E, const dq_wide_uf* H, const int32_t* action_dev, const float* q_dev, EnvUfArgs* a, int* lds, const char* who) {
+dq_status env_wide_uf_prepare(const dq_envb* E, const dq_wide_uf* H, const int32_t* action_dev, const float* q_dev, const UfwWeights* w, EnvUfArgsWeighted* a,
+                              const char* who) {
     DQ_REQUIRE(E && H && action_dev, DQ_ERR_INVALID, "%s: null argument", who);
     DQ_REQUIRE((reinterpret_cast<uintptr_t>(action_dev) & 3) == 0 && (reinterpret_cast<uintptr_t>(q_dev) & 3) == 0, DQ_ERR_INVALID,
                "%s: action_dev and q_dev must be 4-byte aligned", who);
@@ -271,15 +195,16 @@ dq_status env_wide_uf_prepare(const dq_envb* E, const dq_wide_uf* H, const int32
     const unsigned long long dev_bit = dq_device_bit();
     if (!(attr_devs & dev_bit)) {
         const int lds_max = ufw_layout((UFW_MAX_D * UFW_MAX_D - 1) / 2, UFW_MAX_D * UFW_MAX_D, EWU_MAX_DEPTH).bytes;
-        const void* kernels[4] = {reinterpret_cast<const void*>(env_wide_uf_kernel<false>), reinterpret_cast<const void*>(env_wide_guided_uf_kernel<false>),
-                                  reinterpret_cast<const void*>(env_wide_uf_kernel<true>), reinterpret_cast<const void*>(env_wide_guided_uf_kernel<true>)};
-        // the correlated kernels carry their two masks behind that
-        const int lds_max_corr = lds_max + ufw_mask_bytes(EWU_MAX_DEPTH);
-        const void* correlated[2] = {reinterpret_cast<const void*>(env_wide_uf_kernel<true, true>),
-                                     reinterpret_cast<const void*>(env_wide_guided_uf_kernel<true, true>)};
+        const int lds_max_corr = ufw_lds_bytes(UFW_CORRELATED, lds_max, EWU_MAX_DEPTH);       // the correlated kernels carry their two masks behind that
         hipError_t ea = hipSuccess;
-        for (int k = 0; k < 4 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        for (int k = 0; k < 2 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(correlated[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max_corr);
+        for (int k = 0; k < 6; ++k) {                                // every (guided, mode)
+            const UfwMode mode = (UfwMode)(k >> 1);
+            env_wide_uf_kernel_of(k & 1, mode, [&](auto* kernel) {
+                if (ea == hipSuccess)
+                    ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             ufw_lds_bytes(mode, lds_max, EWU_MAX_DEPTH));
+            });
+        }
         if (ea != hipSuccess) {
             (void)hipGetLastError();
             dq_set_error("%s: the device refuses %d bytes of LDS per workgroup: %s", who, lds_max_corr, hipGetErrorString(ea));
@@ -293,66 +218,40 @@ dq_status env_wide_uf_prepare(const dq_envb* E, const dq_wide_uf* H, const int32
     a->node_stab = H->node_stab; a->state = S.state; a->sw = S.sw; a->W = S.W; a->LW = S.LW; a->n_envs = S.n_envs; a->n = H->n; a->d2 = H->d2; a->depth = S.depth;
     a->model = S.model; a->use_Y = S.use_Y; a->identity = S.identity; a->n_actions = S.n_actions; a->env_id_base = S.env_id_base;
     a->action = const_cast<int32_t*>(action_dev);
-    *lds = ufw_layout(H->n, H->d2, S.depth).bytes;
+    if (w) a->w = *w;
     return DQ_OK;
 }
 
-// What the weighted forms check on top, before anything else: without a per-lattice array the uniform pair lies in 1 .. UFW_MAX_WEIGHT (an array is the caller's to
-// check; the kernel clamps it and does not read the uniform pair).
-dq_status env_wide_uf_check_weights(int w_space, int w_time, const uint8_t* weights_each_dev, const char* who) {
-    DQ_REQUIRE(weights_each_dev != nullptr || (w_space >= 1 && w_space <= UFW_MAX_WEIGHT && w_time >= 1 && w_time <= UFW_MAX_WEIGHT), DQ_ERR_INVALID,
-               "%s: weights (%d, %d) outside 1..%d", who, w_space, w_time, UFW_MAX_WEIGHT);
-    return DQ_OK;
+// (a unit-weight kernel takes the EnvUfArgs part of `a`)
+void env_wide_uf_launch(bool guided, UfwMode mode, const EnvUfArgsWeighted& a, void* stream) {
+    const int lds = ufw_lds_bytes(mode, ufw_layout(a.n, a.d2, a.depth).bytes, a.depth);
+    env_wide_uf_kernel_of(guided, mode, [&](auto* kernel) { kernel<<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(a); });
 }
 
-// ... and the correlated forms: the pair as above, the uniform w_corr in 1 .. w_space.
-dq_status env_wide_uf_check_correlated(int w_space, int w_time, int w_corr, const uint8_t* weights_each_dev, const char* who) {
-    const dq_status rc = env_wide_uf_check_weights(w_space, w_time, weights_each_dev, who);
-    if (rc != DQ_OK) return rc;
-    DQ_REQUIRE(weights_each_dev != nullptr || (w_corr >= 1 && w_corr <= w_space), DQ_ERR_INVALID, "%s: w_corr = %d outside 1..w_space = %d", who, w_corr, w_space);
-    return DQ_OK;
-}
-
-// The select entry points: one body, `who` names the caller in the messages.  ww: the weights of a weighted launch, wc: of a correlated one, both NULL for the
-// unit-weight kernel.
-dq_status env_wide_uf_select(const char* who, dq_envb* env, dq_wide_uf* H, int32_t* action_dev, void* stream, const EnvUfWeights* ww = nullptr,
-                             const EnvUfWeightsCorr* wc = nullptr) {
+// The select entry points: one body, `who` names the caller in the messages.  w: the weights of a weighted or a correlated launch (already checked), NULL for
+// the unit-weight kernel.
+dq_status env_wide_uf_select(const char* who, dq_envb* env, dq_wide_uf* H, int32_t* action_dev, void* stream, UfwMode mode = UFW_UNIT,
+                             const UfwWeights* w = nullptr) {
     EnvUfArgsWeighted a;
-    int lds = 0;
-    const dq_status rc = env_wide_uf_prepare(env, H, action_dev, nullptr, &a, &lds, who);
+    const dq_status rc = env_wide_uf_prepare(env, H, action_dev, nullptr, w, &a, who);
     if (rc != DQ_OK) return rc;
-    if (wc) {
-        EnvUfArgsCorrelated ac;
-        static_cast<EnvUfArgs&>(ac) = a; ac.w = *wc;
-        env_wide_uf_kernel<true, true><<<a.n_envs, UFW_THREADS, lds + ufw_mask_bytes(a.depth), (hipStream_t)stream>>>(ac);
-    } else if (ww) {
-        a.w = *ww;
-        env_wide_uf_kernel<true><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(a);
-    } else env_wide_uf_kernel<false><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(static_cast<const EnvUfArgs&>(a));
+    env_wide_uf_launch(false, mode, a, stream);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
 }
 
 dq_status env_wide_uf_guided_select(const char* who, dq_envb* env, dq_wide_uf* H, const float* q_dev, double eps, double guide_share, int masked_greedy,
-                                    const uint32_t seed[2], uint64_t t, int32_t* action_dev, uint8_t* guided_dev, void* stream, const EnvUfWeights* ww = nullptr,
-                                    const EnvUfWeightsCorr* wc = nullptr) {
+                                    const uint32_t seed[2], uint64_t t, int32_t* action_dev, uint8_t* guided_dev, void* stream, UfwMode mode = UFW_UNIT,
+                                    const UfwWeights* w = nullptr) {
     DQ_REQUIRE(seed, DQ_ERR_INVALID, "%s: null argument", who);
     DQ_REQUIRE(eps >= 0.0 && eps <= 1.0, DQ_ERR_INVALID, "%s: eps must be in [0,1]", who);                                    // (NaN fails both compares)
     DQ_REQUIRE(guide_share >= 0.0 && guide_share <= 1.0, DQ_ERR_INVALID, "%s: guide_share must be in [0,1]", who);
     EnvUfArgsWeighted a;
-    int lds = 0;
-    const dq_status rc = env_wide_uf_prepare(env, H, action_dev, q_dev, &a, &lds, who);
+    const dq_status rc = env_wide_uf_prepare(env, H, action_dev, q_dev, w, &a, who);
     if (rc != DQ_OK) return rc;
     a.q = q_dev; a.T_eps = dq_rate_threshold(eps); a.T_share = dq_rate_threshold(guide_share); a.t = t; a.masked_greedy = masked_greedy;
     a.seed0 = seed[0]; a.seed1 = seed[1]; a.guided = guided_dev;
-    if (wc) {
-        EnvUfArgsCorrelated ac;
-        static_cast<EnvUfArgs&>(ac) = a; ac.w = *wc;
-        env_wide_guided_uf_kernel<true, true><<<a.n_envs, UFW_THREADS, lds + ufw_mask_bytes(a.depth), (hipStream_t)stream>>>(ac);
-    } else if (ww) {
-        a.w = *ww;
-        env_wide_guided_uf_kernel<true><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(a);
-    } else env_wide_guided_uf_kernel<false><<<a.n_envs, UFW_THREADS, lds, (hipStream_t)stream>>>(static_cast<const EnvUfArgs&>(a));
+    env_wide_uf_launch(true, mode, a, stream);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
 }
@@ -366,18 +265,18 @@ dq_status dq_envb_uf_select(dq_envb* env, dq_wide_uf* H, int32_t* action_dev, vo
 }
 
 dq_status dq_envb_uf_select_weighted(dq_envb* env, dq_wide_uf* H, int w_space, int w_time, const uint8_t* weights_each_dev, int32_t* action_dev, void* stream) {
-    const dq_status rc = env_wide_uf_check_weights(w_space, w_time, weights_each_dev, "dq_envb_uf_select_weighted");
+    const UfwWeights w = {weights_each_dev, w_space, w_time, 1};
+    const dq_status rc = ufw_check_weights(UFW_WEIGHTED, 0, w, true, "dq_envb_uf_select_weighted");
     if (rc != DQ_OK) return rc;
-    const EnvUfWeights ww = {weights_each_dev, w_space, w_time};
-    return env_wide_uf_select("dq_envb_uf_select_weighted", env, H, action_dev, stream, &ww);
+    return env_wide_uf_select("dq_envb_uf_select_weighted", env, H, action_dev, stream, UFW_WEIGHTED, &w);
 }
 
 dq_status dq_envb_uf_select_correlated(dq_envb* env, dq_wide_uf* H, int w_space, int w_time, int w_corr, const uint8_t* weights_each_dev, int32_t* action_dev,
                                        void* stream) {
-    const dq_status rc = env_wide_uf_check_correlated(w_space, w_time, w_corr, weights_each_dev, "dq_envb_uf_select_correlated");
+    const UfwWeights w = {weights_each_dev, w_space, w_time, w_corr};
+    const dq_status rc = ufw_check_weights(UFW_CORRELATED, 0, w, true, "dq_envb_uf_select_correlated");
     if (rc != DQ_OK) return rc;
-    const EnvUfWeightsCorr wc = {weights_each_dev, w_space, w_time, w_corr};
-    return env_wide_uf_select("dq_envb_uf_select_correlated", env, H, action_dev, stream, nullptr, &wc);
+    return env_wide_uf_select("dq_envb_uf_select_correlated", env, H, action_dev, stream, UFW_CORRELATED, &w);
 }
 
 dq_status dq_envb_guided_select_uf(dq_envb* env, dq_wide_uf* H, const float* q_dev, double eps, double guide_share, int masked_greedy, const uint32_t seed[2],
@@ -388,21 +287,21 @@ dq_status dq_envb_guided_select_uf(dq_envb* env, dq_wide_uf* H, const float* q_d
 dq_status dq_envb_guided_select_uf_weighted(dq_envb* env, dq_wide_uf* H, const float* q_dev, double eps, double guide_share, int masked_greedy,
                                             const uint32_t seed[2], uint64_t t, int w_space, int w_time, const uint8_t* weights_each_dev, int32_t* action_dev,
                                             uint8_t* guided_dev, void* stream) {
-    const dq_status rc = env_wide_uf_check_weights(w_space, w_time, weights_each_dev, "dq_envb_guided_select_uf_weighted");
+    const UfwWeights w = {weights_each_dev, w_space, w_time, 1};
+    const dq_status rc = ufw_check_weights(UFW_WEIGHTED, 0, w, true, "dq_envb_guided_select_uf_weighted");
     if (rc != DQ_OK) return rc;
-    const EnvUfWeights ww = {weights_each_dev, w_space, w_time};
     return env_wide_uf_guided_select("dq_envb_guided_select_uf_weighted", env, H, q_dev, eps, guide_share, masked_greedy, seed, t, action_dev, guided_dev, stream,
-                                     &ww);
+                                     UFW_WEIGHTED, &w);
 }
 
 dq_status dq_envb_guided_select_uf_correlated(dq_envb* env, dq_wide_uf* H, const float* q_dev, double eps, double guide_share, int masked_greedy,
                                               const uint32_t seed[2], uint64_t t, int w_space, int w_time, int w_corr, const uint8_t* weights_each_dev,
                                               int32_t* action_dev, uint8_t* guided_dev, void* stream) {
-    const dq_status rc = env_wide_uf_check_correlated(w_space, w_time, w_corr, weights_each_dev, "dq_envb_guided_select_uf_correlated");
+    const UfwWeights w = {weights_each_dev, w_space, w_time, w_corr};
+    const dq_status rc = ufw_check_weights(UFW_CORRELATED, 0, w, true, "dq_envb_guided_select_uf_correlated");
     if (rc != DQ_OK) return rc;
-    const EnvUfWeightsCorr wc = {weights_each_dev, w_space, w_time, w_corr};
     return env_wide_uf_guided_select("dq_envb_guided_select_uf_correlated", env, H, q_dev, eps, guide_share, masked_greedy, seed, t, action_dev, guided_dev,
-                                     stream, nullptr, &wc);
+                                     stream, UFW_CORRELATED, &w);
 }
 
 }  // extern "C"

@@ -4,11 +4,13 @@
 //   stream_run_wide_uf_kernel  the rounds are drawn in the workgroup by tests/decode_eval_ref.sample_volumes' rule (thread q owns qubit q and, for
 //                              q < n_stab, stabilizer q's measurement flip): the syndromes never reach memory unless a buffer for them is given
 //   verdict_wide_kernel        residual = hidden XOR frame: in code space, homology class, success; no referee is consulted
-// The two stream kernels are templates on Closed (dq_wide_uf_decode_closed / dq_wide_uf_run_closed), as uf_stream.hip's are.
-// and on Weighted (dq_wide_uf_decode_weighted / dq_wide_uf_run_weighted): the same two bodies around ufw_component<Closed, true>, an edge
-// of weight w full at g = 2 w, one (w_space, w_time) per stream; the Weighted = false instantiations are the unit-weight kernels, instruction for instruction.
-// And on Corr (dq_wide_uf_decode_correlated / dq_wide_uf_run_correlated): three component decodes per window, 0 dry, 1, 0, each one's
-// space edges cheap (w_corr) where the one before put its correction; one (w_space, w_time, w_corr) per stream, two masks behind the layout's bytes.
+// The two stream kernels are templates on Closed (dq_wide_uf_decode_closed / dq_wide_uf_run_closed), as uf_stream.hip's are, and on
+// (Weighted, Corr), three variants that differ only in what uf_wide.h's ufw_setup and ufw_window do for the flags:
+//   <Closed, false, false>  unit weights
+//   <Closed, true, false>   DESIGN.md section 23 (dq_wide_uf_*_weighted): an edge of weight w is full at g = 2 w, one (w_space, w_time) per stream
+//   <Closed, true, true>    DESIGN.md section 25 (dq_wide_uf_*_correlated): three component decodes per window, 0 dry, 1, 0, each one's space edges cheap
+//                           (w_corr) where the one before put its correction; one (w_space, w_time, w_corr) per stream, two masks behind the layout's bytes
+// The flags are compile-time: the unit-weight kernels carry no code of the other two.  wide_kernel is the one map from (run, closed, mode) to a kernel.
 // The lattice tables come from LatticeHost inside the handle; no environment handle is needed.
 #include "uf_wide.h"
 #include "lattice_host.h"
@@ -32,69 +34,31 @@ struct WideArgs {
     int32_t *weight, *n_defects, *rounds;      // [n][2] or NULL
 };
 
-// The weights of a weighted launch: one pair for all streams, or a pair per stream.
-struct WideWeights {
-    const u8* each;             // != NULL: [2 i] / [2 i + 1] = (w_space, w_time) of stream i
-    int w_space, w_time;
-};
-
-// The arguments of a weighted launch are the unweighted ones with the weights behind them; the unweighted kernels take WideArgs itself.
+// The arguments of a weighted or a correlated launch are the unweighted ones with the weights behind them; the unit-weight kernels take WideArgs itself.
 struct WideArgsWeighted : WideArgs {
-    WideWeights w;
+    UfwWeights w;
 };
-// The weights of a correlated launch: one triple for all streams, or a triple per stream.
-struct WideWeightsCorr {
-    const u8* each;             // != NULL: [3 i] .. [3 i + 2] = (w_space, w_time, w_corr) of stream i
-    int w_space, w_time, w_corr;
-};
-
-struct WideArgsCorrelated : WideArgs {
-    WideWeightsCorr w;
-};
-template <bool Weighted, bool Corr = false>
-using WideArgsOf = std::conditional_t<Corr, WideArgsCorrelated, std::conditional_t<Weighted, WideArgsWeighted, WideArgs>>;
-
-// The workgroup's own pair, clamped to 1 .. UFW_MAX_WEIGHT: a bad byte of a per-stream array cannot overrun the growth byte.
-static __device__ __forceinline__ void wide_weights(const WideWeights& w, size_t i, int& w_space, int& w_time) {
-    w_space = w.w_space; w_time = w.w_time;
-    if (w.each != nullptr) { w_space = w.each[2 * i]; w_time = w.each[2 * i + 1]; }
-    w_space = min(max(w_space, 1), UFW_MAX_WEIGHT); w_time = min(max(w_time, 1), UFW_MAX_WEIGHT);
-    UFW_IN_VGPR(w_space); UFW_IN_VGPR(w_time);
-}
-
-// The workgroup's own triple: the pair clamped as above, w_corr to 1 .. w_space.
-static __device__ __forceinline__ void wide_weights(const WideWeightsCorr& w, size_t i, int& w_space, int& w_time, int& w_corr) {
-    w_space = w.w_space; w_time = w.w_time; w_corr = w.w_corr;
-    if (w.each != nullptr) { w_space = w.each[3 * i]; w_time = w.each[3 * i + 1]; w_corr = w.each[3 * i + 2]; }
-    w_space = min(max(w_space, 1), UFW_MAX_WEIGHT); w_time = min(max(w_time, 1), UFW_MAX_WEIGHT); w_corr = min(max(w_corr, 1), w_space);
-    UFW_IN_VGPR(w_space); UFW_IN_VGPR(w_time); UFW_IN_VGPR(w_corr);
-}
+template <bool Weighted>
+using WideArgsOf = std::conditional_t<Weighted, WideArgsWeighted, WideArgs>;
 
 // The schedule around a source of rounds: next(j, row0, row1) is called once for every j = 0 .. T - 1, in order, by every thread; it leaves round j's defect
 // rows of the two components in the given LDS words (all UFW_ROW_WORDS of each) and may use barriers; `last` says j = T - 1 (the last row of the final window).
 // Closed: the stream ends on a round of perfect measurements, so the final window has no time edges in its last round.
-// Weighted: ufw_component<Closed, true> with the stream's (w_space, w_time); the schedule, the carry and the closed final window are the same.
-// Corr: per window three component decodes instead of two -- component 0 dry, which only leaves mask A of its correction's space
-// edges; component 1 with w_corr on A, committed, leaving mask B; component 0 again with w_corr on B, committed.  o_mask: the byte offset of the two masks.
-template <bool Closed, bool Weighted, bool Corr = false, class Next>
-static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem, const UfwLayout& L, int tid, Next next, int w_space = 1, int w_time = 1,
-                                                    int w_corr = 1, int o_mask = 0) {
-    u32* s_frame = reinterpret_cast<u32*>(smem + L.o_frame);
-    u32* s_carry = reinterpret_cast<u32*>(smem + L.o_carry);
-    int* s_acc = reinterpret_cast<int*>(smem + L.o_acc);
-    u32* s_ring = reinterpret_cast<u32*>(smem + L.o_ring);
+// Weighted, Corr: what uf_wide.h's ufw_window decodes per window, with the stream's weights of S; the schedule, the carry and the closed final window are the
+// same for all three.
+template <bool Closed, bool Weighted, bool Corr, class Next>
+static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem, const UfwSetup& S, int tid, Next next) {
+    const UfwHead H = ufw_head(smem, S.L);
+    u32 *s_frame = H.s_frame, *s_carry = H.s_carry, *s_ring = H.s_ring;
+    int* s_acc = H.s_acc;
     int window = p.window, commit = p.commit, T = p.T, row_stride = window * UFW_ROW_WORDS;
     UFW_IN_VGPR(window); UFW_IN_VGPR(commit); UFW_IN_VGPR(T); UFW_IN_VGPR(row_stride);
     if (tid < 2 * UFW_FRAME_WORDS) s_frame[tid] = 0;
     if (tid < 2 * UFW_ROW_WORDS) s_carry[tid] = 0;
     if (tid < 8) s_acc[tid] = 0;
     __syncthreads();
-    UfwGraph G;
-    G.n = p.n; G.d2 = p.d2; G.per_round = p.d2 + p.n;
-    G.mag_n = ufw_magic(G.n); G.mag_pr = ufw_magic(G.per_round);
-    UFW_IN_VGPR(G.n); UFW_IN_VGPR(G.d2); UFW_IN_VGPR(G.per_round); UFW_IN_VGPR(G.mag_n); UFW_IN_VGPR(G.mag_pr);
-    const u8 *eu0 = p.c0.eu, *ev0 = p.c0.ev, *eu1 = p.c1.eu, *ev1 = p.c1.ev;
-    UFW_IN_VGPR(eu0); UFW_IN_VGPR(ev0); UFW_IN_VGPR(eu1); UFW_IN_VGPR(ev1);
+    UfwGraph G = ufw_graph_in_vgpr(p.n, p.d2);
+    const UfwEnds E = ufw_ends_in_vgpr(p.c0, p.c1);
     int n_windows = window >= T ? 1 : (T - window + commit - 1) / commit + 1;
     int have = 0, j = 0;                                           // rounds of the window already in the ring; the next round of the stream
     UFW_IN_VGPR(n_windows); UFW_IN_VGPR(have); UFW_IN_VGPR(j);
@@ -110,33 +74,7 @@ static __device__ __forceinline__ void wide_windows(const WideArgs& p, u8* smem,
         }
         __syncthreads();
         G.depth = l; G.B = l * G.n; G.NN = G.B + 1; G.NE = l * G.per_round;
-        if constexpr (Corr) {
-            u32* s_mask = reinterpret_cast<u32*>(smem + o_mask);   // u32 [2][window][8]: A, B
-            int mask_stride = window * UFW_FRAME_WORDS;
-            // without a defect of component 1 in the window nobody reads A: the dry pass is left out (workgroup-uniform)
-            int pass = __syncthreads_or(tid < l * UFW_ROW_WORDS && s_ring[row_stride + tid] != 0) ? 0 : 1;
-            UFW_IN_VGPR(mask_stride); UFW_IN_VGPR(pass);
-            for (; pass < 3; ++pass) {                             // components 0, 1, 0
-                const int c = pass & 1;
-                int dry = pass == 0;
-                UFW_IN_VGPR(dry);
-                G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
-                // pass 0 reads B, which nobody has written for this window, under w_corr = w_space: every space edge weighs w_space
-                ufw_component<Closed, true, true>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS,
-                                                  s_carry + c * UFW_ROW_WORDS, s_acc + c, s_acc + 4 + c, w_space, w_time, s_acc + 6, pass ? w_corr : w_space,
-                                                  s_mask + (c ? 0 : mask_stride), s_mask + (c ? mask_stride : 0), dry);
-            }
-        } else {
-            for (int c = 0; c < 2; ++c) {
-                G.eu = c ? eu1 : eu0; G.ev = c ? ev1 : ev0;
-                if constexpr (Weighted)
-                    ufw_component<Closed, true>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS,
-                                                s_acc + c, s_acc + 4 + c, w_space, w_time, s_acc + 6);
-                else
-                    ufw_component<Closed>(G, s_ring + c * row_stride, smem, L, tid, commit, final, s_frame + c * UFW_FRAME_WORDS, s_carry + c * UFW_ROW_WORDS, s_acc + c,
-                                          s_acc + 4 + c);
-            }
-        }
+        ufw_window<Closed, Weighted, Corr>(G, E, smem, S, H, tid, row_stride, commit, final, 2, s_acc + 6);
         if (final) break;
         // the ring moves down by `commit` rows (2 window UFW_ROW_WORDS <= UFW_THREADS words)
         const int keep = window - commit;
@@ -187,45 +125,35 @@ static __device__ __forceinline__ void wide_store(const WidePtrs& P, u8* smem, c
 }
 
 template <bool Closed, bool Weighted = false, bool Corr = false>
-__global__ __launch_bounds__(UFW_THREADS) void stream_wide_uf_kernel(WideArgsOf<Weighted, Corr> p) {
+__global__ __launch_bounds__(UFW_THREADS) void stream_wide_uf_kernel(WideArgsOf<Weighted> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
     if ((int)blockIdx.x >= p.n_streams) return;                     // workgroup-uniform
-    int w_space = 1, w_time = 1, w_corr = 1, o_mask = 0;
-    if constexpr (Corr) wide_weights(p.w, i, w_space, w_time, w_corr);
-    else if constexpr (Weighted) wide_weights(p.w, i, w_space, w_time);
-    UfwLayout L = ufw_layout(p.n, p.d2, p.window);
-    if constexpr (Corr) { o_mask = L.bytes; UFW_IN_VGPR(o_mask); }  // the two masks: a tail behind the layout of before
-    ufw_layout_in_vgpr(L);
+    const UfwSetup S = ufw_setup<Weighted, Corr>(p, i, p.n, p.d2, p.window);
     const int my_cell = p.node_cell[tid];
     const bool mine = (tid & (UFW_NODE_SLOTS - 1)) < p.n;            // (255 is a cell of the d = 15 grid: the table's padding does not tell)
     const u8* vp = p.syn_in + i * (size_t)p.T * p.G + (mine ? my_cell : 0);
     const WidePtrs P = wide_ptrs(p, i, tid);
     int prev = 0, nd = 0, G = p.G;
     UFW_IN_VGPR(vp); UFW_IN_VGPR(prev); UFW_IN_VGPR(nd); UFW_IN_VGPR(G);
-    wide_windows<Closed, Weighted, Corr>(p, smem, L, tid, [&](int j, bool, u32* row0, u32* row1) {
+    wide_windows<Closed, Weighted, Corr>(p, smem, S, tid, [&](int j, bool, u32* row0, u32* row1) {
         const int cur = vp[(size_t)j * G] != 0;                    // (a thread without a node reads cell 0 of its own stream and masks it)
         wide_rows(mine ? cur : 0, prev, tid, row0, row1, nd);
-    }, w_space, w_time, w_corr, o_mask);
-    wide_store(P, smem, L, tid, nd);
+    });
+    wide_store(P, smem, S.L, tid, nd);
 }
 
 template <bool Closed, bool Weighted = false, bool Corr = false>
-__global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArgsOf<Weighted, Corr> p) {
+__global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArgsOf<Weighted> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x;
     const size_t i = blockIdx.x;
     if ((int)blockIdx.x >= p.n_streams) return;                     // workgroup-uniform
-    int w_space = 1, w_time = 1, w_corr = 1, o_mask = 0;
-    if constexpr (Corr) wide_weights(p.w, i, w_space, w_time, w_corr);
-    else if constexpr (Weighted) wide_weights(p.w, i, w_space, w_time);
-    UfwLayout L = ufw_layout(p.n, p.d2, p.window);
-    if constexpr (Corr) { o_mask = L.bytes; UFW_IN_VGPR(o_mask); }  // the two masks: a tail behind the layout of before
-    ufw_layout_in_vgpr(L);
-    u8* s_ex = smem + L.o_ex;
-    u8* s_ez = smem + L.o_ez;
-    u8* s_v = smem + L.o_v;
+    const UfwSetup S = ufw_setup<Weighted, Corr>(p, i, p.n, p.d2, p.window);
+    u8* s_ex = smem + S.L.o_ex;
+    u8* s_ez = smem + S.L.o_ez;
+    u8* s_v = smem + S.L.o_v;
     u64 T_phys = p.T_phys, T_meas = p.T_meas;
     if (p.T_each != nullptr) { T_phys = p.T_each[2 * i]; T_meas = p.T_each[2 * i + 1]; }
     int has_q = tid < p.d2, has_s = tid < p.n_stab;
@@ -248,7 +176,7 @@ __global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArg
     int x = 0, z = 0, prev = 0, seen = 0, nd = 0;
     UFW_IN_VGPR(has_q); UFW_IN_VGPR(has_s); UFW_IN_VGPR(isx); UFW_IN_VGPR(x); UFW_IN_VGPR(z); UFW_IN_VGPR(prev); UFW_IN_VGPR(seen); UFW_IN_VGPR(nd);
     UFW_IN_VGPR(hid); UFW_IN_VGPR(triv); UFW_IN_VGPR(syn);
-    wide_windows<Closed, Weighted, Corr>(p, smem, L, tid, [&](int j, bool last, u32* row0, u32* row1) {
+    wide_windows<Closed, Weighted, Corr>(p, smem, S, tid, [&](int j, bool last, u32* row0, u32* row1) {
         u32 w[4];                                                  // sample_volumes' round, round counter j
         philox4x32_10((u32)j, 0u, id, (u32)tid, seed0, seed1, w);
         const bool hit = has_q && (u64)w[0] < T_phys;
@@ -271,11 +199,11 @@ __global__ __launch_bounds__(UFW_THREADS) void stream_run_wide_uf_kernel(WideArg
         if (syn) syn[(size_t)j * G] = cs < 255 ? s_v[cs] : (u8)0;
         const int cur = my_stab < 255 && s_v[my_stab] != 0;
         wide_rows(cur, prev, tid, row0, row1, nd);
-    }, w_space, w_time, w_corr, o_mask);
+    });
     const int any_seen = __syncthreads_or(seen);
     if (has_q) *hid = (u8)(x ? (z ? 2 : 1) : (z ? 3 : 0));
     if (tid == 0) *triv = (u8)(any_seen == 0);
-    wide_store(P, smem, L, tid, nd);
+    wide_store(P, smem, S.L, tid, nd);
 }
 
 struct WideVerdictArgs {
@@ -324,71 +252,58 @@ dq_status wide_check(const dq_wide_uf* H, int n, int T, int commit, const int32_
     return DQ_OK;
 }
 
-void wide_args(const dq_wide_uf* H, int n, int T, int commit, WideArgs* a) {
+void wide_args(const dq_wide_uf* H, int n, int T, int commit, const UfwWeights* w, WideArgsWeighted* a) {
     memset(a, 0, sizeof(*a));
     a->c0 = UfwComp{H->ends, H->ends + 256};
     a->c1 = UfwComp{H->ends + 512, H->ends + 768};
     a->node_cell = H->node_cell; a->node_stab = H->node_stab; a->cell_stab = H->cell_stab; a->stab_q = H->stab_q; a->stab_isx = H->stab_isx;
     a->n_streams = n; a->d = H->d; a->n = H->n; a->d2 = H->d2; a->n_stab = H->n_stab; a->G = H->G; a->model = H->model; a->T = T; a->window = H->window;
     a->commit = commit;
+    if (w) a->w = *w;
 }
 
-
-// What the weighted forms check on top: closed is a flag, the uniform pair lies in 1 .. UFW_MAX_WEIGHT (a per-stream array is the caller's to check; the kernel
-// clamps it).
-dq_status wide_check_weighted(int closed, int w_space, int w_time, const char* who) {
-    DQ_REQUIRE(closed == 0 || closed == 1, DQ_ERR_INVALID, "%s: closed = %d is not 0 or 1", who, closed);
-    DQ_REQUIRE(w_space >= 1 && w_space <= UFW_MAX_WEIGHT && w_time >= 1 && w_time <= UFW_MAX_WEIGHT, DQ_ERR_INVALID,
-               "%s: weights (%d, %d) outside 1..%d", who, w_space, w_time, UFW_MAX_WEIGHT);
-    return DQ_OK;
+// The one place that maps (run, closed, mode) to a kernel instantiation: f(kernel) gets the __global__ function, whose argument is WideArgs for the unit weights
+// and WideArgsWeighted otherwise.  The launches (wide_launch) and dq_wide_uf_create's LDS limits both go through it.
+template <class F>
+void wide_kernel(bool run, bool closed, UfwMode mode, F&& f) {
+    ufw_with_mode(mode, [&](auto weighted, auto corr) {
+        constexpr bool W = decltype(weighted)::value, K = decltype(corr)::value;
+        if (run) closed ? f(stream_run_wide_uf_kernel<true, W, K>) : f(stream_run_wide_uf_kernel<false, W, K>);
+        else closed ? f(stream_wide_uf_kernel<true, W, K>) : f(stream_wide_uf_kernel<false, W, K>);
+    });
 }
 
-// ... and the correlated forms on top of that: w_corr in 1 .. w_space.
-dq_status wide_check_correlated(int closed, int w_space, int w_time, int w_corr, const char* who) {
-    const dq_status rc = wide_check_weighted(closed, w_space, w_time, who);
-    if (rc != DQ_OK) return rc;
-    DQ_REQUIRE(w_corr >= 1 && w_corr <= w_space, DQ_ERR_INVALID, "%s: w_corr = %d outside 1..w_space = %d", who, w_corr, w_space);
-    return DQ_OK;
+// (a unit-weight kernel takes the WideArgs part of `a`)
+void wide_launch(bool run, bool closed, UfwMode mode, const dq_wide_uf* H, const WideArgsWeighted& a, hipStream_t st) {
+    const int lds = ufw_lds_bytes(mode, H->lds, H->window);
+    wide_kernel(run, closed, mode, [&](auto* kernel) { kernel<<<a.n_streams, UFW_THREADS, lds, st>>>(a); });
 }
 
-// The open and the closed entry points: one body, `who` names the caller in the messages.  ww: the weights of a weighted launch, wc: of a correlated one, both
-// NULL for the unit-weight kernels.
+// The open and the closed entry points: one body, `who` names the caller in the messages.  w: the weights of a weighted or a correlated launch (already
+// checked), NULL for the unit-weight kernels.
 dq_status wide_decode(bool closed, const char* who, dq_wide_uf* H, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,
-                      int32_t* n_defects_dev, int32_t* rounds_dev, void* stream, const WideWeights* ww = nullptr, const WideWeightsCorr* wc = nullptr) {
+                      int32_t* n_defects_dev, int32_t* rounds_dev, void* stream, UfwMode mode = UFW_UNIT, const UfwWeights* w = nullptr) {
     DQ_REQUIRE(H && syndromes_dev && frame_dev, DQ_ERR_INVALID, "%s: null argument", who);
     const dq_status rc = wide_check(H, n, T, commit, weight_dev, n_defects_dev, rounds_dev, who);
     if (rc != DQ_OK) return rc;
-    WideArgs a;
-    wide_args(H, n, T, commit, &a);
+    WideArgsWeighted a;
+    wide_args(H, n, T, commit, w, &a);
     a.syn_in = syndromes_dev; a.frame = frame_dev; a.weight = weight_dev; a.n_defects = n_defects_dev; a.rounds = rounds_dev;
-    if (wc) {
-        WideArgsCorrelated ac;
-        static_cast<WideArgs&>(ac) = a; ac.w = *wc;
-        const int lds = H->lds + ufw_mask_bytes(H->window);
-        if (closed) stream_wide_uf_kernel<true, true, true><<<n, UFW_THREADS, lds, (hipStream_t)stream>>>(ac);
-        else stream_wide_uf_kernel<false, true, true><<<n, UFW_THREADS, lds, (hipStream_t)stream>>>(ac);
-    } else if (ww) {
-        WideArgsWeighted aw;
-        static_cast<WideArgs&>(aw) = a; aw.w = *ww;
-        if (closed) stream_wide_uf_kernel<true, true><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(aw);
-        else stream_wide_uf_kernel<false, true><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(aw);
-    } else if (closed) stream_wide_uf_kernel<true><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(a);
-    else stream_wide_uf_kernel<false><<<n, UFW_THREADS, H->lds, (hipStream_t)stream>>>(a);
+    wide_launch(false, closed, mode, H, a, (hipStream_t)stream);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
 }
 
 dq_status wide_run(bool closed, const char* who, dq_wide_uf* H, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
                    const double* p_phys_each, const double* p_meas_each, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev,
-                   int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream, const WideWeights* ww = nullptr,
-                   const WideWeightsCorr* wc = nullptr) {
+                   int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream, UfwMode mode = UFW_UNIT, const UfwWeights* w = nullptr) {
     DQ_REQUIRE(H && seed && hidden_dev && trivial_dev && frame_dev, DQ_ERR_INVALID, "%s: null argument", who);
     dq_status rc = wide_check(H, n, T, commit, weight_dev, n_defects_dev, rounds_dev, who);
     if (rc != DQ_OK) return rc;
     DQ_REQUIRE((p_phys_each != nullptr) == (p_meas_each != nullptr), DQ_ERR_INVALID, "%s: per-stream rates come as a pair of arrays", who);
     hipStream_t st = (hipStream_t)stream;
-    WideArgs a;
-    wide_args(H, n, T, commit, &a);
+    WideArgsWeighted a;
+    wide_args(H, n, T, commit, w, &a);
     if (p_phys_each) {
         rc = dq_rate_table_upload(H->rates, n, p_phys_each, p_meas_each, st);
         if (rc != DQ_OK) return rc;
@@ -400,19 +315,7 @@ dq_status wide_run(bool closed, const char* who, dq_wide_uf* H, int n, int T, in
     a.env_id_base = env_id_base; a.seed0 = seed[0]; a.seed1 = seed[1];
     a.hidden = hidden_dev; a.trivial = trivial_dev; a.frame = frame_dev; a.weight = weight_dev; a.n_defects = n_defects_dev; a.rounds = rounds_dev;
     a.syn_out = syndromes_dev;
-    if (wc) {
-        WideArgsCorrelated ac;
-        static_cast<WideArgs&>(ac) = a; ac.w = *wc;
-        const int lds = H->lds + ufw_mask_bytes(H->window);
-        if (closed) stream_run_wide_uf_kernel<true, true, true><<<n, UFW_THREADS, lds, st>>>(ac);
-        else stream_run_wide_uf_kernel<false, true, true><<<n, UFW_THREADS, lds, st>>>(ac);
-    } else if (ww) {
-        WideArgsWeighted aw;
-        static_cast<WideArgs&>(aw) = a; aw.w = *ww;
-        if (closed) stream_run_wide_uf_kernel<true, true><<<n, UFW_THREADS, H->lds, st>>>(aw);
-        else stream_run_wide_uf_kernel<false, true><<<n, UFW_THREADS, H->lds, st>>>(aw);
-    } else if (closed) stream_run_wide_uf_kernel<true><<<n, UFW_THREADS, H->lds, st>>>(a);
-    else stream_run_wide_uf_kernel<false><<<n, UFW_THREADS, H->lds, st>>>(a);
+    wide_launch(true, closed, mode, H, a, st);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
 }
@@ -459,21 +362,16 @@ dq_status dq_wide_uf_create(int d, int error_model, int window, int max_streams,
     const unsigned long long dev_bit = dq_device_bit();
     if (!(attr_devs & dev_bit)) {
         const int lds_max = ufw_layout((UFW_MAX_D * UFW_MAX_D - 1) / 2, UFW_MAX_D * UFW_MAX_D, UFW_MAX_WINDOW).bytes;
-        const void* kernels[8] = {reinterpret_cast<const void*>(stream_wide_uf_kernel<false>), reinterpret_cast<const void*>(stream_run_wide_uf_kernel<false>),
-                                  reinterpret_cast<const void*>(stream_wide_uf_kernel<true>), reinterpret_cast<const void*>(stream_run_wide_uf_kernel<true>),
-                                  reinterpret_cast<const void*>(stream_wide_uf_kernel<false, true>),
-                                  reinterpret_cast<const void*>(stream_run_wide_uf_kernel<false, true>),
-                                  reinterpret_cast<const void*>(stream_wide_uf_kernel<true, true>),
-                                  reinterpret_cast<const void*>(stream_run_wide_uf_kernel<true, true>)};
-        // the correlated kernels carry their two masks behind that
-        const int lds_max_corr = lds_max + ufw_mask_bytes(UFW_MAX_WINDOW);
-        const void* correlated[4] = {reinterpret_cast<const void*>(stream_wide_uf_kernel<false, true, true>),
-                                     reinterpret_cast<const void*>(stream_run_wide_uf_kernel<false, true, true>),
-                                     reinterpret_cast<const void*>(stream_wide_uf_kernel<true, true, true>),
-                                     reinterpret_cast<const void*>(stream_run_wide_uf_kernel<true, true, true>)};
+        const int lds_max_corr = ufw_lds_bytes(UFW_CORRELATED, lds_max, UFW_MAX_WINDOW);      // the correlated kernels carry their two masks behind that
         hipError_t ea = hipSuccess;
-        for (int k = 0; k < 8 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        for (int k = 0; k < 4 && ea == hipSuccess; ++k) ea = hipFuncSetAttribute(correlated[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds_max_corr);
+        for (int k = 0; k < 12; ++k) {                               // every (run, closed, mode)
+            const UfwMode mode = (UfwMode)(k >> 2);
+            wide_kernel(k & 1, k & 2, mode, [&](auto* kernel) {
+                if (ea == hipSuccess)
+                    ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             ufw_lds_bytes(mode, lds_max, UFW_MAX_WINDOW));
+            });
+        }
         if (ea != hipSuccess) {
             (void)hipGetLastError();
             dq_set_error("dq_wide_uf_create: the device refuses %d bytes of LDS per workgroup: %s", lds_max_corr, hipGetErrorString(ea));
@@ -536,42 +434,43 @@ dq_status dq_wide_uf_run_closed(dq_wide_uf* H, int n, int T, int commit, uint32_
 dq_status dq_wide_uf_decode_weighted(dq_wide_uf* H, const uint8_t* syndromes_dev, int n, int T, int commit, int closed, int w_space, int w_time,
                                      const uint8_t* weights_each_dev, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev,
                                      void* stream) {
-    const dq_status rc = wide_check_weighted(closed, w_space, w_time, "dq_wide_uf_decode_weighted");
+    const UfwWeights w = {weights_each_dev, w_space, w_time, 1};
+    const dq_status rc = ufw_check_weights(UFW_WEIGHTED, closed, w, false, "dq_wide_uf_decode_weighted");
     if (rc != DQ_OK) return rc;
-    const WideWeights ww = {weights_each_dev, w_space, w_time};
-    return wide_decode(closed != 0, "dq_wide_uf_decode_weighted", H, syndromes_dev, n, T, commit, frame_dev, weight_dev, n_defects_dev, rounds_dev, stream, &ww);
+    return wide_decode(closed != 0, "dq_wide_uf_decode_weighted", H, syndromes_dev, n, T, commit, frame_dev, weight_dev, n_defects_dev, rounds_dev, stream,
+                       UFW_WEIGHTED, &w);
 }
 
 dq_status dq_wide_uf_run_weighted(dq_wide_uf* H, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
                                   const double* p_phys_each, const double* p_meas_each, int closed, int w_space, int w_time, const uint8_t* weights_each_dev,
                                   uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev,
                                   int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
-    const dq_status rc = wide_check_weighted(closed, w_space, w_time, "dq_wide_uf_run_weighted");
+    const UfwWeights w = {weights_each_dev, w_space, w_time, 1};
+    const dq_status rc = ufw_check_weights(UFW_WEIGHTED, closed, w, false, "dq_wide_uf_run_weighted");
     if (rc != DQ_OK) return rc;
-    const WideWeights ww = {weights_each_dev, w_space, w_time};
     return wide_run(closed != 0, "dq_wide_uf_run_weighted", H, n, T, commit, env_id_base, seed, p_phys, p_meas, p_phys_each, p_meas_each, hidden_dev, trivial_dev,
-                    frame_dev, weight_dev, n_defects_dev, rounds_dev, syndromes_dev, stream, &ww);
+                    frame_dev, weight_dev, n_defects_dev, rounds_dev, syndromes_dev, stream, UFW_WEIGHTED, &w);
 }
 
 dq_status dq_wide_uf_decode_correlated(dq_wide_uf* H, const uint8_t* syndromes_dev, int n, int T, int commit, int closed, int w_space, int w_time, int w_corr,
                                        const uint8_t* weights_each_dev, uint8_t* frame_dev, int32_t* weight_dev, int32_t* n_defects_dev, int32_t* rounds_dev,
                                        void* stream) {
-    const dq_status rc = wide_check_correlated(closed, w_space, w_time, w_corr, "dq_wide_uf_decode_correlated");
+    const UfwWeights w = {weights_each_dev, w_space, w_time, w_corr};
+    const dq_status rc = ufw_check_weights(UFW_CORRELATED, closed, w, false, "dq_wide_uf_decode_correlated");
     if (rc != DQ_OK) return rc;
-    const WideWeightsCorr wc = {weights_each_dev, w_space, w_time, w_corr};
-    return wide_decode(closed != 0, "dq_wide_uf_decode_correlated", H, syndromes_dev, n, T, commit, frame_dev, weight_dev, n_defects_dev, rounds_dev, stream, nullptr,
-                       &wc);
+    return wide_decode(closed != 0, "dq_wide_uf_decode_correlated", H, syndromes_dev, n, T, commit, frame_dev, weight_dev, n_defects_dev, rounds_dev, stream,
+                       UFW_CORRELATED, &w);
 }
 
 dq_status dq_wide_uf_run_correlated(dq_wide_uf* H, int n, int T, int commit, uint32_t env_id_base, const uint32_t seed[2], double p_phys, double p_meas,
                                     const double* p_phys_each, const double* p_meas_each, int closed, int w_space, int w_time, int w_corr,
                                     const uint8_t* weights_each_dev, uint8_t* hidden_dev, uint8_t* trivial_dev, uint8_t* frame_dev, int32_t* weight_dev,
                                     int32_t* n_defects_dev, int32_t* rounds_dev, uint8_t* syndromes_dev, void* stream) {
-    const dq_status rc = wide_check_correlated(closed, w_space, w_time, w_corr, "dq_wide_uf_run_correlated");
+    const UfwWeights w = {weights_each_dev, w_space, w_time, w_corr};
+    const dq_status rc = ufw_check_weights(UFW_CORRELATED, closed, w, false, "dq_wide_uf_run_correlated");
     if (rc != DQ_OK) return rc;
-    const WideWeightsCorr wc = {weights_each_dev, w_space, w_time, w_corr};
     return wide_run(closed != 0, "dq_wide_uf_run_correlated", H, n, T, commit, env_id_base, seed, p_phys, p_meas, p_phys_each, p_meas_each, hidden_dev, trivial_dev,
-                    frame_dev, weight_dev, n_defects_dev, rounds_dev, syndromes_dev, stream, nullptr, &wc);
+                    frame_dev, weight_dev, n_defects_dev, rounds_dev, syndromes_dev, stream, UFW_CORRELATED, &w);
 }
 
 dq_status dq_wide_uf_verdict(dq_wide_uf* H, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev, void* stream) {

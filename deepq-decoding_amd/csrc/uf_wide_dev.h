@@ -117,7 +117,8 @@ static __device__ __forceinline__ int ufw_weight(int t, int k, int d2, int w_spa
 // *s_weight, *s_rounds counts unit growth steps.  With Weighted = false the three arguments are not read and the code is the unit-weight one.
 // Corr (with Weighted): the space edge (t, k) weighs w_corr where bit k of mask_r [t][8] is set; mask_w [depth][8] is zeroed on entry, in front of the early
 // return, and receives the bit of every space edge of the correction, whatever its round.  dry (workgroup-uniform): nothing is committed -- frame, carry, weight
-// and rounds stay as they are.  With Corr = false the four arguments are not read and the code is the one of before.
+// and rounds stay as they are.  With Corr = false the four arguments are not read and the code is the weighted one.
+// uf_wide.h's ufw_window is the one caller: it passes every argument whatever the flags.
 template <bool Closed = false, bool Weighted = false, bool Corr = false>
 static __device__ __forceinline__ void ufw_component(const UfwGraph& G, const u32* dw, u8* __restrict__ s, const UfwLayout& L, int tid, int commit, bool final,
                                                      u32* s_frame, u32* s_carry, int* s_weight, int* s_rounds, int w_space = 1, int w_time = 1,

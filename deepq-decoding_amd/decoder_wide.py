@@ -143,17 +143,23 @@ def with_correlated(weights, correlated):
     return np.ascontiguousarray(np.concatenate([weights, np.full((len(weights), 1), correlated, dtype=np.uint8)], axis=1))
 
 
+def _rate_rows(of_rates, cols, p_phys, p_meas, error_model, n):
+    """of_rates(p_phys, p_meas, error_model) of every stream's own rates: one tuple where the rates are scalars, else uint8 [n, cols], every distinct
+    rate pair computed once."""
+    if isinstance(p_phys, float):
+        return of_rates(p_phys, p_meas, error_model)
+    out = np.empty((n, cols), dtype=np.uint8)
+    seen = {}
+    for i, key in enumerate(zip(p_phys.tolist(), p_meas.tolist())):
+        if key not in seen:
+            seen[key] = of_rates(key[0], key[1], error_model)
+        out[i] = seen[key]
+    return out
+
+
 def rate_weights_correlated(p_phys, p_meas, error_model, n):
     """correlated="rates": uf_weights_correlated of every stream's own (p_phys, p_meas).  Returns one triple where the rates are scalars, else uint8 [n, 3]."""
-    if isinstance(p_phys, float):
-        return uf_weights_correlated(p_phys, p_meas, error_model)
-    out = np.empty((n, 3), dtype=np.uint8)
-    triples = {}
-    for i, key in enumerate(zip(p_phys.tolist(), p_meas.tolist())):
-        if key not in triples:
-            triples[key] = uf_weights_correlated(key[0], key[1], error_model)
-        out[i] = triples[key]
-    return out
+    return _rate_rows(uf_weights_correlated, 3, p_phys, p_meas, error_model, n)
 
 
 def is_correlated(weights):
@@ -162,6 +168,20 @@ def is_correlated(weights):
         return len(weights) == 3
     shape = getattr(weights, "shape", None)
     return shape is not None and len(shape) == 2 and int(shape[1]) == 3
+
+
+def weights_call(weights):
+    """What a validated weights= amounts to for the library, at every call site that hands weights on (WideEvaluator.decode_into / run_into,
+    VectorEnv.uf_select_wide / guided_select_wide): (the entry point's suffix, its scalar weights, its per-row device tensor or None).  None: ("", (),
+    None), the unit-weight entry point, which takes neither.  A pair or triple: ("_weighted" / "_correlated", the tuple, None).  A uint8 device tensor
+    [n, 2] / [n, 3]: (the suffix, ones -- the library wants a valid uniform pair beside an array --, the tensor)."""
+    if weights is None:
+        return "", (), None
+    corr = is_correlated(weights)
+    suffix = "_correlated" if corr else "_weighted"
+    if isinstance(weights, tuple):
+        return suffix, weights, None
+    return suffix, (1,) * (3 if corr else 2), weights
 
 
 def check_weights(weights, n=None, rates=False):
@@ -193,15 +213,7 @@ def check_weights(weights, n=None, rates=False):
 
 def rate_weights(p_phys, p_meas, error_model, n):
     """weights="rates": uf_weights of every stream's own (p_phys, p_meas).  Returns one pair where the rates are scalars, else uint8 [n, 2]."""
-    if isinstance(p_phys, float):
-        return uf_weights(p_phys, p_meas, error_model)
-    out = np.empty((n, 2), dtype=np.uint8)
-    pairs = {}
-    for i, key in enumerate(zip(p_phys.tolist(), p_meas.tolist())):
-        if key not in pairs:
-            pairs[key] = uf_weights(key[0], key[1], error_model)
-        out[i] = pairs[key]
-    return out
+    return _rate_rows(uf_weights, 2, p_phys, p_meas, error_model, n)
 
 
 def check_policy_weights(weights, n=None):
@@ -366,20 +378,14 @@ class WideEvaluator(Counting):
         dq_wide_uf_decode_closed.  weights: a pair (w_space, w_time) or a uint8 device tensor [m, 2], both validated by the caller (check_weights):
         dq_wide_uf_decode_weighted.  A triple (w_space, w_time, w_corr) or a uint8 device tensor [m, 3] (with_correlated): dq_wide_uf_decode_correlated."""
         from . import _lib
-        if is_correlated(weights):
-            triple, each = (weights, None) if isinstance(weights, tuple) else ((1, 1, 1), weights)
-            _lib.check(self.L.dq_wide_uf_decode_correlated(self._h, _lib.ptr(syndromes), m, T, commit, int(check_final_round(final_round)), *triple,
-                                                           _lib.ptr(each), _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
-                                                           self._stream()))
-            return
-        if weights is not None:
-            pair, each = (weights, None) if isinstance(weights, tuple) else ((1, 1), weights)
-            _lib.check(self.L.dq_wide_uf_decode_weighted(self._h, _lib.ptr(syndromes), m, T, commit, int(check_final_round(final_round)), pair[0], pair[1],
-                                                         _lib.ptr(each), _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
-                                                         self._stream()))
-            return
-        fn = self.L.dq_wide_uf_decode_closed if check_final_round(final_round) else self.L.dq_wide_uf_decode
-        _lib.check(fn(self._h, _lib.ptr(syndromes), m, T, commit, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), self._stream()))
+        suffix, w, each = weights_call(weights)
+        closed = check_final_round(final_round)
+        if suffix:
+            fn, mode = getattr(self.L, "dq_wide_uf_decode" + suffix), (int(closed), *w, _lib.ptr(each))
+        else:
+            fn, mode = self.L.dq_wide_uf_decode_closed if closed else self.L.dq_wide_uf_decode, ()
+        _lib.check(fn(self._h, _lib.ptr(syndromes), m, T, commit, *mode, _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
+                      self._stream()))
 
     def run_into(self, m, T, commit, lattice_id, seed, p_phys, p_meas, hidden, trivial, frame, weight=None, n_defects=None, rounds=None, syndromes=None,
                  final_round="faulty", weights=None):
@@ -388,25 +394,14 @@ class WideEvaluator(Counting):
         from . import _lib
         arr = (ctypes.c_uint32 * 2)(*seed)
         each = not isinstance(p_phys, float)
-        if is_correlated(weights):
-            triple, w_each = (weights, None) if isinstance(weights, tuple) else ((1, 1, 1), weights)
-            _lib.check(self.L.dq_wide_uf_run_correlated(self._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
-                                                        p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None,
-                                                        int(check_final_round(final_round)), *triple, _lib.ptr(w_each), _lib.ptr(hidden),
-                                                        _lib.ptr(trivial), _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
-                                                        _lib.ptr(syndromes), self._stream()))
-            return
-        if weights is not None:
-            pair, w_each = (weights, None) if isinstance(weights, tuple) else ((1, 1), weights)
-            _lib.check(self.L.dq_wide_uf_run_weighted(self._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
-                                                      p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None,
-                                                      int(check_final_round(final_round)), pair[0], pair[1], _lib.ptr(w_each), _lib.ptr(hidden),
-                                                      _lib.ptr(trivial), _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds),
-                                                      _lib.ptr(syndromes), self._stream()))
-            return
-        fn = self.L.dq_wide_uf_run_closed if check_final_round(final_round) else self.L.dq_wide_uf_run
+        suffix, w, w_each = weights_call(weights)
+        closed = check_final_round(final_round)
+        if suffix:
+            fn, mode = getattr(self.L, "dq_wide_uf_run" + suffix), (int(closed), *w, _lib.ptr(w_each))
+        else:
+            fn, mode = self.L.dq_wide_uf_run_closed if closed else self.L.dq_wide_uf_run, ()
         _lib.check(fn(self._h, m, T, commit, lattice_id & 0xFFFFFFFF, arr, 0.0 if each else p_phys, 0.0 if each else p_meas,
-                      p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, _lib.ptr(hidden), _lib.ptr(trivial),
+                      p_phys.ctypes.data if each else None, p_meas.ctypes.data if each else None, *mode, _lib.ptr(hidden), _lib.ptr(trivial),
                       _lib.ptr(frame), _lib.ptr(weight), _lib.ptr(n_defects), _lib.ptr(rounds), _lib.ptr(syndromes), self._stream()))
 
     def verdict_into(self, hidden, frame, m, out, referee=None, inexact=None):

@@ -562,11 +562,6 @@ class VectorEnv:
         if int(window) < int(self.volume_depth):
             raise ValueError(f"{who}: the evaluator's window {window} is below the environment's volume_depth {self.volume_depth}")
 
-    @staticmethod
-    def _is_triples(weights):
-        """Whether what _wide_uf_weights returned asks for the correlated launch: a triple, or a device tensor [n_envs, 3]."""
-        return len(weights) == 3 if isinstance(weights, tuple) else int(weights.shape[1]) == 3
-
     def _wide_uf_weights(self, weights, who, correlated=None):
         """weights= of uf_select_wide / guided_select_wide, validated before any library call (decoder_wide.check_weights; ValueError): None; a pair
         (w_space, w_time) of integers in 1 .. 15, returned as a tuple; an integer array [n_envs, 2] of such pairs (numpy or nested lists: uploaded per
@@ -631,15 +626,9 @@ class VectorEnv:
         self._check_outputs("uf_select_wide", (out, torch.int32))
         if out is None:
             out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
-        if weights is None:
-            check(self.L.dq_envb_uf_select(self._h, evaluator._h, ptr(out), self._stream()))
-            return out
-        if self._is_triples(weights):
-            triple, each = (weights, None) if isinstance(weights, tuple) else ((1, 1, 1), weights)
-            check(self.L.dq_envb_uf_select_correlated(self._h, evaluator._h, triple[0], triple[1], triple[2], ptr(each), ptr(out), self._stream()))
-            return out
-        pair, each = (weights, None) if isinstance(weights, tuple) else ((1, 1), weights)
-        check(self.L.dq_envb_uf_select_weighted(self._h, evaluator._h, pair[0], pair[1], ptr(each), ptr(out), self._stream()))
+        from .decoder_wide import weights_call
+        suffix, w, each = weights_call(weights)
+        check(getattr(self.L, "dq_envb_uf_select" + suffix)(self._h, evaluator._h, *w, *((ptr(each),) if suffix else ()), ptr(out), self._stream()))
         return out
 
     def guided_select_wide(self, evaluator, t, q=None, eps=1.0, guide_share=1.0, masked_greedy=False, out=None, out_guided=None, weights=None,
@@ -666,18 +655,10 @@ class VectorEnv:
         if out is None:
             out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
         seed = (ctypes.c_uint32 * 2)(*self.seed)
-        if weights is None:
-            check(self.L.dq_envb_guided_select_uf(self._h, evaluator._h, ptr(q), float(eps), float(guide_share), int(masked_greedy), seed, int(t), ptr(out),
-                                                  ptr(out_guided), self._stream()))
-            return out
-        if self._is_triples(weights):
-            triple, each = (weights, None) if isinstance(weights, tuple) else ((1, 1, 1), weights)
-            check(self.L.dq_envb_guided_select_uf_correlated(self._h, evaluator._h, ptr(q), float(eps), float(guide_share), int(masked_greedy), seed, int(t),
-                                                             triple[0], triple[1], triple[2], ptr(each), ptr(out), ptr(out_guided), self._stream()))
-            return out
-        pair, each = (weights, None) if isinstance(weights, tuple) else ((1, 1), weights)
-        check(self.L.dq_envb_guided_select_uf_weighted(self._h, evaluator._h, ptr(q), float(eps), float(guide_share), int(masked_greedy), seed, int(t),
-                                                       pair[0], pair[1], ptr(each), ptr(out), ptr(out_guided), self._stream()))
+        from .decoder_wide import weights_call
+        suffix, w, each = weights_call(weights)
+        check(getattr(self.L, "dq_envb_guided_select_uf" + suffix)(self._h, evaluator._h, ptr(q), float(eps), float(guide_share), int(masked_greedy), seed,
+                                                                   int(t), *w, *((ptr(each),) if suffix else ()), ptr(out), ptr(out_guided), self._stream()))
         return out
 
     # -- state views --------------------------------------------------------------------------------------
