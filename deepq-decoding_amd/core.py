@@ -59,6 +59,29 @@ def _ring_field(name):
     return property(lambda self: getattr(self.ring, name), lambda self, value: setattr(self.ring, name, value))
 
 
+# The shared ends of DQNCore's acting steps.  Plain functions of the core (`self`), not methods: they need its attributes only, and the tests drive
+# the acting steps on stand-in objects that carry those attributes without being a DQNCore.
+def _step_taken(self, cur, record_stats):
+    """The tail of every acting step.  The episode bookkeeping of the step that filled slot `cur` rides on the next update's TD launch
+    (dq_td_update_stats) when an update follows, else it is launched on its own; the ring moves on."""
+    self._stats_pending = (cur,) if record_stats else None
+    if record_stats and not self.defer_stats:
+        self._flush_stats()
+    self.ring.advance()
+    self.vector_steps += 1
+
+
+def _guided_head(self):
+    """The head of the two guided acting steps: the previous step's bookkeeping, the Q forward on the current observations, the flags buffer.
+    Returns (current slot, next slot, q, flags)."""
+    self._flush_stats()
+    cur, nxt = self.ring.cur, self.ring.next_slot()
+    q = self.net.forward_multi([self._obs_job(params=self.params, slot=cur, batch=self.N, out=self.q_act, packed=self.params_pk)])[0]
+    if self._guide_flags is None:
+        self._guide_flags = torch.zeros((2, self.N), dtype=torch.uint8, device=self.device)
+    return cur, nxt, q, self._guide_flags
+
+
 class DQNCore:
     def __init__(self, env, net, batch_size=32, memory_limit=50000, gamma=0.99, lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
                  target_model_update=10000, enable_double_dqn=True, seed=None, rank=0, world_size=1, process_group=None,
@@ -211,13 +234,7 @@ class DQNCore:
         if presample and r.filled_after() >= MIN_FILLED:
             sj = self._sample_job(self.updates + 1, r.next_slot(), r.filled_after())
         self._launch_env(self._env_step(q, eps, masked_greedy, sj))
-        # episode bookkeeping of this step: rides on the next update's TD launch (dq_td_update_stats) when an update follows, else
-        # launched on its own
-        self._stats_pending = (cur,) if record_stats else None
-        if record_stats and not self.defer_stats:
-            self._flush_stats()
-        r.advance()
-        self.vector_steps += 1
+        _step_taken(self, cur, record_stats)
 
     def guided_act_and_step(self, evaluator, eps, guide_share, masked_greedy=False, record_stats=True, method="matching"):
         """act_and_step() with a teacher: Q forward on the current observations, VectorEnv.guided_select -- an exploring lattice
@@ -227,13 +244,8 @@ class DQNCore:
         lattice.  method: the teacher, "matching" or "union_find" (VectorEnv.guided_select's).  One GPU, the narrow environment."""
         if self._wide or self.world_size > 1:
             raise NotImplementedError("guided_act_and_step: one GPU and the narrow environment (d <= 7)")
-        self._flush_stats()
+        cur, nxt, q, flags = _guided_head(self)
         r, env = self.ring, self.env
-        cur, nxt = r.cur, r.next_slot()
-        q = self.net.forward_multi([self._obs_job(params=self.params, slot=cur, batch=self.N, out=self.q_act, packed=self.params_pk)])[0]
-        if self._guide_flags is None:
-            self._guide_flags = torch.zeros((2, self.N), dtype=torch.uint8, device=self.device)
-        flags = self._guide_flags
         env.guided_select(evaluator, self.vector_steps, q=q, eps=eps, guide_share=guide_share, masked_greedy=masked_greedy, out=r.action[cur],
                           out_guided=flags[0], out_inexact=flags[1], method=method)
         self.guide_counts += flags.sum(dim=1)
@@ -241,11 +253,7 @@ class DQNCore:
             env.arm_patch_output(r.store[nxt])
         env._launch(self.L.dq_env_step, env._h, ptr(r.action[cur]), 1, None if r.compact else ptr(r.store[nxt]), ptr(r.reward[cur]), ptr(r.terminal[cur]),
                     ptr(env.legal), ptr(env.lifetime), ptr(env.was_reset), self._stream())
-        self._stats_pending = (cur,) if record_stats else None
-        if record_stats and not self.defer_stats:
-            self._flush_stats()
-        r.advance()
-        self.vector_steps += 1
+        _step_taken(self, cur, record_stats)
 
     def guided_act_and_step_wide(self, evaluator, eps, guide_share, masked_greedy=False, record_stats=True, weights=None, correlated=None):
         """guided_act_and_step() for the wide environment with the union-find teacher: Q forward on the current observations,
@@ -262,13 +270,8 @@ class DQNCore:
         kw = {} if weights is None else dict(weights=weights)
         if isinstance(weights, tuple) and len(weights) == 3:
             kw = dict(weights=weights[:2], correlated=weights[2])
-        self._flush_stats()
+        cur, nxt, q, flags = _guided_head(self)
         r, env = self.ring, self.env
-        cur, nxt = r.cur, r.next_slot()
-        q = self.net.forward_multi([self._obs_job(params=self.params, slot=cur, batch=self.N, out=self.q_act, packed=self.params_pk)])[0]
-        if self._guide_flags is None:
-            self._guide_flags = torch.zeros((2, self.N), dtype=torch.uint8, device=self.device)
-        flags = self._guide_flags
         env.guided_select_wide(evaluator, self.vector_steps, q=q, eps=eps, guide_share=guide_share, masked_greedy=masked_greedy, out=r.action[cur],
                                out_guided=flags[0], **kw)
         self.guide_counts[0] += flags[0].sum()
@@ -276,11 +279,7 @@ class DQNCore:
         check(self.L.dq_envb_step(env._h, ptr(r.action[cur]), 1, ptr(r.store[nxt]), ptr(r.reward[cur]), ptr(r.terminal[cur]), ptr(env.legal), ptr(env.lifetime),
                                   ptr(env.was_reset), ptr(env.inexact), self._stream()))
         self._inexact_acc += env.inexact.sum()                       # (read and reported at the next read_stats())
-        self._stats_pending = (cur,) if record_stats else None
-        if record_stats and not self.defer_stats:
-            self._flush_stats()
-        r.advance()
-        self.vector_steps += 1
+        _step_taken(self, cur, record_stats)
 
     def _sample_job(self, t, head, filled):
         """dq_sample_job for update number t, to be run on a ring with `head` / `filled`, into the look-ahead buffer (the update in

@@ -248,6 +248,82 @@ __device__ __forceinline__ int kth_set_bit128(u64 lo, u64 hi, int k) {
     return pos;
 }
 
+// ---- the action-selection rule (in numpy: decoder_wide.guided_actions_wide) -----------------------------------------------
+// Every acting path chooses a lattice's action by this rule, stated here once.  With w[0..3] the lattice's policy words (dq_policy_words) and
+// T = dq_rate_threshold:
+//   explore = q == NULL || w[1] < T(eps)                                                                       dq_explores
+//   explore:  the k-th (0-based, ascending) legal action, k = umulhi(w[0], n_legal); -1 for an empty set       dq_explore_action128 / dq_explore_action
+//   else:     the first maximum of the lattice's Q row -- the larger value, the lower index among equals --,   dq_row_first_max / dq_wave_first_max
+//             over the legal set when masked_greedy; 0x7fffffff ("no candidate") where that set is empty
+// (a guided kernel puts its teacher between the two: guided = explore && w[2] < T(guide_share)).  The callers differ in where the legal words live
+// (registers, LDS, global memory: a getter), in how many lanes share a row (16 or 64) and in what else they want to know of the row's values (a
+// functor); nothing below asks which caller it serves.  The two register-resident environment kernels (env_dev.h) keep a scan of their own over
+// prefetched Q values, combined by the same dq_row_argmax / dq_wave_argmax.
+// A row holding NaN: the combination rule is then not commutative, so the index depends on the exchange order; it is an index the scan accepted,
+// hence in range, and is otherwise undefined (the forward's range guard and decode_wide's finiteness flag report such rows).
+__device__ __forceinline__ void dq_policy_words(u64 t, u32 lattice_id, u32 seed0, u32 seed1, u32 (&w)[4]) {
+    philox4x32_10((u32)t, (u32)(t >> 32), lattice_id, (u32)DQ_STREAM_POLICY << 16, seed0, seed1, w);
+}
+__device__ __forceinline__ bool dq_explores(const float* q, u32 w1, u64 T_eps) { return q == nullptr || (u64)w1 < T_eps; }
+
+// the exploring lattice's action out of a two-word legal set ...
+__device__ __forceinline__ int dq_explore_action128(u64 lo, u64 hi, u32 w0) {
+    return kth_set_bit128(lo, hi, (int)__umulhi(w0, (u32)(__popcll(lo) + __popcll(hi))));
+}
+// ... and out of LW words, word(j) = word j of the set
+template <class Word>
+__device__ __forceinline__ int dq_explore_action(int LW, Word&& word, u32 w0) {
+    int n_legal = 0;
+    for (int j = 0; j < LW; ++j) n_legal += __popcll(word(j));
+    int k = (int)__umulhi(w0, (u32)n_legal);
+    for (int j = 0; j < LW; ++j) {
+        const u64 m = word(j);
+        const int c = __popcll(m);
+        if (k < c) return 64 * j + kth_set_bit128(m, 0, k);
+        k -= c;
+    }
+    return -1;
+}
+
+// Which actions the first maximum is taken over: all of them, or the legal set when masked_greedy.
+__device__ __forceinline__ auto dq_admit_all() { return [](int) { return true; }; }
+__device__ __forceinline__ auto dq_admit128(int masked_greedy, u64 lo, u64 hi) {
+    return [=](int k) { return !masked_greedy || (((k < 64 ? lo : hi) >> (k & 63)) & 1); };
+}
+template <class Word>
+__device__ __forceinline__ auto dq_admit_words(int masked_greedy, Word word) {
+    return [=](int k) { return !masked_greedy || ((word(k >> 6) >> (k & 63)) & 1); };
+}
+
+// One lane's part of a row: k = first, first + STRIDE, ...; a candidate is taken when it is admitted and is larger than the lane's best or the lane's
+// first.  see(v) gets every value the lane reads.  Then the lanes' results combined: within a row of 16 lanes (every lane of the row gets the index),
+// or over the wave (wave-uniform).
+struct DqSeeNothing { __device__ void operator()(float) const {} };
+template <int STRIDE, class Admit, class See>
+__device__ __forceinline__ void dq_scan_row(const float* __restrict__ row, int n_actions, int first, Admit&& admit, See&& see, float& best, int& best_a) {
+    best = -INFINITY; best_a = 0x7fffffff;
+    for (int k = first; k < n_actions; k += STRIDE) {
+        const bool ok = admit(k);
+        const float v = row[k];
+        see(v);
+        if (ok && (v > best || best_a == 0x7fffffff)) { best = v; best_a = k; }
+    }
+}
+template <class Admit, class See = DqSeeNothing>
+__device__ __forceinline__ int dq_row_first_max(const float* __restrict__ row, int n_actions, int sub, Admit&& admit, See&& see = See()) {
+    float best; int best_a;
+    dq_scan_row<16>(row, n_actions, sub, admit, see, best, best_a);
+    dq_row_argmax(best, best_a);
+    return best_a;
+}
+template <class Admit, class See = DqSeeNothing>
+__device__ __forceinline__ int dq_wave_first_max(const float* __restrict__ row, int n_actions, int lane, Admit&& admit, See&& see = See()) {
+    float best; int best_a;
+    dq_scan_row<64>(row, n_actions, lane, admit, see, best, best_a);
+    dq_wave_argmax(best, best_a);
+    return best_a;
+}
+
 // Replay row of minibatch sample `sample_id` of update t (shared by every launch that carries the sampling along).
 // Upstream keras-rl 0.4.2 SequentialMemory.sample (restated in oracle/memory_oracle.py): idx = sample_batch_indexes(window_length,
 // nb_entries - 1) + 1, i.e. idx in [2, nb_entries - 1] for window_length 1; the experience is (obs[idx-1], action[idx-1],

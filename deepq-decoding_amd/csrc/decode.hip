@@ -6,7 +6,7 @@
 // with an index gather over the active list) and three small launches of this file:
 //   decode_pack_kernel     once per call: grids -> observation rows (patch words or padded uint8 images), the legal set reset_legal_moves builds
 //                          from the summed volume (ENV:238-258), empty completed / acted masks, corrections = -1, the identity active list;
-//   decode_select_kernel   per iteration: first maximum of each active volume's Q row (policy.hip's rule with eps = 0, optionally over the legal
+//   decode_select_kernel   per iteration: first maximum of each active volume's Q row (common.h's rule with eps = 0, optionally over the legal
 //                          set), the step's bookkeeping (ENV:131, 185-201), the action-plane bit of the chosen action set in place, and the number
 //                          of volumes that go on per partition of DEC_PART positions;
 //   decode_compact_kernel  per iteration: the next active list, stable (a partition's offset is the sum of the counts before it, its volumes
@@ -153,22 +153,8 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_select_kernel(DecArgs a) {
     bool keep = false;
     if (valid) {
         DecState s = a.state[v];
-        // first maximum of the Q row, over the legal set when masked (policy.hip policy_kernel with eps = 0)
-        const float* row = a.q + (size_t)g * a.n_actions;
-        float best = -INFINITY;
-        int best_a = 0x7fffffff;
-        for (int k = sub; k < a.n_actions; k += 16) {
-            const bool ok = !a.masked || (((k < 64 ? s.legal0 : s.legal1) >> (k & 63)) & 1);
-            const float x = row[k];
-            if (ok && (x > best || best_a == 0x7fffffff)) { best = x; best_a = k; }
-        }
-#pragma unroll
-        for (int m = 8; m >= 1; m >>= 1) {
-            const float ov = __shfl_xor(best, m, 16);
-            const int oa = __shfl_xor(best_a, m, 16);
-            if (oa != 0x7fffffff && (best_a == 0x7fffffff || ov > best || (ov == best && oa < best_a))) { best = ov; best_a = oa; }
-        }
-        const int act = best_a;                                     // the same in all 16 lanes
+        // first maximum of the Q row, over the legal set when masked (common.h's rule with eps = 0); the same in all 16 lanes
+        const int act = dq_row_first_max(a.q + (size_t)g * a.n_actions, a.n_actions, sub, dq_admit128(a.masked, s.legal0, s.legal1));
         int st = DQ_DECODE_ACTIVE;
         if (act == a.identity) {
             st = DQ_DECODE_IDENTITY;

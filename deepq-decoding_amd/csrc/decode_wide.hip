@@ -8,7 +8,7 @@
 //   decode_wide_pack_kernel     once per call: the depth slices -> grid words (one ballot per 64 cells) in LDS and their OR; the legal set of
 //                               reset_legal_moves through the qubit -> grid-cell table; the padded row (depth + layers) (2d+1)^2 bytes in 16-byte stores,
 //                               the action planes zero; corrections = -1, the empty state, the identity active list;
-//   decode_wide_select_kernel   per iteration: first maximum of each active volume's Q row (dq_policy_select_wide's rule at eps = 0: the lowest index
+//   decode_wide_select_kernel   per iteration: first maximum of each active volume's Q row (common.h's rule at eps = 0: the lowest index
 //                               among equal maxima, over the legal words when masked), the step's bookkeeping, the one action-plane byte set in place, the
 //                               per-partition keep counts, and a sticky device word where a Q of the row is not finite;
 //   decode_wide_compact_kernel  decode_compact.h's rule, as in decode.hip.
@@ -171,26 +171,12 @@ __global__ __launch_bounds__(DW_THREADS) void decode_wide_select_kernel(WArgs a)
         u64* misc = a.misc + (size_t)v * (3 * DW_QW);
         if (lane < DW_QW) { acted = misc[lane]; fx = misc[DW_QW + lane]; fz = misc[2 * DW_QW + lane]; }
         int cnt = a.cnt[v];
-        // first maximum of the Q row, over the legal words when masked (policy.hip's rule with eps = 0)
-        const float* row = a.q + (size_t)g * a.n_actions;
-        float best = -INFINITY;
-        int best_a = 0x7fffffff;
+        // first maximum of the Q row, over the legal words when masked (common.h's rule with eps = 0; wave-uniform); word j of the set comes from lane j
         bool bad = false;
-#pragma unroll
-        for (int i = 0; i < DW_LW; ++i) {
-            if (i < a.LW) {
-                const u64 lw = wave_bcast64(legal, i);
-                const int k = 64 * i + lane;
-                if (k < a.n_actions) {
-                    const float x = row[k];
-                    bad |= !(fabsf(x) < INFINITY);                  // NaN fails the compare too
-                    const bool ok = !a.masked || ((lw >> lane) & 1);
-                    if (ok && (x > best || best_a == 0x7fffffff)) { best = x; best_a = k; }
-                }
-            }
-        }
-        dq_wave_argmax(best, best_a);                               // wave-uniform
-        int act = best_a, st = DQ_DECODE_ACTIVE;
+        int act = dq_wave_first_max(a.q + (size_t)g * a.n_actions, a.n_actions, lane,
+                                    dq_admit_words(a.masked, [=](int j) { return wave_bcast64(legal, __builtin_amdgcn_readfirstlane(j)); }),
+                                    [&](float x) { bad |= !(fabsf(x) < INFINITY); });                // NaN fails the compare too
+        int st = DQ_DECODE_ACTIVE;
         if ((unsigned)act >= (unsigned)a.n_actions) { bad = true; act = a.identity; }      // (no candidate: the identity is always one)
         if (act == a.identity) {
             st = DQ_DECODE_IDENTITY;

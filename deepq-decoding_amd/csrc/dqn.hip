@@ -35,18 +35,7 @@ __global__ void td_target_kernel(const float* __restrict__ q_online, const float
                                  const int32_t* __restrict__ index, float gamma, int B, int A, float* __restrict__ y) {
     const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= B) return;
-    const float* row = q_online + (size_t)b * A;
-    float best = -INFINITY;
-    int best_a = 0x7fffffff;
-    for (int a = lane; a < A; a += 64) {
-        const float v = row[a];
-        if (best_a == 0x7fffffff || v > best) { best = v; best_a = a; }
-    }
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ov = __shfl_xor(best, m);
-        const int oa = __shfl_xor(best_a, m);
-        if (oa != 0x7fffffff && (best_a == 0x7fffffff || ov > best || (ov == best && oa < best_a))) { best = ov; best_a = oa; }
-    }
+    const int best_a = dq_wave_first_max(q_online + (size_t)b * A, A, lane, dq_admit_all());       // common.h: the first maximum, as the policy takes it
     if (lane == 0) {
         const int r = index ? index[b] : b;
         const float qn = q_target[(size_t)b * A + best_a];
@@ -108,18 +97,7 @@ __global__ __launch_bounds__(256) void td_update_kernel(const float* __restrict_
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float loss = 0.f, mq = 0.f;
     for (int b = blockIdx.x * 4 + wave; b < B; b += td_blocks * 4) {
-        const float* row1 = q_online + (size_t)b * A;
-        float best = -INFINITY;
-        int best_a = 0x7fffffff;
-        for (int a = lane; a < A; a += 64) {
-            const float v = row1[a];
-            if (best_a == 0x7fffffff || v > best) { best = v; best_a = a; }
-        }
-        for (int m = 32; m >= 1; m >>= 1) {
-            const float ov = __shfl_xor(best, m);
-            const int oa = __shfl_xor(best_a, m);
-            if (oa != 0x7fffffff && (best_a == 0x7fffffff || ov > best || (ov == best && oa < best_a))) { best = ov; best_a = oa; }
-        }
+        const int best_a = dq_wave_first_max(q_online + (size_t)b * A, A, lane, dq_admit_all());
         const int r = index ? index[b] : b;
         const float yb = reward[r] + (terminal[r] ? 0.f : gamma * q_target[(size_t)b * A + best_a]);
         if (lane == 0 && y_out) y_out[b] = yb;

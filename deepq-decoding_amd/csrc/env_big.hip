@@ -49,7 +49,7 @@ struct BigParams {
     u32* lifetime;
     u8* was_reset;
     u8* inexact;                        // [n_envs] or NULL: 1 where the referee's fallback was used in this step
-    // fused action selection (the rule of policy.hip, one lattice per wave)
+    // fused action selection (common.h's rule, one lattice per wave)
     int policy;
     const float* q;
     u64 T_eps, pt;
@@ -110,39 +110,12 @@ __global__ __launch_bounds__(64 * BIG_EPB) void env_big_kernel(BigParams p) {
         for (int w = 0; w < W; ++w) { x[w] = 0; z[w] = 0; }
     }
     int a_sel = 0;
-    if (p.policy) {                                                  // EpsGreedyQPolicy / GreedyQPolicy(masked_greedy), see policy.hip
+    if (p.policy) {                                                  // EpsGreedyQPolicy / GreedyQPolicy(masked_greedy): common.h's rule
         u32 wd[4];
-        philox4x32_10((u32)p.pt, (u32)(p.pt >> 32), p.env_id_base + (u32)i, (u32)DQ_STREAM_POLICY << 16, p.pseed0, p.pseed1, wd);
-        if (p.q == nullptr || (u64)wd[1] < p.T_eps) {                // explore: k-th smallest legal action
-            int n_legal = 0;
-            for (int k = 0; k < LW; ++k) n_legal += __popcll(st[O_LEGAL + k]);
-            int kk = (int)__umulhi(wd[0], (u32)n_legal);
-            a_sel = -1;
-            for (int k = 0; k < LW && a_sel < 0; ++k) {
-                u64 m = st[O_LEGAL + k];
-                const int c = __popcll(m);
-                if (kk < c) {
-                    for (int t = 0; t < kk; ++t) m &= m - 1;
-                    a_sel = 64 * k + __ffsll((long long)m) - 1;
-                } else kk -= c;
-            }
-        } else {                                                     // first maximum of the Q row (optionally over the legal set)
-            const float* row = p.q + (size_t)i * p.n_actions;
-            float best = -INFINITY;
-            int best_a = 0x7fffffff;
-            for (int k = lane; k < p.n_actions; k += 64) {
-                const bool ok = !p.masked_greedy || ((st[O_LEGAL + (k >> 6)] >> (k & 63)) & 1);
-                const float v = row[k];
-                if (ok && (v > best || best_a == 0x7fffffff)) { best = v; best_a = k; }
-            }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const float ov = __shfl_xor(best, m);
-                const int oa = __shfl_xor(best_a, m);
-                if (oa != 0x7fffffff && (best_a == 0x7fffffff || ov > best || (ov == best && oa < best_a))) { best = ov; best_a = oa; }
-            }
-            a_sel = best_a;
-        }
+        dq_policy_words(p.pt, p.env_id_base + (u32)i, p.pseed0, p.pseed1, wd);
+        const auto legal = [&](int k) -> u64 { return st[O_LEGAL + k]; };                       // the record's legal words, in LDS
+        a_sel = dq_explores(p.q, wd[1], p.T_eps) ? dq_explore_action(LW, legal, wd[0])
+                                                 : dq_wave_first_max(p.q + (size_t)i * p.n_actions, p.n_actions, lane, dq_admit_words(p.masked_greedy, legal));
         a_sel = __builtin_amdgcn_readfirstlane(a_sel);
         if (lane == 0) p.action_out[i] = a_sel;
     }
@@ -340,7 +313,7 @@ __global__ void env_big_export_kernel(BigParams p, u64* out, int ew) {
     }
 }
 
-// wide action selection: the rule of dq_policy_select over LW-word legal sets, one lattice per wave
+// wide action selection: common.h's rule over LW-word legal sets in global memory, one lattice per wave
 __global__ __launch_bounds__(256) void policy_wide_kernel(const float* __restrict__ q, const u64* __restrict__ legal, int n, int n_actions, int LW,
                                                           u64 T_eps, int masked_greedy, u32 seed0, u32 seed1, u32 env_id_base, u64 t,
                                                           int32_t* __restrict__ action) {
@@ -348,37 +321,10 @@ __global__ __launch_bounds__(256) void policy_wide_kernel(const float* __restric
     if (i >= n) return;
     const u64* lg = legal + (size_t)i * LW;
     u32 w[4];
-    philox4x32_10((u32)t, (u32)(t >> 32), env_id_base + (u32)i, (u32)DQ_STREAM_POLICY << 16, seed0, seed1, w);
-    int a = -1;
-    if (q == nullptr || (u64)w[1] < T_eps) {
-        int n_legal = 0;
-        for (int k = 0; k < LW; ++k) n_legal += __popcll(lg[k]);
-        int kk = (int)__umulhi(w[0], (u32)n_legal);
-        for (int k = 0; k < LW && a < 0; ++k) {
-            u64 m = lg[k];
-            const int c = __popcll(m);
-            if (kk < c) {
-                for (int s = 0; s < kk; ++s) m &= m - 1;
-                a = 64 * k + __ffsll((long long)m) - 1;
-            } else kk -= c;
-        }
-    } else {
-        const float* row = q + (size_t)i * n_actions;
-        float best = -INFINITY;
-        int best_a = 0x7fffffff;
-        for (int k = lane; k < n_actions; k += 64) {
-            const bool ok = !masked_greedy || ((lg[k >> 6] >> (k & 63)) & 1);
-            const float v = row[k];
-            if (ok && (v > best || best_a == 0x7fffffff)) { best = v; best_a = k; }
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            const float ov = __shfl_xor(best, m);
-            const int oa = __shfl_xor(best_a, m);
-            if (oa != 0x7fffffff && (best_a == 0x7fffffff || ov > best || (ov == best && oa < best_a))) { best = ov; best_a = oa; }
-        }
-        a = best_a;
-    }
+    dq_policy_words(t, env_id_base + (u32)i, seed0, seed1, w);
+    const auto word = [=](int k) { return lg[k]; };
+    const int a = dq_explores(q, w[1], T_eps) ? dq_explore_action(LW, word, w[0])
+                                              : dq_wave_first_max(q + (size_t)i * n_actions, n_actions, lane, dq_admit_words(masked_greedy, word));
     if (lane == 0) action[i] = a;
 }
 

@@ -120,10 +120,10 @@ __global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfAr
     if ((int)blockIdx.x >= p.n_envs) return;                        // workgroup-uniform
     const u64* rec = p.state + i * p.sw;
     u32 w[4];                                                       // the words dq_policy_select_wide draws for the lattice, drawn by every thread
-    philox4x32_10((u32)p.t, (u32)(p.t >> 32), p.env_id_base + (u32)blockIdx.x, (u32)DQ_STREAM_POLICY << 16, p.seed0, p.seed1, w);
+    dq_policy_words(p.t, p.env_id_base + (u32)blockIdx.x, p.seed0, p.seed1, w);
     const u32 w0 = (u32)__builtin_amdgcn_readfirstlane((int)w[0]), w1 = (u32)__builtin_amdgcn_readfirstlane((int)w[1]);
     const u32 w2 = (u32)__builtin_amdgcn_readfirstlane((int)w[2]);
-    const bool explore = p.q == nullptr || (u64)w1 < p.T_eps;
+    const bool explore = dq_explores(p.q, w1, p.T_eps);
     const bool follow = explore && (u64)w2 < p.T_share;
     int32_t* out = p.action + i;
     u8* flag = p.guided ? p.guided + i : nullptr;
@@ -134,31 +134,9 @@ __global__ __launch_bounds__(UFW_THREADS) void env_wide_guided_uf_kernel(EnvUfAr
     } else {
         if (tid >= 64) return;                                      // one wave suffices, and no barrier follows
         const u64* lg = rec + 3 * p.W + 2 + p.LW;                   // the record's legal set: what the last reset / step also wrote to its legal_dev
-        if (explore) {                                              // policy_wide_kernel's rule
-            int n_legal = 0;
-            for (int k = 0; k < p.LW; ++k) n_legal += __popcll(lg[k]);
-            int kk = (int)__umulhi(w0, (u32)n_legal);
-            a = -1;
-            for (int k = 0; k < p.LW && a < 0; ++k) {
-                u64 m = lg[k];
-                const int c = __popcll(m);
-                if (kk < c) {
-                    for (int s = 0; s < kk; ++s) m &= m - 1;
-                    a = 64 * k + __ffsll((long long)m) - 1;
-                } else kk -= c;
-            }
-        } else {                                                    // larger value, the lower index among equals: independent of how many threads share the row
-            const float* row = p.q + i * p.n_actions;
-            float bv = -INFINITY;
-            int ba = EWU_NONE;
-            for (int k = tid; k < p.n_actions; k += 64) {
-                const bool ok = !p.masked_greedy || ((lg[k >> 6] >> (k & 63)) & 1);
-                const float v = row[k];
-                if (ok && (v > bv || ba == EWU_NONE)) { bv = v; ba = k; }
-            }
-            dq_wave_argmax(bv, ba);
-            a = __builtin_amdgcn_readfirstlane(ba);
-        }
+        const auto word = [=](int k) { return lg[k]; };
+        a = explore ? dq_explore_action(p.LW, word, w0)             // common.h's rule, as policy_wide_kernel applies it
+                    : __builtin_amdgcn_readfirstlane(dq_wave_first_max(p.q + i * p.n_actions, p.n_actions, tid, dq_admit_words(p.masked_greedy, word)));
     }
     if (tid == 0) {
         *out = a;

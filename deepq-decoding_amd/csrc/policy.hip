@@ -7,8 +7,8 @@
 // are either adjacent to violated stabilizer, or adjacent to previously acted on qubits") and
 // README.md:262 (masked_greedy: argmax restricted to the legal actions).
 //
-// 16 lanes cooperate on one lattice (4 lattices per wavefront): coalesced reads of the Q row, then a
-// 4-step butterfly over (value, index) keeping the first maximum like np.argmax.
+// The rule itself is common.h's ("the action-selection rule").  Here 16 lanes cooperate on one lattice (4 lattices per
+// wavefront): coalesced reads of the Q row, then the row's first maximum like np.argmax.
 #include "common.h"
 
 __global__ __launch_bounds__(256) void policy_kernel(const float* __restrict__ q, const u64* __restrict__ legal, int n,
@@ -19,29 +19,9 @@ __global__ __launch_bounds__(256) void policy_kernel(const float* __restrict__ q
     if (i >= n) return;          // whole 16-lane groups leave together
     const u64 lo = legal[2 * (size_t)i], hi = legal[2 * (size_t)i + 1];
     u32 w[4];
-    philox4x32_10((u32)t, (u32)(t >> 32), env_id_base + (u32)i, (u32)DQ_STREAM_POLICY << 16, seed0, seed1, w);
-    const bool explore = q == nullptr || (u64)w[1] < T_eps;
-    int a;
-    if (explore) {
-        const int n_legal = __popcll(lo) + __popcll(hi);
-        a = kth_set_bit128(lo, hi, (int)__umulhi(w[0], (u32)n_legal));
-    } else {
-        float best = -INFINITY;
-        int best_a = 0x7fffffff;
-        const float* row = q + (size_t)i * n_actions;
-        for (int k = sub; k < n_actions; k += 16) {
-            const bool ok = !masked_greedy || (((k < 64 ? lo : hi) >> (k & 63)) & 1);
-            const float v = row[k];
-            if (ok && (v > best || best_a == 0x7fffffff)) { best = v; best_a = k; }
-        }
-#pragma unroll
-        for (int m = 8; m >= 1; m >>= 1) {
-            const float ov = __shfl_xor(best, m, 16);
-            const int oa = __shfl_xor(best_a, m, 16);
-            if (oa != 0x7fffffff && (best_a == 0x7fffffff || ov > best || (ov == best && oa < best_a))) { best = ov; best_a = oa; }
-        }
-        a = best_a;
-    }
+    dq_policy_words(t, env_id_base + (u32)i, seed0, seed1, w);
+    const int a = dq_explores(q, w[1], T_eps) ? dq_explore_action128(lo, hi, w[0])
+                                              : dq_row_first_max(q + (size_t)i * n_actions, n_actions, sub, dq_admit128(masked_greedy, lo, hi));
     if (sub == 0) action[i] = a;
 }
 

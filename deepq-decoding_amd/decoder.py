@@ -729,40 +729,21 @@ def guided_actions(q, legal, teacher_actions, eps, guide_share, masked_greedy, s
         explore = q is None or w[1] < T(eps);    guided = explore and w[2] < T(guide_share)
         guided: the teacher's action;  else explore: the k-th (0-based, ascending) legal action, k = (w[0] * n_legal) >> 32 (-1 for an empty set);
         else: the first maximum of the Q row, over the legal set when masked_greedy.
-    Returns (actions int32 [n], guided_flags uint8 [n])."""
-    from . import _lib, _philox
+    Returns (actions int32 [n], guided_flags uint8 [n]).  The loop itself is decoder_wide.guided_actions_wide's, on the [n, 2] words: the rule is stated once."""
+    from .decoder_wide import guided_actions_wide
     for name, v in (("eps", eps), ("guide_share", guide_share)):
         if not 0.0 <= float(v) <= 1.0:
             raise ValueError(f"guided_actions: {name} must lie in [0, 1], not {v!r}")
-    words = np.ascontiguousarray(np.asarray(legal)).astype(np.int64, copy=False).view(np.uint64).reshape(-1, 2)
+    words = np.ascontiguousarray(np.asarray(legal)).astype(np.int64, copy=False).reshape(-1, 2)
     n = len(words)
     teacher = np.asarray(teacher_actions).reshape(-1)
     if len(teacher) != n:
         raise ValueError(f"guided_actions: {len(teacher)} teacher actions for {n} legal sets")
-    t = int(t)
-    ids = (int(env_id_base) + np.arange(n, dtype=np.uint64)) & np.uint64(0xFFFFFFFF)
-    w0, w1, w2, _ = _philox.philox4x32(t & 0xFFFFFFFF, t >> 32, ids, _lib.STREAM_POLICY << 16, seed)
-    explore = np.ones(n, dtype=bool) if q is None else w1.astype(np.uint64) < np.uint64(rate_threshold(eps))
-    guided = explore & (w2.astype(np.uint64) < np.uint64(rate_threshold(guide_share)))
     if q is not None:
         q = np.asarray(q, dtype=np.float32)
         if q.ndim != 2 or q.shape[0] != n or not 1 <= q.shape[1] <= 128:
             raise ValueError(f"guided_actions: q must have shape [{n}, num_actions <= 128], got {q.shape}")
-    actions = np.empty(n, dtype=np.int32)
-    for i in range(n):
-        if guided[i]:
-            actions[i] = teacher[i]
-            continue
-        mask = int(words[i, 0]) | int(words[i, 1]) << 64
-        if explore[i]:
-            members = [a for a in range(128) if (mask >> a) & 1]
-            k = (int(w0[i]) * len(members)) >> 32
-            actions[i] = members[k] if members else -1
-        else:
-            row = q[i]
-            cand = [a for a in range(len(row)) if not masked_greedy or (mask >> a) & 1]
-            actions[i] = max(cand, key=lambda a: (row[a], -a))                  # the larger value, the lower index among equals
-    return actions, guided.astype(np.uint8)
+    return guided_actions_wide(q, words, teacher, eps, guide_share, masked_greedy, seed, env_id_base, t)
 
 
 def check_match_policy_args(env, evaluator=None, chunk=DEFAULT_CHUNK):

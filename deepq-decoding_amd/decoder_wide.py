@@ -611,7 +611,10 @@ def completed_from_state(state_row, d, legal_words):
 def guided_actions_wide(q, legal_words, teacher, eps, guide_share, masked_greedy, seed, env_id_base, t):
     """decoder.guided_actions for legal sets of any number of 64-bit words: the rule of dq_envb_guided_select_uf in numpy.  legal_words: [n, LW] (VectorEnv.legal
     of the wide backend; bit a of the set = action a); teacher: int [n], what uf_select_wide emits for the lattices as they stand; the other arguments and
-    the result (actions int32 [n], guided flags uint8 [n]) are guided_actions'.  With two words it returns exactly what that function returns."""
+    the result (actions int32 [n], guided flags uint8 [n]) are guided_actions'.  This loop is the one numpy statement of the selection rule (DESIGN.md
+    section 28; on the device: csrc/common.h): decoder.guided_actions is this function on two words.  An empty legal set: an exploring lattice gets -1;
+    the first maximum over the legal set (masked_greedy) has no candidate -- the kernels then write the scan's "no candidate" index 0x7fffffff, this
+    function raises ValueError; no environment produces such a set (the identity is always legal)."""
     from . import _lib, _philox
     for name, v in (("eps", eps), ("guide_share", guide_share)):
         if not 0.0 <= float(v) <= 1.0:

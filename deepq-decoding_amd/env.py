@@ -520,6 +520,16 @@ class VectorEnv:
             if t is not None and not (t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (self.n_envs,)):
                 raise ValueError(f"{who}: outputs are contiguous device tensors of n_envs = {self.n_envs} entries (int32 actions, uint8 flags)")
 
+    def _check_policy_args(self, who, eps, guide_share, t, q):
+        """What guided_select and guided_select_wide require of eps, guide_share, the policy counter and q, before any library call."""
+        for name, v in (("eps", eps), ("guide_share", guide_share)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+                raise ValueError(f"{who}: {name} must be a number in [0, 1], not {v!r}")
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) or t < 0:
+            raise ValueError(f"{who}: the policy counter t must be a non-negative integer, not {t!r}")
+        if q is not None and not (q.dtype == torch.float32 and q.is_cuda and q.is_contiguous() and tuple(q.shape) == (self.n_envs, self.num_actions)):
+            raise ValueError(f"{who}: q is a contiguous float32 device tensor [{self.n_envs}, {self.num_actions}] or None")
+
     def guided_select(self, evaluator, t, q=None, eps=1.0, guide_share=1.0, masked_greedy=False, out=None, out_guided=None, out_inexact=None,
                       method="matching"):
         """Epsilon-greedy selection whose exploring lattices follow the matching decoder with probability guide_share (include/deepq_hip.h
@@ -532,13 +542,7 @@ class VectorEnv:
         union-find decoder (dq_env_guided_select_uf: match_select(method="union_find")'s action for a guided lattice; out_inexact all 0)."""
         self._check_method(method, "guided_select")
         self._check_matching(evaluator, "guided_select")
-        for name, v in (("eps", eps), ("guide_share", guide_share)):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
-                raise ValueError(f"guided_select: {name} must be a number in [0, 1], not {v!r}")
-        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) or t < 0:
-            raise ValueError(f"guided_select: the policy counter t must be a non-negative integer, not {t!r}")
-        if q is not None and not (q.dtype == torch.float32 and q.is_cuda and q.is_contiguous() and tuple(q.shape) == (self.n_envs, self.num_actions)):
-            raise ValueError(f"guided_select: q is a contiguous float32 device tensor [{self.n_envs}, {self.num_actions}] or None")
+        self._check_policy_args("guided_select", eps, guide_share, t, q)
         if out is None:
             out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
         self._check_outputs("guided_select", (out, torch.int32), (out_guided, torch.uint8), (out_inexact, torch.uint8))
@@ -644,13 +648,7 @@ class VectorEnv:
         if weights is not None or correlated is not None:
             weights = self._wide_uf_weights(weights, "guided_select_wide", correlated)
         self._check_wide_uf(evaluator, "guided_select_wide")
-        for name, v in (("eps", eps), ("guide_share", guide_share)):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
-                raise ValueError(f"guided_select_wide: {name} must be a number in [0, 1], not {v!r}")
-        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) or t < 0:
-            raise ValueError(f"guided_select_wide: the policy counter t must be a non-negative integer, not {t!r}")
-        if q is not None and not (q.dtype == torch.float32 and q.is_cuda and q.is_contiguous() and tuple(q.shape) == (self.n_envs, self.num_actions)):
-            raise ValueError(f"guided_select_wide: q is a contiguous float32 device tensor [{self.n_envs}, {self.num_actions}] or None")
+        self._check_policy_args("guided_select_wide", eps, guide_share, t, q)
         self._check_outputs("guided_select_wide", (out, torch.int32), (out_guided, torch.uint8))
         if out is None:
             out = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
