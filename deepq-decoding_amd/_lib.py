@@ -139,6 +139,7 @@ SIGNATURES = {
     "dq_envb_destroy": (None, [_vp]),
     "dq_envb_get_info": (_i, [_vp, ctypes.POINTER(EnvInfo), ctypes.POINTER(_i)]),
     "dq_envb_set_rates": (_i, [_vp, _dbl, _dbl]),
+    "dq_envb_set_referee": (_i, [_vp, _i]),
     "dq_envb_set_rates_per_lattice": (_i, [_vp, _vp, _vp, _i, _vp]),
     "dq_envb_reset": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_envb_step": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -213,6 +214,8 @@ SIGNATURES = {
     "dq_wide_uf_run": (_i, [_vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_verdict": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "dq_wide_uf_verdict_refereed": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "dq_wide_uf_verdict_refereed_uf": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "dq_uf_referee_decode": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "dq_wide_uf_decode_closed": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_run_closed": (_i, [_vp, _i, _i, _i, _u32, _seedp, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dq_wide_uf_decode_weighted": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

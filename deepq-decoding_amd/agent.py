@@ -553,7 +553,8 @@ class DQNAgent:
         phases run / decode / verdict.  referee=None: no referee is consulted, alive := success, so death_rate equals failure_rate by construction.
         referee="matching": every verdict of the call -- the agent's row, the union-find row and no_decoder -- is the refereed one (DESIGN.md section
         22): alive is what the wide environment's step would decide on the residual, and EvalResult.inexact counts the volumes on which the referee's
-        flagged fallback fired.  Anything else is a ValueError.  With no_decoder the refereed verdict of the uncorrected errors is the slow part at
+        flagged fallback fired.  referee="uf": the same with the union-find referee, whose inexact is always 0.  Anything else is a
+        ValueError.  With no_decoder the refereed verdict of the uncorrected errors is the slow part at
         d >= 13 (decoder_wide.refereed_uncorrected_into: launches of at most 2048 volumes, 0.24 s each at d = 15, depth 5, p = 0.006): keep n_volumes
         modest there.  weights (with baseline="union_find" only, else ValueError): None, a pair (w_space, w_time) of integers in
         1 .. 15, or "rates" -- the union-find row is decoded on the weighted graph exactly as memory_experiment_wide(weights=...) decodes it, with

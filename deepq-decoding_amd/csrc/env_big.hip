@@ -7,11 +7,14 @@
 // 2^((d^2-1)/2) syndromes per component no longer exists.  At d <= 7 it reproduces env.hip bit for bit (the reference's golden traces are
 // replayed through both; tests/test_env_gpu.py).  Written for correctness first: the lattice record lives in LDS and is updated in place;
 // the headline configurations (d = 5, 7) keep env.hip's register-resident kernel.
+// The referee is a template flag of the kernel (dq_envb_set_referee): the matching decoder, or the union-find referee of uf_plane_dev.h.
 //
 // Record per lattice (uint64 words): x[W] z[W] acted[W] round meta(lifetime | done << 32) completed[LW] legal[LW] volume[depth][W].
 // Export (dq_envb_export_state): x[W] z[W] true_syndrome[W] summed[W] acted[W] round completed[LW] legal[LW] meta volume[depth][W].
 #include <new>
+#include <type_traits>
 #include "match_dev.h"
+#include "uf_plane_dev.h"
 #include "lattice_host.h"
 #include "env_big_view.h"
 
@@ -58,17 +61,29 @@ struct BigParams {
     int32_t* action_out;
 };
 
-static inline size_t big_wave_lds(int sw) { return (size_t)((sw * 8 + 15) & ~15) + DQ_MATCH_LDS; }
+// The union-find referee's launch takes the matching one's arguments with its two endpoint tables behind them; the matching kernels take
+// BigParams itself, so their argument block is what it was.
+struct BigParamsUf : BigParams {
+    UfPlane ux, uz;
+};
+template <int R>
+using BigParamsOf = std::conditional_t<R == DQ_REFEREE_UNION_FIND, BigParamsUf, BigParams>;
 
-template <int W>
-__global__ __launch_bounds__(64 * BIG_EPB) void env_big_kernel(BigParams p) {
+// a wave's LDS: its lattice record, then the referee's bytes -- DQ_MATCH_LDS (35 104) for the matching, UFP_LDS (1 520) for union-find
+static inline size_t big_wave_lds(int sw, int referee) {
+    return (size_t)((sw * 8 + 15) & ~15) + (referee == DQ_REFEREE_UNION_FIND ? UFP_LDS : DQ_MATCH_LDS);
+}
+
+// R: the referee of the step (include/deepq_hip.h DQ_REFEREE_*), a compile-time flag: the matching kernels carry no code of the union-find referee.
+template <int W, int R>
+__global__ __launch_bounds__(64 * BIG_EPB) void env_big_kernel(BigParamsOf<R> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x * BIG_EPB + wave;
     if (i >= p.n_envs) return;                                       // wave-uniform; no block-wide barrier below
-    const size_t wave_lds = (size_t)((p.sw * 8 + 15) & ~15) + DQ_MATCH_LDS;
+    const size_t wave_lds = (size_t)((p.sw * 8 + 15) & ~15) + (R == DQ_REFEREE_UNION_FIND ? UFP_LDS : DQ_MATCH_LDS);
     volatile u64* st = reinterpret_cast<volatile u64*>(smem + wave * wave_lds);
-    u8* s_match = smem + wave * wave_lds + ((p.sw * 8 + 15) & ~15);
+    u8* s_match = smem + wave * wave_lds + ((p.sw * 8 + 15) & ~15);     // the referee's bytes
     const int LW = p.LW, depth = p.depth;
     const int O_X = 0, O_Z = W, O_ACT = 2 * W, O_ROUND = 3 * W, O_META = 3 * W + 1, O_COMP = 3 * W + 2, O_LEGAL = O_COMP + LW, O_VOL = O_LEGAL + LW;
     u64* rec = p.state + (size_t)i * p.sw;
@@ -156,8 +171,14 @@ __global__ __launch_bounds__(64 * BIG_EPB) void env_big_kernel(BigParams p) {
                 }
                 df[comp][ww] = __ballot(bit);
             }
-        int dec = match_classify(p.mx, df[0][0], df[0][1], s_match, lane, &flag);
-        if (p.model != DQ_MODEL_X) dec += 2 * match_classify(p.mz, df[1][0], df[1][1], s_match, lane, &flag);
+        int dec;
+        if constexpr (R == DQ_REFEREE_UNION_FIND) {                  // no pool, no lock, no fallback: `flag` stays 0
+            dec = uf_plane_classify(p.ux, df[0][0], df[0][1], s_match, lane);
+            if (p.model != DQ_MODEL_X) dec += 2 * uf_plane_classify(p.uz, df[1][0], df[1][1], s_match, lane);
+        } else {
+            dec = match_classify(p.mx, df[0][0], df[0][1], s_match, lane, &flag);
+            if (p.model != DQ_MODEL_X) dec += 2 * match_classify(p.mz, df[1][0], df[1][1], s_match, lane, &flag);
+        }
         if (cls == 0 && any == 0) reward = 1.f;                      // ENV:148-149
         else if (dec != cls) done = 1;                               // ENV:150-151
         if (done_identity) {
@@ -344,7 +365,32 @@ struct dq_envb {
     BigTables tab;
     dq_match* match;
     u64* d_state;
+    int referee;                        // DQ_REFEREE_*: which instantiation of env_big_kernel the launches take (dq_envb_set_referee)
+    u8* d_ends;                         // [2][2][256] the union-find referee's endpoint tables (lattice_host.h lattice_uf_ends); NULL until it is first chosen
 };
+
+// The one map from (W, referee) to a kernel instantiation: f(kernel) gets the __global__ function, whose argument is BigParams for the matching referee and
+// BigParamsUf for union-find.  The launches and dq_envb_create's LDS limits both go through it.
+template <class F>
+static void big_kernel(int W, int referee, F&& f) {
+    if (referee == DQ_REFEREE_UNION_FIND) {
+        constexpr int R = DQ_REFEREE_UNION_FIND;
+        switch (W) {
+            case 1: f(env_big_kernel<1, R>); break;
+            case 2: f(env_big_kernel<2, R>); break;
+            case 3: f(env_big_kernel<3, R>); break;
+            default: f(env_big_kernel<4, R>); break;
+        }
+    } else {
+        constexpr int R = DQ_REFEREE_MATCHING;
+        switch (W) {
+            case 1: f(env_big_kernel<1, R>); break;
+            case 2: f(env_big_kernel<2, R>); break;
+            case 3: f(env_big_kernel<3, R>); break;
+            default: f(env_big_kernel<4, R>); break;
+        }
+    }
+}
 
 template <typename T>
 static size_t blob_put(std::vector<u8>& blob, const std::vector<T>& v) {
@@ -361,6 +407,7 @@ void dq_envb_destroy(dq_envb* E) {
     if (E->d_blob) (void)hipFree(E->d_blob);
     if (E->d_state) (void)hipFree(E->d_state);
     if (E->match) dq_match_destroy(E->match);
+    if (E->d_ends) (void)hipFree(E->d_ends);
     dq_rate_table_free(E->rate_tab);
     delete E;
 }
@@ -377,6 +424,7 @@ dq_status dq_envb_create(const dq_env_cfg* cfg, dq_envb** out) {
     dq_envb* E = new (std::nothrow) dq_envb();
     DQ_REQUIRE(E, DQ_ERR_NOMEM, "out of host memory");
     E->cfg = *cfg; E->d_blob = nullptr; E->d_state = nullptr; E->match = nullptr; E->rates_set = false; E->per_lattice = false;
+    E->referee = DQ_REFEREE_MATCHING; E->d_ends = nullptr;
     const int d = cfg->d, d2 = d * d, n = 2 * d + 1;
     const int layers = cfg->error_model == DQ_MODEL_X ? 1 : (cfg->use_Y ? 3 : 2);             // ENV:55-65
     E->info.n_action_layers = layers;
@@ -438,10 +486,11 @@ dq_status dq_envb_create(const dq_env_cfg* cfg, dq_envb** out) {
     static unsigned long long attr_devs = 0;                          // per device (common.h dq_device_bit)
     const unsigned long long dev_bit = dq_device_bit();
     if (!(attr_devs & dev_bit)) {
-        hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(env_big_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (ae == hipSuccess) ae = hipFuncSetAttribute(reinterpret_cast<const void*>(env_big_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (ae == hipSuccess) ae = hipFuncSetAttribute(reinterpret_cast<const void*>(env_big_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (ae == hipSuccess) ae = hipFuncSetAttribute(reinterpret_cast<const void*>(env_big_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t ae = hipSuccess;                                     // every (W, referee): what can be launched has its LDS limit raised
+        for (int k = 0; k < 8; ++k)
+            big_kernel(1 + (k & 3), k >> 2, [&](auto* kernel) {
+                if (ae == hipSuccess) ae = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            });
         if (ae != hipSuccess) {
             dq_set_error("dq_envb_create: hipFuncSetAttribute: %s", hipGetErrorString(ae));
             dq_envb_destroy(E);                                         // (frees the tables and the matching referee)
@@ -470,6 +519,27 @@ dq_status dq_envb_set_rates(dq_envb* E, double p_phys, double p_meas) {
     return DQ_OK;
 }
 
+dq_status dq_envb_set_referee(dq_envb* E, int kind) {
+    DQ_REQUIRE(E, DQ_ERR_INVALID, "dq_envb_set_referee: null handle");
+    DQ_REQUIRE(kind == DQ_REFEREE_MATCHING || kind == DQ_REFEREE_UNION_FIND, DQ_ERR_INVALID, "dq_envb_set_referee: kind = %d is no DQ_REFEREE_*", kind);
+    if (kind == DQ_REFEREE_UNION_FIND && !E->d_ends) {                // the handle's own copy of the endpoint tables, built once
+        LatticeHost L;
+        lattice_build(E->cfg.d, &L);
+        std::vector<u8> ends;
+        lattice_uf_ends(L, &ends);
+        hipError_t e = hipMalloc(&E->d_ends, ends.size());
+        if (e == hipSuccess) e = hipMemcpy(E->d_ends, ends.data(), ends.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (E->d_ends) { (void)hipFree(E->d_ends); E->d_ends = nullptr; }
+            dq_set_error("dq_envb_set_referee: table allocation / upload: %s", hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? DQ_ERR_NOMEM : DQ_ERR_HIP;
+        }
+    }
+    E->referee = kind;
+    return DQ_OK;
+}
+
 dq_status dq_envb_set_rates_per_lattice(dq_envb* E, const double* p_phys, const double* p_meas, int n, void* stream) {
     DQ_REQUIRE(E, DQ_ERR_INVALID, "dq_envb_set_rates_per_lattice: null handle");
     DQ_REQUIRE(n == E->cfg.n_envs, DQ_ERR_INVALID, "dq_envb_set_rates_per_lattice: n=%d, the handle has %d lattices", n, E->cfg.n_envs);
@@ -492,7 +562,7 @@ dq_status envb_state_view(const dq_envb* E, EnvbStateView* v) {
     return DQ_OK;
 }
 
-static dq_status big_fill(dq_envb* E, BigParams& p) {
+static dq_status big_fill(dq_envb* E, BigParamsUf& p) {
     DQ_REQUIRE(E, DQ_ERR_INVALID, "null environment");
     DQ_REQUIRE(E->rates_set, DQ_ERR_STATE, "dq_envb_set_rates has not been called");
     memset(&p, 0, sizeof(p));
@@ -507,21 +577,22 @@ static dq_status big_fill(dq_envb* E, BigParams& p) {
     p.env_id_base = E->cfg.env_id_base; p.seed0 = E->cfg.seed[0]; p.seed1 = E->cfg.seed[1];
     p.T_phys = E->T_phys; p.T_meas = E->T_meas;
     p.T_lat = E->per_lattice ? E->rate_tab.dev : nullptr;
+    if (E->referee == DQ_REFEREE_UNION_FIND) {                        // (set only together with its tables: dq_envb_set_referee)
+        const int n = (p.d2 - 1) / 2;
+        p.ux = UfPlane{E->d_ends, E->d_ends + 256, n, E->cfg.d, 0};
+        p.uz = UfPlane{E->d_ends + 512, E->d_ends + 768, n, E->cfg.d, 1};
+    }
     return DQ_OK;
 }
 
-static dq_status big_launch(dq_envb* E, const BigParams& p, hipStream_t st) {
+// (a matching kernel takes the BigParams part of `p`)
+static dq_status big_launch(dq_envb* E, const BigParamsUf& p, hipStream_t st) {
     const int blocks = (p.n_envs + BIG_EPB - 1) / BIG_EPB;
-    const size_t lds = BIG_EPB * big_wave_lds(p.sw);
+    const size_t lds = BIG_EPB * big_wave_lds(p.sw, E->referee);
     DQ_REQUIRE(lds <= 160 * 1024, DQ_ERR_UNSUPPORTED, "lattice record too large for LDS");
-    { const dq_status rc = match_reset_locks(E->match, st); if (rc != DQ_OK) return rc; }
+    if (E->referee == DQ_REFEREE_MATCHING) { const dq_status rc = match_reset_locks(E->match, st); if (rc != DQ_OK) return rc; }
     dq_prof_begin(DQ_K_ENV, st);
-    switch (E->W) {
-        case 1: env_big_kernel<1><<<blocks, 64 * BIG_EPB, lds, st>>>(p); break;
-        case 2: env_big_kernel<2><<<blocks, 64 * BIG_EPB, lds, st>>>(p); break;
-        case 3: env_big_kernel<3><<<blocks, 64 * BIG_EPB, lds, st>>>(p); break;
-        default: env_big_kernel<4><<<blocks, 64 * BIG_EPB, lds, st>>>(p); break;
-    }
+    big_kernel(E->W, E->referee, [&](auto* kernel) { kernel<<<blocks, 64 * BIG_EPB, lds, st>>>(p); });
     dq_prof_end(DQ_K_ENV, st);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
@@ -530,7 +601,7 @@ static dq_status big_launch(dq_envb* E, const BigParams& p, hipStream_t st) {
 extern "C" {
 
 dq_status dq_envb_reset(dq_envb* E, const uint8_t* which_dev, uint8_t* obs_dev, uint64_t* legal_dev, uint32_t* lifetime_dev, void* stream) {
-    BigParams p;
+    BigParamsUf p;
     const dq_status s = big_fill(E, p);
     if (s != DQ_OK) return s;
     p.mode = 0; p.which = which_dev; p.obs = obs_dev; p.legal = legal_dev; p.lifetime = lifetime_dev;
@@ -539,7 +610,7 @@ dq_status dq_envb_reset(dq_envb* E, const uint8_t* which_dev, uint8_t* obs_dev, 
 
 dq_status dq_envb_step(dq_envb* E, const int32_t* action_dev, int auto_reset, uint8_t* obs_dev, float* reward_dev, uint8_t* done_dev,
                        uint64_t* legal_dev, uint32_t* lifetime_dev, uint8_t* was_reset_dev, uint8_t* inexact_dev, void* stream) {
-    BigParams p;
+    BigParamsUf p;
     const dq_status s = big_fill(E, p);
     if (s != DQ_OK) return s;
     DQ_REQUIRE(action_dev, DQ_ERR_INVALID, "dq_envb_step: null action");
@@ -551,7 +622,7 @@ dq_status dq_envb_step(dq_envb* E, const int32_t* action_dev, int auto_reset, ui
 dq_status dq_envb_act_step(dq_envb* E, const float* q_dev, double eps, int masked_greedy, const uint32_t seed[2], uint64_t t,
                            int32_t* action_dev, int auto_reset, uint8_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint64_t* legal_dev,
                            uint32_t* lifetime_dev, uint8_t* was_reset_dev, uint8_t* inexact_dev, void* stream) {
-    BigParams p;
+    BigParamsUf p;
     const dq_status s = big_fill(E, p);
     if (s != DQ_OK) return s;
     DQ_REQUIRE(action_dev && seed, DQ_ERR_INVALID, "dq_envb_act_step: null argument");
@@ -564,7 +635,7 @@ dq_status dq_envb_act_step(dq_envb* E, const float* q_dev, double eps, int maske
 }
 
 dq_status dq_envb_export_state(dq_envb* E, uint64_t* state_dev, void* stream) {
-    BigParams p;
+    BigParamsUf p;
     const dq_status s = big_fill(E, p);
     if (s != DQ_OK) return s;
     DQ_REQUIRE(state_dev, DQ_ERR_INVALID, "dq_envb_export_state: null argument");

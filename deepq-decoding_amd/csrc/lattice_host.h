@@ -102,6 +102,19 @@ static inline void lattice_match_tables(const LatticeHost& L, int comp, std::vec
     *w10 = best;
 }
 
+// Union-find endpoint tables of both components, u8 [2][2][256]: ends [512 c + q] / [512 c + 256 + q] = the first / second plaquette of component c that
+// qubit q touches, as its node index (ref_bit), 255: none -- the qubit's space edge goes to the boundary (uf_wide_dev.h UfwComp, uf_plane_dev.h UfPlane).
+static inline void lattice_uf_ends(const LatticeHost& L, std::vector<u8>* ends) {
+    ends->assign(1024, 255);
+    for (int c = 0; c < 2; ++c) {
+        const int typ = c == 0 ? 3 : 1;
+        for (int q = 0; q < L.d2; ++q) {                              // the qubit's plaquettes of the component, as match_st_tables walks them
+            int ne = 0;
+            for (int s : L.qubit_stabs[q]) if (L.stab_type[s] == typ && ne < 2) (*ends)[512 * c + 256 * ne++ + q] = (u8)L.ref_bit[s];
+        }
+    }
+}
+
 // One shortest path per entry of lattice_match_tables, as the set of its data qubits (bit q = qubit x * d + y; d^2 <= 64): path [n][n][2] for
 // dist, pathB [n][2] for distB -- the same breadth-first search over (node, class) with the parent of every state kept.  A path that passes a qubit twice
 // drops it (XOR): the set still has the path's end points and class.  Entries without a path (dist 255) stay 0.  For csrc/match_st.hip.

@@ -337,19 +337,15 @@ dq_status dq_wide_uf_create(int d, int error_model, int window, int max_streams,
     DQ_REQUIRE((int)Lh.typed[0].size() == n && (int)Lh.typed[1].size() == n && n <= UFW_NODE_SLOTS && G <= UFW_THREADS, DQ_ERR_UNSUPPORTED,
                "dq_wide_uf_create: d = %d: the lattice does not fit a workgroup of %d threads", d, UFW_THREADS);
     const size_t o_ends = 0, o_cell = 1024, o_nstab = o_cell + 256, o_cstab = o_nstab + 256, o_sq = o_cstab + 256, o_isx = o_sq + 1024, bytes = o_isx + 256;
-    std::vector<u8> host(bytes, 255);
-    for (int c = 0; c < 2; ++c) {
-        const int typ = c == 0 ? 3 : 1;
+    std::vector<u8> host(bytes, 255), ends;
+    lattice_uf_ends(Lh, &ends);
+    memcpy(host.data() + o_ends, ends.data(), ends.size());
+    for (int c = 0; c < 2; ++c)
         for (int j = 0; j < n; ++j) {
             const int s = Lh.typed[c][j];
             host[o_cell + UFW_NODE_SLOTS * c + j] = (u8)(Lh.sa[s] * (d + 1) + Lh.sb[s]);
             host[o_nstab + UFW_NODE_SLOTS * c + j] = (u8)s;
         }
-        for (int q = 0; q < d2; ++q) {                                // the qubit's plaquettes of the component, as match_st_tables walks them
-            int ne = 0;
-            for (int s : Lh.qubit_stabs[q]) if (Lh.stab_type[s] == typ && ne < 2) host[o_ends + 512 * c + 256 * ne++ + q] = (u8)Lh.ref_bit[s];
-        }
-    }
     for (int cidx = 0; cidx < G; ++cidx) if (Lh.index[cidx] >= 0) host[o_cstab + cidx] = (u8)Lh.index[cidx];
     for (int s = 0; s < ns; ++s) {
         DQ_REQUIRE(Lh.stab_qubits[s].size() <= 4, DQ_ERR_UNSUPPORTED, "dq_wide_uf_create: a stabilizer of more than four qubits");

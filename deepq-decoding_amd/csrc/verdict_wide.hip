@@ -6,8 +6,11 @@
 //                                  component are ballots of node lane + 64 ww's parity, in the look-up referee's index order (lattice_host.h `typed`); a
 //                                  residual in the code space leaves before the matching's LDS is touched (wave-uniform; the referee gives class 0 to the
 //                                  empty syndrome, so decoded = 0 is exact)
+// verdict_wide_refereed_kernel<true> (dq_wide_uf_verdict_refereed_uf) is the same kernel with the union-find referee (uf_plane_dev.h) in
+// the matching's place: UFP_LDS bytes of dynamic LDS, no referee handle, no flags.  The flag is compile-time: the matching kernel carries no code of the other.
 // verdict_wide_kernel (uf_wide.hip) stays the unrefereed form: in_code and cls here are its definitions bit for bit.
 #include "match_dev.h"
+#include "uf_plane_dev.h"
 #include "uf_wide.h"
 
 #define VW_WORDS 4                                               // ceil(15^2 / 64) words per plane
@@ -36,7 +39,15 @@ static __device__ __forceinline__ int plane_bit(const u64 (&w)[VW_WORDS], int q)
     return (int)((word >> (q & 63)) & 1);
 }
 
-__global__ __launch_bounds__(64) void verdict_wide_refereed_kernel(VerdictRefArgs p) {
+// The union-find launch takes the matching one's arguments with its two endpoint tables behind them.
+struct VerdictRefArgsUf : VerdictRefArgs {
+    UfPlane ux, uz;
+};
+template <bool Uf>
+using VerdictRefArgsOf = std::conditional_t<Uf, VerdictRefArgsUf, VerdictRefArgs>;
+
+template <bool Uf>
+__global__ __launch_bounds__(64) void verdict_wide_refereed_kernel(VerdictRefArgsOf<Uf> p) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     const int i = blockIdx.x, lane = threadIdx.x;
     if (i >= p.n_streams) return;                                   // wave-uniform
@@ -88,17 +99,41 @@ __global__ __launch_bounds__(64) void verdict_wide_refereed_kernel(VerdictRefArg
         return;
     }
     int flag = 0;
-    int dec = match_classify(p.mx, df[0][0], df[0][1], smem, lane, &flag);
-    if (p.model != DQ_MODEL_X) dec += 2 * match_classify(p.mz, df[1][0], df[1][1], smem, lane, &flag);
+    int dec;
+    if constexpr (Uf) {
+        dec = uf_plane_classify(p.ux, df[0][0], df[0][1], smem, lane);
+        if (p.model != DQ_MODEL_X) dec += 2 * uf_plane_classify(p.uz, df[1][0], df[1][1], smem, lane);
+    } else {
+        dec = match_classify(p.mx, df[0][0], df[0][1], smem, lane, &flag);
+        if (p.model != DQ_MODEL_X) dec += 2 * match_classify(p.mz, df[1][0], df[1][1], smem, lane, &flag);
+    }
     if (lane == 0) {
         *out = (u8)((cls << DQ_VERDICT_CLASS_SHIFT) | (dec == cls ? DQ_VERDICT_ALIVE : 0) | ((dec & 3) << DQ_VERDICT_DECODED_SHIFT));
         if (flag_out) *flag_out = (u8)flag;
     }
 }
 
+static void verdict_ref_args(const dq_wide_uf* H, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev, VerdictRefArgs* a) {
+    a->node_stab = H->node_stab; a->stab_q = H->stab_q; a->n_streams = n; a->d = H->d; a->d2 = H->d2; a->model = H->model;
+    a->hidden = hidden_dev; a->frame = frame_dev; a->verdict = verdict_dev;
+}
+
 }  // namespace
 
 extern "C" {
+
+dq_status dq_wide_uf_verdict_refereed_uf(dq_wide_uf* H, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev, void* stream) {
+    DQ_REQUIRE(H && hidden_dev && verdict_dev, DQ_ERR_INVALID, "dq_wide_uf_verdict_refereed_uf: null argument");
+    DQ_REQUIRE(n >= 1 && n <= H->max_streams, DQ_ERR_INVALID, "dq_wide_uf_verdict_refereed_uf: n = %d outside 1..max_streams %d", n, H->max_streams);
+    VerdictRefArgsUf a;
+    memset(&a, 0, sizeof(a));
+    verdict_ref_args(H, hidden_dev, frame_dev, n, verdict_dev, &a);
+    a.ux = UfPlane{H->ends, H->ends + 256, H->n, H->d, 0};
+    a.uz = UfPlane{H->ends + 512, H->ends + 768, H->n, H->d, 1};
+    verdict_wide_refereed_kernel<true><<<n, 64, UFP_LDS, (hipStream_t)stream>>>(a);
+    DQ_LAUNCH_CHECK();
+    return DQ_OK;
+}
 
 dq_status dq_wide_uf_verdict_refereed(dq_wide_uf* H, const dq_match* M, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev,
                                       uint8_t* inexact_dev, void* stream) {
@@ -112,7 +147,7 @@ dq_status dq_wide_uf_verdict_refereed(dq_wide_uf* H, const dq_match* M, const ui
     static unsigned long long attr_devs = 0;                          // per device (common.h dq_device_bit)
     const unsigned long long dev_bit = dq_device_bit();
     if (!(attr_devs & dev_bit)) {
-        const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(verdict_wide_refereed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DQ_MATCH_LDS);
+        const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(verdict_wide_refereed_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, DQ_MATCH_LDS);
         if (ae != hipSuccess) {
             (void)hipGetLastError();
             dq_set_error("dq_wide_uf_verdict_refereed: hipFuncSetAttribute: %s", hipGetErrorString(ae));
@@ -124,10 +159,10 @@ dq_status dq_wide_uf_verdict_refereed(dq_wide_uf* H, const dq_match* M, const ui
     memset(&a, 0, sizeof(a));
     match_comp(M, 0, &a.mx);
     match_comp(M, 1, &a.mz);
-    a.node_stab = H->node_stab; a.stab_q = H->stab_q; a.n_streams = n; a.d = H->d; a.d2 = H->d2; a.model = H->model;
-    a.hidden = hidden_dev; a.frame = frame_dev; a.verdict = verdict_dev; a.inexact = inexact_dev;
+    verdict_ref_args(H, hidden_dev, frame_dev, n, verdict_dev, &a);
+    a.inexact = inexact_dev;
     { const dq_status rc = match_reset_locks(M, st); if (rc != DQ_OK) return rc; }
-    verdict_wide_refereed_kernel<<<n, 64, DQ_MATCH_LDS, st>>>(a);
+    verdict_wide_refereed_kernel<false><<<n, 64, DQ_MATCH_LDS, st>>>(a);
     DQ_LAUNCH_CHECK();
     return DQ_OK;
 }

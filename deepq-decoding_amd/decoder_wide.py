@@ -5,7 +5,8 @@ The algorithm and the window schedule are section 17's; for d <= 7 and window <=
 (`WideEvaluator`) owns the lattice tables: no environment is needed.  By default no referee is consulted -- the verdict is "the residual is a stabilizer"
 (in the code space, trivial homology class), and EvalResult.death_rate then EQUALS failure_rate by construction and means nothing more.  referee="matching"
 (verdict_wide, memory_experiment_wide, DQNAgent.decode_benchmark_wide) sends the residual's true syndrome through the matching referee,
-as the wide environment's step does: death_rate is then the share of volumes on which the environment would have ended the episode.
+as the wide environment's step does: death_rate is then the share of volumes on which the environment would have ended the episode.  referee="uf"
+ asks the union-find referee instead, as VectorEnv(referee="uf")'s step does: no flags, and no launch that has to be sliced.
 
 weights= (stream_decode_wide, memory_experiment_wide) decodes on a weighted graph: an edge of weight w is full at growth 2 w, w_space
 for the space edges and w_time for the time edges, so that a misread stabilizer and a flipped qubit cost what their rates say (uf_weights).  None is the
@@ -61,11 +62,14 @@ def check_wide_schedule(d, rounds, window, commit):
     return int(rounds), int(window), int(commit)
 
 
+REFEREES = ("matching", "uf")
+
+
 def check_referee(referee):
-    """None (no referee: alive := success) or "matching" (the matching referee on the residual's true syndrome), else ValueError.  Returns whether a
-    referee is asked for."""
-    if referee is not None and not (isinstance(referee, str) and referee == "matching"):
-        raise ValueError(f"referee must be None or 'matching', not {referee!r}")
+    """None (no referee: alive := success), "matching" (the matching referee on the residual's true syndrome) or "uf" (the union-find referee on it;
+    DESIGN.md section 29), else ValueError.  Returns whether a referee is asked for."""
+    if referee is not None and not (isinstance(referee, str) and referee in REFEREES):
+        raise ValueError(f"referee must be None, 'matching' or 'uf', not {referee!r}")
     return referee is not None
 
 
@@ -406,12 +410,18 @@ class WideEvaluator(Counting):
 
     def verdict_into(self, hidden, frame, m, out, referee=None, inexact=None):
         """The verdict bytes of m <= chunk volumes (frame None: no correction).  referee=None: dq_wide_uf_verdict (alive := success, decoded 0);
-        referee="matching": dq_wide_uf_verdict_refereed, with inexact (uint8 [m] or None) receiving the referee's fallback flags."""
+        referee="matching": dq_wide_uf_verdict_refereed, with inexact (uint8 [m] or None) receiving the referee's fallback flags; referee="uf":
+        dq_wide_uf_verdict_refereed_uf, whose referee has no fallback: inexact (a tensor or None) is zeroed."""
         from . import _lib
         if not check_referee(referee):
             if inexact is not None:
                 raise ValueError("inexact flags come from the referee: give referee='matching'")
             _lib.check(self.L.dq_wide_uf_verdict(self._h, _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), self._stream()))
+            return
+        if referee == "uf":
+            _lib.check(self.L.dq_wide_uf_verdict_refereed_uf(self._h, _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), self._stream()))
+            if inexact is not None:
+                inexact[:m].zero_()
             return
         _lib.check(self.L.dq_wide_uf_verdict_refereed(self._h, self._referee(), _lib.ptr(hidden), _lib.ptr(frame), m, _lib.ptr(out), _lib.ptr(inexact),
                                                       self._stream()))
@@ -473,8 +483,8 @@ def verdict_wide(hidden, frame, d, error_model="DP", referee=None, chunk=DEFAULT
     frame: Pauli codes 0..3 [N, d, d], numpy or torch; frame=None: no correction).  referee=None: the bytes of dq_wide_uf_verdict (in code space, class,
     success; alive := success).  referee="matching": dq_decode_verdict's byte with the matching referee -- alive and the decoded class as the wide
     environment's step has them (X model: the referee is asked for component 0 only) -- and the result is (bytes, inexact uint8 [N]: 1 where a
-    flagged fallback of the referee fired).  evaluator: a WideEvaluator of this d (its error model and chunk are used and it stays open).  Device
-    tensors unless to_host."""
+    flagged fallback of the referee fired).  referee="uf": the same byte with the union-find referee, and the flags are all zero.
+    evaluator: a WideEvaluator of this d (its error model and chunk are used and it stays open).  Device tensors unless to_host."""
     import torch
     d, error_model, n, refereed, chunk = check_verdict_wide_args(hidden, frame, d, error_model, referee, chunk, evaluator)
     ev = WideEvaluator(d, error_model, 1, chunk=min(chunk, n)) if evaluator is None else evaluator
@@ -489,7 +499,7 @@ def verdict_wide(hidden, frame, d, error_model="DP", referee=None, chunk=DEFAULT
             for s in range(0, n, ev.chunk):
                 m = min(ev.chunk, n - s)
                 if refereed and frm is None:
-                    refereed_uncorrected_into(ev, hid[s:s + m], m, out[s:s + m], flags[s:s + m])
+                    refereed_uncorrected_into(ev, hid[s:s + m], m, out[s:s + m], flags[s:s + m], referee)
                 else:
                     ev.verdict_into(hid[s:s + m], None if frm is None else frm[s:s + m], m, out[s:s + m], referee=referee,
                                     inexact=flags[s:s + m] if refereed else None)
@@ -505,25 +515,25 @@ def verdict_wide(hidden, frame, d, error_model="DP", referee=None, chunk=DEFAULT
 UNCORRECTED_REFEREE_D, UNCORRECTED_REFEREE_SLICE = 13, 2048
 
 
-def refereed_uncorrected_into(ev, hidden, m, out, flags):
+def refereed_uncorrected_into(ev, hidden, m, out, flags, referee="matching"):
     """The refereed verdict of m volumes with NO correction (the no_decoder row).  Every error is then still on the lattice: nearly every volume reaches
     the referee, and at d >= 13 a few in a hundred hold a cluster of 15 .. 20 defects that walks 2^15 .. 2^20 subsets in one of the referee's eight
     scratch-pool slots.  Measured at d = 15: 2048 such volumes take 0.24 s in one launch, while one launch of 2^16 did not end within minutes (DESIGN.md
     section 22), and a launch cannot be interrupted.  So at d >= UNCORRECTED_REFEREE_D the volumes go in launches of at most UNCORRECTED_REFEREE_SLICE, the
-    size that was measured; the bytes and flags of a volume do not depend on the launch around it."""
-    step = UNCORRECTED_REFEREE_SLICE if ev.d >= UNCORRECTED_REFEREE_D else m
+    size that was measured; the bytes and flags of a volume do not depend on the launch around it.  referee="uf" has no such clusters: one launch."""
+    step = UNCORRECTED_REFEREE_SLICE if ev.d >= UNCORRECTED_REFEREE_D and referee == "matching" else m
     for s in range(0, m, step):
         k = min(step, m - s)
-        ev.verdict_into(hidden[s:s + k], None, k, out[s:s + k], referee="matching", inexact=flags[s:s + k])
+        ev.verdict_into(hidden[s:s + k], None, k, out[s:s + k], referee=referee, inexact=flags[s:s + k])
 
 
-def uncorrected_into(ev, hidden, m, out, flags=None):
+def uncorrected_into(ev, hidden, m, out, flags=None, referee="matching"):
     """The verdict of m volumes with no correction, as a scoring call's no_decoder row asks for it: unrefereed, or with `flags` (uint8 [m]) the refereed
-    one in its measured launches."""
+    one of `referee` in its measured launches."""
     if flags is None:
         ev.verdict_into(hidden, None, m, out)
     else:
-        refereed_uncorrected_into(ev, hidden, m, out, flags)
+        refereed_uncorrected_into(ev, hidden, m, out, flags, referee)
 
 
 def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, rates=None, p_phys=None, p_meas=None, seed=None, env_id_base=0,
@@ -537,7 +547,9 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
     EvalResult.no_decoder counts the verdict for frame = 0.  referee=None: no referee is consulted, alive := success, so death_rate equals failure_rate
     by construction.  referee="matching": every verdict of the call goes through dq_wide_uf_verdict_refereed -- alive is what the
     wide environment's step would decide on the residual, every other counter is unchanged, and EvalResult.inexact (of the no_decoder row too) counts
-    the volumes on which a flagged fallback of the referee fired.  With no_decoder the refereed verdict of the uncorrected errors is the slow part at
+    the volumes on which a flagged fallback of the referee fired.  referee="uf": the same through dq_wide_uf_verdict_refereed_uf, the
+    union-find referee of VectorEnv(referee="uf"); inexact is 0 and no launch is sliced.  With no_decoder the matching-refereed verdict of the uncorrected
+    errors is the slow part at
     d >= 13 (refereed_uncorrected_into: launches of at most 2048 volumes, 0.24 s each at d = 15, depth 5, p = 0.006, more at higher rates): keep
     n_runs modest there.
     timings: a dict that receives the wall seconds of the phases run / verdict.  evaluator: a WideEvaluator of this lattice and window.  return_streams:
@@ -577,7 +589,7 @@ def memory_experiment_wide(lattice, n_runs, rounds, window=None, commit=None, ra
 
         with torch.cuda.device(dev):
             results, streams = score_streams(ev, dev, n, T, ph, pm, blk, run, lambda hid, frame, m, out: ev.verdict_into(hid, frame, m, out, **ref_kw),
-                                             (lambda hid, m, out: uncorrected_into(ev, hid, m, out, flags)) if no_decoder else None, flags=flags,
+                                             (lambda hid, m, out: uncorrected_into(ev, hid, m, out, flags, referee or "matching")) if no_decoder else None, flags=flags,
                                              keep=return_streams, timings=timings)
     finally:
         if evaluator is None:
@@ -1018,8 +1030,9 @@ def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=No
                       timings=None, referee=None, weights=None, correlated=None):
     """The loop behind DQNAgent.decode_benchmark_wide for a validated request: per chunk ONE dq_wide_uf_run (T = window = commit = volume_depth, with
     syndromes) yields the agent's input, the hidden state and the union-find frame of the same volumes; then dq_decode_wide_run, dq_wide_uf_verdict
-    and dq_decode_count with the agent's status and correction count.  referee=None: no referee is consulted, alive := success; referee="matching":
-    the verdicts of all three rows (the agent's, the union-find baseline's, no_decoder's) go through dq_wide_uf_verdict_refereed and each row's
+    and dq_decode_count with the agent's status and correction count.  referee=None: no referee is consulted, alive := success; referee="matching" or
+    "uf" (the union-find referee; no flags): the verdicts of all three rows (the agent's, the union-find baseline's, no_decoder's)
+    go through the refereed verdict launch and each row's
     EvalResult.inexact counts its flagged volumes.  weights (validated: None, a pair or "rates"): the sampling launch is
     dq_wide_uf_run_weighted, as memory_experiment_wide's -- the volumes and the hidden state do not depend on the weights, only the union-find frame does, so
     the agent's row keeps its bits; the baseline's EvalResult of every block reports .weights.  correlated (validated: None, an integer or "rates";
@@ -1069,7 +1082,7 @@ def score_decode_wide(dec, params, n, ph, pm, seed, base, blk, keys, baseline=No
             return verd2[:m], triv[sl], uf_status[:m], corrected_cells(uf_frame[sl]), flags
 
         def uncorrected(m, sl):
-            uncorrected_into(ev, hid[sl], m, verd2[:m], flags)
+            uncorrected_into(ev, hid[sl], m, verd2[:m], flags, referee or "matching")
             return verd2[:m], triv[sl], None, None, flags
 
         with torch.cuda.device(dev):

@@ -150,13 +150,18 @@ def validate_rates(value, n_envs, name="rate"):
     return a
 
 
+WIDE_REFEREES = {"matching": 0, "uf": 1}                          # include/deepq_hip.h DQ_REFEREE_MATCHING / DQ_REFEREE_UNION_FIND
+
+
 class VectorEnv:
     """Batched environment: lattice i has global id ``env_id_base + i`` (its RNG stream)."""
 
     def __init__(self, d=5, p_phys=0.01, p_meas=0.01, error_model="DP", use_Y=True, volume_depth=3,
                  n_envs=1, seed=DEFAULT_SEED, env_id_base=0, device=None, referee="lut", backend="auto"):
         """backend: "auto" -- d <= 7: one 64-bit word per bit-plane, look-up referee (csrc/env.hip); d >= 9: the wide environment with the
-        matching referee (csrc/env_big.hip, include/deepq_hip.h dq_envb_*) --, or "wide" to force the latter at any d (tests)."""
+        matching referee (csrc/env_big.hip, include/deepq_hip.h dq_envb_*) --, or "wide" to force the latter at any d (tests).
+        referee="matching" or "uf" selects the wide backend at any d; "uf" is the union-find referee (dq_envb_set_referee): the closed
+        union-find decode of the perfect syndrome, without the matching referee's cluster limits, pool or fallback."""
         if d % 2 != 1:
             raise Exception("for the surface code d must be odd!")          # Function_Library.py:28-29
         if error_model not in _MODELS:
@@ -169,7 +174,7 @@ class VectorEnv:
         cfg = EnvCfg(d, _MODELS[error_model], int(bool(use_Y)), volume_depth, self.n_envs, self.env_id_base,
                      (ctypes.c_uint32 * 2)(*self.seed))
         h = ctypes.c_void_p()
-        self.wide = backend == "wide" or referee == "matching" or (backend == "auto" and d > 7)
+        self.wide = backend == "wide" or (isinstance(referee, str) and referee in WIDE_REFEREES) or (backend == "auto" and d > 7)
         self._pfx = "dq_envb_" if self.wide else "dq_env_"
         with torch.cuda.device(self.device):
             check(getattr(self.L, self._pfx + "create")(ctypes.byref(cfg), ctypes.byref(h)))
@@ -203,9 +208,12 @@ class VectorEnv:
         self._lut = None
         self.mlp_referee, self._mlp_w = False, None
         self.inexact = torch.zeros(n, dtype=torch.uint8, device=dev)         # wide backend: referee fallback used in the last step
+        self._referee_kind = "matching" if self.wide else None
         if self.wide:
-            if referee not in ("lut", "matching", None):
-                raise NotImplementedError("the wide environment (d >= 9) decodes with the built-in matching referee")
+            if isinstance(referee, str) and referee == "uf":
+                self.set_referee_kind("uf")
+            elif referee not in ("lut", "matching", None):
+                raise NotImplementedError("the wide environment (d >= 9) decodes with its built-in referees: 'matching' or 'uf'")
         elif referee == "lut":
             with torch.cuda.device(self.device):
                 check(self.L.dq_env_build_referee(self._h, self._stream()))
@@ -293,6 +301,21 @@ class VectorEnv:
     def p_meas(self, v):
         self.set_rates(self._rate_forms()[0], v)
 
+    @property
+    def referee_kind(self):
+        """The wide backend's referee: "matching" or "uf" (set_referee_kind).  None on the narrow backend, whose referee is a table or a Dense stack."""
+        return self._referee_kind
+
+    def set_referee_kind(self, kind):
+        """Chooses the referee of the wide backend's step (dq_envb_set_referee): "matching" (the state after construction without referee="uf") or "uf".
+        Every later step, fused selection included, follows it; the lattices' records do not depend on it, so it may change between any two steps."""
+        if not self.wide:
+            raise NotImplementedError("set_referee_kind: the narrow environment's referee is a table or a Dense stack (set_referee*)")
+        if not (isinstance(kind, str) and kind in WIDE_REFEREES):
+            raise ValueError(f"set_referee_kind: kind must be one of {tuple(WIDE_REFEREES)}, not {kind!r}")
+        check(self.L.dq_envb_set_referee(self._h, WIDE_REFEREES[kind]))
+        self._referee_kind = kind
+
     def build_ml_referee(self, q_flip):
         """Installs the maximum-likelihood referee for independent X- / Z-component flips with probability q_flip per qubit."""
         with torch.cuda.device(self.device):
@@ -342,7 +365,7 @@ class VectorEnv:
         """Install a Dense-stack referee (referee.FeedForwardReferee: .dims, .flat_weights()) to be EVALUATED on the device before every
         step (dq_env_set_referee_mlp) -- the reference's own kind of static_decoder (ENV:53,144), for any d <= 7; None uninstalls."""
         if self.wide:
-            raise NotImplementedError("the wide environment (d >= 9) decodes with the built-in matching referee")
+            raise NotImplementedError("the wide environment (d >= 9) decodes with its built-in referees: 'matching' or 'uf'")
         if referee is None:
             check(self.L.dq_env_set_referee_mlp(self._h, 0, None, None))
             self.mlp_referee, self._mlp_w = False, None
@@ -733,8 +756,8 @@ class Surface_Code_Environment_Multi_Decoding_Cycles:
             referee = tuple(static_decoder)
         elif hasattr(static_decoder, "predict"):
             referee = static_decoder            # the reference's protocol (ENV:144): tabulated once over all syndromes (d <= 5)
-        elif static_decoder == "matching":
-            referee = "matching"
+        elif isinstance(static_decoder, str) and static_decoder in WIDE_REFEREES:
+            referee = static_decoder            # the wide backend's referees: "matching", "uf" 
         else:
             raise NotImplementedError("static_decoder must be None/'lut', 'ml', a (lut_x, lut_z) pair or an object with .predict")
         self._v = VectorEnv(d, p_phys, p_meas, error_model, use_Y, volume_depth, n_envs=1, seed=seed, env_id_base=env_id,

@@ -79,7 +79,47 @@ class FeedForwardReferee:
         return out
 
 
-class MatchingReferee:
+class _DefectReferee:
+    """What the referees that decode defect words share: the plaquettes' (component, bit) order, `pack` and the reference's `predict` protocol around a
+    `decode(defects)` that returns (class tensor, flags)."""
+
+    def _index_plaquettes(self):
+        # plaquette (a, b) -> (component, bit) in row-major order per type (FL:32-35, 42-50: type 3 when a + b is odd)
+        self._where = {}
+        rank = [0, 0]
+        dd = self.d
+        for a in range(dd + 1):
+            for b in range(dd + 1):
+                if (a == 0 and b % 2 == 0) or (a == dd and b % 2 == 1) or (b == 0 and a % 2 == 1) or (b == dd and a % 2 == 0):
+                    continue
+                comp = 0 if (a + b) % 2 == 1 else 1
+                self._where[(a, b)] = (comp, rank[comp])
+                rank[comp] += 1
+
+    def _defects_on_device(self, defects):
+        torch = self._torch
+        if torch.is_tensor(defects):
+            return defects
+        return torch.as_tensor(np.array(defects, dtype=np.uint64, order="C").view(np.int64)).cuda()       # (a copy: read-only arrays are welcome)
+
+    def pack(self, grids):
+        """[batch, d+1, d+1] syndrome grids -> defects uint64 [batch, 2, 2]."""
+        grids = np.asarray(grids).reshape(-1, self.d + 1, self.d + 1)
+        out = np.zeros((len(grids), 2, 2), dtype=np.uint64)
+        for i, g in enumerate(grids):
+            for (a, b) in zip(*np.nonzero(g)):
+                comp, bit = self._where[(int(a), int(b))]
+                out[i, comp, bit >> 6] |= np.uint64(1) << np.uint64(bit & 63)
+        return out
+
+    def predict(self, x, batch_size=None, verbose=0):
+        cls, _ = self.decode(self.pack(x))
+        out = np.zeros((len(cls), self.n_classes), dtype=np.float32)
+        out[np.arange(len(cls)), cls.cpu().numpy()] = 1.0
+        return out
+
+
+class MatchingReferee(_DefectReferee):
     """The exact minimum-weight referee for lattices too large for look-up tables (d >= 9; any odd 3 <= d <= 15), on the GPU:
     include/deepq_hip.h ``dq_match_*`` (csrc/match.hip).  Same definition as the environment's built-in look-up referee -- class 1 iff the
     lightest error with that syndrome and class 1 is strictly lighter than with class 0 -- and the same ``predict`` protocol the reference
@@ -97,17 +137,7 @@ class MatchingReferee:
         n, k, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         _lib.check(_lib.lib().dq_match_info(h, ctypes.byref(n), ctypes.byref(k), ctypes.byref(w)))
         self.nodes, self.max_defects, self.distance = n.value, k.value, w.value
-        # plaquette (a, b) -> (component, bit) in row-major order per type (FL:32-35, 42-50: type 3 when a + b is odd)
-        self._where = {}
-        rank = [0, 0]
-        dd = self.d
-        for a in range(dd + 1):
-            for b in range(dd + 1):
-                if (a == 0 and b % 2 == 0) or (a == dd and b % 2 == 1) or (b == 0 and a % 2 == 1) or (b == dd and a % 2 == 0):
-                    continue
-                comp = 0 if (a + b) % 2 == 1 else 1
-                self._where[(a, b)] = (comp, rank[comp])
-                rank[comp] += 1
+        self._index_plaquettes()
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -126,7 +156,7 @@ class MatchingReferee:
         """defects: integer array [batch, 2 components, 2 words] (bit i = i-th plaquette of the component) -> (class uint8 [batch],
         inexact uint8 [batch]) as torch CUDA tensors."""
         torch = self._torch
-        dev = torch.as_tensor(np.ascontiguousarray(defects, dtype=np.uint64).view(np.int64)).cuda() if not torch.is_tensor(defects) else defects
+        dev = self._defects_on_device(defects)
         batch = dev.shape[0]
         cls = torch.empty(batch, dtype=torch.uint8, device="cuda")
         flag = torch.empty(batch, dtype=torch.uint8, device="cuda")
@@ -135,18 +165,44 @@ class MatchingReferee:
                                                        torch.cuda.current_stream().cuda_stream))
         return cls, flag
 
-    def pack(self, grids):
-        """[batch, d+1, d+1] syndrome grids -> defects uint64 [batch, 2, 2]."""
-        grids = np.asarray(grids).reshape(-1, self.d + 1, self.d + 1)
-        out = np.zeros((len(grids), 2, 2), dtype=np.uint64)
-        for i, g in enumerate(grids):
-            for (a, b) in zip(*np.nonzero(g)):
-                comp, bit = self._where[(int(a), int(b))]
-                out[i, comp, bit >> 6] |= np.uint64(1) << np.uint64(bit & 63)
-        return out
 
-    def predict(self, x, batch_size=None, verbose=0):
-        cls, _ = self.decode(self.pack(x))
-        out = np.zeros((len(cls), self.n_classes), dtype=np.float32)
-        out[np.arange(len(cls)), cls.cpu().numpy()] = 1.0
-        return out
+class UnionFindReferee(_DefectReferee):
+    """The union-find referee for any odd 3 <= d <= 15, on the GPU (include/deepq_hip.h ``dq_uf_referee_decode``; csrc/uf_plane_dev.h):
+    the closed union-find decode of the perfect syndrome on a one-round window, class = the parity of the correction's logical bits.  What
+    ``VectorEnv(referee="uf")`` asks inside its step, with MatchingReferee's ``decode`` / ``pack`` / ``predict``: nothing is inexact, so the flags ``decode``
+    returns are zeros."""
+
+    def __init__(self, d, error_model="DP"):
+        d = int(d)
+        if d % 2 != 1 or not 3 <= d <= 15:
+            raise ValueError(f"UnionFindReferee: d = {d!r}: odd d in 3 .. 15")
+        if error_model not in ("X", "DP", "IIDXZ"):
+            raise ValueError("specified error model not currently supported!")
+        from . import _lib
+        import torch
+        self._lib, self._torch = _lib, torch
+        self.d, self.error_model = d, error_model
+        self.n_classes = 2 if error_model == "X" else 4
+        self.nodes = (d * d - 1) // 2
+        _lib.require_gpu()
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib().dq_wide_uf_create(d, {"X": 0, "DP": 1, "IIDXZ": 2}[error_model], 1, 1, ctypes.byref(h)))
+        self._h = h
+        self._index_plaquettes()
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.lib().dq_wide_uf_destroy(h)
+
+    def decode(self, defects, both=None):
+        """defects: integer array [batch, 2 components, 2 words] (bit i = i-th plaquette of the component) -> (class uint8 [batch], inexact uint8 [batch]:
+        zeros) as torch CUDA tensors, MatchingReferee.decode's pair."""
+        torch = self._torch
+        dev = self._defects_on_device(defects)
+        batch = dev.shape[0]
+        cls = torch.empty(batch, dtype=torch.uint8, device="cuda")
+        both = (self.error_model != "X") if both is None else both
+        self._lib.check(self._lib.lib().dq_uf_referee_decode(self._h, dev.data_ptr(), batch, int(both), cls.data_ptr(),
+                                                            torch.cuda.current_stream().cuda_stream))
+        return cls, torch.zeros(batch, dtype=torch.uint8, device="cuda")

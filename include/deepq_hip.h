@@ -301,6 +301,16 @@ dq_status dq_envb_act_step(dq_envb* env, const float* q_dev, double eps, int mas
                            int32_t* action_dev, int auto_reset, uint8_t* obs_dev, float* reward_dev, uint8_t* done_dev, uint64_t* legal_dev,
                            uint32_t* lifetime_dev, uint8_t* was_reset_dev, uint8_t* inexact_dev, void* stream);
 dq_status dq_envb_export_state(dq_envb* env, uint64_t* state_dev, void* stream);
+/* The referee of the wide environment's step.  dq_version() stays 8: the capability is the presence of this symbol.
+ * DQ_REFEREE_MATCHING (the state after dq_envb_create): the matching referee above.  DQ_REFEREE_UNION_FIND: the union-find referee -- section 20's closed
+ * union-find decode of the perfect syndrome on a one-round window, one Pauli component per wavefront (csrc/uf_plane_dev.h; dq_uf_referee_decode below is
+ * the same function on given defects): no scratch pool, no lock, no fallback, so inexact_dev receives zeros.  The handle owns the tables it needs (built at
+ * the first choice of union-find: DQ_ERR_NOMEM / DQ_ERR_HIP, the setting then stays as it was).  Any other kind, or a null handle, is DQ_ERR_INVALID.  Every
+ * later launch that steps the lattices -- dq_envb_step, dq_envb_act_step, and so every selection that rides on them -- follows the setting; resets, exports
+ * and the lattices' records do not depend on it, so it may be switched between any two steps. */
+#define DQ_REFEREE_MATCHING 0
+#define DQ_REFEREE_UNION_FIND 1
+dq_status dq_envb_set_referee(dq_envb* env, int kind);
 /* dq_policy_select (below) over legal sets of legal_words uint64 per lattice: same rule, same Philox words */
 dq_status dq_policy_select_wide(const float* q_dev, const uint64_t* legal_dev, int n, int n_actions, int legal_words, double eps,
                                 int masked_greedy, const uint32_t seed[2], uint32_t env_id_base, uint64_t t, int32_t* action_dev,
@@ -903,6 +913,18 @@ dq_status dq_wide_uf_verdict(dq_wide_uf* h, const uint8_t* hidden_dev, const uin
  * have ended.  No reference counterpart beyond the step's rule (Environments.py:139-151). */
 dq_status dq_wide_uf_verdict_refereed(dq_wide_uf* h, const dq_match* m, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev,
                                       uint8_t* inexact_dev, void* stream);
+/* The union-find referee (csrc/uf_plane.hip, csrc/uf_plane_dev.h).  dq_version() stays 8: the capability is the presence of these two
+ * symbols.  The class of a perfect syndrome by the closed union-find decode of a one-round window: per component only the d^2 space edges exist (edge id =
+ * qubit id), growth, min-labels and lowest-edge-id peeling are dq_wide_uf_decode_closed's at T = window = 1, and the class is the parity of the logical bits of
+ * the correction's qubits.  The empty syndrome gives class 0.  One wavefront per (syndrome, component), 1520 bytes of LDS each; nothing is inexact.
+ * dq_uf_referee_decode: dq_match_decode's layouts without the inexact array -- defects_dev uint64 [batch][2 components][2 words], class_dev uint8 [batch] =
+ * X part (+ 2 * Z part when both_components != 0); the handle supplies the lattice (its error model and window are not read).  batch >= 1; a null argument or
+ * a batch below 1 is DQ_ERR_INVALID before any device work.
+ * dq_wide_uf_verdict_refereed_uf: dq_wide_uf_verdict_refereed's byte, field for field, with this referee in the matching referee's place (component 1 unless
+ * the handle's error model is DQ_MODEL_X); a residual in the code space is not sent to the referee.  No referee handle, no flags, and no launch is slow: any
+ * n in 1 .. max_streams goes in one launch whatever the density of the residuals. */
+dq_status dq_uf_referee_decode(const dq_wide_uf* h, const uint64_t* defects_dev, int batch, int both_components, uint8_t* class_dev, void* stream);
+dq_status dq_wide_uf_verdict_refereed_uf(dq_wide_uf* h, const uint8_t* hidden_dev, const uint8_t* frame_dev, int n, uint8_t* verdict_dev, void* stream);
 /* The closed forms (a final round of perfect measurements): dq_stream_decode_uf_closed's and dq_stream_run_uf_closed's rule on this handle, with
  * dq_wide_uf_decode's and dq_wide_uf_run's arguments, validation and contract.  For d <= 7 and window <= 16 every field equals the narrow closed forms'. */
 dq_status dq_wide_uf_decode_closed(dq_wide_uf* h, const uint8_t* syndromes_dev, int n, int T, int commit, uint8_t* frame_dev, int32_t* weight_dev,

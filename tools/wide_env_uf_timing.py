@@ -1,6 +1,7 @@
 """Launch times of the wide environment's union-find selection (DESIGN.md sections 19, 24 and 26): recorded, not gated.
 
-    python tools/wide_env_uf_timing.py [--lattices 4096] [--p 0.006] [--rounds 5] [--play 8] [--meas-ratio R] [--weights rates|WS,WT] [--correlated] [--out FILE]
+    python tools/wide_env_uf_timing.py [--lattices 4096] [--p 0.006] [--rounds 5] [--play 8] [--meas-ratio R] [--weights rates|WS,WT] [--correlated] [--referee matching|uf]
+                                        [--out FILE]
 
 Per configuration (d = 9 / volume_depth 9 and d = 15 / volume_depth 5, DP) on --lattices mid-episode lattices (--play agent steps of the union-find policy
 from a reset): the select launch (env_wide_uf_kernel), dq_envb_step, dq_wide_uf_decode on the same volumes exported as grids with window = commit =
@@ -12,7 +13,9 @@ played by the unweighted policy, and the record goes to profiles/wide_env_uf_wei
 step and a fresh export, so that all launches of a round see the same volumes.  Median, min and max.  Writes profiles/wide_env_uf_timing.json.
 --correlated (with --weights) adds the correlated select launch (env_wide_uf_kernel<true, true>) and the correlated guided launch at
 the three fractions under the pair with w_corr = 1 and with w_corr = w_space -- with --weights rates the pair of decoder_wide.uf_weights_correlated, which the
-weighted launches then take too --, each reported over the WEIGHTED launch at the same pair; the record goes to profiles/wide_env_uf_correlated_timing.json."""
+weighted launches then take too --, each reported over the WEIGHTED launch at the same pair; the record goes to profiles/wide_env_uf_correlated_timing.json.
+--referee plays and steps under the named referee of the wide environment, VectorEnv(referee=...); the record names it and, unless --out
+says otherwise, goes to the default file's name with _<referee> in front of .json.  tools/wide_env_referee_timing.py holds the two referees' steps against each other."""
 import argparse
 import importlib
 import json
@@ -40,7 +43,7 @@ def timed_us(fn):
 
 
 class Config:
-    def __init__(self, d, depth, n, p, p_meas=None, weights=None, correlated=False):
+    def __init__(self, d, depth, n, p, p_meas=None, weights=None, correlated=False, referee=None):
         from oracle import lattice
         self.d, self.depth, self.n = d, depth, n
         p_meas = p if p_meas is None else p_meas
@@ -48,7 +51,8 @@ class Config:
         self.correlated = correlated
         if correlated and weights == "rates":
             self.pair = dq.uf_weights_correlated(p, p_meas, "DP")[:2]
-        self.env = dq.VectorEnv(n_envs=n, seed=SEED, d=d, error_model="DP", use_Y=False, volume_depth=depth, p_phys=p, p_meas=p_meas, backend="wide")
+        self.env = dq.VectorEnv(n_envs=n, seed=SEED, d=d, error_model="DP", use_Y=False, volume_depth=depth, p_phys=p, p_meas=p_meas, backend="wide",
+                                **({"referee": referee} if referee else {}))
         self.ev = dq.WideEvaluator(d, "DP", window=depth, chunk=n, device=self.env.device)
         dev = self.env.device
         self.action, self.other = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
@@ -106,13 +110,14 @@ def main():
     ap.add_argument("--meas-ratio", type=float, default=1.0)
     ap.add_argument("--weights", default=None)
     ap.add_argument("--correlated", action="store_true")
+    ap.add_argument("--referee", default=None, choices=["matching", "uf"])
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     weights = None if a.weights is None else a.weights if a.weights == "rates" else tuple(int(x) for x in a.weights.split(","))
     if a.correlated and weights is None:
         ap.error("--correlated times against the weighted launch: give --weights")
     p_meas = min(1.0, a.meas_ratio * a.p)
-    cfgs = {f"d{d}_depth{depth}": Config(d, depth, a.lattices, a.p, p_meas, weights, a.correlated) for d, depth in SHAPES}
+    cfgs = {f"d{d}_depth{depth}": Config(d, depth, a.lattices, a.p, p_meas, weights, a.correlated, a.referee) for d, depth in SHAPES}
     for c in cfgs.values():
         for _ in range(a.play):
             c.play()
@@ -132,7 +137,7 @@ def main():
             c.t += 1
             c.export()
     record = dict(device=torch.cuda.get_device_name(0), lattices=a.lattices, p=a.p, p_meas=p_meas, weights=a.weights, correlated=a.correlated, model="DP",
-                  played_steps=a.play,
+                  referee=a.referee or "matching", played_steps=a.play,
                   timing_rounds=a.rounds, configurations={})
     for k, c in cfgs.items():
         rows = {name: dict(median_us=float(np.median(v)), min_us=float(np.min(v)), max_us=float(np.max(v))) for name, v in t[k].items()}
@@ -153,6 +158,8 @@ def main():
             print(f"{k:12s} pair {c.pair}: " + "  ".join(f"{name} x {v:.3f}" for name, v in over.items()))
     path = a.out or os.path.join(ROOT, "profiles", "wide_env_uf_correlated_timing.json" if a.correlated else
                                  "wide_env_uf_weighted_timing.json" if weights else "wide_env_uf_timing.json")
+    if a.referee and not a.out:
+        path = path[:-len(".json")] + f"_{a.referee}.json"
     with open(path, "w") as f:
         json.dump(record, f, indent=1)
         f.write("\n")

@@ -1,7 +1,7 @@
 """Episode lifetimes of the wide environment under the union-find policy against the identity (DESIGN.md sections 19, 24 and 26): recorded, not gated.
 
     python tools/wide_uf_lifetimes.py [--d 9 11 13 15] [--rates 0.016 ... 0.002] [--lattices 64] [--episodes 64] [--max-steps 40000]
-                                      [--meas-ratio R] [--weights rates|WS,WT] [--correlated rates|W] [--out FILE]
+                                      [--meas-ratio R] [--weights rates|WS,WT] [--correlated rates|W] [--referee matching|uf] [--out FILE]
 
 DP, volume_depth 5, p_meas = p_phys (--meas-ratio R: p_meas = R p).  Per d one environment of --lattices lattices (one seed, ids 0 ..), and per rate one
 WideUnionFindAgent.test_error_rates(env, [rate]) for the union-find row and one for the identity row: the same seed and ids for both.  --weights adds a third
@@ -13,7 +13,11 @@ episodes do not end within --max-steps vector steps is recorded as censored and 
 correlated passes: "rates" (beside --weights rates) takes decoder_wide.uf_weights_correlated of the row's own rates, W one w_corr beside the pair WS,WT; the
 row records the triple it played with and the ratio of its mean lifetime to the WEIGHTED row's, with both episode counts and whether the two 95 % intervals
 overlap -- where they are apart the row says which policy lives longer.  Writes profiles/wide_uf_lifetimes_dp.json (with --weights:
-profiles/wide_uf_lifetimes_weighted.json, with --correlated: profiles/wide_uf_lifetimes_correlated.json)."""
+profiles/wide_uf_lifetimes_weighted.json, with --correlated: profiles/wide_uf_lifetimes_correlated.json).
+--referee plays under the named referee of the wide environment, VectorEnv(referee=...): "matching" is what the tool played under before
+the option existed, "uf" the union-find referee, which has no cluster limit and so reaches d = 13 and 15.  The record then goes to
+profiles/wide_uf_lifetimes_referee.json, which holds one record per referee: a run replaces its own referee's rows of the distances it played and keeps
+everything else that the file held."""
 import argparse
 import importlib
 import json
@@ -60,6 +64,7 @@ def main():
     ap.add_argument("--meas-ratio", type=float, default=1.0)
     ap.add_argument("--weights", default=None)
     ap.add_argument("--correlated", default=None)
+    ap.add_argument("--referee", default=None, choices=["matching", "uf"])
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     weights = None if a.weights is None else a.weights if a.weights == "rates" else tuple(int(x) for x in a.weights.split(","))
@@ -68,10 +73,17 @@ def main():
         ap.error("--correlated compares against the weighted row: give --weights")
     record = dict(device=torch.cuda.get_device_name(0), model="DP", volume_depth=5, lattices=a.lattices, episodes=a.episodes, max_vector_steps=a.max_steps,
                   seed=list(SEED), p_meas="= p" if a.meas_ratio == 1.0 else f"= {a.meas_ratio:g} p", weights=a.weights, correlated=a.correlated, rows={})
-    path = a.out or os.path.join(ROOT, "profiles", "wide_uf_lifetimes_correlated.json" if correlated is not None else
-                                 "wide_uf_lifetimes_weighted.json" if weights else "wide_uf_lifetimes_dp.json")
+    path = a.out or os.path.join(ROOT, "profiles", "wide_uf_lifetimes_referee.json" if a.referee else "wide_uf_lifetimes_correlated.json" if correlated is not None
+                                 else "wide_uf_lifetimes_weighted.json" if weights else "wide_uf_lifetimes_dp.json")
+    whole = record
+    if a.referee:                                                                        # one record per referee in one file
+        record["referee"] = a.referee
+        whole = json.load(open(path)) if os.path.exists(path) else {}
+        record["rows"] = dict(whole.get(a.referee, {}).get("rows", {}))
+        whole[a.referee] = record
     for d in a.d:
-        env = dq.VectorEnv(n_envs=a.lattices, seed=SEED, d=d, error_model="DP", use_Y=False, volume_depth=5, p_phys=0.01, p_meas=0.01, backend="wide")
+        env = dq.VectorEnv(n_envs=a.lattices, seed=SEED, d=d, error_model="DP", use_Y=False, volume_depth=5, p_phys=0.01, p_meas=0.01, backend="wide",
+                           **({"referee": a.referee} if a.referee else {}))
         ev = dq.WideEvaluator(d, "DP", window=5, chunk=a.lattices, device=env.device)
         uf, ident = dq.WideUnionFindAgent(evaluator=ev), dq.WideUnionFindAgent(policy="identity")
         weighted = dq.WideUnionFindAgent(evaluator=ev, weights=weights) if weights else None
@@ -104,7 +116,7 @@ def main():
                          + (" (intervals overlap)" if c["intervals_overlap"] else f" ({c['resolved_longer']} lives longer, resolved)")), flush=True)
             rows[f"{rate:g}"] = row
             with open(path, "w") as f:                                                   # after every row: a time limit loses the row in progress only
-                json.dump(record, f, indent=1)
+                json.dump(whole, f, indent=1)
                 f.write("\n")
             if u.get("censored") or (weighted is not None and row["union_find_weighted"].get("censored")) or (
                     corr is not None and row["union_find_correlated"].get("censored")):
