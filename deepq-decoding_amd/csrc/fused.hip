@@ -1577,6 +1577,7 @@ size_t fused_packed_u32x4(const dq_qnet* Q) {
 dq_status fused_pack_weights(const dq_qnet* Q, const float* params_dev, void* packed_dev, hipStream_t st) {
     DQ_REQUIRE(Q && params_dev && packed_dev, DQ_ERR_INVALID, "dq_qnet_pack: null argument");
     DQ_REQUIRE(fused_forward_supported(Q), DQ_ERR_UNSUPPORTED, "dq_qnet_pack: the fused chains do not cover this configuration");
+    DQ_REQUIRE((reinterpret_cast<uintptr_t>(packed_dev) & 15) == 0, DQ_ERR_INVALID, "dq_qnet_pack: packed_dev must be 16-byte aligned");
     const int nc = Q->cfg.n_conv;
     const Layer &D1 = Q->L[nc], &D2 = Q->L[nc + 1];
     PackArgs a;
@@ -1905,6 +1906,7 @@ dq_status fused_forward_multi(dq_qnet* Q, int n_jobs, const dq_qnet_job* jobs, h
         DQ_REQUIRE(jb.batch >= 1 && jb.batch <= Q->cfg.max_batch, DQ_ERR_INVALID, "dq_qnet_forward: batch %d outside 1..%d", jb.batch, Q->cfg.max_batch);
         DQ_REQUIRE((reinterpret_cast<uintptr_t>(jb.params_dev) & 15) == 0, DQ_ERR_INVALID, "fused_forward: params_dev must be 16-byte aligned");
         DQ_REQUIRE(!patch || (reinterpret_cast<uintptr_t>(jb.obs_dev) & 15) == 0, DQ_ERR_INVALID, "fused_forward: patch-word rows must be 16-byte aligned");
+        DQ_REQUIRE((reinterpret_cast<uintptr_t>(jb.packed_dev) & 15) == 0, DQ_ERR_INVALID, "fused_forward: packed_dev must be 16-byte aligned");
         const int training = jb.training ? 1 : 0;
         n_train += training;
         DQ_REQUIRE(n_train <= 1, DQ_ERR_INVALID, "dq_qnet_forward_multi: at most one training job per launch");

@@ -342,6 +342,9 @@ dq_status dq_policy_select(const float* q_dev, const uint64_t* legal_dev, int n,
  * the fused chains carry every f32 operand as two f16 pieces (22 significant bits, round to nearest) and issue three f16 MFMAs per
  * product with f32 accumulation (two where an operand is binary): error below that of an ordinary f32 GEMM's accumulation, different
  * summation order (csrc/qnet.h "f16x2").  Operands of the fused chains must be finite and below 65504 in magnitude.
+ * Alignment: params_dev must be 16-byte aligned wherever the fused chains run (they read bias rows as 16-byte words; DQ_ERR_INVALID before any
+ * launch otherwise); q_dev, dq_dev, grads_dev, m_dev, v_dev and index_dev need only their element's 4 bytes (where all of grads_dev, m_dev and
+ * v_dev are 16-byte aligned the final reduction takes 16-byte accesses: the same bits).
  * ------------------------------------------------------------------------------------------- */
 typedef struct dq_qnet dq_qnet;
 
@@ -441,7 +444,9 @@ dq_status dq_qnet_set_patch_input(dq_qnet* net, int n_syndrome_planes, int strid
 /* The fused chains read the conv kernels and Dense(512) as f16 pieces in matrix-core operand order.  A caller that runs several
  * forwards on the same weights packs them once per parameter change (dq_qnet_packed_bytes(net) bytes of device memory) and
  * passes the buffer in dq_qnet_job.packed_dev; it MUST repack after every change of params_dev (dq_adam_step, weight loading).
- * dq_qnet_forward and jobs with packed_dev == NULL pack on every call.  The backward reuses the training forward's pack. */
+ * dq_qnet_forward and jobs with packed_dev == NULL pack on every call.  The backward reuses the training forward's pack.
+ * packed_dev must be 16-byte aligned (it is written and read as 16-byte words): DQ_ERR_INVALID otherwise, from dq_qnet_pack and from a job that
+ * brings it, before any launch. */
 size_t dq_qnet_packed_bytes(const dq_qnet* net);
 dq_status dq_qnet_pack(const dq_qnet* net, const float* params_dev, void* packed_dev, void* stream);
 
