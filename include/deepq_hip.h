@@ -491,7 +491,8 @@ dq_status dq_qnet_range_discarded(dq_qnet* net, unsigned* count, void* stream);
 
 /* The same backward in two phases, for overlapping the gradient all-reduce with compute on several GPUs (no reference
  * counterpart): phase 0 = dueling + dense layers -> grads_dev[dq_qnet_conv_param_count(net) ..) complete; phase 1 = the
- * convolutions -> grads_dev[0 .. dq_qnet_conv_param_count(net)).  Phase 0 must run first; dq_dev is only read by phase 0. */
+ * convolutions -> grads_dev[0 .. dq_qnet_conv_param_count(net)).  Phase 0 must run first; dq_dev is only read by phase 0.  On the fused
+ * chains phase 0 (and dq_qnet_td_backward_phase0[_env]) leaves grads_dev[0 .. dq_qnet_conv_param_count(net)) untouched. */
 dq_status dq_qnet_backward_phase(dq_qnet* net, const float* params_dev, const float* dq_dev, float* grads_dev, int phase,
                                  void* stream);
 size_t dq_qnet_conv_param_count(const dq_qnet* net);
@@ -507,7 +508,10 @@ dq_status dq_qnet_backward_adam(dq_qnet* net, float* params_dev, const float* dq
  * step: lattice i's running reward / length advance (not on a step spent being reset); a lattice that ends an episode while
  * quota_dev[i] > 0 appends int32 {step, i, reward bits (float), length, lifetime} to records_dev [capacity][5] (slot = atomic increment
  * of counter_dev[0]; sort by (step, lattice) for the serial loop's order) and pays one unit of quota.  The host only reads counter_dev
- * every few dozen steps to see whether the evaluation is complete.  No reference counterpart. */
+ * every few dozen steps to see whether the evaluation is complete.  A full table: a record whose slot is >= capacity is dropped -- nothing
+ * is stored past row capacity - 1 --, its unit of quota is paid all the same and counter_dev[0] still counts it, so counter_dev[0] >
+ * capacity tells the host how many records were lost.  quota_dev, ep_reward_dev, ep_len_dev int32 / float / int32 [n] and counter_dev int32
+ * [1] are read and written; records_dev is only written.  No reference counterpart. */
 dq_status dq_test_bookkeeping(const uint8_t* done_dev, const uint8_t* was_reset_dev, const float* reward_dev, const uint32_t* lifetime_dev, int n,
                               int step, int32_t* quota_dev, float* ep_reward_dev, int32_t* ep_len_dev, int32_t* records_dev, int capacity,
                               int32_t* counter_dev, void* stream);
@@ -520,8 +524,11 @@ dq_status dq_qnet_adam_step(dq_qnet* net, float* params_dev, const float* grads_
                             double beta_2, double epsilon, uint64_t t, void* stream);
 
 /* The learner half of one DQNAgent.backward in the fewest launches: dq_td_step (+ dq_episode_stats when n > 0) computed in the
- * dense backward's first kernel, then dq_qnet_backward, then dq_adam_step on the final reduction.  Same y / dq / gradient / parameter
- * bits as the separate calls; the loss / mean_q partials are summed in a different order (dq_td_metrics reads them the same way).
+ * dense backward's first kernel, then dq_qnet_backward, then dq_adam_step on the final reduction.  Same y / dq bits as the separate
+ * calls; the loss / mean_q partials are summed in a different order (dq_td_metrics reads them the same way).  Gradient, parameters and
+ * moments: the separate calls' bits on the per-layer path; on the fused chains the bits of every form of this launch (_adam, _adam_env,
+ * _phase0[_env] + phase 1) are equal, and equal to the separate calls' to round-off only (with the TD step fused in, dq has one non-zero
+ * per row and the backward forms dq W3^T as a scalar times a table row instead of on the matrix pipe).
  * y_dev, dq_dev (needed only by the per-layer path), metrics_dev nullable.
  * m_dev == v_dev == NULL (dq_qnet_td_backward_adam, _adam_env, dq_qnet_backward_adam): the gradient only, no optimizer step -- the several-GPU
  * path, where the all-reduce of grads_dev comes between the backward and dq_adam_step (one final reduction launch instead of the two of the

@@ -7,6 +7,8 @@ holds every buffer of a case as [guard | payload | guard]:
     a = Arena("cuda", 0x00)
     a.request("obs", (B, C, H, W), torch.uint8, align=1, init=obs)   # an input: copied in, inputs_unchanged() compares it
     a.request("q", (B, A), torch.float32, align=4)                   # an output: prefilled with 0x77
+    a.request("ring", (S, n), torch.uint8, align=1, init=ring, inout=True)   # read and written: copied in, exempt from inputs_unchanged(),
+                                                                     # part of outputs() -- the caller compares ALL of it with the reference
     q = a.take("q")                                                  # the first take() sizes and fills the allocation
     ... launch ...
     a.check(); a.inputs_unchanged()
@@ -16,7 +18,7 @@ boundary plus `align` bytes (aligned to `align` and to nothing coarser) and its 
 once with fill 0x00 and once with 0xFF: the two differ in every bit, as uint8 (0 / 255), int32 (0 / -1), f32 and f16 (0.0 / NaN), so an
 output that depends on a guard byte cannot have equal bits in both runs.
 
-take(name, shape, dtype, align, init) requests and takes in one call while the arena is still unsized."""
+take(name, shape, dtype, align, init, inout) requests and takes in one call while the arena is still unsized."""
 import numpy as np
 import torch
 
@@ -30,7 +32,7 @@ def _itemsize(dtype):
 
 
 class _Buf:
-    __slots__ = ("name", "shape", "dtype", "align", "init", "lo", "start", "nbytes", "hi_end")
+    __slots__ = ("name", "shape", "dtype", "align", "init", "inout", "lo", "start", "nbytes", "hi_end")
 
 
 class Arena:
@@ -43,7 +45,7 @@ class Arena:
         self._mem = None
 
     # ---- layout ------------------------------------------------------------------------------------------------------------
-    def request(self, name, shape, dtype, align, init=None):
+    def request(self, name, shape, dtype, align, init=None, inout=False):
         assert self._mem is None, "the arena is already sized: request every buffer before the first take()"
         assert name not in self._bufs, f"buffer {name!r} requested twice"
         align = int(align)
@@ -54,7 +56,8 @@ class Arena:
         b = _Buf()
         b.name, b.shape, b.dtype, b.align = name, shape, dtype, align
         b.nbytes = int(np.prod(shape, dtype=np.int64)) * isz
-        b.init = None
+        b.init, b.inout = None, bool(inout)
+        assert init is not None or not inout, f"{name}: an in/out buffer starts from its init"
         if init is not None:
             t = torch.as_tensor(init).detach().to("cpu").contiguous()
             assert t.dtype == dtype and tuple(t.shape) == shape, f"{name}: init is {t.dtype} {tuple(t.shape)}, wanted {dtype} {shape}"
@@ -84,9 +87,9 @@ class Arena:
             else:
                 p.copy_(b.init)
 
-    def take(self, name, shape=None, dtype=None, align=None, init=None):
+    def take(self, name, shape=None, dtype=None, align=None, init=None, inout=False):
         if name not in self._bufs:
-            self.request(name, shape, dtype, align, init)
+            self.request(name, shape, dtype, align, init, inout)
         if self._mem is None:
             self._build()
         b = self._bufs[name]
@@ -137,7 +140,7 @@ class Arena:
         if self._mem is None:
             self._build()
         for b in self._bufs.values():
-            if b.init is None:
+            if b.init is None or b.inout:
                 continue
             now = self._mem[b.start:b.start + b.nbytes].cpu()
             if not torch.equal(now, b.init):
@@ -150,8 +153,8 @@ class Arena:
         return self.take(name).reshape(-1).view(torch.uint8).cpu().numpy().copy() if b.nbytes else np.zeros(0, np.uint8)
 
     def outputs(self):
-        """{name: payload bytes} of every buffer that had no init."""
-        return {n: self.bytes_of(n) for n, b in self._bufs.items() if b.init is None}
+        """{name: payload bytes} of every buffer that had no init, and of every in/out buffer."""
+        return {n: self.bytes_of(n) for n, b in self._bufs.items() if b.init is None or b.inout}
 
     def verify(self):
         """(a) and (b) of the rule; returns outputs() for (c) and (d)."""

@@ -98,6 +98,36 @@ def test_input_change_is_reported(fill):
         a.verify()
 
 
+@pytest.mark.parametrize("fill", G.FILLS)
+def test_inout_buffer(fill):
+    """request(..., inout=True): the initial contents are copied in, a change of them is no input change, the whole payload is part of outputs(), and
+    its guards are checked like any other's; an in/out buffer without initial contents is refused."""
+    ring0 = torch.arange(9 * 5, dtype=torch.int64).to(torch.uint8).view(9, 5)
+    a = G.Arena("cpu", fill)
+    a.request("obs", (4,), torch.uint8, 1, init=torch.tensor([1, 2, 3, 4], dtype=torch.uint8))
+    a.request("ring", (9, 5), torch.uint8, 1, init=ring0, inout=True)
+    a.request("q", (3,), torch.float32, 4)
+    with pytest.raises(AssertionError, match="starts from its init"):
+        a.request("m", (3,), torch.float32, 4, inout=True)
+    ring = a.take("ring")
+    assert torch.equal(ring, ring0)
+    assert sorted(a.outputs()) == ["q", "ring"]
+    assert np.array_equal(a.outputs()["ring"], ring0.numpy().reshape(-1))
+    ring[3] = 200                                   # the call writes slot 3 ...
+    out = a.verify()                                # ... which is no input change
+    want = ring0.clone()
+    want[3] = 200
+    assert np.array_equal(out["ring"].reshape(9, 5), want.numpy())      # every other slot holds its initial contents
+    lo, s, e, hi = a.span("ring")
+    a.raw()[e] = fill ^ 0x01
+    with pytest.raises(AssertionError, match="'ring' changed on its high side"):
+        a.verify()
+    a.raw()[e] = fill
+    a.take("obs")[0] = 9                            # a pure input beside it is still watched
+    with pytest.raises(AssertionError, match="input buffer 'obs'"):
+        a.verify()
+
+
 def test_same_bits():
     G.same_bits({"q": np.zeros(4, np.uint8)}, {"q": np.zeros(4, np.uint8)})
     with pytest.raises(AssertionError, match="'q' depends on the guard bytes: first difference at byte 2"):
